@@ -233,6 +233,8 @@ def run_edit(args, world, rank, dev):
         step(i)
     good0 = trainer.scaler.good_steps() if trainer.scaler is not None else 0          # host read, outside the timed region
     dt, (loss, ld) = _timed(step, args, world, dist)
+    if getattr(args, "dump", None) is not None and rank == 0:
+        collect_outputs("edit", loss, ld, model, args.dump)
     skipped = args.steps - (trainer.scaler.good_steps() - good0) if trainer.scaler is not None else 0
     # (every rank goes on: the roofline leg below runs two more steps, i.e. two more gradient exchanges — a rank that returned here left its
     # peers waiting in the all-to-all: found by tests/test_gpu_dp_two_ranks.py in round 5, before any multi-GPU hardware saw it)
@@ -371,6 +373,8 @@ def run_recon(args, world, rank, dev):
     good0 = trainer.scaler.good_steps() if trainer.scaler is not None else 0          # host read, outside the timed region
     stage = _StageEvents() if getattr(args, "stage_events", False) else None       # events between the kernels of the scatter / the field backward
     dt, (loss, out) = _timed(step, args, world, dist)
+    if getattr(args, "dump", None) is not None and rank == 0:
+        collect_outputs("recon", loss, out, model, args.dump)
     ge.set_profile(None)
     trainer._exchange_events = None
     stage_ms = stage.finish() if stage is not None else None
@@ -451,6 +455,55 @@ def _json_safe(x):
     if isinstance(x, (list, tuple)):
         return [_json_safe(v) for v in x]
     return x
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all arrays together
+DUMP_SAMPLE = 1 << 20           # elements kept of a larger array: a fixed, seeded sample (the same positions in every run)
+
+
+def _dump_array(t):
+    """tensor / number -> host float32 array (float64 for float64 and integer tensors, which float32 would round); larger than DUMP_SAMPLE
+    elements: the flat array at DUMP_SAMPLE sorted positions drawn with a fixed seed"""
+    import numpy as np
+    if not torch.is_tensor(t):
+        return np.asarray(float(t), dtype=np.float64)
+    t = t.detach()
+    wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+    if t.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+
+
+def collect_outputs(prefix, loss, extra, model, dump):
+    """--dump-outputs: what the timed path's last step handed its caller — the loss, the tensors of `extra` (the render results of a
+    reconstruction step, the loss terms of an edit step) — and the parameters that step left in `model`, copied to the host into `dump`
+    under `<prefix>_<name>`.  Called right after the timed region, before anything else runs on the model.  Render-result entries that are
+    computed on first access (renderer._Lazy) were not computed by the step and are left out."""
+    from customnerf_amd.nerf.renderer import _Lazy
+
+    def walk(name, v):
+        if isinstance(v, dict):
+            for k, x in dict.items(v):                    # (dict.items: does not materialise lazy entries)
+                walk(f"{name}_{k.lstrip('_')}", x)
+        elif isinstance(v, _Lazy) or v is None or isinstance(v, str):
+            return
+        elif torch.is_tensor(v) or isinstance(v, (int, float)):
+            dump[name] = _dump_array(v)
+    walk(f"{prefix}_loss", loss)
+    walk(f"{prefix}_out", extra)
+    for n, p in model.named_parameters():
+        walk(f"{prefix}_param_{n.replace('.', '_')}", p)
+
+
+def write_outputs(dump, directory):
+    import numpy as np
+    total = sum(a.nbytes for a in dump.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in dump.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _free_port():
@@ -625,7 +678,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--gemm-table", default=None, help="edit leg: write the per-shape table of one step's GEMM launches to this file (tuning aid)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, render results / loss terms, updated parameters; "
+                         "arrays above 2^20 elements as a fixed seeded sample) as DIR/<leg>_<name>.npy, float32 or float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.dump = {} if args.dump_outputs else None        # host copies of the timed legs' outputs (variants do not add to it)
 
     # `python bench.py --gpus N` (no torchrun): this process becomes the launcher — before anything here touches the GPU runtime
     if args.dry_launch or (args.gpus > 1 and "WORLD_SIZE" not in os.environ):
@@ -674,6 +733,7 @@ def main():
         a rank that swallowed one would leave its peers waiting in a collective"""
         a = _copy.copy(args)
         a.no_cpu_baseline = True
+        a.dump = None
         for k, v in over.items():
             setattr(a, k, v)
         if world > 1:
@@ -774,6 +834,8 @@ def main():
         result["rccl_ranks"] = rccl_ranks
         if backend != "nccl":
             result["collective_backend"] = backend + " (host-staged: test mode, no links)"
+        if args.dump is not None:
+            write_outputs(args.dump, args.dump_outputs)
         os.write(record_fd, (json.dumps(_json_safe(result)) + "\n").encode())
     os.close(record_fd)
     if world > 1:

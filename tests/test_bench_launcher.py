@@ -121,3 +121,37 @@ def test_record_line_is_strict_json():
     rec = bench._json_safe({"value": 1.0, "config": {"final_loss": float("nan"), "xs": [float("inf"), 2.0, (3.0, float("-inf"))]}})
     text = json.dumps(rec, allow_nan=False)
     assert json.loads(text) == {"value": 1.0, "config": {"final_loss": None, "xs": [None, 2.0, [3.0, None]]}}
+
+
+def test_dump_outputs_host_copies(tmp_path):
+    """--dump-outputs: the loss, the tensors of the step's result dict (nested ones too; entries computed on first access are neither computed
+    nor written) and the parameters, as float32 (float64 for float64 / integer tensors); an array above DUMP_SAMPLE elements is sampled at
+    positions that are the same in every run; the total is held to 64 MB"""
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    from customnerf_amd.nerf.renderer import _Lazy, _LazyResults
+    calls = []
+    model = torch.nn.Linear(3, 2).half()
+    big = torch.arange(bench.DUMP_SAMPLE + 5, dtype=torch.float32)
+    res = _LazyResults({"image": torch.ones(4, 3, dtype=torch.float16), "_out_ray": big, "num_points": 7, "note": "x",
+                        "weights": _Lazy(lambda: calls.append(1)), "fg": _LazyResults({"depth": torch.zeros(4, dtype=torch.float64)}),
+                        "rays": torch.tensor([[0, 5]], dtype=torch.int32)})
+    dump = {}
+    bench.collect_outputs("recon", torch.tensor(0.25), res, model, dump)
+    assert not calls
+    assert sorted(dump) == ["recon_loss", "recon_out_fg_depth", "recon_out_image", "recon_out_num_points", "recon_out_out_ray", "recon_out_rays",
+                            "recon_param_bias", "recon_param_weight"]
+    assert dump["recon_out_image"].dtype == np.float32 and dump["recon_out_fg_depth"].dtype == np.float64 and dump["recon_out_rays"].dtype == np.float64
+    assert dump["recon_param_weight"].dtype == np.float32 and dump["recon_param_weight"].shape == (2, 3) and float(dump["recon_loss"]) == 0.25
+    s = dump["recon_out_out_ray"]
+    assert s.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(s) > 0)             # sorted distinct positions of the flat array
+    again = {}
+    bench.collect_outputs("recon", torch.tensor(0.25), res, model, again)
+    assert np.array_equal(again["recon_out_out_ray"], s)
+    bench.write_outputs(dump, str(tmp_path / "out"))
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(k + ".npy" for k in dump)
+    assert np.array_equal(np.load(tmp_path / "out" / "recon_out_rays.npy"), [[0.0, 5.0]])
+    with pytest.raises(SystemExit):
+        bench.write_outputs({"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)}, str(tmp_path / "big"))

@@ -1,108 +1,107 @@
-"""Reference-on-shims conformance (CPU, build container only): the reference's OWN nerf/{encoding,network_grid,renderer}.py,
-unmodified, imported with customnerf_amd/dropin first on sys.path, so that its `import raymarching`, `from gridencoder import GridEncoder`
-and `import tinycudann as tcnn` resolve to this package:
+"""Reference-on-shims conformance (CPU): what the reference's OWN nerf/{encoding,network_grid,renderer}.py ask of the
+native surfaces, recorded in tests/golden/reference_shims.json (tests/golden/make_shims_golden.py: the reference's modules imported
+unmodified with customnerf_amd/dropin first on sys.path), replayed against the shims — `import raymarching`, `from gridencoder import
+GridEncoder` and `import tinycudann as tcnn` resolve to this package, and:
 
-  * `NeRFNetwork(opt)` (network_grid.py:70-139) constructs, for cuda_ray on and off and for every rgb-head variant;
-  * its state-dict keys / shapes equal the product class's for the same geometry (checkpoints interchange);
+  * every GridEncoder / tcnn.Network constructor call that `NeRFNetwork(opt)` (network_grid.py:70-139) made, for cuda_ray on and off and for
+    every rgb-head variant, binds and constructs on the shims;
+  * the reference model's state-dict keys / shapes / dtypes equal the product class's for the same geometry (checkpoints interchange);
   * every `raymarching.*` / `GridEncoder(...)` / `tcnn.Network(...)` call site in those three files (AST walk; renderer.py:297, 612-688,
-    1680, 1709 among them) binds against the shim's signature — positional count and keyword names.
+    1680, 1709 among them) binds against the shim's signature — positional count and keyword names;
+  * the encoders the reference builds through its get_encoder (encoding.py:52-71) come out of the shim with the reference's geometry.
 
-Skipped where /root/reference does not exist (the GPU box).  Nothing of the reference is stored: it is imported from where it lies."""
+The record holds data only (arguments, names, shapes); no reference source is stored or read."""
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("CUSTOMNERF_REFERENCE", "/root/reference")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "nerf")), reason="reference tree not present (build container only)")
+RECORD = os.path.join(ROOT, "tests", "golden", "reference_shims.json")
 
 WORKER = r'''
-import ast, inspect, os, sys, types, warnings
+import inspect, json, os, sys, warnings
 warnings.filterwarnings("ignore")
-ROOT, REF = %r, %r
+ROOT, RECORD = %r, %r
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "customnerf_amd", "dropin"))       # shadows the reference's raymarching / gridencoder / tinycudann
-for name in ("trimesh", "plyfile", "skimage", "skimage.measure"):          # third-party modules the image lacks; none is on the path under test
-    sys.modules[name] = types.ModuleType(name)
-sys.modules["skimage"].measure = sys.modules["skimage.measure"]
-class _TT:
-    def __class_getitem__(cls, item): return cls
-sys.modules["torchtyping"] = types.ModuleType("torchtyping"); sys.modules["torchtyping"].TensorType = _TT
-sys.path.append(REF)                                                        # AFTER the shims: only `nerf.*` comes from the reference
+sys.path.insert(0, os.path.join(ROOT, "customnerf_amd", "dropin"))       # the names the reference imports: raymarching / gridencoder / tinycudann
 import torch
 import raymarching, gridencoder, tinycudann as tcnn
 assert raymarching.__file__.startswith(ROOT) and gridencoder.__file__.startswith(ROOT) and tcnn.__file__.startswith(ROOT)
-import nerf.network_grid as ref_ng, nerf.encoding as ref_enc, nerf.renderer as ref_rd
-assert ref_ng.__file__.startswith(REF) and ref_rd.__file__.startswith(REF)
 from customnerf_amd import scene as sc
 from customnerf_amd.nerf.network_grid import NeRFNetwork as Ours
+rec = json.load(open(RECORD))
+surfaces = {"GridEncoder": gridencoder.GridEncoder, "tcnn.Network": tcnn.Network}
 
 # ---- 1. constructor + state dict, every head variant the reference's __init__ branches on (network_grid.py:112-139)
-variants = [dict(), dict(cuda_ray=True), dict(train_conf=0), dict(detach_mask_from_field=True), dict(mask_no_dir=True), dict(keyword2="x", detach_mask_from_field=True)]
-for kw in variants:
+assert len(rec["variants"]) == 6
+built = set()
+for v in rec["variants"]:
+    kw = v["kw"]
+    assert v["pos_en_dim"] == 32 and v["embeddings_shape"] == [23967296, 2]                        # SURVEY §8: the bear table
+    for label, args, kwargs in v["constructor_calls"]:
+        cls = surfaces[label]
+        sig = inspect.signature(cls.__init__)
+        try:
+            sig.bind(None, *args, **kwargs)
+        except TypeError as e:
+            raise AssertionError(f"{kw}: {label}{tuple(args)} {kwargs} does not bind against {sig}: {e}")
+        key = json.dumps([label, args, kwargs], sort_keys=True)
+        if key not in built:
+            m = cls(*args, **kwargs)
+            built.add(key)
+            if label == "GridEncoder":
+                assert list(m.embeddings.shape) == v["embeddings_shape"] and m.output_dim == v["pos_en_dim"], kw
+            del m
+    assert sum(c[0] == "GridEncoder" for c in v["constructor_calls"]) == 1, kw
     opt = sc.make_opt(grid_type="tiledgrid", log2_hashmap_size=21, desired_resolution=8192, **kw)
-    devnull = open(os.devnull, "w"); old = sys.stdout; sys.stdout = devnull       # the reference prints from its constructor
-    try:
-        theirs = ref_ng.NeRFNetwork(opt)
-    finally:
-        sys.stdout = old
-    assert type(theirs.pos_en).__module__.startswith("customnerf_amd.gridencoder") and type(theirs.network).__module__.startswith("customnerf_amd.tcnn")
     ours = Ours(opt)
-    a = {k: tuple(v.shape) for k, v in theirs.state_dict().items()}
-    b = {k: tuple(v.shape) for k, v in ours.state_dict().items()}
+    a = {k: (tuple(s), d) for k, (s, d) in v["state"].items()}
+    b = {k: (tuple(t.shape), str(t.dtype)) for k, t in ours.state_dict().items()}
     assert a == b, (kw, sorted(set(a.items()) ^ set(b.items())))
-    assert {k: v.dtype for k, v in theirs.state_dict().items()} == {k: v.dtype for k, v in ours.state_dict().items()}, kw
-    assert theirs.pos_en_dim == 32 and theirs.pos_en.embeddings.shape == (23967296, 2)             # SURVEY §8: the bear table
-    pa, pb = theirs.get_params(5e-4), ours.get_params(5e-4)                                        # optimiser groups: grid lr x10 (network_grid.py:196-206)
-    assert [(len(list(g["params"])), g["lr"]) for g in pa] == [(len(list(g["params"])), g["lr"]) for g in pb], kw
-    del theirs, ours
+    assert ours.pos_en_dim == v["pos_en_dim"] and list(ours.pos_en.embeddings.shape) == v["embeddings_shape"], kw
+    pb = [[len(list(g["params"])), g["lr"]] for g in ours.get_params(5e-4)]                        # optimiser groups: grid lr x10 (network_grid.py:196-206)
+    assert pb == v["param_groups"], (kw, pb, v["param_groups"])
+    del ours
 print("constructors ok")
 
 # ---- 2. every call site of the three native surfaces binds against the shim
 targets = {"raymarching": raymarching, "tcnn": tcnn}
 n_sites = {}
-for path in (ref_rd.__file__, ref_ng.__file__, ref_enc.__file__):
-    tree = ast.parse(open(path).read())
-    for node in ast.walk(tree):
-        if not isinstance(node, ast.Call):
-            continue
-        f = node.func
-        fn = None
-        if isinstance(f, ast.Attribute) and isinstance(f.value, ast.Name) and f.value.id in targets:
-            assert hasattr(targets[f.value.id], f.attr), f"{path}:{node.lineno}: {f.value.id}.{f.attr} missing from the shim"
-            fn, label = getattr(targets[f.value.id], f.attr), f"{f.value.id}.{f.attr}"
-        elif isinstance(f, ast.Name) and f.id == "GridEncoder":
-            fn, label = gridencoder.GridEncoder, "GridEncoder"
-        if fn is None:
-            continue
-        if any(isinstance(a, ast.Starred) for a in node.args) or any(k.arg is None for k in node.keywords):
-            continue
-        sig = inspect.signature(fn.__init__) if inspect.isclass(fn) else inspect.signature(fn)
-        args = ([None] if inspect.isclass(fn) else []) + [None] * len(node.args)
-        try:
-            sig.bind(*args, **{k.arg: None for k in node.keywords})
-        except TypeError as e:
-            raise AssertionError(f"{path}:{node.lineno}: {label} call does not bind against {sig}: {e}")
-        n_sites[label] = n_sites.get(label, 0) + 1
+for site in rec["call_sites"]:
+    label = site["callee"]
+    if label == "GridEncoder":
+        fn = gridencoder.GridEncoder
+    else:
+        mod, attr = label.split(".")
+        assert hasattr(targets[mod], attr), f"{site['where']}: {label} missing from the shim"
+        fn = getattr(targets[mod], attr)
+    if site["starred"]:
+        continue
+    sig = inspect.signature(fn.__init__) if inspect.isclass(fn) else inspect.signature(fn)
+    args = ([None] if inspect.isclass(fn) else []) + [None] * site["n_positional"]
+    try:
+        sig.bind(*args, **{k: None for k in site["keywords"]})
+    except TypeError as e:
+        raise AssertionError(f"{site['where']}: {label} call does not bind against {sig}: {e}")
+    n_sites[label] = n_sites.get(label, 0) + 1
 for need in ("raymarching.near_far_from_aabb", "raymarching.march_rays_train", "raymarching.composite_rays_train", "raymarching.march_rays",
              "raymarching.composite_rays", "raymarching.morton3D", "raymarching.packbits", "tcnn.Network", "GridEncoder"):
     assert n_sites.get(need, 0) >= 1, (need, n_sites)
 print("call sites ok", sorted(n_sites.items()))
 
 # ---- 3. the encoder the reference builds through ITS get_encoder is the product's, with the reference's geometry (encoding.py:52-71)
-for enc_name, gt in (("hashgrid", "hash"), ("tiledgrid", "tiled")):
-    e, dim = ref_enc.get_encoder(enc_name, input_dim=3, log2_hashmap_size=19, desired_resolution=2048)
-    assert dim == 32 and e.gridtype == gt and e.embeddings.shape[0] == int(e.offsets[-1]) and e.n_params == e.embeddings.numel()
+assert [(e["encoding"], e["gridtype"]) for e in rec["encoders"]] == [("hashgrid", "hash"), ("tiledgrid", "tiled")]
+for enc in rec["encoders"]:
+    e = gridencoder.GridEncoder(*enc["args"], **enc["kwargs"])
+    dim = e.output_dim
+    assert dim == enc["dim"] == 32 and e.gridtype == enc["gridtype"] and e.embeddings.shape[0] == int(e.offsets[-1]) and e.n_params == e.embeddings.numel()
 print("encoders ok")
 '''
 
 
 def test_reference_modules_run_on_the_shims(tmp_path):
     script = tmp_path / "conformance.py"
-    script.write_text(WORKER % (ROOT, REF))
+    script.write_text(WORKER % (ROOT, RECORD))
     out = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-3000:], out.stderr[-3000:])
     assert "constructors ok" in out.stdout and "call sites ok" in out.stdout and "encoders ok" in out.stdout
