@@ -539,10 +539,6 @@ int bn_backward(const void *grad, const float *inputs, const GridLevels &lv, flo
                 uint32_t interp, int dtype, void *workspace, hipStream_t st, bool prepared);
 int bn_prepare(const float *inputs, const GridLevels &lv, uint32_t B, uint32_t nl, uint32_t gridtype, int ac, uint32_t interp, int dtype,
                void *workspace, hipStream_t st);
-int bn_prepare_rows(const float *inputs, const GridLevels &lv, uint32_t B, uint32_t nl, uint32_t gridtype, int ac, uint32_t interp, int dtype,
-                    void *workspace, hipStream_t st, uint32_t row0, uint32_t rows);
-int bn_prepare_finish(const GridLevels &lv, uint32_t B, uint32_t nl, int dtype, void *workspace, hipStream_t st);
-uint32_t bn_hist_block_points(int dtype);
 bool bn_needs_plan(uint32_t B, uint32_t nl, const GridLevels &lv, int dtype, uint32_t gridtype);
 void bn_grid_adam_arm(const CnerfGridAdam *cfg);
 int bn_grid_adam_consumed();
@@ -641,10 +637,10 @@ int cnerf_grid_encode_backward(const void *grad, const float *inputs, const int3
     return CNERF_EINVAL;
 }
 
-// The coordinate-only half of the binned backward (histogram + scans), issued ahead of time — typically on a second stream right after
-// the samples exist, so that it overlaps the forward and the field backward.  Returns CNERF_OK with *prepared = 1 when the binned path
-// applies and the plan now sits in `workspace`; *prepared = 0 (nothing launched) when cnerf_grid_encode_backward would take the atomic
-// kernel for this shape.  The matching cnerf_grid_encode_backward_prepared must get the same inputs / shape / workspace.
+// The coordinate-only half of the first form of the binned backward (histogram + scans), issued ahead of time — typically on a second stream
+// right after the samples exist, so that it overlaps the forward and the field backward.  Returns CNERF_OK with *prepared = 1 when the shape
+// takes the first form and the plan now sits in `workspace`; *prepared = 0 (nothing launched) when cnerf_grid_encode_backward would take the
+// atomic kernel or the third form.  The matching cnerf_grid_encode_backward_prepared must get the same inputs / shape / workspace.
 int cnerf_grid_encode_backward_prepare(const float *inputs, const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                                        uint32_t max_level, float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
                                        void *workspace, uint64_t workspace_bytes, int *prepared, void *stream) {
@@ -667,16 +663,6 @@ int cnerf_grid_encode_backward_prepare(const float *inputs, const int32_t *offse
     return rc;
 }
 
-// cnerf_grid_encode_backward_prepare in pieces: the histogram of rows [row0, row0 + rows) of the B-sample list can be taken as soon as THOSE
-// coordinates exist (row0 a multiple of *block_points of cnerf_grid_encode_backward_prepare_block; the range ends on a block border or at B), each
-// piece on whatever stream suits the caller; ..._finish runs the scans once every row has been counted and leaves the plan that
-// cnerf_grid_encode_backward_prepared consumes.  *prepared = 0 (nothing launched): the shape takes the atomic kernel, or the records are float32.
-int cnerf_grid_encode_backward_prepare_block(int dtype, uint32_t *block_points) {
-    if (!block_points) return CNERF_ENULL;
-    *block_points = bn_hist_block_points(dtype);
-    return CNERF_OK;
-}
-
 int cnerf_grid_encode_backward_needs_plan(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level, float S,
                                           uint32_t H, uint32_t gridtype, int dtype, int *needs_plan) {
     if (!needs_plan) return CNERF_ENULL;
@@ -688,48 +674,6 @@ int cnerf_grid_encode_backward_needs_plan(const int32_t *offsets_host, uint32_t 
     if (dtype != CNERF_F32 && dtype != CNERF_F16) return CNERF_EINVAL;
     if (B && nl && (uint64_t)B * nl >= BN_MIN_UPDATES && bn_eligible(B, D, C, nl, lv) && bn_needs_plan(B, nl, lv, dtype, gridtype)) *needs_plan = 1;
     return CNERF_OK;
-}
-
-static int ge_prepare_common(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
-                             uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes, GridLevels &lv, bool &go) {
-    go = false;
-    if (gridtype > 1 || interp > 1) return CNERF_EINVAL;
-    int rc = ge_levels(offsets_host, L, L, S, H, lv);
-    if (rc) return rc;
-    if (dtype != CNERF_F32 && dtype != CNERF_F16) return CNERF_EINVAL;
-    go = dtype == CNERF_F16 && B && workspace && (uint64_t)B * L >= BN_MIN_UPDATES && bn_eligible(B, D, C, L, lv) &&
-         workspace_bytes >= bn_workspace_bytes(B, L, lv, dtype) && !(((uintptr_t)workspace) & 255) && bn_hist_block_points(dtype) != 0 &&
-         bn_needs_plan(B, L, lv, dtype, gridtype);
-    return CNERF_OK;
-}
-
-int cnerf_grid_encode_backward_prepare_rows(const float *inputs, const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
-                                            uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype, uint32_t row0, uint32_t rows,
-                                            void *workspace, uint64_t workspace_bytes, int *prepared, void *stream) {
-    if (!prepared) return CNERF_ENULL;
-    *prepared = 0;
-    GridLevels lv;
-    bool go;
-    int rc = ge_prepare_common(offsets_host, B, D, C, L, S, H, gridtype, interp, dtype, workspace, workspace_bytes, lv, go);
-    if (rc || !go) return rc;
-    if (!inputs) return CNERF_ENULL;
-    rc = bn_prepare_rows(inputs, lv, B, L, gridtype, align_corners, interp, dtype, workspace, CN_STREAM(stream), row0, rows);
-    if (rc == 0) *prepared = 1;
-    return rc;
-}
-
-int cnerf_grid_encode_backward_prepare_finish(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                                              uint32_t gridtype, uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes, int *prepared,
-                                              void *stream) {
-    if (!prepared) return CNERF_ENULL;
-    *prepared = 0;
-    GridLevels lv;
-    bool go;
-    int rc = ge_prepare_common(offsets_host, B, D, C, L, S, H, gridtype, interp, dtype, workspace, workspace_bytes, lv, go);
-    if (rc || !go) return rc;
-    rc = bn_prepare_finish(lv, B, L, dtype, workspace, CN_STREAM(stream));
-    if (rc == 0) *prepared = 1;
-    return rc;
 }
 
 int cnerf_grid_encode_backward_prepared(const void *grad, const float *inputs, const int32_t *offsets_host, float *grad_embeddings, uint32_t B,

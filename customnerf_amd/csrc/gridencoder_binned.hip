@@ -22,10 +22,12 @@
 // scatter itself (2048 B/sample fp32), all of it coalesced or L2-merged.
 // D = 3, C = 2 only (the configuration CustomNeRF uses); other shapes take the atomic kernel in gridencoder.hip.
 //
-// Forms in this file (round 6): the FIRST form described above (k_bin_*: histogram + scans + one record per corner) serves float32 records and the
-// fp16 shapes the third form does not take (more than 512 bins per level, hashed levels of odd size or fewer than 32 entries); the THIRD form (k_bin3_*: no histogram,
-// 8-byte pair records, block-local counting, fixed-capacity bin regions with spill) serves everything CustomNeRF runs — the benchmark table and the
-// reference field's own 2^21-entry table.  The second form (histogram-driven pair records, rounds 2-4) is gone; its record format lives on.
+// Two forms live in this file.  The FIRST form described above (k_bin_*: histogram + scans + one 8/12-byte record per corner) serves float32
+// records and the fp16 tables the third form does not take (hashed levels whose size is not a power of two or is below 32 entries); its
+// coordinate-only half (histogram + scans) can be issued ahead of time, on a side stream (cnerf_grid_encode_backward_prepare).  The THIRD form
+// (k_bin3_*: no histogram, block-local counting, fixed-capacity bin regions with spill, interleaved bins on the hashed levels) serves every fp16
+// table CustomNeRF runs — the benchmark table and the reference field's own 2^21-entry table.  Its records are 8-byte fp16 PAIR records (one per
+// x-pair of corners, see "fp16 pair records" below).  The form numbering follows docs/HISTORY.md.
 #include "grid_common.h"
 #include <vector>
 #include <algorithm>
@@ -36,7 +38,7 @@
 #define BN_THREADS 256
 #define BN_PPT 4                                   // points per thread in the hist / emit sweeps
 #define BN_PTS (BN_THREADS * BN_PPT)               // points per block
-#define BN_MAX_CHUNKS 512                          // 2^21-entry level / 4096 (the reference's bear table); the staged emit serves <= B2S_MAX_CHUNKS
+#define BN_MAX_CHUNKS 512                          // 2^21-entry level / 4096 (the reference's bear table); larger levels take the atomic kernel
 #define BN_SEG (1u << 18)                          // records per accumulate workgroup (split unit for oversized bins)
 
 struct BinPlan {
@@ -249,7 +251,7 @@ __global__ void __launch_bounds__(BN_THREADS) k_bin_emit(const T *__restrict__ g
         using Vec = FeatVec<T, 2>;
         const Vec g = reinterpret_cast<const Vec *>(grad)[(size_t)level * B + b];
         const float g0 = ge_to_float(g.v[0]), g1 = ge_to_float(g.v[1]);
-        if constexpr (sizeof(T) == 2) {                      // fixed-point sums: see b2_poison below
+        if constexpr (sizeof(T) == 2) {                      // fixed-point sums: see b3_poison below
             if (!(fabsf(g0) <= 65504.0f) || !(fabsf(g1) <= 65504.0f)) {
                 grad_grid[((size_t)lv.offset[level] + index[0]) * 2] = __builtin_nanf("");
                 if (found_inf) *found_inf = 1.0f;
@@ -371,8 +373,7 @@ __global__ void __launch_bounds__(1024) k_bin_accum(const BinRec<T> *__restrict_
 }
 
 
-// ================================================================================================ fp16 pair records (rounds 2-4: the "second form"; its
-// histogram-driven emit / accumulate kernels were removed in round 6 — what follows is the record format and the helpers the third form keeps)
+// ================================================================================================ fp16 pair records (the third form's records)
 // What the first form above pays for (rocprofv3, 2.1 M samples x 16 levels): 2.1 GB of records written by 16-byte stores that land in
 // up to 128 bins per wave instruction, then read back — emit 1.0 ms + accumulate 0.55 ms, one after the other.  Measured on the side
 // (scratch/mall_bench.hip, scratch/lds_atomic_bench.hip): (i) the LDS integer atomics are NOT the accumulate's limit (>= 1.6 T
@@ -388,18 +389,11 @@ __global__ void __launch_bounds__(1024) k_bin_accum(const BinRec<T> *__restrict_
 // Sums stay 64-bit fixed point with 24 fractional bits (order-independent, so bit-deterministic wherever one workgroup owns a chunk);
 // the per-corner products are rounded to that grid instead of to binary16 (the reference rounds w*g to half, gridencoder.cu:328: the
 // difference is below one half ulp of each product).
-#define B2_SEG_MIN ((1u << 16) + (1u << 13))       // records per accumulate workgroup, see b2_seg()
-#define B2_SINGLE 15u
-
-struct Bin2Plan {
-    uint32_t bin_first[GE_MAX_LEVELS + 1];         // first bin of each SLOT; slot i serves level lv.order[i] (coarse / fine interleaved)
-    uint32_t nb;                                   // point blocks per level
-    uint32_t total_bins;
-};
+#define B3_SINGLE 15u                              // pair shift t of a single record (one corner)
 
 
 // the four (y, z) corner pairs of a sample on one level: entries of the x and x+1 corner, the weight of the pair, the x fraction
-__device__ __forceinline__ void b2_pairs(const float (&in)[3], const GridLevels &lv, uint32_t level, uint32_t gridtype, bool align_corners,
+__device__ __forceinline__ void b3_pairs(const float (&in)[3], const GridLevels &lv, uint32_t level, uint32_t gridtype, bool align_corners,
                                          uint32_t interp, uint32_t (&i0)[4], uint32_t (&i1)[4], float (&wyz)[4], float &fx) {
     const uint32_t hashmap_size = lv.size[level];
     const float scale = lv.scale[level];
@@ -453,14 +447,14 @@ __device__ __forceinline__ void b2_pairs(const float (&in)[3], const GridLevels 
 }
 
 // can the pair travel as one record?  (same chunk, and the two entries differ by a run of low ones)
-__device__ __forceinline__ bool b2_paired(uint32_t i0, uint32_t i1) {
+__device__ __forceinline__ bool b3_paired_d(uint32_t i0, uint32_t i1) {
     const uint32_t m = i0 ^ i1;
     return m != 0 && (m >> BN_CHUNK_LOG2) == 0 && (m & (m + 1)) == 0;
 }
 
 // LDS counter ticket, wave-aggregated when every active lane wants the same counter — the rule on the dense levels, where a wave's samples
 // (neighbours on one ray) fall into one chunk and 64 same-address atomics would serialise; hashed levels take the per-lane atomic.
-__device__ __forceinline__ uint32_t b2_ticket(uint32_t *counters, uint32_t c) {
+__device__ __forceinline__ uint32_t b3_ticket(uint32_t *counters, uint32_t c) {
     const uint64_t act = __ballot(1);
     const uint32_t c_lead = __builtin_amdgcn_readfirstlane(c);
     if (__ballot(c == c_lead) == act) {
@@ -475,7 +469,7 @@ __device__ __forceinline__ uint32_t b2_ticket(uint32_t *counters, uint32_t c) {
 // The fixed-point sums cannot carry an infinity or a NaN (llrint of one is an arbitrary finite pattern), but the loss scaler finds overflow by
 // looking for exactly those in the gradients (the reference's half2 atomics propagate them: gridencoder.cu:324-337).  A non-finite incoming
 // gradient therefore poisons one of its destination entries directly; the accumulate's read-modify-write keeps it non-finite.
-__device__ __forceinline__ void b2_poison(float g0, float g1, float *__restrict__ grad_grid, const GridLevels &lv, uint32_t level, uint32_t entry,
+__device__ __forceinline__ void b3_poison(float g0, float g1, float *__restrict__ grad_grid, const GridLevels &lv, uint32_t level, uint32_t entry,
                                           float *__restrict__ found_inf) {
     if (!(fabsf(g0) <= 65504.0f) || !(fabsf(g1) <= 65504.0f)) {
         grad_grid[((size_t)lv.offset[level] + entry) * 2] = __builtin_nanf("");
@@ -483,45 +477,39 @@ __device__ __forceinline__ void b2_poison(float g0, float g1, float *__restrict_
     }
 }
 
-// (The second form's emit kernels — direct and LDS-staged, both driven by a histogram pre-pass — were removed in round 6: the histogram-free
-// third form below serves every table they served, up to 512 bins per level.)
-#define B2S_MAX_CHUNKS 128                        // bins per level of a NARROW level of the third form (one-byte bin ids in its staging area)
 // llrint(a) as a two's-complement 64-bit pattern, a = (value * 2^24) already in float32, |a| < 2^41.  The library's float -> int64
 // conversion is a dozen vector instructions (no such conversion in hardware) and there are four of them per record: they were most of this
 // kernel's instruction stream, and the kernel is issue-bound.  In double precision the classic "add 1.5 * 2^52" trick does it in one add:
 // the sum's mantissa holds the integer, rounded to nearest-even by the add itself; the low word of the constant's bit pattern is zero, so
 // only the high word needs the constant subtracted.  The 2^24 scale rides on the weight (a power of two commutes with the float32
 // rounding of the product), so the values are those of __float2ll_rn((w * f) * 16777216.0f), bit for bit.
-__device__ __forceinline__ unsigned long long b2_fix(float a) {
+__device__ __forceinline__ unsigned long long b3_fix(float a) {
     const double y = (double)a + 6755399441055744.0;                                // 1.5 * 2^52
     return __builtin_bit_cast(unsigned long long, y) - 0x4338000000000000ull;
 }
 // the LDS image keeps the two channels in separate halves (acc[e], acc[BN_CHUNK + e]): random 8-byte atomics at a 16-byte stride reach
 // only half of the bank pairs (scratch/lds_atomic_peak.hip: 2.6 T ds_add_u64/s interleaved, 3.8 T/s split)
-__device__ __forceinline__ void b2_add(long long *acc, uint32_t e, float a, float b) {
+__device__ __forceinline__ void b3_add(long long *acc, uint32_t e, float a, float b) {
     // |value| <= 65504: value * 2^24 < 2^41, rounded to the fixed-point grid
-    atomicAdd(reinterpret_cast<unsigned long long *>(&acc[e]), b2_fix(a));
-    atomicAdd(reinterpret_cast<unsigned long long *>(&acc[BN_CHUNK + e]), b2_fix(b));
+    atomicAdd(reinterpret_cast<unsigned long long *>(&acc[e]), b3_fix(a));
+    atomicAdd(reinterpret_cast<unsigned long long *>(&acc[BN_CHUNK + e]), b3_fix(b));
 }
 
-__device__ __forceinline__ void b2_add_record(long long *acc, const uint2 r) {
+__device__ __forceinline__ void b3_add_record(long long *acc, const uint2 r) {
     union { uint32_t u; __half2 h; } v;
     v.u = r.y;
     const float2 f = __half22float2(v.h);
     const uint32_t e = r.x & (BN_CHUNK - 1), t = (r.x >> 12) & 15u;
-    if (t == B2_SINGLE) {
-        b2_add(acc, e, f.x * 16777216.0f, f.y * 16777216.0f);
+    if (t == B3_SINGLE) {
+        b3_add(acc, e, f.x * 16777216.0f, f.y * 16777216.0f);
     } else {
         const float w1 = (float)(r.x >> 16) * (1.0f / 65536.0f), w0 = 1.0f - w1;
         const float w1s = w1 * 16777216.0f, w0s = w0 * 16777216.0f;
-        b2_add(acc, e, w0s * f.x, w0s * f.y);
-        b2_add(acc, e ^ ((2u << t) - 1u), w1s * f.x, w1s * f.y);
+        b3_add(acc, e, w0s * f.x, w0s * f.y);
+        b3_add(acc, e ^ ((2u << t) - 1u), w1s * f.x, w1s * f.y);
     }
 }
 
-#ifndef B2_COMBINE
-#define B2_COMBINE 1
-#endif
 #ifndef B3_WALK
 #define B3_WALK 8                                  // consecutive records of a run per thread in the run walk (combined in registers when they share entries);
                                                   // measured: 4 -> 372 / 195 us (random init / fitted field), 8 -> 368 / 180, 16 -> 461 / 223 (over the 64-VGPR budget of two
@@ -533,7 +521,7 @@ __device__ __forceinline__ void b3_flush_pending(long long *acc, const B3Pending
     const uint32_t e = c.key & (BN_CHUNK - 1), t = (c.key >> 12) & 15u;
     atomicAdd(reinterpret_cast<unsigned long long *>(&acc[e]), c.a0);
     atomicAdd(reinterpret_cast<unsigned long long *>(&acc[BN_CHUNK + e]), c.b0);
-    if (t != B2_SINGLE) {
+    if (t != B3_SINGLE) {
         const uint32_t e1 = e ^ ((2u << t) - 1u);
         atomicAdd(reinterpret_cast<unsigned long long *>(&acc[e1]), c.a1);
         atomicAdd(reinterpret_cast<unsigned long long *>(&acc[BN_CHUNK + e1]), c.b1);
@@ -545,13 +533,13 @@ __device__ __forceinline__ void b3_push_record(long long *acc, B3Pending &c, con
     const float2 f = __half22float2(v.h);
     const uint32_t key = r.x & 0xFFFFu, t = (r.x >> 12) & 15u;
     unsigned long long a0, b0, a1 = 0, b1 = 0;
-    if (t == B2_SINGLE) {
-        a0 = b2_fix(f.x * 16777216.0f); b0 = b2_fix(f.y * 16777216.0f);
-    } else {                                                                        // (the arithmetic of b2_add_record, value for value)
+    if (t == B3_SINGLE) {
+        a0 = b3_fix(f.x * 16777216.0f); b0 = b3_fix(f.y * 16777216.0f);
+    } else {                                                                        // (the arithmetic of b3_add_record, value for value)
         const float w1 = (float)(r.x >> 16) * (1.0f / 65536.0f), w0 = 1.0f - w1;
         const float w1s = w1 * 16777216.0f, w0s = w0 * 16777216.0f;
-        a0 = b2_fix(w0s * f.x); b0 = b2_fix(w0s * f.y);
-        a1 = b2_fix(w1s * f.x); b1 = b2_fix(w1s * f.y);
+        a0 = b3_fix(w0s * f.x); b0 = b3_fix(w0s * f.y);
+        a1 = b3_fix(w1s * f.x); b1 = b3_fix(w1s * f.y);
     }
     if (key == c.key) {
         c.a0 += a0; c.b0 += b0; c.a1 += a1; c.b1 += b1;
@@ -562,9 +550,9 @@ __device__ __forceinline__ void b3_push_record(long long *acc, B3Pending &c, con
 }
 
 // ================================================================================================ fp16 records, third form (round 5)
-// The second form needs the EXACT record count of every (point block, bin) pair before the first record is written: a histogram pass over
+// A histogram-driven emit needs the EXACT record count of every (point block, bin) pair before the first record is written: a histogram pass over
 // all 16 levels (the corner arithmetic of the emit, a second time) plus two scans, issued on a side stream beside the forward.  Measured with
-// the plan frozen (scratch/stale_plan.py, profiles/r05_stale_plan_control.json): that "hidden" pre-pass costs the step 113 us — its 1.1 ms of
+// the plan frozen (profiles/r05_stale_plan_control.json, docs/HISTORY.md B.11): that "hidden" pre-pass cost the step 113 us — its 1.1 ms of
 // side-stream kernel time takes CUs from the gathers and the field backward.  It also fixes the record count before the gradients exist, so
 // samples whose gradient is exactly zero still travel as records.  Since the sums became exact fixed point the ORDER of a bin's records is
 // free, so nothing has to be counted ahead of time — the emit counts for itself:
@@ -583,7 +571,7 @@ __device__ __forceinline__ void b3_push_record(long long *acc, B3Pending &c, con
 //   k_bin3_accum      a segment of a hashed bin streams its range of the bin's region; a segment of a dense bin (and the first segment of an
 //                     overflowed hashed bin, for the spill) walks the runs of the point blocks through a tile list in LDS
 //   k_bin3_reduce_split
-// Same 8-byte pair records, same exact 64-bit fixed-point sums, same split-bin reduction: the gradient is bit-identical to the second form's.
+// The records are the 8-byte pair records above, summed as exact 64-bit fixed point: the gradient does not depend on the order they land in.
 #ifndef B3_PTS
 #define B3_PTS 2048
 #endif
@@ -594,6 +582,7 @@ __device__ __forceinline__ void b3_push_record(long long *acc, B3Pending &c, con
 // block; 8448 +- 31 with the 32-entry granules of round 5), a dense one 4; 8832 leaves room for both (what still does not fit spills), and two
 // blocks (2 x 79.1 KiB) share a CU
 #define B3_CAP (B3_PTS * 4 + 640)
+#define B3_NARROW_CHUNKS 128                       // bins per level of a narrow level (one-byte bin ids in the staging area)
 #define B3_WIDE_CHUNKS BN_MAX_CHUNKS               // bins per level of a wide level (T = 2^21: 512 chunks of 4096 entries)
 #ifndef B3_WALK_BLOCKS
 #define B3_WALK_BLOCKS 256                       // point blocks whose runs the run walk flattens at a time (a multiple of 64; round 6: 64 -> 256, see b3_walk_runs)
@@ -601,8 +590,15 @@ __device__ __forceinline__ void b3_push_record(long long *acc, B3Pending &c, con
 #define B3_MAXT (B3_WALK_BLOCKS + 8)             // LDS word pairs of the run walk: B3_WALK_BLOCKS + 1 prefix words + B3_WALK_BLOCKS run positions
 #define B3_REGION (B3_PTS * 8)                    // records a block may emit on one level (8 single records per sample): its region on a dense level
 
+// the bins of the level slots (slot i serves level lv.order[i]: coarse / fine interleaved)
+struct Bin3Slots {
+    uint32_t bin_first[GE_MAX_LEVELS + 1];         // first bin of each SLOT
+    uint32_t nb;                                   // point blocks per level
+    uint32_t total_bins;
+};
+
 struct Bin3Plan {
-    Bin2Plan p;
+    Bin3Slots p;
     uint32_t capb;                                 // record capacity of a hashed bin's region
     uint32_t dense_slot[GE_MAX_LEVELS];            // slot -> index among the dense slots (block-major regions), or 0xFFFFFFFF for a hashed level
     uint8_t hbits[GE_MAX_LEVELS];                  // hashed slot: log2(bins of the level)
@@ -659,15 +655,15 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
     // WIDE levels (round 6: more than 128 bins — T = 2^20 / 2^21 tables, the reference field's own): B3_WIDE_CHUNKS-entry counter tables in place of
     // the one-byte bin ids of the staged records (the copy-out then goes bin by bin instead of slot by slot), so that the workgroup's LDS
     // stays below half a CU's.  Block-uniform.
-    const bool wide = nch > B2S_MAX_CHUNKS;
-    const uint32_t NBN = wide ? B3_WIDE_CHUNKS : B2S_MAX_CHUNKS;
+    const bool wide = nch > B3_NARROW_CHUNKS;
+    const uint32_t NBN = wide ? B3_WIDE_CHUNKS : B3_NARROW_CHUNKS;
     uint32_t *cnt = reinterpret_cast<uint32_t *>(b3_lds + (size_t)B3_CAP * (wide ? 8 : 9));
     uint32_t *start = cnt + NBN;
     uint32_t *gdst = start + NBN;                                                   // hashed: first record of the block's run inside the bin's region
     uint32_t *s_total = gdst + NBN;
     auto bin_of = [&](uint32_t e) { return dense_lvl ? e >> BN_CHUNK_LOG2 : b3_bin_of(e, hb); };
     auto local_of = [&](uint32_t e) { return dense_lvl ? e & (BN_CHUNK - 1) : b3_local_of(e, hb); };
-    auto paired = [&](uint32_t a, uint32_t b) { return dense_lvl ? b2_paired(a, b) : b3_paired_h(a, b); };
+    auto paired = [&](uint32_t a, uint32_t b) { return dense_lvl ? b3_paired_d(a, b) : b3_paired_h(a, b); };
     if (threadIdx.x < NBN) cnt[threadIdx.x] = 0;
     __syncthreads();
     constexpr int PPT = B3_PTS / B3_THREADS;
@@ -699,15 +695,15 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
                 for (int q = 0; q < 4; q++) { i0[i][q] = (b * 4 + q) * 2654435761u % lv.size[level]; i1[i][q] = i0[i][q] ^ 1u; wyz[i][q] = 0.25f; }
                 fx[i] = in[0] - floorf(in[0]);
             } else {
-                b2_pairs(in, lv, level, gridtype, align_corners, interp, i0[i], i1[i], wyz[i], fx[i]);
+                b3_pairs(in, lv, level, gridtype, align_corners, interp, i0[i], i1[i], wyz[i], fx[i]);
             }
-            b2_poison(g0[i], g1[i], grad_grid, lv, level, i0[i][0], found_inf);
+            b3_poison(g0[i], g1[i], grad_grid, lv, level, i0[i][0], found_inf);
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 if (abl & 16) { tk[i][q] = 0; continue; }
                 const uint32_t c0 = bin_of(i0[i][q]);
                 if (paired(i0[i][q], i1[i][q])) {
-                    tk[i][q] = dense_lvl ? b2_ticket(cnt, c0) : atomicAdd(&cnt[c0], 1u);
+                    tk[i][q] = dense_lvl ? b3_ticket(cnt, c0) : atomicAdd(&cnt[c0], 1u);
                 } else {
                     const uint32_t t0 = atomicAdd(&cnt[c0], 1u);
                     const uint32_t t1 = atomicAdd(&cnt[bin_of(i1[i][q])], 1u);
@@ -820,9 +816,9 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
             } else {
                 const float w0 = (1 - fx[i]) * wyz[i][q], w1 = fx[i] * wyz[i][q];
                 v.h = __floats2half2_rn(w0 * g0[i], w0 * g1[i]);
-                put(c0, tk[i][q] & 0xFFFFu, local_of(a0) | (B2_SINGLE << 12), v.u);
+                put(c0, tk[i][q] & 0xFFFFu, local_of(a0) | (B3_SINGLE << 12), v.u);
                 v.h = __floats2half2_rn(w1 * g0[i], w1 * g1[i]);
-                put(bin_of(a1), tk[i][q] >> 16, local_of(a1) | (B2_SINGLE << 12), v.u);
+                put(bin_of(a1), tk[i][q] >> 16, local_of(a1) | (B3_SINGLE << 12), v.u);
             }
         }
     }
@@ -994,7 +990,7 @@ __device__ __forceinline__ void b3_adam_apply(const B3Adam &ad, const B3AdamCons
 
 // flush of a finished LDS image: sole owner -> read-modify-write of the gradient table; a split bin parks its fixed-point image.
 // hbits = 0xFF: dense level (the bin is a contiguous chunk); else a hashed level's interleaved bin.
-__device__ __forceinline__ void b3_flush(const long long *acc, const GridLevels &lv, const Bin2Plan &plan, uint32_t slot, uint32_t bin, uint32_t nseg, uint32_t gseg,
+__device__ __forceinline__ void b3_flush(const long long *acc, const GridLevels &lv, const Bin3Slots &plan, uint32_t slot, uint32_t bin, uint32_t nseg, uint32_t gseg,
                                          float *__restrict__ grad_grid, long long *__restrict__ partial, uint32_t hbits, const B3Adam &ad,
                                          const B3AdamConst &adc) {
     const uint32_t level = lv.order[slot];
@@ -1259,11 +1255,11 @@ __global__ void __launch_bounds__(1024, 8) k_bin3_accum(const uint2 *__restrict_
     const uint32_t *__restrict__ rt = runs + (size_t)bin * nb, *__restrict__ pt = pre + (size_t)bin * nb;
     const uint2 *__restrict__ lvl_slab = dslab + (size_t)slot * nb * B3_REGION;
     if (plan.dense_slot[slot] == 0xFFFFFFFFu) {
-        // ---- hashed level: the bin's records are one contiguous range of its region (the second form's stream: 16-byte loads, two records per lane)
+        // ---- hashed level: the bin's records are one contiguous range of its region (16-byte loads, two records per lane)
         const uint2 *__restrict__ slab = hslab + (size_t)bin * plan.capb;           // (capb is even: the region starts 16-byte aligned)
         uint32_t b2 = min(begin, treg), e2 = min(end, treg);                          // the segment's part of the region
-        if ((b2 & 1u) && b2 < e2) { if (threadIdx.x == 0) b2_add_record(acc, slab[b2]); b2++; }
-        if ((e2 & 1u) && b2 < e2) { e2--; if (threadIdx.x == 0) b2_add_record(acc, slab[e2]); }
+        if ((b2 & 1u) && b2 < e2) { if (threadIdx.x == 0) b3_add_record(acc, slab[b2]); b2++; }
+        if ((e2 & 1u) && b2 < e2) { e2--; if (threadIdx.x == 0) b3_add_record(acc, slab[e2]); }
         const uint4 *__restrict__ slab2 = reinterpret_cast<const uint4 *>(slab);
         const uint32_t pend = e2 >> 1;
         constexpr int UNR = 4;
@@ -1275,14 +1271,14 @@ __global__ void __launch_bounds__(1024, 8) k_bin3_accum(const uint2 *__restrict_
             for (int u = 0; u < UNR; u++) r[u] = slab2[crowded ? ib + threadIdx.x * UNR + u : ib + u * 1024 + threadIdx.x];
 #pragma unroll
             for (int u = 0; u < UNR; u++) {
-                b2_add_record(acc, make_uint2(r[u].x, r[u].y));
-                b2_add_record(acc, make_uint2(r[u].z, r[u].w));
+                b3_add_record(acc, make_uint2(r[u].x, r[u].y));
+                b3_add_record(acc, make_uint2(r[u].z, r[u].w));
             }
         }
         for (uint32_t i = ib + threadIdx.x; i < pend; i += 1024) {
             const uint4 r = slab2[i];
-            b2_add_record(acc, make_uint2(r.x, r.y));
-            b2_add_record(acc, make_uint2(r.z, r.w));
+            b3_add_record(acc, make_uint2(r.x, r.y));
+            b3_add_record(acc, make_uint2(r.z, r.w));
         }
         // some runs of this bin did not fit — its region is full (a sample distribution that crowds a few entries of a coarse hashed level) or a
         // block's staging area was: the bin's record index space continues behind the region with the spilled runs, where the point blocks left them
@@ -1330,51 +1326,30 @@ static uint64_t bn_layout(const BinPlan &plan, uint32_t B, uint32_t nl, int dtyp
     return off;
 }
 
-
-// ---- second form, host side
-static int b2_env(const char *name, int dflt) { return cn_tune_env(name, dflt); }
-static bool b2_enabled(int dtype) {
-    static int v1 = -1;
-    if (v1 < 0) v1 = b2_env("CNERF_BIN_V1", 0);
-    return dtype == CNERF_F16 && !v1;
-}
-
-// points per block and level in the hist / emit sweeps
+// ---- third form, host side
+#define B3_SEG_MIN ((1u << 16) + (1u << 13))       // least records per accumulate workgroup
 // Records per accumulate workgroup: 1/8 above the expected size of a hashed level's bin (4 pair records per sample over 128 bins), so
 // that those bins keep one owner each (plain read-modify-write flush) while the crowded bins of the small dense levels split into
 // workgroups of about the same length (uniform durations pack the last round of workgroups better: 0.40 -> 0.38 ms).
-static uint32_t b2_seg(uint32_t B, uint32_t max_chunks = 128) {
+static uint32_t b3_seg(uint32_t B, uint32_t max_chunks) {
     const uint64_t hashed_bin = (uint64_t)B * 4 / (max_chunks ? max_chunks : 1);
     const uint64_t s = hashed_bin + hashed_bin / 8;
     // small tables (few bins per level) would otherwise get a handful of million-record workgroups: cap, and let those bins split
     // ... and beyond 2^18 records a typical hashed bin is divided into EQUAL segments (round 6; the flat 2^17 cap gave every hashed bin of a 32768-ray
     // batch a second segment of a few thousand records — two 64 KiB partial images and a reduction per bin for nothing: 3.91 -> 3.80 ms per step;
     // one segment per bin at 65536 rays, on the other hand, costs the accumulate 13 %: profiles/r06_reduce_split_ab.txt)
-    static const uint64_t cap = (uint64_t)b2_env("CNERF_B3_SEG_CAP", 1 << 18);
-    if (s < B2_SEG_MIN) return B2_SEG_MIN;
+    static const uint64_t cap = (uint64_t)cn_tune_env("CNERF_B3_SEG_CAP", 1 << 18);
+    if (s < B3_SEG_MIN) return B3_SEG_MIN;
     const uint64_t k = (s + cap - 1) / cap;
     return (uint32_t)((s + k - 1) / k);
 }
 
-static uint32_t b2_max_chunks(const Bin2Plan &plan, uint32_t nl) {
+static uint32_t b3_max_bins(const Bin3Slots &plan, uint32_t nl) {
     uint32_t m = 1;
     for (uint32_t s = 0; s < nl; s++) m = m > plan.bin_first[s + 1] - plan.bin_first[s] ? m : plan.bin_first[s + 1] - plan.bin_first[s];
     return m;
 }
 
-
-static void b2_plan(const GridLevels &lv, uint32_t nl, uint32_t B, Bin2Plan &plan) {
-    plan.nb = cn_div_up(B, B3_PTS);                 // (point blocks of the third form; the first form plans with BinPlan)
-    uint32_t acc = 0;
-    for (uint32_t s = 0; s < nl; s++) {
-        plan.bin_first[s] = acc;
-        acc += cn_div_up(lv.size[lv.order[s]], BN_CHUNK);
-    }
-    for (uint32_t s = nl; s <= GE_MAX_LEVELS; s++) plan.bin_first[s] = acc;
-    plan.total_bins = acc;
-}
-
-// ---- third form, host side
 struct Bin3Ws {
     uint32_t *runs, *pre, *cursor, *bin_base, *seg_first, *seg_bin, *split_list;
     float *adam_const;
@@ -1393,8 +1368,15 @@ static bool b3_is_dense(const GridLevels &lv, uint32_t level, int ac) {
 // -> false when a level is neither dense nor a power-of-two hashed / wrapped level made of whole 4096-entry bins (or, round 6, of ONE bin of at
 // most 4096 entries: the small tables): such tables take the first form
 static bool b3_plan(const GridLevels &lv, uint32_t nl, uint32_t B, Bin3Plan &plan, uint32_t &n_dense, int ac) {
-    b2_plan(lv, nl, B, plan.p);
-    plan.p.nb = cn_div_up(B, B3_PTS);
+    Bin3Slots &ps = plan.p;
+    ps.nb = cn_div_up(B, B3_PTS);
+    uint32_t acc = 0;
+    for (uint32_t s = 0; s < nl; s++) {
+        ps.bin_first[s] = acc;
+        acc += cn_div_up(lv.size[lv.order[s]], BN_CHUNK);
+    }
+    for (uint32_t s = nl; s <= GE_MAX_LEVELS; s++) ps.bin_first[s] = acc;
+    ps.total_bins = acc;
     n_dense = 0;
     uint64_t cap = 0;
     bool ok = true;
@@ -1402,7 +1384,7 @@ static bool b3_plan(const GridLevels &lv, uint32_t nl, uint32_t B, Bin3Plan &pla
     for (uint32_t s = 0; s < nl; s++) {
         const uint32_t level = lv.order[s], size = lv.size[level];
         if (b3_is_dense(lv, level, ac)) { plan.dense_slot[s] = n_dense++; continue; }
-        const uint32_t nch = plan.p.bin_first[s + 1] - plan.p.bin_first[s];
+        const uint32_t nch = ps.bin_first[s + 1] - ps.bin_first[s];
         // interleaved bins need 2^k bins of exactly 4096 entries — or a single bin that IS the (power-of-two, >= 32-entry) level
         if ((size & (size - 1)) != 0 || (nch & (nch - 1)) != 0 || !(size == nch * BN_CHUNK || (nch == 1 && size >= 32))) ok = false;
         uint32_t hb = 0;
@@ -1416,39 +1398,38 @@ static bool b3_plan(const GridLevels &lv, uint32_t nl, uint32_t B, Bin3Plan &pla
     return ok;
 }
 
-// the third form serves float16 records on tables of at most B2S_MAX_CHUNKS bins per level (the staging area's counters); larger tables
-// (T = 2^20, 2^21: the reference's bear table) keep the second form with its histogram
-// (gridtype 1 = tiled: its wrapping levels are x-contiguous, the interleave does not balance them — second form)
+// the third form serves float16 records on tables of up to B3_WIDE_CHUNKS bins per level (more than B3_NARROW_CHUNKS: the WIDE emit, with
+// per-bin counter tables in place of the one-byte bin ids — T = 2^20, 2^21: the reference's bear table); every other binned shape takes the first form
 static bool b3_enabled(const GridLevels &lv, uint32_t nl, uint32_t B, int dtype, uint32_t gridtype, int ac) {
-    static const int on = b2_env("CNERF_B3", 1);
-    static const int wide_on = b2_env("CNERF_B3_WIDE", 1);                     // tuning builds: 0 = tables of more than 128 bins per level keep the second form
+    static const int on = cn_tune_env("CNERF_B3", 1);
+    static const int wide_on = cn_tune_env("CNERF_B3_WIDE", 1);                // tuning builds: 0 = tables of more than 128 bins per level take the first form
     (void)gridtype;                                                            // (round 6: tiled levels that wrap take the interleaved bins like hashed ones)
-    if (!on || !b2_enabled(dtype)) return false;
+    if (!on || dtype != CNERF_F16) return false;
     Bin3Plan plan;
     uint32_t nd;
     if (!b3_plan(lv, nl, B, plan, nd, ac)) return false;
-    const uint32_t mc = b2_max_chunks(plan.p, nl);
-    if (mc > (wide_on ? (uint32_t)B3_WIDE_CHUNKS : (uint32_t)B2S_MAX_CHUNKS)) return false;
+    const uint32_t mc = b3_max_bins(plan.p, nl);
+    if (mc > (wide_on ? (uint32_t)B3_WIDE_CHUNKS : (uint32_t)B3_NARROW_CHUNKS)) return false;
     if ((uint64_t)plan.p.total_bins * plan.capb >= 0xF0000000ull) return false;           // record positions inside the bin-major slab stay 32-bit in the accumulate
     return (uint64_t)nl * plan.p.nb * B3_REGION < 0xF0000000ull && (uint64_t)B * 8 < 0x7FFFFFFFull;
 }
 
 static uint64_t b3_layout(const Bin3Plan &plan, uint32_t n_dense, uint32_t B, uint32_t nl, Bin3Ws *ws, void *base) {
-    const Bin2Plan &p2 = plan.p;
+    const Bin3Slots &ps = plan.p;
     uint64_t off = 0;
-    const uint64_t o_runs = off; off = bn_align(off + (uint64_t)p2.total_bins * p2.nb * 4);
-    const uint64_t o_pre = off; off = bn_align(off + (uint64_t)p2.total_bins * p2.nb * 4);
-    const uint64_t o_cur = off; off = bn_align(off + ((uint64_t)p2.total_bins + 2) * 4);       // (+ the partner word of a 64-bit pair reservation past the last bin)
-    const uint64_t o_base = off; off = bn_align(off + (uint64_t)(p2.total_bins + 1) * 4);
-    const uint64_t o_seg = off; off = bn_align(off + (uint64_t)(p2.total_bins + 1) * 4);
-    const uint64_t o_split = off; off = bn_align(off + (uint64_t)(p2.total_bins + 1) * 4);
+    const uint64_t o_runs = off; off = bn_align(off + (uint64_t)ps.total_bins * ps.nb * 4);
+    const uint64_t o_pre = off; off = bn_align(off + (uint64_t)ps.total_bins * ps.nb * 4);
+    const uint64_t o_cur = off; off = bn_align(off + ((uint64_t)ps.total_bins + 2) * 4);       // (+ the partner word of a 64-bit pair reservation past the last bin)
+    const uint64_t o_base = off; off = bn_align(off + (uint64_t)(ps.total_bins + 1) * 4);
+    const uint64_t o_seg = off; off = bn_align(off + (uint64_t)(ps.total_bins + 1) * 4);
+    const uint64_t o_split = off; off = bn_align(off + (uint64_t)(ps.total_bins + 1) * 4);
     const uint64_t o_adamc = off; off = bn_align(off + 16);                                   // B3AdamConst of this backward pass (k_bin_scan_bins)    // count + the bins that were split (k_bin_scan_bins -> k_bin3_reduce_split)
-    const uint64_t h_records = (uint64_t)p2.total_bins * plan.capb;               // bin-major regions (the dense levels' bins leave theirs unused)
-    const uint64_t d_records = (uint64_t)nl * p2.nb * B3_REGION;                   // the point blocks' private regions: every record of a dense level, the spill of a hashed one
+    const uint64_t h_records = (uint64_t)ps.total_bins * plan.capb;               // bin-major regions (the dense levels' bins leave theirs unused)
+    const uint64_t d_records = (uint64_t)nl * ps.nb * B3_REGION;                   // the point blocks' private regions: every record of a dense level, the spill of a hashed one
     (void)n_dense;
     const uint64_t o_h = off; off = bn_align(off + h_records * 8);
     const uint64_t o_d = off; off = bn_align(off + d_records * 8);
-    const uint64_t max_seg = (uint64_t)p2.total_bins + cn_div_up64((uint64_t)B * nl * 8, b2_seg(B, b2_max_chunks(p2, nl)));
+    const uint64_t max_seg = (uint64_t)ps.total_bins + cn_div_up64((uint64_t)B * nl * 8, b3_seg(B, b3_max_bins(ps, nl)));
     const uint64_t o_segbin = off; off = bn_align(off + max_seg * 4);
     const uint64_t o_part = off; off = bn_align(off + max_seg * BN_CHUNK * 2 * 8);
     if (ws) {
@@ -1456,7 +1437,7 @@ static uint64_t b3_layout(const Bin3Plan &plan, uint32_t n_dense, uint32_t B, ui
         ws->runs = (uint32_t *)(p + o_runs);
         ws->pre = (uint32_t *)(p + o_pre);
         ws->cursor = (uint32_t *)(p + o_cur);
-        ws->cursor_bytes = (uint64_t)p2.total_bins * 4;
+        ws->cursor_bytes = (uint64_t)ps.total_bins * 4;
         ws->bin_base = (uint32_t *)(p + o_base);
         ws->seg_first = (uint32_t *)(p + o_seg);
         ws->split_list = (uint32_t *)(p + o_split);
@@ -1508,7 +1489,7 @@ static int b3_backward(const __half *grad, const float *inputs, const GridLevels
     Bin3Ws ws;
     b3_layout(plan, n_dense, B, nl, &ws, workspace);
     static const int emit_pad = cn_tune_env("CNERF_B3_EMIT_LDS_PAD", 0);        // tuning builds: extra LDS bytes per emit workgroup (occupancy experiments)
-    const uint32_t lds_n = B3_CAP * 9 + B2S_MAX_CHUNKS * 12 + 16, lds_w = B3_CAP * 8 + B3_WIDE_CHUNKS * 12 + 16;
+    const uint32_t lds_n = B3_CAP * 9 + B3_NARROW_CHUNKS * 12 + 16, lds_w = B3_CAP * 8 + B3_WIDE_CHUNKS * 12 + 16;
     const uint32_t emit_lds = (lds_n > lds_w ? lds_n : lds_w) + (uint32_t)emit_pad, acc_lds = BN_CHUNK * 2 * sizeof(long long) + 32 + B3_MAXT * 8;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1516,26 +1497,26 @@ static int b3_backward(const __half *grad, const float *inputs, const GridLevels
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bin3_accum), hipFuncAttributeMaxDynamicSharedMemorySize, acc_lds);
         attr_set = true;
     }
-    const Bin2Plan &p2 = plan.p;
-    const uint32_t seg = b2_seg(B, b2_max_chunks(p2, nl));
+    const Bin3Slots &ps = plan.p;
+    const uint32_t seg = b3_seg(B, b3_max_bins(ps, nl));
     B3Adam ad = b3_take_adam(gemb, lv, nl, true);
     ad.cst = ws.adam_const;
-    hipLaunchKernelGGL(k_bin3_zero, dim3(cn_div_up(p2.total_bins, 256)), dim3(256), 0, st, ws.cursor, p2.total_bins);    // (a kernel, not a memset node: hipGraph capture)
+    hipLaunchKernelGGL(k_bin3_zero, dim3(cn_div_up(ps.total_bins, 256)), dim3(256), 0, st, ws.cursor, ps.total_bins);    // (a kernel, not a memset node: hipGraph capture)
     cn_stage(0, st);
-    hipLaunchKernelGGL(k_bin3_emit, dim3(p2.nb * nl), dim3(B3_THREADS), emit_lds, st, grad, inputs, lv, plan, ws.runs, ws.cursor, ws.hslab, ws.dslab, B, gridtype, ac,
-                       interp, gemb, nl, (uint32_t)b2_env("CNERF_B3_EMIT_ABL", 0), g_cn_found_inf);
+    hipLaunchKernelGGL(k_bin3_emit, dim3(ps.nb * nl), dim3(B3_THREADS), emit_lds, st, grad, inputs, lv, plan, ws.runs, ws.cursor, ws.hslab, ws.dslab, B, gridtype, ac,
+                       interp, gemb, nl, (uint32_t)cn_tune_env("CNERF_B3_EMIT_ABL", 0), g_cn_found_inf);
     cn_stage(1, st);
-    hipLaunchKernelGGL(k_bin3_totals, dim3(p2.total_bins), dim3(BN_SCAN_THREADS), 0, st, (const uint32_t *)ws.runs, ws.pre, (const uint32_t *)ws.cursor, ws.bin_base,
+    hipLaunchKernelGGL(k_bin3_totals, dim3(ps.total_bins), dim3(BN_SCAN_THREADS), 0, st, (const uint32_t *)ws.runs, ws.pre, (const uint32_t *)ws.cursor, ws.bin_base,
                        plan, nl);
     static const uint32_t rs_bins = (uint32_t)cn_tune_env("CNERF_B3_RS_BINS", B3_RS_BINS);
     static const int rs_list = cn_tune_env("CNERF_B3_RSLIST", 1);                 // tuning builds: 0 = one workgroup column per bin (profiles/r06_reduce_split_ab.txt)
-    hipLaunchKernelGGL(k_bin_scan_bins, dim3(1), dim3(1024), 0, st, ws.bin_base, ws.bin_base, ws.seg_first, p2.total_bins, seg, ws.seg_bin, ws.split_list, ad.on,
+    hipLaunchKernelGGL(k_bin_scan_bins, dim3(1), dim3(1024), 0, st, ws.bin_base, ws.bin_base, ws.seg_first, ps.total_bins, seg, ws.seg_bin, ws.split_list, ad.on,
                        ad.state, ad.lr, ad.beta1, ad.beta2, ad.extra_inv, ad.on ? ws.adam_const : (float *)nullptr);
     hipLaunchKernelGGL(k_bin3_accum, dim3((uint32_t)ws.max_seg), dim3(1024), acc_lds, st, (const uint2 *)ws.hslab, (const uint2 *)ws.dslab, (const uint32_t *)ws.runs,
                        (const uint32_t *)ws.pre, (const uint32_t *)ws.cursor, (const uint32_t *)ws.bin_base, (const uint32_t *)ws.seg_first, lv, plan, gemb, ws.partial,
-                       (const uint32_t *)ws.seg_bin, nl, seg, (uint32_t)b2_env("CNERF_B3_ONLY", 0), ad);
+                       (const uint32_t *)ws.seg_bin, nl, seg, (uint32_t)cn_tune_env("CNERF_B3_ONLY", 0), ad);
     cn_stage(2, st);
-    hipLaunchKernelGGL(k_bin3_reduce_split, dim3(!rs_list || p2.total_bins < rs_bins ? p2.total_bins : rs_bins, BN_CHUNK * 2 / 4 / B3_RS_GROUPS), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_bin3_reduce_split, dim3(!rs_list || ps.total_bins < rs_bins ? ps.total_bins : rs_bins, BN_CHUNK * 2 / 4 / B3_RS_GROUPS), dim3(256), 0, st,
                        (const long long *)ws.partial, ws.seg_first, lv, plan, gemb, nl, rs_list ? (const uint32_t *)ws.split_list : (const uint32_t *)nullptr, ad);
     cn_stage(3, st);
 #ifdef CNERF_TUNING
@@ -1545,16 +1526,16 @@ static int b3_backward(const __half *grad, const float *inputs, const GridLevels
         uint32_t n_split = 0, n_seg = 0;
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(&n_split, ws.split_list, 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(&n_seg, ws.seg_first + p2.total_bins, 4, hipMemcpyDeviceToHost);
-        std::vector<uint32_t> sf(p2.total_bins + 1), bb(p2.total_bins + 1);
+        (void)hipMemcpy(&n_seg, ws.seg_first + ps.total_bins, 4, hipMemcpyDeviceToHost);
+        std::vector<uint32_t> sf(ps.total_bins + 1), bb(ps.total_bins + 1);
         (void)hipMemcpy(sf.data(), ws.seg_first, sf.size() * 4, hipMemcpyDeviceToHost);
         (void)hipMemcpy(bb.data(), ws.bin_base, bb.size() * 4, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[b3] call %d: bins %u segments %u split bins %u seg %u | per slot (bins, segments, records, max bin):", dbg_calls, p2.total_bins, n_seg, n_split, seg);
+        fprintf(stderr, "[b3] call %d: bins %u segments %u split bins %u seg %u | per slot (bins, segments, records, max bin):", dbg_calls, ps.total_bins, n_seg, n_split, seg);
         for (uint32_t sl = 0; sl < nl; sl++) {
             uint32_t mx = 0;
-            for (uint32_t b_ = p2.bin_first[sl]; b_ < p2.bin_first[sl + 1]; b_++) mx = std::max(mx, bb[b_ + 1] - bb[b_]);
-            fprintf(stderr, " L%u(%u,%u,%u,%u)", lv.order[sl], p2.bin_first[sl + 1] - p2.bin_first[sl], sf[p2.bin_first[sl + 1]] - sf[p2.bin_first[sl]],
-                    bb[p2.bin_first[sl + 1]] - bb[p2.bin_first[sl]], mx);
+            for (uint32_t b_ = ps.bin_first[sl]; b_ < ps.bin_first[sl + 1]; b_++) mx = std::max(mx, bb[b_ + 1] - bb[b_]);
+            fprintf(stderr, " L%u(%u,%u,%u,%u)", lv.order[sl], ps.bin_first[sl + 1] - ps.bin_first[sl], sf[ps.bin_first[sl + 1]] - sf[ps.bin_first[sl]],
+                    bb[ps.bin_first[sl + 1]] - bb[ps.bin_first[sl]], mx);
         }
         fprintf(stderr, "\n");
     }
@@ -1595,10 +1576,11 @@ uint64_t bn_workspace_bytes(uint32_t B, uint32_t nl, const GridLevels &lv, int d
     return b1 > b3 ? b1 : b3;
 }
 
-// phase 1 (needs the sample coordinates only): histogram + scans.  phase 2 (needs the gradients): emit + accumulate.
+// First form.  Phase 1 (bn_prepare; needs the sample coordinates only): histogram + scans.  Phase 2 (bn_phase2; needs the gradients): emit +
+// accumulate.
 // The two phases may be issued separately (cnerf_grid_encode_backward_prepare) so that phase 1 overlaps the forward / field backward.
-static int bn_phase1(const float *inputs, const GridLevels &lv, uint32_t B, uint32_t nl, uint32_t gridtype, int ac, uint32_t interp, int dtype,
-                     void *workspace, hipStream_t st) {
+int bn_prepare(const float *inputs, const GridLevels &lv, uint32_t B, uint32_t nl, uint32_t gridtype, int ac, uint32_t interp, int dtype,
+               void *workspace, hipStream_t st) {
     BinPlan plan;
     bn_plan(lv, nl, B, plan);
     BinWs ws;
@@ -1633,23 +1615,12 @@ static int bn_phase2(const T *grad, const float *inputs, const GridLevels &lv, f
     return cn_launch_status();
 }
 
-// The plan in pieces (cnerf_grid_encode_backward_prepare_rows / _finish) was the second form's: with that form gone (round 6) no shape offers it —
-// bn_hist_block_points() = 0 makes the entry points report *prepared = 0 before they get here.
-int bn_prepare_rows(const float *, const GridLevels &, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t, uint32_t, uint32_t) { return CNERF_EINVAL; }
-int bn_prepare_finish(const GridLevels &, uint32_t, uint32_t, int, void *, hipStream_t) { return CNERF_EINVAL; }
-uint32_t bn_hist_block_points(int) { return 0u; }
-
-int bn_prepare(const float *inputs, const GridLevels &lv, uint32_t B, uint32_t nl, uint32_t gridtype, int ac, uint32_t interp, int dtype,
-               void *workspace, hipStream_t st) {
-    return bn_phase1(inputs, lv, B, nl, gridtype, ac, interp, dtype, workspace, st);
-}
-
 int bn_backward(const void *grad, const float *inputs, const GridLevels &lv, float *gemb, uint32_t B, uint32_t nl, uint32_t gridtype, int ac,
                 uint32_t interp, int dtype, void *workspace, hipStream_t st, bool prepared) {
     if (b3_enabled(lv, nl, B, dtype, gridtype, ac)) return b3_backward((const __half *)grad, inputs, lv, gemb, B, nl, gridtype, ac, interp, workspace, st);
     if (nl) (void)b3_take_adam(gemb, lv, nl, false);                                 // (the first form does not carry the optimiser step: disarm)
     if (!prepared) {
-        const int rc = bn_phase1(inputs, lv, B, nl, gridtype, ac, interp, dtype, workspace, st);
+        const int rc = bn_prepare(inputs, lv, B, nl, gridtype, ac, interp, dtype, workspace, st);
         if (rc) return rc;
     }
     if (dtype == CNERF_F16) return bn_phase2<__half>((const __half *)grad, inputs, lv, gemb, B, nl, gridtype, ac, interp, dtype, workspace, st);

@@ -40,11 +40,11 @@ LEVEL_MAJOR, SAMPLE_MAJOR = 0, 1          # include/customnerf_hip.h CNERF_GRID_
 
 class TraversalTuner:
     """Which traversal of the forward gather (cnerf_grid_encode_forward_ordered) a call site should use, MEASURED in place: the two forms are
-    bit-identical, and which one is faster depends on the scene's state — importance samples of a random-initialised field are spread over the
-    volume (level-major wins), those of a fitted field hug a surface (sample-major wins: profiles/r05_fused_fwd_lab.log).  On a trial call the
-    caller runs BOTH forms back to back on the same samples (the second overwrites the first's identical output) between event pairs; the
-    events are read without blocking on a later call, and the faster form is used until the next trial.  Two trial calls (order swapped) at
-    calls `first` / `first + 1`, then every `period` calls: 2 extra gathers per `period` steps."""
+    bit-identical, and which one is faster depends on the scene's state — on the importance samples of a random-initialised field
+    sample-major wins, on those of a fitted field level-major does (a real surface does not cluster them like the lab's samples: DESIGN.md
+    §4a).  On a trial call the caller runs BOTH forms back to back on the same samples (the second overwrites the first's identical output)
+    between event pairs; the events are read without blocking on a later call, and the faster form is used until the next trial.  Two trial
+    calls (order swapped) at calls `first` / `first + 1`, then every `period` calls: 2 extra gathers per `period` steps."""
 
     def __init__(self, first=2, period=256, margin=0.02):
         self.choice = LEVEL_MAJOR
@@ -194,8 +194,8 @@ class _Plan:
     """a prepared scatter plan (lives on the autograd node: dropped with the graph if the backward never runs)"""
     __slots__ = ('ws', 'event', 'inputs_ptr', 'rows', '__weakref__')
 
-    def __init__(self, ws, event):
-        self.ws, self.event = ws, event
+    def __init__(self, ws, event, inputs_ptr, rows):
+        self.ws, self.event, self.inputs_ptr, self.rows = ws, event, inputs_ptr, rows
 
 
 def _side(device):
@@ -214,8 +214,9 @@ _NEEDS_PLAN = {}
 
 
 def _needs_plan(offsets_host, B, D, C, L, S, H, dt, gridtype):
-    """does the backward scatter of this shape use a plan prepared ahead of time?  (cnerf_grid_encode_backward_needs_plan, cached per shape: the
-    round-5 scatter counts inside its emit kernel, so the run() path of the benchmark configuration prepares nothing)"""
+    """does the backward scatter of this shape use a plan prepared ahead of time?  (cnerf_grid_encode_backward_needs_plan, cached per shape: only
+    the first form of the binned scatter takes one — float32 records, and fp16 tables the third form does not take; the third form, which
+    serves the fp16 tables of the run() path, counts inside its emit kernel and prepares nothing)"""
     import ctypes
     key = (offsets_host.ctypes.data, B, D, C, L, S, H, dt, gridtype)
     v = _NEEDS_PLAN.get(key)
@@ -230,8 +231,9 @@ def _needs_plan(offsets_host, B, D, C, L, S, H, dt, gridtype):
 
 
 def _prepare_plan(inputs, offsets_host, B, D, C, L, S, H, gridtype, align_corners, interpolation, dt, device):
-    """Issue the coordinate-only half of the binned backward scatter (histogram + scans) for `inputs` [B, D] on the side stream of the
-    current compute stream -> _Plan, or None when the side stream still holds an earlier plan / the problem takes the atomic kernel."""
+    """Issue the coordinate-only half of the binned backward scatter's first form (histogram + scans) for `inputs` [B, D] on the side stream of
+    the current compute stream -> _Plan, or None when the side stream still holds an earlier plan / the shape takes no plan (atomic kernel,
+    third form)."""
     import ctypes
     if not _needs_plan(offsets_host, B, D, C, L, S, H, dt, gridtype):
         return None
@@ -257,64 +259,17 @@ def _prepare_plan(inputs, offsets_host, B, D, C, L, S, H, gridtype, align_corner
         return None
     ev = torch.cuda.Event()
     ev.record(side['stream'])
-    plan = _Plan(ws, ev)
-    plan.inputs_ptr, plan.rows = inputs.data_ptr(), B
+    plan = _Plan(ws, ev, inputs.data_ptr(), B)
     side['owner'] = weakref.ref(plan)
-    return plan
-
-
-def _plan_rows(state, inputs, offsets_host, B, D, C, L, S, H, gridtype, align_corners, interpolation, dt, device, row0, rows, finish):
-    """The plan of _prepare_plan in pieces (cnerf_grid_encode_backward_prepare_rows / _finish): `state` is None for the first piece and the
-    value returned by the previous call afterwards; every piece is issued on the side stream after the current stream's work so far (the
-    coordinates of ITS rows must exist).  -> state (a dict) while pieces are pending, a _Plan once `finish`, or None when the shape takes the
-    atomic kernel / the side stream is busy (then nothing was issued and attach_backward plans by itself)."""
-    import ctypes
-    if state is None and not _needs_plan(offsets_host, B, D, C, L, S, H, dt, gridtype):
-        return None
-    side = _side(device)
-    if state is None:
-        if _side_busy(side):
-            return None
-        need = ctypes.c_uint64(0)
-        check(lib.cnerf_grid_encode_backward_workspace_bytes(offsets_host.ctypes.data, B, D, C, L, L, S, H, dt, ctypes.addressof(need)),
-              "grid_encode_backward_workspace_bytes")
-        if not need.value:
-            return None
-        if side['ws'] is None or side['ws'].numel() < need.value:
-            side['ws'] = torch.empty(int(need.value * 1.25) + 256, dtype=torch.uint8, device=device)
-            scratch_reallocated()
-        state = {'ws': side['ws'], 'token': _Plan(side['ws'], None)}
-        state['token'].inputs_ptr, state['token'].rows = inputs.data_ptr(), B
-        side['owner'] = weakref.ref(state['token'])                  # the side stream's workspace is taken from the first piece on
-    ws = state['ws']
-    cur = torch.cuda.current_stream()
-    side['stream'].wait_stream(cur)
-    ok = ctypes.c_int(0)
-    if rows:
-        check(lib.cnerf_grid_encode_backward_prepare_rows(ptr(inputs), offsets_host.ctypes.data, B, D, C, L, S, H, gridtype, int(align_corners),
-                                                          interpolation, dt, int(row0), int(rows), ptr(ws), ws.numel(), ctypes.addressof(ok),
-                                                          side['stream'].cuda_stream), "grid_encode_backward_prepare_rows")
-        if not ok.value:
-            side['owner'] = None
-            return None
-    if not finish:
-        return state
-    check(lib.cnerf_grid_encode_backward_prepare_finish(offsets_host.ctypes.data, B, D, C, L, S, H, gridtype, interpolation, dt, ptr(ws), ws.numel(),
-                                                        ctypes.addressof(ok), side['stream'].cuda_stream), "grid_encode_backward_prepare_finish")
-    if not ok.value:
-        side['owner'] = None
-        return None
-    plan = state['token']
-    plan.event = torch.cuda.Event()
-    plan.event.record(side['stream'])
     return plan
 
 
 class _grid_attach(Function):
     """Backward half of _grid_encode for a feature buffer that was filled by GridEncoder.encode_into calls: forward hands the buffer
     on unchanged, backward scatters d(loss)/d(features) [L,B,C] into the table gradient for ALL B rows of `inputs`.
-    The coordinate-only half of that scatter (histogram + scans of the binned backward) is issued here, in the forward, on a second
-    stream: it overlaps the rest of the forward pass and the field backward instead of sitting on the critical path."""
+    When the scatter takes the first form of the binned backward (float32 records, see _needs_plan), its coordinate-only half (histogram + scans) is issued
+    here, in the forward, on a second stream: it overlaps the rest of the forward pass and the field backward instead of sitting on the
+    critical path.  The third form (fp16 records) has no such half: nothing is issued."""
 
     @staticmethod
     def forward(ctx, enc, inputs, embeddings, offsets_host, per_level_scale, base_resolution, gridtype, align_corners, interpolation, overlap,
@@ -500,34 +455,18 @@ class GridEncoder(nn.Module):
     def prepare_backward(self, inputs_unit, half):
         """Issue the coordinate-only half of the backward scatter for inputs_unit [P, D] (float32, contiguous, [0, 1] grid coordinates) NOW, on
         the side stream — as soon as the coordinates exist, e.g. before the last encode_into, whose gather it then overlaps — and return the
-        plan for attach_backward(..., plan=).  None when nothing was issued (attach_backward then does it itself)."""
+        plan for attach_backward(..., plan=).  None when nothing was issued: the shape takes no plan (only the first form of the binned
+        scatter does: see _needs_plan), or the side stream is busy (attach_backward then plans by itself)."""
         assert inputs_unit.is_contiguous() and inputs_unit.dtype == torch.float32
         P, D = inputs_unit.shape
         dt = dtype_id(torch.empty(0, dtype=torch.float16 if half else torch.float32))
         return _prepare_plan(inputs_unit, self._offsets_host, P, D, self.level_dim, self.num_levels, float(np.log2(self.per_level_scale)),
                              int(self.base_resolution), self.gridtype_id, self.align_corners, self.interp_id, dt, inputs_unit.device)
 
-    def hist_block_points(self, half):
-        """granularity (rows) of prepare_backward_rows for this precision; 0 = the piecewise plan is not available (float32 records)"""
-        import ctypes
-        n = ctypes.c_uint32(0)
-        check(lib.cnerf_grid_encode_backward_prepare_block(dtype_id(torch.empty(0, dtype=torch.float16 if half else torch.float32)), ctypes.addressof(n)),
-              "grid_encode_backward_prepare_block")
-        return int(n.value)
-
-    def prepare_backward_rows(self, state, inputs_unit, half, row0, rows, finish):
-        """prepare_backward in pieces: count rows [row0, row0 + rows) of inputs_unit [P, D] now (they must be written), `finish` on the last piece
-        -> state to pass to the next call, the plan after the last one, or None (nothing issued; attach_backward then plans by itself)."""
-        assert inputs_unit.is_contiguous() and inputs_unit.dtype == torch.float32
-        P, D = inputs_unit.shape
-        dt = dtype_id(torch.empty(0, dtype=torch.float16 if half else torch.float32))
-        return _plan_rows(state, inputs_unit, self._offsets_host, P, D, self.level_dim, self.num_levels, float(np.log2(self.per_level_scale)),
-                          int(self.base_resolution), self.gridtype_id, self.align_corners, self.interp_id, dt, inputs_unit.device, row0, rows, finish)
-
     def attach_backward(self, enc, inputs_unit, overlap=True, plan=None):
         """enc [L, P, C] filled by encode_into for the rows of inputs_unit [P, D] -> the same features, differentiable in the table.
-        overlap: issue the coordinate-only half of the backward scatter now, on a second stream (see _grid_attach); plan: it was issued
-        earlier by prepare_backward on these coordinates."""
+        overlap: issue the coordinate-only half of the backward scatter now, on a second stream, if the shape takes one (see _grid_attach);
+        plan: it was issued earlier by prepare_backward on these coordinates."""
         return _grid_attach.apply(enc, inputs_unit.contiguous().float(), self.embeddings, self._offsets_host, self.per_level_scale, self.base_resolution,
                                   self.gridtype_id, self.align_corners, self.interp_id, bool(overlap), bool(getattr(self, 'grad_in_place', False)), plan)
 

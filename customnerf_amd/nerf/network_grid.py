@@ -192,23 +192,13 @@ class NeRFNetwork(NeRFRenderer):
 
     def split_prepare(self, unit, grad_enabled):
         """As soon as every row of `unit` is written (i.e. before the last split_encode): start the coordinate-only half of the backward
-        scatter on the side stream, where it overlaps that gather instead of the field kernels.  -> plan for split_forward, or None."""
+        scatter on the side stream, where it overlaps that gather instead of the field kernels.  -> plan for split_forward, or None (also
+        whenever the scatter takes no plan: only its float32-record form does, gridencoder.grid._needs_plan)."""
         if not (grad_enabled and self.pos_en.embeddings.requires_grad and self._overlap_plan()):
             return None
         if not getattr(self.opt, 'early_scatter_plan', True):
             return None
         return self.pos_en.prepare_backward(unit, self._half())
-
-    def split_prepare_rows(self, state, unit, grad_enabled, row0, rows, finish):
-        """split_prepare in pieces: the histogram of rows [row0, row0 + rows) as soon as those coordinates exist (the coarse block right after the
-        coarse sampling, the fine block after the importance sampling), so that the whole plan is ready before the field backward starts.
-        -> (state | plan | None, piecewise): piecewise False = not available for this shape / precision: use split_prepare."""
-        if not (grad_enabled and self.pos_en.embeddings.requires_grad and self._overlap_plan() and getattr(self.opt, 'early_scatter_plan', True)):
-            return None, True
-        blk = self.pos_en.hist_block_points(self._half())
-        if not blk or row0 % blk or (rows % blk and row0 + rows != unit.shape[0]) or not getattr(self.opt, 'piecewise_scatter_plan', True):
-            return None, False
-        return self.pos_en.prepare_backward_rows(state, unit, self._half(), row0, rows, finish), True
 
     def split_forward(self, enc, unit, x, d, dir_group, plan=None):
         """forward() on a complete feature buffer: (sigma [P], rgbc [P, 4]); gradients reach the table through attach_backward"""

@@ -203,9 +203,6 @@ class NeRFRenderer(nn.Module):
                 # near_far_from_aabb (:297) rides on the coarse sampler's launch
                 nears, fars, z_vals, xyz_c = render_ops.sample_coarse_aabb(rays_o, rays_d, aabb.contiguous().float(), self.min_near, num_steps, noise,
                                                                            xyz_list[:Pc].view(N, num_steps, 3), unit[:Pc].view(N, num_steps, 3), bnd)
-                # the scatter plan's histogram in two pieces: the coarse block's rows now (beside the coarse gather), the fine block's after the
-                # importance sampling — all of it is then done before the field backward starts
-                pstate, piecewise = self.split_prepare_rows(None, unit, grad_on, 0, Pc, False)
                 self.split_encode(enc, unit, xyz_list[:Pc], 0, unit_ready=True)
                 blockwise = bool(getattr(self.opt, 'blockwise_field', True)) and self._fused_cfg()[2] == 4
                 if blockwise:
@@ -219,10 +216,7 @@ class NeRFRenderer(nn.Module):
                 z_all, xyz_f, src = render_ops.sample_fine_merge_split(rays_o, rays_d, nears, fars, aabb, z_vals, sig_c, upsample_steps, u_draw(),
                                                                         xyz_fine_out=xyz_list[Pc:].view(N, upsample_steps, 3),
                                                                         unit_fine_out=unit[Pc:].view(N, upsample_steps, 3), bound=bnd)
-                if piecewise and pstate is not None:
-                    plan, _ = self.split_prepare_rows(pstate, unit, grad_on, Pc, P - Pc, True)
-                elif not piecewise:
-                    plan = self.split_prepare(unit, grad_on)                 # all coordinates exist: the scatter's histogram runs beside the gather below
+                plan = self.split_prepare(unit, grad_on)                     # all coordinates exist: a scatter plan (float32 records) runs beside the gather below
                 self.split_encode(enc, unit, xyz_list[Pc:], Pc, unit_ready=True, importance=True)
                 if blockwise:
                     self.split_forward_rows(enc, Pc, xyz_list[Pc:], rays_d, upsample_steps, sig_all, rgbc_all)

@@ -33,8 +33,9 @@ extern "C" {
 /* ABI version of this header; cnerf_abi_version() of the loaded library must match.
  * 2: the GroupNorm / GEMM-epilogue statistics buffers of customnerf_sd.h are int64[B][G][2] fixed point (were float[B][G][2]).
  * 4: struct CnerfSdGemm grew the ln_* fields (LayerNorm of the output rows in the split-K tail); new entry points
- *    cnerf_grid_encode_forward_ordered, cnerf_sd_concat_gn, cnerf_sd_gemm_serves_ln, cnerf_profile_stage_events. */
-#define CNERF_ABI_VERSION 5
+ *    cnerf_grid_encode_forward_ordered, cnerf_sd_concat_gn, cnerf_sd_gemm_serves_ln, cnerf_profile_stage_events.
+ * 6: the plan in pieces is gone — the _block / _rows / _finish variants of cnerf_grid_encode_backward_prepare (no shape took them since ABI 5). */
+#define CNERF_ABI_VERSION 6
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
 const char *cnerf_target_arch(void);
@@ -185,35 +186,23 @@ int cnerf_grid_encode_backward(const void *grad, const float *inputs, const int3
                                uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level, float S, uint32_t H,
                                const void *dy_dx, float *grad_inputs, uint32_t gridtype, int align_corners,
                                uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes, void *stream);
-/* Two-phase form of the binned backward.  _prepare runs the part that needs only the sample coordinates (per-chunk histogram and
- * scans) into `workspace` — issue it early, on a second stream, and it overlaps the forward pass and the field backward; *prepared
- * tells whether the binned path applies to this shape (0: nothing was launched, use cnerf_grid_encode_backward).  _prepared then runs
- * the gradient-dependent part (record emit + LDS accumulation) and must see the same inputs, shape and workspace, after _prepare's
- * work has completed (event / stream order is the caller's). */
+/* Two-phase form of the binned backward, for the shapes that take its FIRST form (cnerf_grid_encode_backward_needs_plan = 1): that form
+ * counts its records per table chunk in a histogram pass over the sample coordinates before it emits them.  _prepare runs that
+ * coordinate-only part (histogram + scans) into `workspace` — issue it early, on a second stream, and it overlaps the forward pass and the
+ * field backward; *prepared tells whether it launched anything (0: nothing was launched — the shape takes the atomic kernel, or the third
+ * form, which counts inside its emit kernel — use cnerf_grid_encode_backward).  _prepared then runs the gradient-dependent part (record
+ * emit + LDS accumulation) and must see the same inputs, shape and workspace, after _prepare's work has completed (event / stream order is
+ * the caller's). */
 int cnerf_grid_encode_backward_prepare(const float *inputs, const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                                        uint32_t max_level, float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp,
                                        int dtype, void *workspace, uint64_t workspace_bytes, int *prepared, void *stream);
-/* The plan in pieces (float16 records): the histogram of rows [row0, row0 + rows) of the B-sample list can be taken as soon as THOSE coordinates
- * exist — run()'s coarse block at the very beginning of the forward, its fine block after the importance sampling — so that all of it is done
- * before the field backward starts (a histogram that is still running then slows that kernel from 407 to 491 us: DESIGN.md §4 round 3).
- * row0 must be a multiple of *block_points (cnerf_grid_encode_backward_prepare_block) and the range must end on a block border or at B;
- * ..._finish runs the scans once every row has been counted.  *prepared = 0: nothing launched (the shape takes the atomic kernel / float32 records).
- * Round 6: the histogram-driven float16 form these pieces belonged to is gone (the histogram-free form took over its shapes); the three entry points
- * stay in the ABI and report *block_points = 0 / *prepared = 0 for every shape. */
-int cnerf_grid_encode_backward_prepare_block(int dtype, uint32_t *block_points);
-/* *needs_plan = 1 when cnerf_grid_encode_backward of this shape profits from a plan prepared ahead of time (the forms that need the exact record
- * counts before the emit: float32 records; float16 records on hashed levels smaller than one 4096-entry bin or of more than 512 bins); 0 when there
- * is nothing to prepare — the atomic kernel, or the scatter that counts inside its emit kernel (round 5; round 6: up to 512 bins per level, hash and
- * tiled grids — the benchmark table and the reference field's own T = 2^21 table).
- * The _prepare* entry points report *prepared = 0 for such shapes; this query lets a caller skip them (and their workspace) altogether. */
+/* *needs_plan = 1 when cnerf_grid_encode_backward of this shape takes the first form: float32 records, and float16 records on a table the
+ * third form does not take (a hashed level whose size is not a power of two, or is below 32 entries).  0 when there is nothing to prepare —
+ * the atomic kernel, or the third form (float16 records, hash and tiled grids of up to 512 bins per level: the benchmark table and the
+ * reference field's own T = 2^21 table).  _prepare reports *prepared = 0 for such shapes; this query lets a caller skip it (and its
+ * workspace) altogether. */
 int cnerf_grid_encode_backward_needs_plan(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level, float S,
                                           uint32_t H, uint32_t gridtype, int dtype, int *needs_plan);
-int cnerf_grid_encode_backward_prepare_rows(const float *inputs, const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
-                                            float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype, uint32_t row0,
-                                            uint32_t rows, void *workspace, uint64_t workspace_bytes, int *prepared, void *stream);
-int cnerf_grid_encode_backward_prepare_finish(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                                              uint32_t gridtype, uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes,
-                                              int *prepared, void *stream);
 int cnerf_grid_encode_backward_prepared(const void *grad, const float *inputs, const int32_t *offsets_host, float *grad_embeddings,
                                         uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level, float S, uint32_t H,
                                         uint32_t gridtype, int align_corners, uint32_t interp, int dtype, void *workspace,

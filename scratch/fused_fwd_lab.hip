@@ -15,9 +15,10 @@ bool bn_eligible(uint32_t, uint32_t, uint32_t, uint32_t, const GridLevels &) { r
 uint64_t bn_workspace_bytes(uint32_t, uint32_t, const GridLevels &, int) { return 0; }
 int bn_backward(const void *, const float *, const GridLevels &, float *, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t, bool) { return -1; }
 int bn_prepare(const float *, const GridLevels &, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t) { return -1; }
-int bn_prepare_rows(const float *, const GridLevels &, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t, uint32_t, uint32_t) { return -1; }
-int bn_prepare_finish(const GridLevels &, uint32_t, uint32_t, int, void *, hipStream_t) { return -1; }
-uint32_t bn_hist_block_points(int) { return 0; }
+bool bn_needs_plan(uint32_t, uint32_t, const GridLevels &, int, uint32_t) { return false; }
+void bn_grid_adam_arm(const CnerfGridAdam *) {}
+int bn_grid_adam_consumed() { return 0; }
+float *g_cn_found_inf = nullptr;
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 

@@ -124,7 +124,7 @@ def test_argument_validation_without_launch():
     assert lib.cnerf_set_floats(one, ctypes.cast(vals, ctypes.c_void_p), 17, None) == -1 and lib.cnerf_set_floats(None, ctypes.cast(vals, ctypes.c_void_p), 2, None) == -2
     needs = ctypes.c_int(7)
     assert lib.cnerf_grid_encode_backward_needs_plan(big.ctypes.data, 2097152, 3, 2, 16, 16, S, 16, 0, 1, ctypes.addressof(needs)) == 0 and needs.value == 0   # third form: no plan
-    assert lib.cnerf_grid_encode_backward_needs_plan(big.ctypes.data, 2097152, 3, 2, 16, 16, S, 16, 0, 0, ctypes.addressof(needs)) == 0 and needs.value == 1   # float32 records: second form
+    assert lib.cnerf_grid_encode_backward_needs_plan(big.ctypes.data, 2097152, 3, 2, 16, 16, S, 16, 0, 0, ctypes.addressof(needs)) == 0 and needs.value == 1   # float32 records: first form
 
 
 def test_host_side_modules_on_cpu():
