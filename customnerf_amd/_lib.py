@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcustomnerf_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 vp, u32, u64, f32, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float, C.c_int
 
@@ -87,6 +87,9 @@ SIGNATURES = {
     "cnerf_dp_reduce": [vp, u32, u64, vp, vp, vp],
     "cnerf_scaler_update": [vp, f32, f32, u32, vp],
     "cnerf_adam_step_scaled_multi": [vp, f32, f32, f32, vp, f32, i32, i32, f32, f32, u32, vp],
+    "cnerf_marching_cubes_workspace_bytes": [u32, u32, u32, vp],
+    "cnerf_marching_cubes_count": [vp, u32, u32, u32, f32, vp, u64, vp, vp],
+    "cnerf_marching_cubes_emit": [vp, u32, u32, u32, f32, vp, vp, vp, u64, vp, vp, vp, u32, u32, vp],
     # ---- include/customnerf_sd.h (score-distillation primitives)
     "cnerf_sd_gemm": [vp, vp, u64, vp],
     "cnerf_sd_gemm_workspace_bytes": [vp, vp],

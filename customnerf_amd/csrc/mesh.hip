@@ -1,0 +1,301 @@
+// Marching cubes over a dense float32 volume (cnerf_marching_cubes_*): count -> scan -> emit vertices -> emit faces, all on the caller's
+// stream, no atomics, no host synchronisation.  Table and cube conventions: mc_tables.h / gen_mc_tables.py; the NumPy restatement the
+// tests pin it to: tests/mc_restatement.py.
+//
+//   k_mc_count : one thread per grid point: the case of the cell whose minimum corner it is, the 3-bit mask of its crossing owned edges
+//                (edge (p, p + e_axis) is owned by p); per-workgroup (vertex, triangle) totals by ballot / popcount + LDS
+//   k_mc_scan  : one workgroup: exclusive scan of the workgroup totals (in place) and counts[2] = (vertices, triangles)
+//   k_mc_verts : the in-workgroup prefix again (ballot + mbcnt, LDS wave totals); vertex base of every point, positions, normals
+//   k_mc_faces : the same prefix over the triangle counts; each table edge -> owner point's base + rank of its axis in the owner's mask
+//
+// Vertices are ordered by (linear point index, axis), triangles by (linear cell index, table order): the output does not depend on
+// scheduling.  Workspace: header (overflow flag) | case bytes [N] | mask bytes [N] | vertex bases uint32 [N] | workgroup totals uint2 [N/256].
+#include "common.h"
+#include "mc_tables.h"
+
+#define MC_BLOCK 256
+#define MC_WAVES (MC_BLOCK / CN_WAVE)
+#define MC_SCAN_BLOCK 1024
+#define MC_SCAN_PER_THREAD 4
+
+namespace {
+
+struct McLayout {
+    uint64_t cases, masks, vbase, sums, total;
+};
+
+inline uint64_t mc_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+
+McLayout mc_layout(uint64_t n) {
+    McLayout l;
+    l.cases = 256;                                   // [0, 256): uint32 overflow flag
+    l.masks = l.cases + mc_align(n);
+    l.vbase = l.masks + mc_align(n);
+    l.sums = l.vbase + mc_align(4 * n);
+    l.total = l.sums + mc_align(8 * cn_div_up64(n, MC_BLOCK));
+    return l;
+}
+
+struct McGeom {
+    float org[3], sp[3];
+};
+
+__device__ __forceinline__ uint32_t mc_rank(uint64_t ballot) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+
+// exclusive prefix of v (< 2^BITS) over the workgroup in thread order; every thread of the block must call it.  `red` = LDS [MC_WAVES]
+template <int BITS>
+__device__ __forceinline__ uint32_t mc_block_prefix(uint32_t v, uint32_t *red) {
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < BITS; ++k) {
+        const uint64_t b = __ballot((v >> k) & 1u);
+        pre += mc_rank(b) << k;
+        tot += (uint32_t)__popcll(b) << k;
+    }
+    const uint32_t w = threadIdx.x / CN_WAVE;
+    if (cn_lane() == 0) red[w] = tot;
+    __syncthreads();
+    for (uint32_t j = 0; j < w; ++j) pre += red[j];
+    return pre;
+}
+
+template <int BITS>
+__device__ __forceinline__ uint32_t mc_block_total(uint32_t v, uint32_t *red) {
+    uint32_t tot = 0;
+#pragma unroll
+    for (int k = 0; k < BITS; ++k) tot += (uint32_t)__popcll(__ballot((v >> k) & 1u)) << k;
+    if (cn_lane() == 0) red[threadIdx.x / CN_WAVE] = tot;
+    __syncthreads();
+    uint32_t s = 0;
+    for (int j = 0; j < MC_WAVES; ++j) s += red[j];
+    return s;
+}
+
+__device__ __forceinline__ bool mc_in(float v, float level) { return v >= level; }   // NaN: outside
+
+__global__ __launch_bounds__(MC_BLOCK) void k_mc_count(const float *__restrict__ vol, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                                                       uint8_t *__restrict__ cases, uint8_t *__restrict__ masks, uint2 *__restrict__ sums) {
+    __shared__ uint32_t red_v[MC_WAVES], red_t[MC_WAVES];
+    const uint32_t nyz = ny * nz, n = nx * nyz;
+    const uint32_t i = blockIdx.x * MC_BLOCK + threadIdx.x;
+    uint32_t m = 0, ntri = 0;
+    if (i < n) {
+        const uint32_t x = i / nyz, r = i - x * nyz, y = r / nz, z = r - y * nz;
+        const bool hx = x + 1 < nx, hy = y + 1 < ny, hz = z + 1 < nz;
+        const bool in0 = mc_in(vol[i], level);
+        if (hx && mc_in(vol[i + nyz], level) != in0) m |= 1u;
+        if (hy && mc_in(vol[i + nz], level) != in0) m |= 2u;
+        if (hz && mc_in(vol[i + 1], level) != in0) m |= 4u;
+        uint32_t c = 0;
+        if (hx && hy && hz) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t off = (k & 1 ? nyz : 0u) + (k & 2 ? nz : 0u) + (k & 4 ? 1u : 0u);
+                c |= (uint32_t)mc_in(vol[i + off], level) << k;
+            }
+            ntri = cn_mc_ntri[c];
+        }
+        cases[i] = (uint8_t)c;
+        masks[i] = (uint8_t)m;
+    }
+    const uint32_t tv = mc_block_total<2>((uint32_t)__popc(m), red_v);
+    const uint32_t tt = mc_block_total<3>(ntri, red_t);
+    if (threadIdx.x == 0) sums[blockIdx.x] = make_uint2(tv, tt);
+}
+
+// one workgroup; sums[0..nblk) -> exclusive offsets in place; counts = totals, or 0xffffffff both (and flag = 1) when either exceeds INT32_MAX
+__global__ __launch_bounds__(MC_SCAN_BLOCK) void k_mc_scan(uint2 *__restrict__ sums, uint32_t nblk, uint32_t *__restrict__ counts,
+                                                           uint32_t *__restrict__ flag) {
+    __shared__ uint32_t wv[MC_SCAN_BLOCK / CN_WAVE], wt[MC_SCAN_BLOCK / CN_WAVE];
+    const uint32_t nw = MC_SCAN_BLOCK / CN_WAVE, w = threadIdx.x / CN_WAVE, lane = cn_lane();
+    uint64_t cv = 0, ct = 0;                         // carry: totals of the tiles before this one
+    for (uint32_t base = 0; base < nblk; base += MC_SCAN_BLOCK * MC_SCAN_PER_THREAD) {
+        const uint32_t j0 = base + threadIdx.x * MC_SCAN_PER_THREAD;
+        uint2 e[MC_SCAN_PER_THREAD];
+        uint32_t sv = 0, st = 0;
+#pragma unroll
+        for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
+            e[k] = j0 + k < nblk ? sums[j0 + k] : make_uint2(0, 0);
+            sv += e[k].x;
+            st += e[k].y;
+        }
+        const uint32_t iv = cn_wave_incl_scan(sv), it = cn_wave_incl_scan(st);
+        if (lane == CN_WAVE - 1) { wv[w] = iv; wt[w] = it; }
+        __syncthreads();
+        uint32_t ov = iv - sv, ot = it - st, tile_v = 0, tile_t = 0;
+        for (uint32_t j = 0; j < nw; ++j) {
+            if (j < w) { ov += wv[j]; ot += wt[j]; }
+            tile_v += wv[j];
+            tile_t += wt[j];
+        }
+        __syncthreads();                             // wv / wt are rewritten by the next tile
+        uint64_t pv = cv + ov, pt = ct + ot;
+#pragma unroll
+        for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
+            if (j0 + k < nblk) sums[j0 + k] = make_uint2((uint32_t)pv, (uint32_t)pt);
+            pv += e[k].x;
+            pt += e[k].y;
+        }
+        cv += tile_v;
+        ct += tile_t;
+    }
+    if (threadIdx.x == 0) {
+        const bool over = cv > 0x7fffffffull || ct > 0x7fffffffull;
+        counts[0] = over ? 0xffffffffu : (uint32_t)cv;
+        counts[1] = over ? 0xffffffffu : (uint32_t)ct;
+        flag[0] = over ? 1u : 0u;
+    }
+}
+
+// d(vol)/d(axis b) at point p: central difference inside, one-sided at the volume's faces, divided by the spacing
+__device__ __forceinline__ float mc_grad(const float *__restrict__ vol, uint32_t p, uint32_t idx, uint32_t len, uint32_t stride, float sp) {
+    const bool lo = idx > 0, hi = idx + 1 < len;
+    const float vp = hi ? vol[p + stride] : vol[p];
+    const float vm = lo ? vol[p - stride] : vol[p];
+    const float h = (lo && hi) ? 2.0f : 1.0f;
+    return (vp - vm) / (h * sp);
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_mc_verts(const float *__restrict__ vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, McGeom g,
+                                                       const uint8_t *__restrict__ masks, const uint2 *__restrict__ sums,
+                                                       const uint32_t *__restrict__ flag, uint32_t *__restrict__ vbase, float *__restrict__ verts,
+                                                       float *__restrict__ normals, uint32_t max_verts) {
+    __shared__ uint32_t red[MC_WAVES];
+    if (flag[0]) return;                             // the totals overflowed int32: nothing is written
+    const uint32_t nyz = ny * nz, n = nx * nyz;
+    const uint32_t i = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t m = i < n ? masks[i] : 0u;
+    const uint32_t base = sums[blockIdx.x].x + mc_block_prefix<2>((uint32_t)__popc(m), red);
+    if (i >= n) return;
+    vbase[i] = base;
+    if (!m) return;
+    const uint32_t x = i / nyz, r = i - x * nyz, y = r / nz, z = r - y * nz;
+    const uint32_t idx[3] = {x, y, z}, len[3] = {nx, ny, nz}, stride[3] = {nyz, nz, 1u};
+    const float v0 = vol[i];
+    uint32_t vid = base;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!((m >> a) & 1u)) continue;
+        const uint32_t j = i + stride[a];
+        if (vid < max_verts) {
+            const float v1 = vol[j];
+            float t = (level - v0) / (v1 - v0);
+            t = t != t ? 0.5f : fminf(fmaxf(t, 0.0f), 1.0f);
+            float p[3];
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                const float fi = (float)idx[b];
+                p[b] = b == a ? g.org[b] + (fi + t) * g.sp[b] : g.org[b] + fi * g.sp[b];
+            }
+            const uint64_t o = 3 * (uint64_t)vid;
+            verts[o] = p[0];
+            verts[o + 1] = p[1];
+            verts[o + 2] = p[2];
+            if (normals) {
+                float nv[3];
+#pragma unroll
+                for (int b = 0; b < 3; ++b) {
+                    const uint32_t jb = b == a ? idx[b] + 1 : idx[b];
+                    const float g0 = mc_grad(vol, i, idx[b], len[b], stride[b], g.sp[b]);
+                    const float g1 = mc_grad(vol, j, jb, len[b], stride[b], g.sp[b]);
+                    nv[b] = -(g0 + t * (g1 - g0));
+                }
+                const float l = sqrtf(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+                const float s = l > 0.0f ? l : 1.0f;
+                normals[o] = nv[0] / s;
+                normals[o + 1] = nv[1] / s;
+                normals[o + 2] = nv[2] / s;
+            }
+        }
+        ++vid;
+    }
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_mc_faces(uint32_t nx, uint32_t ny, uint32_t nz, const uint8_t *__restrict__ cases,
+                                                       const uint8_t *__restrict__ masks, const uint2 *__restrict__ sums,
+                                                       const uint32_t *__restrict__ flag, const uint32_t *__restrict__ vbase,
+                                                       int32_t *__restrict__ faces, uint32_t max_faces) {
+    __shared__ uint32_t red[MC_WAVES];
+    if (flag[0]) return;
+    const uint32_t nyz = ny * nz, n = nx * nyz;
+    const uint32_t i = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t c = i < n ? cases[i] : 0u;
+    const uint32_t nt = cn_mc_ntri[c];               // 0 for the points that own no cell (their case byte is 0)
+    const uint32_t base = sums[blockIdx.x].y + mc_block_prefix<3>(nt, red);
+    for (uint32_t k = 0; k < nt; ++k) {
+        const uint32_t f = base + k;
+        if (f >= max_faces) break;
+        int32_t tri[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const uint32_t e = (uint32_t)cn_mc_tri[c][3 * k + q];
+            const uint32_t corner = cn_mc_edge_corner[e], axis = cn_mc_edge_axis[e];
+            const uint32_t owner = i + (corner & 1u ? nyz : 0u) + (corner & 2u ? nz : 0u) + (corner & 4u ? 1u : 0u);
+            tri[q] = (int32_t)(vbase[owner] + (uint32_t)__popc(masks[owner] & ((1u << axis) - 1u)));
+        }
+        const uint64_t o = 3 * (uint64_t)f;
+        faces[o] = tri[0];
+        faces[o + 1] = tri[1];
+        faces[o + 2] = tri[2];
+    }
+}
+
+int mc_check_dims(uint32_t nx, uint32_t ny, uint32_t nz) {
+    if (nx < 2 || ny < 2 || nz < 2) return CNERF_EINVAL;
+    if ((uint64_t)nx * ny * nz >= (1ull << 31)) return CNERF_EINVAL;
+    return CNERF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cnerf_marching_cubes_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz, uint64_t *bytes_host) {
+    if (const int rc = mc_check_dims(nx, ny, nz)) return rc;
+    if (!bytes_host) return CNERF_ENULL;
+    *bytes_host = mc_layout((uint64_t)nx * ny * nz).total;
+    return CNERF_OK;
+}
+
+int cnerf_marching_cubes_count(const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, void *ws, uint64_t ws_bytes,
+                               uint32_t *counts, void *stream) {
+    if (const int rc = mc_check_dims(nx, ny, nz)) return rc;
+    if (!vol || !ws || !counts) return CNERF_ENULL;
+    const uint32_t n = nx * ny * nz;
+    const McLayout l = mc_layout(n);
+    if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return CNERF_EINVAL;
+    uint8_t *w = (uint8_t *)ws;
+    const uint32_t nblk = cn_div_up(n, MC_BLOCK);
+    hipLaunchKernelGGL(k_mc_count, dim3(nblk), dim3(MC_BLOCK), 0, CN_STREAM(stream), vol, nx, ny, nz, level, w + l.cases, w + l.masks,
+                       (uint2 *)(w + l.sums));
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, CN_STREAM(stream), (uint2 *)(w + l.sums), nblk, counts, (uint32_t *)w);
+    return cn_launch_status();
+}
+
+int cnerf_marching_cubes_emit(const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, const float *origin_host,
+                              const float *spacing_host, void *ws, uint64_t ws_bytes, float *verts, float *normals, int32_t *faces,
+                              uint32_t max_verts, uint32_t max_faces, void *stream) {
+    if (const int rc = mc_check_dims(nx, ny, nz)) return rc;
+    if (!vol || !origin_host || !spacing_host || !ws || (max_verts && !verts) || (max_faces && !faces)) return CNERF_ENULL;
+    const uint32_t n = nx * ny * nz;
+    const McLayout l = mc_layout(n);
+    if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return CNERF_EINVAL;
+    McGeom g;
+    for (int b = 0; b < 3; ++b) {
+        g.org[b] = origin_host[b];
+        g.sp[b] = spacing_host[b];
+    }
+    uint8_t *w = (uint8_t *)ws;
+    const uint32_t nblk = cn_div_up(n, MC_BLOCK);
+    hipLaunchKernelGGL(k_mc_verts, dim3(nblk), dim3(MC_BLOCK), 0, CN_STREAM(stream), vol, nx, ny, nz, level, g, (const uint8_t *)(w + l.masks),
+                       (const uint2 *)(w + l.sums), (const uint32_t *)w, (uint32_t *)(w + l.vbase), verts, max_verts ? normals : nullptr,
+                       max_verts);
+    hipLaunchKernelGGL(k_mc_faces, dim3(nblk), dim3(MC_BLOCK), 0, CN_STREAM(stream), nx, ny, nz, (const uint8_t *)(w + l.cases),
+                       (const uint8_t *)(w + l.masks), (const uint2 *)(w + l.sums), (const uint32_t *)w, (const uint32_t *)(w + l.vbase),
+                       faces, max_faces);
+    return cn_launch_status();
+}
+
+}  // extern "C"

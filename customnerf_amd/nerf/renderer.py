@@ -1,8 +1,9 @@
 """NeRFRenderer — counterpart of the hot-path part of the reference's nerf/renderer.py.
 
 Implemented (reference lines): sample_pdf (21-55), NeRFRenderer.__init__ (199-243), reset_extra_state (266-276),
-run (278-405), weights_sum_i (407-474), run_cuda (597-718), update_extra_state (1658-1715), render (1719-1733).
-Out of scope: the SDF/NeuS paths, mesh export, the unused run_cuda2 / render_cuda duplicates.
+run (278-405), weights_sum_i (407-474), run_cuda (597-718), update_extra_state (1658-1715), render (1719-1733),
+convert_sigma_samples_to_ply (128-196) and the density_mesh hook (251) as NeRFRenderer.extract_mesh / save_mesh (marching cubes in mesh.hip).
+Out of scope: the SDF/NeuS paths, the unused run_cuda2 / render_cuda duplicates.
 Every function here ends in HIP kernels (render.hip, raymarching.hip, occupancy.hip): there is no torch restatement of the
 reference's bodies in the product — that lives in oracle/torch_oracle.py, for the tests.
 
@@ -19,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import raymarching
+from .. import raymarching, mesh as _mesh
 from .._lib import lib, check, ptr, stream, require_cuda
 from . import render_ops
 
@@ -38,6 +39,25 @@ def sample_pdf(bins, weights, n_samples, det=False, u=None):
     out = torch.empty(B, n_samples, dtype=torch.float32, device=bins.device)
     check(lib.cnerf_sample_pdf(ptr(bins), ptr(weights), None if det else ptr(u.contiguous().float()), B, T, int(n_samples), ptr(out), stream()), "sample_pdf")
     return out
+
+
+def convert_sigma_samples_to_ply(input_3d_sigma_array, voxel_grid_origin, volume_size, ply_filename_out, level=5.0, offset=None, scale=None):
+    """renderer.py:128-196 with the marching cubes on the GPU (mesh.marching_cubes) and the PLY written by mesh.write_ply.
+    input_3d_sigma_array [X, Y, Z] (NumPy array or tensor); volume_size = the spacing per axis; the written points are
+    (origin + verts) / scale - offset.  Returns skimage-style (verts, faces, normals) NumPy arrays, verts = index * spacing (no origin)."""
+    vol = input_3d_sigma_array
+    vol = (vol if torch.is_tensor(vol) else torch.from_numpy(np.ascontiguousarray(vol))).float()
+    if not vol.is_cuda:
+        vol = vol.cuda()
+    verts, faces, normals = _mesh.marching_cubes(vol, level, spacing=tuple(volume_size), origin=(0.0, 0.0, 0.0))
+    verts, faces, normals = verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy()
+    mesh_points = verts + np.asarray(voxel_grid_origin, dtype=np.float32)
+    if scale is not None:
+        mesh_points = mesh_points / scale
+    if offset is not None:
+        mesh_points = mesh_points - offset
+    _mesh.write_ply(ply_filename_out, mesh_points, faces)
+    return verts, faces, normals
 
 
 class _Lazy:
@@ -420,6 +440,75 @@ class NeRFRenderer(nn.Module):
             _coll.all_reduce(tot)
             tot = tot / dist.get_world_size()
         return int(tot.item() / total_step)
+
+    # ------------------------------------------------------------------------------------------ mesh export (the reference's density_mesh hook, :251)
+    def _mesh_lattice(self, resolution, aabb):
+        aabb = (self.aabb_infer if aabb is None else torch.as_tensor(aabb, dtype=torch.float32)).detach().float().cpu().reshape(6)
+        lo, hi = aabb[:3], aabb[3:]
+        if resolution < 2 or not bool((hi > lo).all()):
+            raise ValueError(f"extract_mesh: need resolution >= 2 and a non-empty box, got {resolution} and {aabb.tolist()}")
+        return lo, (hi - lo) / (resolution - 1)
+
+    @torch.no_grad()
+    def density_volume(self, resolution=256, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0)):
+        """sigma on a resolution^3 lattice over `aabb` (default aabb_infer), [R, R, R] float32 in meshgrid('ij') order (z fastest).
+        part 'all': self.density(x) (the fused density pass).  part 'fg' / 'bg': sigma and confidence from forward(x, view_dir), masked as
+        run() masks the edit-region / background composites (renderer.py:386-395): soft mask sigmoid((conf - conf_thr) * 100) under
+        opt.soft_mask, otherwise conf > 0.5; a field without a confidence channel raises ValueError."""
+        if part not in ('all', 'fg', 'bg'):
+            raise ValueError(f"extract_mesh: part must be 'all', 'fg' or 'bg', got {part!r}")
+        R = int(resolution)
+        lo, step = self._mesh_lattice(R, aabb)
+        dev = self.aabb_infer.device
+        lo, step = lo.to(dev), step.to(dev)
+        n = R ** 3
+        vol = torch.empty(n, dtype=torch.float32, device=dev)
+        d = torch.tensor(view_dir, dtype=torch.float32, device=dev).reshape(1, 3)
+        soft, thr = bool(getattr(self.opt, 'soft_mask', False)), float(getattr(self.opt, 'conf_thr', 0.5))
+        for s in range(0, n, chunk):
+            i = torch.arange(s, min(s + chunk, n), device=dev, dtype=torch.int64)
+            ijk = torch.stack([i // (R * R), (i // R) % R, i % R], dim=1).float()
+            x = (lo + ijk * step).contiguous()
+            if part == 'all':
+                vol[s:s + len(i)] = self.density(x)['sigma'].reshape(-1).float()
+                continue
+            sigma, rgbc = self(x, d.expand(len(i), 3).contiguous())[:2]
+            if rgbc.shape[-1] < 4:
+                raise ValueError("extract_mesh: part='fg' / 'bg' needs a field with a confidence channel (opt.train_conf)")
+            sigma, conf = sigma.reshape(-1).float(), rgbc[:, 3].float()
+            if soft:
+                m = torch.sigmoid((conf - thr) * 100)
+                vol[s:s + len(i)] = sigma * m if part == 'fg' else sigma * (1 - m)
+            else:
+                m = conf > 0.5
+                vol[s:s + len(i)] = torch.where(m if part == 'fg' else ~m, sigma, torch.zeros_like(sigma))
+        return vol.view(R, R, R)
+
+    @torch.no_grad()
+    def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False):
+        """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
+        aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
+        each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
+        coordinates), faces [F, 3] int32 (wound outwards), normals [V, 3] (outward), colors [V, 3] uint8 or None, and the volume."""
+        threshold = float(self.opt.density_thresh if threshold is None else threshold)
+        R = int(resolution)
+        lo, step = self._mesh_lattice(R, aabb)
+        vol = self.density_volume(R, aabb, chunk, part, view_dir)
+        verts, faces, normals = _mesh.marching_cubes(vol, threshold, spacing=step.tolist(), origin=lo.tolist())
+        colors = None
+        if color:
+            colors = torch.empty(verts.shape[0], 3, dtype=torch.uint8, device=verts.device)
+            for s in range(0, verts.shape[0], chunk):
+                x = verts[s:s + chunk].contiguous()
+                rgb = self(x, (-normals[s:s + chunk]).contiguous())[1][:, :3].float()
+                colors[s:s + chunk] = (rgb.clamp(0, 1) * 255).round().to(torch.uint8)
+        return {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold}
+
+    def save_mesh(self, path, **kw):
+        """extract_mesh(**kw) written as a binary PLY (mesh.write_ply: positions, normals, and colours when color=True) -> the mesh dict"""
+        m = self.extract_mesh(**kw)
+        _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=m['colors'])
+        return m
 
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=2048, **kwargs):
         """renderer.py:1719-1733."""

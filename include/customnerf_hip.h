@@ -34,8 +34,9 @@ extern "C" {
  * 2: the GroupNorm / GEMM-epilogue statistics buffers of customnerf_sd.h are int64[B][G][2] fixed point (were float[B][G][2]).
  * 4: struct CnerfSdGemm grew the ln_* fields (LayerNorm of the output rows in the split-K tail); new entry points
  *    cnerf_grid_encode_forward_ordered, cnerf_sd_concat_gn, cnerf_sd_gemm_serves_ln, cnerf_profile_stage_events.
- * 6: the plan in pieces is gone — the _block / _rows / _finish variants of cnerf_grid_encode_backward_prepare (no shape took them since ABI 5). */
-#define CNERF_ABI_VERSION 6
+ * 6: the plan in pieces is gone — the _block / _rows / _finish variants of cnerf_grid_encode_backward_prepare (no shape took them since ABI 5).
+ * 7: mesh extraction — cnerf_marching_cubes_workspace_bytes / _count / _emit. */
+#define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
 const char *cnerf_target_arch(void);
@@ -493,6 +494,29 @@ int cnerf_adam_step_scaled_multi(const CnerfAdamJobs *jobs, float beta1, float b
  * ---------------------------------------------------------------------------------------------- */
 int cnerf_dp_pack(float *grad, void *payload_half, uint64_t n, float scale, void *stream);
 int cnerf_dp_reduce(const void *recv_half, uint32_t world, uint64_t shard, float *out, float *scaler_state, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Marching cubes over a dense volume (mesh export: customnerf_amd/mesh.py; the reference's convert_sigma_samples_to_ply,
+ * nerf/renderer.py:128-196, calls skimage.measure.marching_cubes on the host).
+ * vol float32 [nx][ny][nz] (z fastest, meshgrid('ij') order); corner inside <=> v >= level (NaN: outside); one vertex per crossing edge
+ * (p, p + e_axis), owned by p.  Case table: csrc/mc_tables.h (generated by csrc/gen_mc_tables.py; crack-free for any input).
+ *   workspace_bytes : bytes of the workspace `ws` (about 6 per grid point).  nx, ny, nz >= 2 and nx * ny * nz < 2^31, else CNERF_EINVAL.
+ *   count           : counts[2] (device uint32) = (vertices, triangles); both 0xffffffff if either exceeds INT32_MAX (emit then writes nothing).
+ *                     ws (16-byte aligned, >= workspace_bytes, else CNERF_EINVAL) keeps the per-point state that emit reads.
+ *   emit            : after count on the same stream with the same ws and level.  verts [V,3], normals [V,3] (NULL: none), faces [F,3] int32;
+ *                     entries at or past max_verts / max_faces are not written (verts / faces may be NULL when their max is 0).
+ *                     Vertices in (linear point index, axis) order: t = clamp((level - v0) / (v1 - v0), 0, 1) (NaN t: 0.5),
+ *                     pos = origin + (idx + t) * spacing on the crossing axis and origin + idx * spacing on the others.  Normals: -(g0 + t (g1 - g0))
+ *                     normalised, g = central differences of vol / spacing (one-sided on the volume's faces), i.e. towards lower values.
+ *                     Triangles in (linear cell index, table order), winding (v1 - v0) x (v2 - v0) from inside to outside.
+ * origin_host / spacing_host: float[3] on the host.  No atomics: the output is bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_marching_cubes_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz, uint64_t *bytes_host);
+int cnerf_marching_cubes_count(const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, void *ws, uint64_t ws_bytes,
+                               uint32_t *counts, void *stream);
+int cnerf_marching_cubes_emit(const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, const float *origin_host,
+                              const float *spacing_host, void *ws, uint64_t ws_bytes, float *verts, float *normals, int32_t *faces,
+                              uint32_t max_verts, uint32_t max_faces, void *stream);
 
 #ifdef __cplusplus
 }
