@@ -90,6 +90,12 @@ SIGNATURES = {
     "cnerf_marching_cubes_workspace_bytes": [u32, u32, u32, vp],
     "cnerf_marching_cubes_count": [vp, u32, u32, u32, f32, vp, u64, vp, vp],
     "cnerf_marching_cubes_emit": [vp, u32, u32, u32, f32, vp, vp, vp, u64, vp, vp, vp, u32, u32, vp],
+    "cnerf_mesh_components_workspace_bytes": [u32, u32, vp],
+    "cnerf_mesh_components_count": [vp, u32, u32, u32, i32, vp, u64, vp, vp],
+    "cnerf_mesh_components_emit": [vp, vp, u32, vp, u32, u32, i32, vp, u64, vp, vp, vp, vp, u32, u32, vp],
+    "cnerf_mesh_cluster_workspace_bytes": [u32, u32, vp, vp],
+    "cnerf_mesh_cluster_count": [vp, u32, vp, u32, vp, vp, vp, vp, u64, vp, vp],
+    "cnerf_mesh_cluster_emit": [vp, vp, u32, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp, u32, u32, vp],
     # ---- include/customnerf_sd.h (score-distillation primitives)
     "cnerf_sd_gemm": [vp, vp, u64, vp],
     "cnerf_sd_gemm_workspace_bytes": [vp, vp],

@@ -12,11 +12,7 @@
 // scheduling.  Workspace: header (overflow flag) | case bytes [N] | mask bytes [N] | vertex bases uint32 [N] | workgroup totals uint2 [N/256].
 #include "common.h"
 #include "mc_tables.h"
-
-#define MC_BLOCK 256
-#define MC_WAVES (MC_BLOCK / CN_WAVE)
-#define MC_SCAN_BLOCK 1024
-#define MC_SCAN_PER_THREAD 4
+#include "mesh_scan.h"          // MC_BLOCK, mc_block_prefix / mc_block_total, mc_scan_totals
 
 namespace {
 
@@ -39,39 +35,6 @@ McLayout mc_layout(uint64_t n) {
 struct McGeom {
     float org[3], sp[3];
 };
-
-__device__ __forceinline__ uint32_t mc_rank(uint64_t ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// exclusive prefix of v (< 2^BITS) over the workgroup in thread order; every thread of the block must call it.  `red` = LDS [MC_WAVES]
-template <int BITS>
-__device__ __forceinline__ uint32_t mc_block_prefix(uint32_t v, uint32_t *red) {
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < BITS; ++k) {
-        const uint64_t b = __ballot((v >> k) & 1u);
-        pre += mc_rank(b) << k;
-        tot += (uint32_t)__popcll(b) << k;
-    }
-    const uint32_t w = threadIdx.x / CN_WAVE;
-    if (cn_lane() == 0) red[w] = tot;
-    __syncthreads();
-    for (uint32_t j = 0; j < w; ++j) pre += red[j];
-    return pre;
-}
-
-template <int BITS>
-__device__ __forceinline__ uint32_t mc_block_total(uint32_t v, uint32_t *red) {
-    uint32_t tot = 0;
-#pragma unroll
-    for (int k = 0; k < BITS; ++k) tot += (uint32_t)__popcll(__ballot((v >> k) & 1u)) << k;
-    if (cn_lane() == 0) red[threadIdx.x / CN_WAVE] = tot;
-    __syncthreads();
-    uint32_t s = 0;
-    for (int j = 0; j < MC_WAVES; ++j) s += red[j];
-    return s;
-}
 
 __device__ __forceinline__ bool mc_in(float v, float level) { return v >= level; }   // NaN: outside
 
@@ -108,39 +71,8 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_count(const float *__restrict__
 // one workgroup; sums[0..nblk) -> exclusive offsets in place; counts = totals, or 0xffffffff both (and flag = 1) when either exceeds INT32_MAX
 __global__ __launch_bounds__(MC_SCAN_BLOCK) void k_mc_scan(uint2 *__restrict__ sums, uint32_t nblk, uint32_t *__restrict__ counts,
                                                            uint32_t *__restrict__ flag) {
-    __shared__ uint32_t wv[MC_SCAN_BLOCK / CN_WAVE], wt[MC_SCAN_BLOCK / CN_WAVE];
-    const uint32_t nw = MC_SCAN_BLOCK / CN_WAVE, w = threadIdx.x / CN_WAVE, lane = cn_lane();
-    uint64_t cv = 0, ct = 0;                         // carry: totals of the tiles before this one
-    for (uint32_t base = 0; base < nblk; base += MC_SCAN_BLOCK * MC_SCAN_PER_THREAD) {
-        const uint32_t j0 = base + threadIdx.x * MC_SCAN_PER_THREAD;
-        uint2 e[MC_SCAN_PER_THREAD];
-        uint32_t sv = 0, st = 0;
-#pragma unroll
-        for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
-            e[k] = j0 + k < nblk ? sums[j0 + k] : make_uint2(0, 0);
-            sv += e[k].x;
-            st += e[k].y;
-        }
-        const uint32_t iv = cn_wave_incl_scan(sv), it = cn_wave_incl_scan(st);
-        if (lane == CN_WAVE - 1) { wv[w] = iv; wt[w] = it; }
-        __syncthreads();
-        uint32_t ov = iv - sv, ot = it - st, tile_v = 0, tile_t = 0;
-        for (uint32_t j = 0; j < nw; ++j) {
-            if (j < w) { ov += wv[j]; ot += wt[j]; }
-            tile_v += wv[j];
-            tile_t += wt[j];
-        }
-        __syncthreads();                             // wv / wt are rewritten by the next tile
-        uint64_t pv = cv + ov, pt = ct + ot;
-#pragma unroll
-        for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
-            if (j0 + k < nblk) sums[j0 + k] = make_uint2((uint32_t)pv, (uint32_t)pt);
-            pv += e[k].x;
-            pt += e[k].y;
-        }
-        cv += tile_v;
-        ct += tile_t;
-    }
+    uint64_t cv, ct;
+    mc_scan_totals(sums, nblk, cv, ct);
     if (threadIdx.x == 0) {
         const bool over = cv > 0x7fffffffull || ct > 0x7fffffffull;
         counts[0] = over ? 0xffffffffu : (uint32_t)cv;

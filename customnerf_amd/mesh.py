@@ -1,4 +1,5 @@
-"""Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*) and a binary PLY writer.
+"""Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*), mesh cleanup on the GPU (csrc/mesh_clean.hip:
+removal of small connected components, simplification by vertex clustering) and a binary PLY writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -53,6 +54,114 @@ def marching_cubes(volume, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0
     check(lib.cnerf_marching_cubes_emit(ptr(vol), nx, ny, nz, level, org, sp, ptr(ws), nbytes, ptr(verts) if V else None,
                                         ptr(nrm) if V else None, ptr(faces) if F else None, V, F, stream()), "marching_cubes_emit")
     return verts, faces, nrm
+
+
+def _mesh_args(verts, faces, normals, what):
+    require_cuda(verts, faces, normals)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: verts and faces must be [V, 3] and [F, 3], got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    if normals is not None and tuple(normals.shape) != tuple(verts.shape):
+        raise ValueError(f"{what}: normals must be [V, 3] like verts, got {tuple(normals.shape)}")
+    v = verts.detach().contiguous().float()
+    f = faces.detach().contiguous().to(torch.int32)
+    n = None if normals is None else normals.detach().contiguous().float()
+    return v, f, n
+
+
+def _counts(counts, what):
+    V, F, flags = (int(c) & 0xffffffff for c in counts.cpu())                  # the one host read
+    if flags & 1:
+        raise ValueError(f"{what}: a face index lies outside [0, V)")
+    return V, F
+
+
+def components_workspace_bytes(V, F):
+    out = C.c_uint64(0)
+    check(lib.cnerf_mesh_components_workspace_bytes(int(V), int(F), C.byref(out)), "mesh_components_workspace_bytes")
+    return out.value
+
+
+def remove_small_components(verts, faces, normals=None, min_faces=1, largest=False):
+    """Drop the connected components (vertices joined by a face) with fewer than `min_faces` faces — and, with largest=True, every component
+    but the one with the most faces (the one holding the smallest vertex index on a tie).  A vertex no face references is a 0-face component.
+    CUDA tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None.  Kept vertices and faces keep their order.
+    -> (verts [V', 3] float32, faces [F', 3] int32, normals [V', 3] or None, old_index [V'] int32: input index of each output vertex).
+    A face index outside [0, V) raises ValueError."""
+    v, f, n = _mesh_args(verts, faces, normals, "remove_small_components")
+    V, F = v.shape[0], f.shape[0]
+    mf = int(min_faces)
+    if mf < 0 or mf >= 2 ** 32:
+        raise ValueError(f"remove_small_components: min_faces must be in [0, 2^32), got {min_faces}")
+    dev = v.device
+    nbytes = components_workspace_bytes(V, F)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    lg = 1 if largest else 0
+    check(lib.cnerf_mesh_components_count(ptr(f) if F else None, V, F, mf, lg, ptr(ws), nbytes, ptr(counts), stream()),
+          "mesh_components_count")
+    V2, F2 = _counts(counts, "remove_small_components")
+    vo = torch.empty(V2, 3, dtype=torch.float32, device=dev)
+    no = torch.empty(V2, 3, dtype=torch.float32, device=dev) if n is not None else None
+    fo = torch.empty(F2, 3, dtype=torch.int32, device=dev)
+    old = torch.empty(V2, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_components_emit(ptr(v) if V else None, ptr(n) if V and n is not None else None, V, ptr(f) if F else None, F, mf, lg,
+                                         ptr(ws), nbytes, ptr(vo) if V2 else None, ptr(no) if V2 and no is not None else None,
+                                         ptr(fo) if F2 else None, ptr(old) if V2 else None, V2, F2, stream()), "mesh_components_emit")
+    return vo, fo, no, old
+
+
+def cluster_grid(verts, cell, origin=None):
+    """(origin float32 [3], cell float32 [3], grid (gx, gy, gz)) of simplify(): `origin` defaults to the vertices' minimum, and the grid
+    reaches the cell of the maximum under simplify's float32 cell formula."""
+    c = np.array(cell if np.ndim(cell) else (cell, cell, cell), dtype=np.float32).reshape(3)
+    if not (np.isfinite(c).all() and (c > 0).all()):
+        raise ValueError(f"simplify: cell must be finite and > 0, got {cell}")
+    if verts.shape[0] == 0:
+        o = np.zeros(3, np.float32) if origin is None else np.array(origin, dtype=np.float32).reshape(3)
+        return o, c, (1, 1, 1)
+    lo, hi = (t.cpu().numpy().astype(np.float32) for t in torch.aminmax(verts.detach().float(), dim=0))
+    o = lo if origin is None else np.array(origin, dtype=np.float32).reshape(3)
+    if not (np.isfinite(o).all() and np.isfinite(hi).all()):
+        raise ValueError("simplify: origin and vertices must be finite")
+    top = np.floor((hi - o) / c)
+    g = tuple(int(max(t, 0.0)) + 1 for t in top)
+    return o, c, g
+
+
+def cluster_workspace_bytes(V, F, grid):
+    out = C.c_uint64(0)
+    check(lib.cnerf_mesh_cluster_workspace_bytes(int(V), int(F), (C.c_uint32 * 3)(*grid), C.byref(out)), "mesh_cluster_workspace_bytes")
+    return out.value
+
+
+def simplify(verts, faces, cell, normals=None, origin=None, grid=None):
+    """Vertex clustering with a quadric representative (Lindstrom 2000) on a grid of cells of edge `cell` (scalar or per axis) from `origin`
+    (default: the vertices' minimum) — grid = (gx, gy, gz) cells, by default enough to reach the vertices' maximum.  One output vertex per
+    occupied cell, in linear cell order: the minimiser of the cell's face quadrics (clamped to the cell); normals = normalised mean of the
+    members'.  Faces are mapped to clusters; faces with two equal clusters and repeats of an unordered cluster triple are dropped.
+    -> (verts [K, 3] float32, faces [F', 3] int32, normals [K, 3] or None).  A face index outside [0, V) raises ValueError."""
+    v, f, n = _mesh_args(verts, faces, normals, "simplify")
+    V, F = v.shape[0], f.shape[0]
+    o, c, g = cluster_grid(v, cell, origin)
+    if grid is not None:
+        g = tuple(int(x) for x in grid)
+    if len(g) != 3 or min(g) < 1 or g[0] * g[1] * g[2] >= 2 ** 31:
+        raise ValueError(f"simplify: the grid {g} needs 1 <= g and gx * gy * gz < 2^31 (a larger cell)")
+    dev = v.device
+    og, cg, gg = (C.c_float * 3)(*o.tolist()), (C.c_float * 3)(*c.tolist()), (C.c_uint32 * 3)(*g)
+    nbytes = cluster_workspace_bytes(V, F, g)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_cluster_count(ptr(v) if V else None, V, ptr(f) if F else None, F, og, cg, gg, ptr(ws), nbytes, ptr(counts), stream()),
+          "mesh_cluster_count")
+    K, F2 = _counts(counts, "simplify")
+    vo = torch.empty(K, 3, dtype=torch.float32, device=dev)
+    no = torch.empty(K, 3, dtype=torch.float32, device=dev) if n is not None else None
+    fo = torch.empty(F2, 3, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_cluster_emit(ptr(v) if V else None, ptr(n) if V and n is not None else None, V, ptr(f) if F else None, F, og, cg, gg,
+                                      ptr(ws), nbytes, ptr(vo) if K else None, ptr(no) if K and no is not None else None,
+                                      ptr(fo) if F2 else None, K, F2, stream()), "mesh_cluster_emit")
+    return vo, fo, no
 
 
 def _host(a, dtype):

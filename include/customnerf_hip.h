@@ -35,7 +35,8 @@ extern "C" {
  * 4: struct CnerfSdGemm grew the ln_* fields (LayerNorm of the output rows in the split-K tail); new entry points
  *    cnerf_grid_encode_forward_ordered, cnerf_sd_concat_gn, cnerf_sd_gemm_serves_ln, cnerf_profile_stage_events.
  * 6: the plan in pieces is gone — the _block / _rows / _finish variants of cnerf_grid_encode_backward_prepare (no shape took them since ABI 5).
- * 7: mesh extraction — cnerf_marching_cubes_workspace_bytes / _count / _emit. */
+ * 7: mesh extraction — cnerf_marching_cubes_workspace_bytes / _count / _emit; mesh cleanup (additive, same version: a binding that
+ *    needs them fails at load on the missing symbol) — cnerf_mesh_components_* and cnerf_mesh_cluster_* (workspace_bytes / _count / _emit). */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -517,6 +518,48 @@ int cnerf_marching_cubes_count(const float *vol, uint32_t nx, uint32_t ny, uint3
 int cnerf_marching_cubes_emit(const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, const float *origin_host,
                               const float *spacing_host, void *ws, uint64_t ws_bytes, float *verts, float *normals, int32_t *faces,
                               uint32_t max_verts, uint32_t max_faces, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh cleanup (customnerf_amd/mesh.py remove_small_components / simplify; csrc/mesh_clean.hip; the reference has none — NeRF-to-mesh tools
+ * do it on the host).  Any triangle mesh: verts float32 [V][3], optional normals float32 [V][3] (NULL: none), faces int32 [F][3].
+ * V, F < 2^31, else CNERF_EINVAL.  Two passes on `stream` like marching cubes: count writes counts[3] (device uint32) =
+ * (vertices, faces, flags) — the one host read — and emit, after count on the same stream with the same ws and arguments, writes the
+ * output; entries at or past max_verts / max_faces are not written (outputs may be NULL when their max is 0).  flags bit 0: some face
+ * index lies outside [0, V); emit then writes nothing.  ws: 16-byte aligned, >= workspace_bytes, else CNERF_EINVAL.
+ * The output does not depend on scheduling: integer atomics only, compaction by scan, input order kept.
+ *
+ * components : two vertices are connected when a face holds both; the label of a component is its smallest vertex index.  Component c is
+ *              kept iff faces(c) >= min_faces and, when `largest` != 0, c has the most faces (the smaller label on a tie) and at least one.
+ *              faces(c) counts the faces whose first vertex is in c; an unreferenced vertex is a 0-face component.  min_faces = 0 with
+ *              largest = 0 keeps everything.  Kept vertices and faces keep their input order; faces are remapped to the new indices.
+ *   workspace_bytes : about 12 bytes per vertex + 8 per 256 of max(V, F).
+ *   emit            : verts_out [V'][3], normals_out [V'][3] (written when normals != NULL), faces_out [F'][3],
+ *                     old_index [V'] int32 (NULL: none) = the input index of each output vertex.
+ *
+ * cluster    : vertex clustering with a quadric representative (Lindstrom 2000).  Grid grid_host[3] = (gx, gy, gz) >= 1 cells of edge
+ *              cell_host[3] (finite, > 0) from origin_host[3] (finite), gx * gy * gz < 2^31, else CNERF_EINVAL.  The cluster of vertex p is
+ *              clamp(floor((p - origin) / cell), 0, g - 1) per axis in float32 (NaN -> 0); output vertex i is the i-th occupied cell in
+ *              linear order (x slowest, z fastest).  Its position: in the cell's frame u = (p - corner) / cell, x = xbar + A+ (-b - A xbar),
+ *              xbar the members' mean, (A, b) the sum of a n n^T, a n d over the faces of nonzero area a with a vertex in the cluster (plane
+ *              n . u + d = 0 through the face's first vertex), A+ without eigenvalues < 1e-3 of the largest; x clamped to [0, 1]^3.  Sums are
+ *              64-bit fixed point (bounds: mesh_clean.hip).  Normals: the normalised sum of the members' normals.  Faces map to the clusters
+ *              of their vertices in input winding; a face with two equal clusters is dropped, and of the faces with one unordered cluster
+ *              triple only the first survives.  Survivors keep input order.
+ *   workspace_bytes : 4 bytes per vertex + 5 per cell + 12 to 20 per face + 132 per possible cluster (min(V, G)).
+ *   emit            : verts_out [K][3], normals_out [K][3] (written when normals != NULL), faces_out [F'][3].
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_components_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_components_count(const int32_t *faces, uint32_t V, uint32_t F, uint32_t min_faces, int largest, void *ws, uint64_t ws_bytes,
+                                uint32_t *counts, void *stream);
+int cnerf_mesh_components_emit(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t min_faces,
+                               int largest, void *ws, uint64_t ws_bytes, float *verts_out, float *normals_out, int32_t *faces_out,
+                               int32_t *old_index, uint32_t max_verts, uint32_t max_faces, void *stream);
+int cnerf_mesh_cluster_workspace_bytes(uint32_t V, uint32_t F, const uint32_t *grid_host, uint64_t *bytes_host);
+int cnerf_mesh_cluster_count(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, const float *origin_host, const float *cell_host,
+                             const uint32_t *grid_host, void *ws, uint64_t ws_bytes, uint32_t *counts, void *stream);
+int cnerf_mesh_cluster_emit(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, const float *origin_host,
+                            const float *cell_host, const uint32_t *grid_host, void *ws, uint64_t ws_bytes, float *verts_out, float *normals_out,
+                            int32_t *faces_out, uint32_t max_verts, uint32_t max_faces, void *stream);
 
 #ifdef __cplusplus
 }
