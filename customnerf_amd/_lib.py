@@ -96,6 +96,10 @@ SIGNATURES = {
     "cnerf_mesh_cluster_workspace_bytes": [u32, u32, vp, vp],
     "cnerf_mesh_cluster_count": [vp, u32, vp, u32, vp, vp, vp, vp, u64, vp, vp],
     "cnerf_mesh_cluster_emit": [vp, vp, u32, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp, u32, u32, vp],
+    "cnerf_mesh_decimate_workspace_bytes": [u32, u32, vp],
+    "cnerf_mesh_decimate_init": [vp, u32, vp, u32, vp, u64, vp, vp],
+    "cnerf_mesh_decimate_round": [u32, u32, u32, vp, u64, vp, vp],
+    "cnerf_mesh_decimate_emit": [vp, u32, u32, vp, u64, vp, vp, vp, vp, u32, u32, vp],
     # ---- include/customnerf_sd.h (score-distillation primitives)
     "cnerf_sd_gemm": [vp, vp, u64, vp],
     "cnerf_sd_gemm_workspace_bytes": [vp, vp],

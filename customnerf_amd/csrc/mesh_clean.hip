@@ -25,8 +25,8 @@
 //   k_cl_ids    : (emit) cluster id of every occupied cell, its cell, and its sums zeroed
 //   k_cl_vsum   : per vertex: local position (relative to its cell's corner, in cell units), count and normal, added in fixed point
 //   k_cl_fsum   : per face of nonzero area: its area-weighted plane quadric (A = a n n^T, b = a n d), in each distinct cluster's local frame
-//   k_cl_solve  : per cluster in fp64: x = xbar + A+ (-b - A xbar), A+ from a 3x3 Jacobi eigen-solve without eigenvalues < 1e-3 lambda_max,
-//                 clamped to the cell; normal = normalised sum of the member normals
+//   k_cl_solve  : per cluster in fp64: x = xbar + A+ (-b - A xbar), A+ from a 3x3 Jacobi eigen-solve without eigenvalues < 1e-3 lambda_max
+//                 (mesh_qef.h), clamped to the cell; normal = normalised sum of the member normals
 //   k_cl_faces  : survivors in input order, remapped to cluster ids in their input winding
 //
 // Fixed point (exact integer sums, order-independent: docs/HARDWARE_FACTS.md A.2; no float atomics).  Counts are < 2^31.
@@ -37,6 +37,7 @@
 //     A marching-cubes face under cells of >= 2 lattice steps has a < 1 and |d| < 3; a cluster collects a few hundred of them.
 #include "common.h"
 #include "mesh_scan.h"
+#include "mesh_qef.h"
 
 #define CC_BAD_INDEX 1u
 #define CL_NONE 0xffffffffu
@@ -44,7 +45,6 @@
 #define CL_SN 268435456.0                            // 2^28: normals
 #define CL_SQ 4294967296.0                           // 2^32: quadric entries
 #define CL_ACC 16                                    // int64 per cluster: A00 A01 A02 A11 A12 A22 | b0 b1 b2 | u0 u1 u2 | n0 n1 n2 | count
-#define CL_EIG_CUT 1e-3
 
 namespace {
 
@@ -458,44 +458,6 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cl_fsum(const float *__restrict__ 
     }
 }
 
-// eigen-decomposition of the symmetric 3x3 s (s00 s01 s02 s11 s12 s22) by cyclic Jacobi: w = eigenvalues, columns of v = eigenvectors
-__device__ void cl_jacobi(const double s[6], double w[3], double v[3][3]) {
-    double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 32; ++sweep) {
-        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-        const double dia = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
-        if (!(off > 1e-36 * dia)) break;
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-            if (a[p][q] == 0.0) continue;
-            const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-            for (int k = 0; k < 3; ++k) {            // a <- a J (columns p, q)
-                const double akp = a[k][p], akq = a[k][q];
-                a[k][p] = c * akp - sn * akq;
-                a[k][q] = sn * akp + c * akq;
-            }
-            for (int k = 0; k < 3; ++k) {            // a <- J^T a (rows p, q)
-                const double apk = a[p][k], aqk = a[q][k];
-                a[p][k] = c * apk - sn * aqk;
-                a[q][k] = sn * apk + c * aqk;
-            }
-            for (int k = 0; k < 3; ++k) {
-                const double vkp = v[k][p], vkq = v[k][q];
-                v[k][p] = c * vkp - sn * vkq;
-                v[k][q] = sn * vkp + c * vkq;
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) w[i] = a[i][i];
-}
-
 __global__ __launch_bounds__(MC_BLOCK) void k_cl_solve(ClGeom g, const uint32_t *__restrict__ ccell, const int64_t *__restrict__ acc,
                                                        const uint32_t *__restrict__ hdr, int has_normals, float *__restrict__ verts_out,
                                                        float *__restrict__ normals_out, uint32_t max_verts) {
@@ -512,22 +474,8 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cl_solve(ClGeom g, const uint32_t 
         b[j] = (double)a[6 + j] / CL_SQ;
         xb[j] = (double)a[9 + j] / CL_SP / cnt;
     }
-    double w[3], v[3][3];
-    cl_jacobi(s, w, v);
-    const double wmax = fmax(w[0], fmax(w[1], w[2]));
-    // r = -b - A xbar; x = xbar + sum over kept eigenpairs of v (v . r) / w
-    const double r[3] = {-b[0] - (s[0] * xb[0] + s[1] * xb[1] + s[2] * xb[2]), -b[1] - (s[1] * xb[0] + s[3] * xb[1] + s[4] * xb[2]),
-                         -b[2] - (s[2] * xb[0] + s[4] * xb[1] + s[5] * xb[2])};
-    double x[3] = {xb[0], xb[1], xb[2]};
-    if (wmax > 0.0) {
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            if (!(w[e] >= CL_EIG_CUT * wmax)) continue;
-            const double c = (v[0][e] * r[0] + v[1][e] * r[1] + v[2][e] * r[2]) / w[e];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) x[j] += c * v[j][e];
-        }
-    }
+    double x[3];
+    qef_solve(s, b, xb, x);
     double o[3];
     cl_corner(ccell[k], g, o);
     const uint64_t d = 3 * (uint64_t)k;

@@ -1,5 +1,6 @@
 """Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*), mesh cleanup on the GPU (csrc/mesh_clean.hip:
-removal of small connected components, simplification by vertex clustering) and a binary PLY writer.
+removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
+face count) and a binary PLY writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -162,6 +163,61 @@ def simplify(verts, faces, cell, normals=None, origin=None, grid=None):
                                       ptr(ws), nbytes, ptr(vo) if K else None, ptr(no) if K and no is not None else None,
                                       ptr(fo) if F2 else None, K, F2, stream()), "mesh_cluster_emit")
     return vo, fo, no
+
+
+def decimate_workspace_bytes(V, F):
+    out = C.c_uint64(0)
+    check(lib.cnerf_mesh_decimate_workspace_bytes(int(V), int(F), C.byref(out)), "mesh_decimate_workspace_bytes")
+    return out.value
+
+
+_DECIMATE_FLAGS = ((1, "a face index lies outside [0, V)"), (2, "an edge lies in more than two faces or two faces use it in one direction"),
+                   (4, "a face repeats a vertex index"))
+
+
+def decimate(verts, faces, target_faces, normals=None, rounds=None):
+    """Quadric edge-collapse decimation (Garland & Heckbert 1997) on the device to `target_faces` faces, in parallel rounds of independent
+    collapses (csrc/mesh_decimate.hip; the rules are in include/customnerf_hip.h).  The mesh must be edge-manifold and consistently oriented
+    with no face repeating an index, as marching cubes and remove_small_components give; boundary vertices stay where they are, the genus is
+    kept.  Stops at F <= target_faces (then F is target_faces or one less) or when no valid collapse is left (F stays above the target).
+    CUDA tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None.  -> (verts [V', 3] float32, faces [F', 3] int32 (surviving input
+    faces in input order), normals [V', 3] (normals[old_index]) or None, old_index [V'] int32).  Unreferenced vertices are dropped.
+    rounds: a list that receives counts (referenced vertices, faces, collapses) after each round.  Bad input raises ValueError."""
+    v, f, n = _mesh_args(verts, faces, normals, "decimate")
+    V, F = v.shape[0], f.shape[0]
+    target = int(target_faces)
+    if target < 0 or target >= 2 ** 32:
+        raise ValueError(f"decimate: target_faces must be in [0, 2^32), got {target_faces}")
+    dev = v.device
+    nbytes = decimate_workspace_bytes(V, F)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+
+    def read():
+        r = [int(c) & 0xffffffff for c in counts.cpu()]                         # the one host read per call
+        for bit, what in _DECIMATE_FLAGS:
+            if r[3] & bit:
+                raise ValueError(f"decimate: {what}")
+        return r
+
+    check(lib.cnerf_mesh_decimate_init(ptr(v) if V else None, V, ptr(f) if F else None, F, ptr(ws), nbytes, ptr(counts), stream()),
+          "mesh_decimate_init")
+    nv, nf, _, _ = read()
+    while nf > target:
+        check(lib.cnerf_mesh_decimate_round(V, nf, target, ptr(ws), nbytes, ptr(counts), stream()), "mesh_decimate_round")
+        nv, nf, done, _ = read()
+        if rounds is not None:
+            rounds.append((nv, nf, done))
+        if done == 0:
+            break
+    vo = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    no = torch.empty(nv, 3, dtype=torch.float32, device=dev) if n is not None else None
+    fo = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    old = torch.empty(nv, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_decimate_emit(ptr(n) if V and n is not None else None, V, nf, ptr(ws), nbytes, ptr(vo) if nv else None,
+                                       ptr(no) if nv and no is not None else None, ptr(fo) if nf else None, ptr(old) if nv else None,
+                                       nv, nf, stream()), "mesh_decimate_emit")
+    return vo, fo, no, old
 
 
 def _host(a, dtype):

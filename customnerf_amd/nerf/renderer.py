@@ -486,15 +486,16 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
-                     min_component_faces=0, keep_largest=False, simplify=0):
+                     min_component_faces=0, keep_largest=False, simplify=0, target_faces=0):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
         coordinates), faces [F, 3] int32 (wound outwards), normals [V, 3] (outward), colors [V, 3] uint8 or None, and the volume.
         Cleanup on the device (mesh.py, csrc/mesh_clean.hip), in this order, before the colours are sampled at the final vertices:
         min_component_faces > 0 drops the connected components with fewer faces (floaters); keep_largest=True keeps only the component with
-        the most faces; simplify=k >= 2 clusters the vertices in cells of k lattice steps from the lattice's lower corner (mesh.simplify).
-        The defaults return the marching-cubes mesh as it is."""
+        the most faces; simplify=k >= 2 clusters the vertices in cells of k lattice steps from the lattice's lower corner (mesh.simplify);
+        target_faces > 0 decimates by quadric edge collapse to that many faces (mesh.decimate; not with simplify, whose output need not be
+        manifold).  The defaults return the marching-cubes mesh as it is."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -503,12 +504,19 @@ class NeRFRenderer(nn.Module):
         k = int(simplify)
         if k == 1 or k < 0:
             raise ValueError(f"extract_mesh: simplify must be 0 (off) or a cluster size >= 2 lattice steps, got {simplify}")
+        tf = int(target_faces)
+        if tf < 0:
+            raise ValueError(f"extract_mesh: target_faces must be 0 (off) or a face count, got {target_faces}")
+        if tf and k:
+            raise ValueError("extract_mesh: target_faces and simplify exclude each other (clustered meshes need not be manifold)")
         if int(min_component_faces) > 0 or keep_largest:
             verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
                                                                      largest=bool(keep_largest))
         if k >= 2:
             g = (-(-(R - 1) // k),) * 3                                          # ceil((R - 1) / k) cells cover the lattice
             verts, faces, normals = _mesh.simplify(verts, faces, (step * k).tolist(), normals=normals, origin=lo.tolist(), grid=g)
+        if tf:
+            verts, faces, normals, _ = _mesh.decimate(verts, faces, tf, normals=normals)
         colors = None
         if color:
             colors = torch.empty(verts.shape[0], 3, dtype=torch.uint8, device=verts.device)
@@ -520,7 +528,7 @@ class NeRFRenderer(nn.Module):
 
     def save_mesh(self, path, **kw):
         """extract_mesh(**kw) written as a binary PLY (mesh.write_ply: positions, normals, and colours when color=True) -> the mesh dict.
-        The cleanup options of extract_mesh (min_component_faces, keep_largest, simplify) pass through."""
+        The cleanup options of extract_mesh (min_component_faces, keep_largest, simplify, target_faces) pass through."""
         m = self.extract_mesh(**kw)
         _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=m['colors'])
         return m

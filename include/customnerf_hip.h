@@ -36,7 +36,8 @@ extern "C" {
  *    cnerf_grid_encode_forward_ordered, cnerf_sd_concat_gn, cnerf_sd_gemm_serves_ln, cnerf_profile_stage_events.
  * 6: the plan in pieces is gone — the _block / _rows / _finish variants of cnerf_grid_encode_backward_prepare (no shape took them since ABI 5).
  * 7: mesh extraction — cnerf_marching_cubes_workspace_bytes / _count / _emit; mesh cleanup (additive, same version: a binding that
- *    needs them fails at load on the missing symbol) — cnerf_mesh_components_* and cnerf_mesh_cluster_* (workspace_bytes / _count / _emit). */
+ *    needs them fails at load on the missing symbol) — cnerf_mesh_components_* and cnerf_mesh_cluster_* (workspace_bytes / _count / _emit);
+ *    quadric decimation (additive, same version) — cnerf_mesh_decimate_workspace_bytes / _init / _round / _emit. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -560,6 +561,40 @@ int cnerf_mesh_cluster_count(const float *verts, uint32_t V, const int32_t *face
 int cnerf_mesh_cluster_emit(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, const float *origin_host,
                             const float *cell_host, const uint32_t *grid_host, void *ws, uint64_t ws_bytes, float *verts_out, float *normals_out,
                             int32_t *faces_out, uint32_t max_verts, uint32_t max_faces, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Quadric edge-collapse decimation to a target face count (customnerf_amd/mesh.py decimate; csrc/mesh_decimate.hip; Garland & Heckbert
+ * 1997).  Input: verts float32 [V][3], faces int32 [F][3], edge-manifold and consistently oriented (an undirected edge in at most two faces,
+ * which use it in opposite directions), no face repeating an index; zero-area faces are allowed.  V, F < 2^31 and F <= 0x55555555 (edge
+ * ids 3 f + k fit 32 bits), else CNERF_EINVAL; ws 16-byte aligned and >= workspace_bytes(V, F of init), else CNERF_EINVAL.  The caller's
+ * stream and workspace; no allocation, no host sync.  counts[4] (device uint32) = (referenced vertices, live faces, collapses in this call,
+ * flags) is the one host read after init and after each round; F passed to _round / _emit is the live count of the last read (launch
+ * grids shrink with the mesh).  flags bit 0: an index outside [0, V); bit 1: a non-manifold or inconsistently oriented edge; bit 2: a face
+ * repeating an index.  After a flag, rounds and emit write nothing.
+ *   init  : positions copied into ws; per vertex the quadric sum, in increasing face index, over its faces of nonzero area of
+ *           area (n n^T, n d, d^2) in fp64, n the unit normal and d = -n . p0 from the float32 positions.
+ *   round : one round of independent collapses.  A boundary vertex (on an edge with one face) never moves and is never removed.  Candidates:
+ *           edges with two faces and at most one boundary endpoint; with one, the edge collapses onto it and is costed there; otherwise
+ *           min(u, v) is kept at x = m + A+ (-b - A m) (m the midpoint, A+ by Jacobi without eigenvalues < 1e-3 lambda_max, x = m when A = 0).
+ *           cost = x^T A x + 2 b^T x + c of Q_u + Q_v in fp64, clamped at 0, as float32; key = cost bits << 32 | (3 f + k), the canonical
+ *           half-edge (f[k], f[k+1]) with f[k] < f[k+1].  Valid: both endpoints in <= 32 faces, exactly 2 shared neighbours, no two surviving
+ *           faces around the kept vertex with one vertex set, no surviving face with n_old != 0 and n_new . n_old <= 0.2 |n_new||n_old|
+ *           (n = (p1 - p0) x (p2 - p0), kept vertex at (float) x).  A valid edge whose key is the minimum at both endpoints and then at every
+ *           vertex of every face around them wins; winners apply together, or, when they would take F below target_faces, only the
+ *           ceil((F - target) / 2) smallest keys, so F' is target or target - 1.  The kept vertex gets (float) x and Q_u + Q_v, the two faces
+ *           of the edge go, the others are remapped and compacted in order.  collapses = 0: no valid edge is left (or F <= target).
+ *   emit  : verts_out [V'][3] the referenced vertices in increasing input index, old_index [V'] (NULL: none) their input indices,
+ *           normals_out [V'][3] = normals[old_index] (written when normals != NULL), faces_out [F'][3] the surviving input faces in input
+ *           order, remapped, winding kept.  Entries at or past max_verts / max_faces are not written (outputs may be NULL when their max is 0).
+ *   workspace_bytes : about 127 bytes per vertex + 73 per face.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_decimate_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_decimate_init(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, void *ws, uint64_t ws_bytes,
+                             uint32_t *counts, void *stream);
+int cnerf_mesh_decimate_round(uint32_t V, uint32_t F, uint32_t target_faces, void *ws, uint64_t ws_bytes, uint32_t *counts, void *stream);
+int cnerf_mesh_decimate_emit(const float *normals, uint32_t V, uint32_t F, void *ws, uint64_t ws_bytes, float *verts_out,
+                             float *normals_out, int32_t *faces_out, int32_t *old_index, uint32_t max_verts, uint32_t max_faces,
+                             void *stream);
 
 #ifdef __cplusplus
 }
