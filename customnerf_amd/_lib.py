@@ -100,6 +100,11 @@ SIGNATURES = {
     "cnerf_mesh_decimate_init": [vp, u32, vp, u32, vp, u64, vp, vp],
     "cnerf_mesh_decimate_round": [u32, u32, u32, vp, u64, vp, vp],
     "cnerf_mesh_decimate_emit": [vp, u32, u32, vp, u64, vp, vp, vp, vp, u32, u32, vp],
+    "cnerf_mesh_atlas_layout": [u32, u32, vp, vp],
+    "cnerf_mesh_atlas_uvs": [vp, u32, u32, u32, vp, u32, vp, vp],
+    "cnerf_mesh_atlas_points": [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, vp, u32, vp],
+    "cnerf_mesh_atlas_store": [u32, u32, u32, u32, vp, u32, vp, vp, vp, vp],
+    "cnerf_mesh_atlas_fill": [u32, u32, vp, vp, vp],
     # ---- include/customnerf_sd.h (score-distillation primitives)
     "cnerf_sd_gemm": [vp, vp, u64, vp],
     "cnerf_sd_gemm_workspace_bytes": [vp, vp],

@@ -1,6 +1,6 @@
 """Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*), mesh cleanup on the GPU (csrc/mesh_clean.hip:
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
-face count) and a binary PLY writer.
+face count), texture baking into a per-face-pair atlas on the GPU (csrc/mesh_texture.hip), a binary PLY writer and an OBJ + MTL + PNG writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -8,6 +8,9 @@ The table is crack-free for any input (csrc/gen_mc_tables.py); it is not skimage
 from skimage's while describing the same isosurface.
 """
 import ctypes as C
+import os
+import struct
+import zlib
 
 import numpy as np
 import torch
@@ -260,3 +263,141 @@ def write_ply(path, verts, faces, normals=None, colors=None):
         fh.write(rec.tobytes())
         fh.write(frec.tobytes())
 
+
+
+def atlas_layout(F, resolution):
+    """(n, s) of the texture atlas of F faces on a resolution x resolution image: n cells per row, s texels per cell edge (the rules are in
+    include/customnerf_hip.h, cnerf_mesh_atlas_*).  ValueError when the resolution is outside [16, 16384] or the cells would be smaller than
+    4 x 4 texels."""
+    F, R = int(F), int(resolution)
+    if F < 0 or F >= 2 ** 31 or R < 16 or R > 16384:
+        raise ValueError(f"atlas_layout: need 0 <= F < 2^31 and 16 <= resolution <= 16384, got F = {F}, resolution = {R}")
+    n, s = C.c_uint32(0), C.c_uint32(0)
+    if lib.cnerf_mesh_atlas_layout(F, R, C.byref(n), C.byref(s)) != 0:
+        raise ValueError(f"atlas_layout: {F} faces leave cells of fewer than 4 x 4 texels on a {R} x {R} texture; decimate the mesh "
+                         f"(target_faces=) or raise the resolution")
+    return n.value, s.value
+
+
+def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21, fill=(0, 0, 0)):
+    """Bake color_fn into a resolution x resolution RGB8 texture atlas of the mesh (csrc/mesh_texture.hip).  Each face pair owns a square cell
+    of s x s texels (atlas_layout); every texel of a face is evaluated at the point of the face's plane under its centre, looking at the
+    surface: color_fn(x [N, 3] float32, d [N, 3] float32) -> RGB in [0, 1], [N, >= 3], any float dtype, called on chunks of at most `chunk`
+    texels.  d = -(interpolated vertex normal), or -(face normal) without normals.  Texels no face owns get `fill` (uint8 RGB).
+    CUDA tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None.  -> (uvs [F, 3, 2] float32: the UV of corner k of face f,
+    v pointing up; texture [R, R, 3] uint8, row 0 at the top), on the device.  A face index outside [0, V) raises ValueError."""
+    v, f, n = _mesh_args(verts, faces, normals, "bake_texture")
+    V, F = v.shape[0], f.shape[0]
+    R = int(resolution)
+    _, s = atlas_layout(F, R)
+    fl = tuple(int(c) for c in fill)
+    if len(fl) != 3 or min(fl) < 0 or max(fl) > 255:
+        raise ValueError(f"bake_texture: fill must be 3 values in [0, 255], got {fill}")
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"bake_texture: chunk must be >= 1, got {chunk}")
+    fill_c = (C.c_uint8 * 3)(*fl)
+    dev = v.device
+    uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_atlas_uvs(ptr(f) if F else None, V, F, R, ptr(uvs) if F else None, F, ptr(flags), stream()), "mesh_atlas_uvs")
+    if int(flags.cpu()[0]) & 1:                                                 # the one host read
+        raise ValueError("bake_texture: a face index lies outside [0, V)")
+    tex = torch.empty(R, R, 3, dtype=torch.uint8, device=dev)
+    check(lib.cnerf_mesh_atlas_fill(F, R, fill_c, ptr(tex), stream()), "mesh_atlas_fill")
+    total = (F + 1) // 2 * s * s
+    m = max(1, min(chunk, total))
+    x = torch.empty(m, 3, dtype=torch.float32, device=dev)
+    d = torch.empty(m, 3, dtype=torch.float32, device=dev)
+    for t0 in range(0, total, m):
+        t1 = min(t0 + m, total)
+        k = t1 - t0
+        check(lib.cnerf_mesh_atlas_points(ptr(v), ptr(n) if n is not None else None, V, ptr(f), F, R, t0, t1, ptr(flags), ptr(x), ptr(d), k,
+                                          stream()), "mesh_atlas_points")
+        rgb = color_fn(x[:k], d[:k])
+        if not torch.is_tensor(rgb) or rgb.dim() != 2 or rgb.shape[0] != k or rgb.shape[1] < 3 or not rgb.is_floating_point():
+            raise ValueError(f"bake_texture: color_fn must return a floating tensor [N, >= 3] for N = {k} points, got "
+                             f"{tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__}")
+        rgb = rgb.detach()[:, :3].float()
+        if rgb.stride(1) != 1 or rgb.device != dev:
+            rgb = rgb.to(dev).contiguous()
+        check(lib.cnerf_mesh_atlas_store(F, R, t0, t1, ptr(rgb), rgb.stride(0), fill_c, ptr(flags), ptr(tex), stream()), "mesh_atlas_store")
+    return uvs, tex
+
+
+def write_png(path, image):
+    """8-bit RGB PNG (no interlace, filter 0 on every row), standard library only.  image: [H, W, 3] uint8 tensor (any device) or array."""
+    a = _host(image, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"write_png: image must be [H, W, 3] uint8, got {a.shape}")
+    H, W = a.shape[:2]
+    raw = np.zeros((H, 1 + 3 * W), dtype=np.uint8)                              # a filter-type byte (0) in front of every row
+    raw[:, 1:] = a.reshape(H, 3 * W)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n")
+        fh.write(chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)))
+        fh.write(chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)))
+        fh.write(chunk(b"IEND", b""))
+
+
+def _lines(fmt, a):
+    """fmt applied to every row of the 2-D array a, as one string (one formatting call, no Python loop per row)"""
+    return (fmt * len(a)) % tuple(a.ravel().tolist()) if len(a) else ""
+
+
+def write_obj(path, verts, faces, uvs=None, normals=None, texture=None):
+    """Wavefront OBJ: `v x y z`, `vt u v` (three per face, in face order, when uvs [F, 3, 2] are given), `vn` (one per vertex, when normals
+    [V, 3] are given) and `f v/vt/vn` lines, 1-based.  Floats are written with 9 significant digits, so float32 values read back exactly.
+    With `texture` ([R, R, 3] uint8, needs uvs) the material goes to <stem>.mtl (map_Kd) and the image to <stem>.png beside the OBJ.
+    Accepts tensors (any device) or arrays."""
+    v = _host(verts, np.float32).reshape(-1, 3)
+    f = _host(faces, np.int64).reshape(-1, 3)
+    uv = _host(uvs, np.float32)
+    n = _host(normals, np.float32)
+    F = len(f)
+    if uv is not None:
+        uv = uv.reshape(-1, 2)
+        if len(uv) != 3 * F:
+            raise ValueError(f"write_obj: uvs must be [F, 3, 2] for F = {F} faces, got {len(uv)} corners")
+    if n is not None:
+        n = n.reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError(f"write_obj: normals must be [V, 3] like verts, got {len(n)} for V = {len(v)}")
+    if texture is not None and uv is None:
+        raise ValueError("write_obj: a texture needs uvs")
+    if F and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("write_obj: a face index lies outside [0, V)")
+    root, _ = os.path.splitext(path)
+    stem = os.path.basename(root)
+    head = ["# customnerf_amd mesh export", f"# {len(v)} vertices, {F} faces"]
+    if texture is not None:
+        head += [f"mtllib {stem}.mtl"]
+    out = ["\n".join(head) + "\n", _lines("v %.9g %.9g %.9g\n", v.astype(np.float64))]
+    if uv is not None:
+        out.append(_lines("vt %.9g %.9g\n", uv.astype(np.float64)))
+    if n is not None:
+        out.append(_lines("vn %.9g %.9g %.9g\n", n.astype(np.float64)))
+    if texture is not None:
+        out.append("usemtl material0\n")
+    vi = f + 1
+    if uv is not None:
+        ti = np.arange(1, 3 * F + 1, dtype=np.int64).reshape(F, 3)
+        idx = np.stack([vi, ti, vi], -1) if n is not None else np.stack([vi, ti], -1)
+        fmt = "/".join(["%d"] * idx.shape[2])
+    elif n is not None:
+        idx = np.stack([vi, vi], -1)
+        fmt = "%d//%d"
+    else:
+        idx = vi[..., None]
+        fmt = "%d"
+    out.append(_lines(f"f {fmt} {fmt} {fmt}\n", idx.reshape(F, 3 * idx.shape[2])))
+    with open(path, "w") as fh:
+        fh.write("".join(out))
+    if texture is not None:
+        with open(root + ".mtl", "w") as fh:
+            fh.write(f"newmtl material0\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {stem}.png\n")
+        write_png(root + ".png", texture)

@@ -486,7 +486,7 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
-                     min_component_faces=0, keep_largest=False, simplify=0, target_faces=0):
+                     min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -495,7 +495,9 @@ class NeRFRenderer(nn.Module):
         min_component_faces > 0 drops the connected components with fewer faces (floaters); keep_largest=True keeps only the component with
         the most faces; simplify=k >= 2 clusters the vertices in cells of k lattice steps from the lattice's lower corner (mesh.simplify);
         target_faces > 0 decimates by quadric edge collapse to that many faces (mesh.decimate; not with simplify, whose output need not be
-        manifold).  The defaults return the marching-cubes mesh as it is."""
+        manifold).  The defaults return the marching-cubes mesh as it is.
+        texture=R > 0 bakes the field's colour, looking at the surface, into an R x R texture atlas of the final mesh (mesh.bake_texture,
+        csrc/mesh_texture.hip): 'uvs' [F, 3, 2] float32 and 'texture' [R, R, 3] uint8 join the dict (both None with texture=0)."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -509,6 +511,9 @@ class NeRFRenderer(nn.Module):
             raise ValueError(f"extract_mesh: target_faces must be 0 (off) or a face count, got {target_faces}")
         if tf and k:
             raise ValueError("extract_mesh: target_faces and simplify exclude each other (clustered meshes need not be manifold)")
+        tex_r = int(texture)
+        if tex_r < 0:
+            raise ValueError(f"extract_mesh: texture must be 0 (off) or a texture resolution, got {texture}")
         if int(min_component_faces) > 0 or keep_largest:
             verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
                                                                      largest=bool(keep_largest))
@@ -524,13 +529,25 @@ class NeRFRenderer(nn.Module):
                 x = verts[s:s + chunk].contiguous()
                 rgb = self(x, (-normals[s:s + chunk]).contiguous())[1][:, :3].float()
                 colors[s:s + chunk] = (rgb.clamp(0, 1) * 255).round().to(torch.uint8)
-        return {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold}
+        uvs = tex = None
+        if tex_r:
+            uvs, tex = _mesh.bake_texture(verts, faces, tex_r, lambda x, d: self(x, d)[1][:, :3], normals=normals, chunk=chunk)
+        return {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
+                'uvs': uvs, 'texture': tex}
 
     def save_mesh(self, path, **kw):
-        """extract_mesh(**kw) written as a binary PLY (mesh.write_ply: positions, normals, and colours when color=True) -> the mesh dict.
-        The cleanup options of extract_mesh (min_component_faces, keep_largest, simplify, target_faces) pass through."""
+        """extract_mesh(**kw) written to `path` -> the mesh dict.  A path ending in .obj writes a Wavefront OBJ (mesh.write_obj: positions,
+        normals, and with texture=R the UVs, <stem>.mtl and the R x R <stem>.png beside it; vertex colours are not written to OBJ); any other
+        path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
+        extract_mesh (min_component_faces, keep_largest, simplify, target_faces) pass through."""
+        obj = str(path).lower().endswith(".obj")
+        if int(kw.get('texture', 0) or 0) and not obj:
+            raise ValueError(f"save_mesh: texture= needs an .obj path (PLY carries no texture), got {path!r}")
         m = self.extract_mesh(**kw)
-        _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=m['colors'])
+        if obj:
+            _mesh.write_obj(path, m['verts'], m['faces'], uvs=m['uvs'], normals=m['normals'], texture=m['texture'])
+        else:
+            _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=m['colors'])
         return m
 
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=2048, **kwargs):

@@ -37,7 +37,8 @@ extern "C" {
  * 6: the plan in pieces is gone — the _block / _rows / _finish variants of cnerf_grid_encode_backward_prepare (no shape took them since ABI 5).
  * 7: mesh extraction — cnerf_marching_cubes_workspace_bytes / _count / _emit; mesh cleanup (additive, same version: a binding that
  *    needs them fails at load on the missing symbol) — cnerf_mesh_components_* and cnerf_mesh_cluster_* (workspace_bytes / _count / _emit);
- *    quadric decimation (additive, same version) — cnerf_mesh_decimate_workspace_bytes / _init / _round / _emit. */
+ *    quadric decimation (additive, same version) — cnerf_mesh_decimate_workspace_bytes / _init / _round / _emit; texture baking (additive,
+ *    same version) — cnerf_mesh_atlas_layout / _uvs / _points / _store / _fill. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -595,6 +596,46 @@ int cnerf_mesh_decimate_round(uint32_t V, uint32_t F, uint32_t target_faces, voi
 int cnerf_mesh_decimate_emit(const float *normals, uint32_t V, uint32_t F, void *ws, uint64_t ws_bytes, float *verts_out,
                              float *normals_out, int32_t *faces_out, int32_t *old_index, uint32_t max_verts, uint32_t max_faces,
                              void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Texture atlas and baking (customnerf_amd/mesh.py atlas_layout / bake_texture; csrc/mesh_texture.hip; the reference writes positions only,
+ * NeRF-to-mesh tools bake with xatlas + nvdiffrast on the host).  A trivial per-face-pair layout with no search, so every texel's owner
+ * follows from its index; every face gets the same texels whatever its area (area-proportional or seam-minimising charts are not made).
+ *   Image: R x R texels, 16 <= R <= 16384, RGB8 [R][R][3], row Y = image row (top first).  Pair p holds faces 2p (A) and 2p + 1 (B),
+ *   P = ceil(F / 2); n = max(1, ceil(sqrt(P))) cells per row, s = floor(R / n) texels per cell edge, s >= 4 (else CNERF_EINVAL: decimate or
+ *   raise R); F = 0 gives n = 1, s = R and no cell.  Pair p owns cell (cx, cy) = (p mod n, p div n); its local texel (i, j) is global
+ *   texel (X, Y) = (cx s + i, cy s + j).  Cell texel index t = p s^2 + j s + i, t < P s^2.
+ *   Corners (local texel centres): A (0, 0), (0, s-2), (s-2, 0); B (s-1, s-1), (s-1, 2), (2, s-1) — counter-clockwise with v up, like the
+ *   faces.  Owner of local (i, j): A if i + j <= s - 1, else B; B of an odd F's last cell and the texels outside the first P cells are
+ *   un-owned and get the fill colour.  Seam invariant: every texel with a nonzero bilinear weight at a point of a face's UV triangle is
+ *   owned by that face (A reads i + j <= s-1 with i, j <= s-2; B reads i + j >= s with i, j >= 2), so nothing bleeds across faces or
+ *   cells under bilinear filtering (mipmaps are not covered).
+ *   UV of corner texel (X, Y), float32: u = (X + 0.5) / R, v = 1 - (Y + 0.5) / R.
+ *   Texel -> surface point, unclamped (affine) barycentrics: A w1 = j / (s-2), w2 = i / (s-2); B w1 = (s-1-j) / (s-3), w2 = (s-1-i) / (s-3);
+ *   p = p0 + w1 (p1 - p0) + w2 (p2 - p0) in float32, in this order, except at a corner texel, where p is that vertex (bit for bit).
+ *   Texels beside the triangle extrapolate in its plane, so a colour affine in position is reproduced by bilinear lookup exactly, up to
+ *   the uint8 rounding.  View direction d = -normalize(n0 + w1 (n1 - n0) + w2 (n2 - n0)) (the vertex normal at a corner texel); when
+ *   that has zero (or non-finite) squared length, or normals is NULL, -normalize((p1 - p0) x (p2 - p0)); when that is zero too, (0, 0, -1).
+ *   An un-owned cell texel gets x = (0, 0, 0), d = (0, 0, -1).
+ * faces int32 [F][3], verts / normals float32 [V][3], V < 2^31.  The caller's stream; no allocation, no host sync, no float atomics.
+ *   layout : host only: n_host, s_host, or CNERF_EINVAL.
+ *   uvs    : uvs [F][3][2] (corner k of face f at [f][k]); entries of faces >= max_faces are not written.  Zeroes flags[0] (device uint32)
+ *            first, then sets bit 0 when a face index lies outside [0, V): the one host read before baking; after it points and store
+ *            write nothing.
+ *   points : cell texels t in [t0, t1) (t1 <= P s^2, else CNERF_EINVAL): x [N][3] and d [N][3] at row t - t0; rows >= max_points are not
+ *            written.  normals may be NULL.
+ *   store  : rgb float32 rows [N] of rgb_stride >= 3 floats (first three used) for t in [t0, t1) -> round(clamp(rgb, 0, 1) * 255) (half to
+ *            even, NaN -> 0) at the texel's global position; an un-owned cell texel gets fill_host[3] (uint8 on the host).
+ *   fill   : fill_host on every texel outside the first P cells (what store does not write).
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_atlas_layout(uint32_t F, uint32_t R, uint32_t *n_host, uint32_t *s_host);
+int cnerf_mesh_atlas_uvs(const int32_t *faces, uint32_t V, uint32_t F, uint32_t R, float *uvs, uint32_t max_faces, uint32_t *flags,
+                         void *stream);
+int cnerf_mesh_atlas_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, uint32_t t0,
+                            uint32_t t1, const uint32_t *flags, float *x, float *d, uint32_t max_points, void *stream);
+int cnerf_mesh_atlas_store(uint32_t F, uint32_t R, uint32_t t0, uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host,
+                           const uint32_t *flags, uint8_t *image, void *stream);
+int cnerf_mesh_atlas_fill(uint32_t F, uint32_t R, const uint8_t *fill_host, uint8_t *image, void *stream);
 
 #ifdef __cplusplus
 }
