@@ -7,9 +7,12 @@ after the other, with the same K / W, and prints them in ONE JSON line:
   * top level = training rays/s.  One step = one full reconstruction step of the reference's loop body (utils_init_nerf.py:194-241,
     599-629) on one 128x128 synthetic view per GPU: ray batch -> NeRFRenderer.render (the `run()` path the reference's -O2 recipe uses,
     64+64 samples; or --path march for the occupancy-march `run_cuda()` path) -> loss -> backward -> [RCCL all-reduce of the gradients
-    when N>1] -> Adam.  `roofline` = the hash-grid gather against HBM, `cpu_baseline` = the oracle renderer on the host cores.
-  * "secondary" = SDS edit-steps/s (utils_init_nerf.py:353-394, sd.py:115-155), same keys (value / ms_per_step / steps / warmup /
-    roofline{bound: mfma} / cpu_baseline / config).
+    when N>1] -> Adam.  `roofline` = the hash-grid gather against HBM (event pairs around the timed region's own gather launches).
+  * "secondary" = SDS edit-steps/s (utils_init_nerf.py:353-394, sd.py:115-155), same keys (value / ms_per_step / steps / warmup / config).
+
+A plain run does only that: set up, warm up, time, [--dump-outputs], print.  `--full` adds everything else the benchmark measures, each
+in runs of its own after the timed legs: `cpu_baseline` of both halves (the oracles on the host cores), the recon `variants` (one GPU) or
+`strong` / `strong_graphed` (N > 1), the edit leg's GEMM `roofline{bound: mfma}` (two more eager steps) and its `multi_view` record.
 
 `--task recon` / `--task edit` time one half only (profiling runs).  Inputs (rays, targets, tables, weights) are resident in HBM before
 either timed region.  Prints ONE JSON line from rank 0.
@@ -245,7 +248,7 @@ def run_edit(args, world, rank, dev):
                          "sds_views_per_step": nv, "views_per_s": world * nv * args.steps / dt,
                          "parallelism": f"dp{world} (view-parallel SDS, RCCL {trainer.dp_describe()})" if world > 1 else "single GPU", "final_loss": float(loss),
                          "loss_scale": f"dynamic (GradScaler policy on device), now {trainer.scaler.get_scale():g}", "steps_skipped_on_overflow": skipped}}
-    if not args.no_roofline:
+    if (args.full or args.gemm_table) and not args.no_roofline:
         prof = []
         use_graph = guidance.use_graph
         guidance.use_graph = False                                       # eager launches so that each GEMM can be bracketed by events
@@ -283,7 +286,7 @@ def run_edit(args, world, rank, dev):
                               "gemm_ms_per_step": ms, "algorithmic_tflop_per_step": fl / 1e12,
                               "timing": "per-launch HIP event pairs on the launch stream over one eager step enqueued behind a device-side sleep (queue kept full: "
                                         "the brackets hold kernel time, not host launch pacing); the timed region itself replays the UNet as a hipGraph"}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             result["cpu_baseline"] = cpu_baseline_edit()
         except Exception as e:
@@ -436,7 +439,7 @@ def run_recon(args, world, rank, dev):
                                                         "last_trial_ms": ({"level_major": tuner.history[-1][1], "sample_major": tuner.history[-1][2]} if tuner.history else None)}
             if args.grid == "synthetic" and args.prefit == 0:         # the PMC pass was taken on this table in this (random-initialised) state
                 result["roofline"]["l2_fabric"] = l2_fabric(args.dtype, sum(pts) / len(pts), tot_ms / len(ms))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 result["cpu_baseline"] = cpu_baseline(opt)
             except Exception as e:                                    # the baseline leg must never take the GPU number down
@@ -674,10 +677,14 @@ def main():
     ap.add_argument("--dp-selftest", action="store_true", help="one GPU: force the sharded gradient exchange on over a one-rank RCCL group (no link time)")
     ap.add_argument("--graph", action="store_true", help="recon leg (one GPU, run() path): forward + backward of each view as one hipGraph (ReconTrainer.train_step_graphed)")
     ap.add_argument("--dry-launch", action="store_true", help="print the child environments `--gpus N` would spawn and exit (no GPU needed)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the `variants` sub-records (bear table, march path, trained field; strong scaling at N>1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--gemm-table", default=None, help="edit leg: write the per-shape table of one step's GEMM launches to this file (tuning aid)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed legs, also measure everything beside the headline figures: CPU baselines, the recon `variants` (strong "
+                         "scaling at N>1), the edit leg's GEMM roofline and its multi-view record (off by default: a plain run times the metric only)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the `variants` sub-records (bear table, march path, trained field; strong scaling at N>1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="no gather event pairs in the recon leg's timed region; with --full: no edit GEMM roofline")
+    ap.add_argument("--gemm-table", default=None,
+                    help="edit leg: write the per-shape table of one step's GEMM launches to this file (tuning aid; runs the edit GEMM roofline pass without --full)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (loss, render results / loss terms, updated parameters; "
                          "arrays above 2^20 elements as a fixed seeded sample) as DIR/<leg>_<name>.npy, float32 or float64, at most 64 MB in all")
@@ -757,8 +764,9 @@ def main():
     result = None
     if args.task in ("both", "recon"):
         result = run_recon(args, world, rank, dev)
-        plain = args.path == "run" and args.grid == "synthetic" and args.prefit == 0 and not args.no_variants and not args.graph and not args.rays  # rank-independent conditions only
-        if plain and world == 1 and not args.dp_selftest:
+        variants = (args.full and args.path == "run" and args.grid == "synthetic" and args.prefit == 0 and not args.no_variants and not args.graph
+                    and not args.rays)                               # rank-independent conditions only
+        if variants and world == 1 and not args.dp_selftest:
             # the claims that used to live in builder-run profiles/, under the driver's clock: the reference field's own table
             # (network_grid.py:89-96), the occupancy-march path (renderer.py:597-718) and the gather on a FITTED field
             v = {"bear_table": brief(variant(run_recon, grid="bear")),
@@ -797,7 +805,7 @@ def main():
                     dist.destroy_process_group()
             if rank == 0:
                 result["variants"] = v
-        if plain and world > 1 and args.scaling == "weak":
+        if variants and world > 1 and args.scaling == "weak":
             st = brief(variant(run_recon, scaling="strong", no_roofline=True))
             sg = brief(variant(run_recon, scaling="strong", no_roofline=True, graph=True))     # the same with each rank's chunk replayed as a hipGraph
             if rank == 0:
@@ -818,7 +826,7 @@ def main():
             first = {"ms_per_step": edit["ms_per_step"], "final_loss": edit["config"].get("final_loss"), "steps_skipped_on_overflow": args.steps}
             edit = run_edit(args, world, rank, dev)
             edit["nonfinite_first_attempt"] = first
-        if args.task == "both" and args.sds_views == 1 and not args.no_variants and not (world == 1 and edit.get("error")):
+        if args.full and args.task == "both" and args.sds_views == 1 and not args.no_variants and not (world == 1 and edit.get("error")):
             # the same leg with 4 camera views per step through one UNet batch of 8 (north_star: "optionally SDS camera views"), reported beside
             # the single-view figure: fixed per-launch costs amortise and the GEMMs' M quadruples.  The condition is rank-independent.
             mv = variant(run_edit, sds_views=4)

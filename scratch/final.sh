@@ -7,8 +7,8 @@ out=gpurun_out/$tag
 mkdir -p $out
 timeout 600 python -m pytest tests -x -q -m gpu > $out/pytest_gpu.log 2>&1; tail -2 $out/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1; tail -1 $out/smoke.log
-timeout 600 python bench.py > $out/bench_recon.json 2> $out/bench_recon.err; tail -c 600 $out/bench_recon.json; echo
-timeout 900 python bench.py --task edit > $out/bench_edit.json 2> $out/bench_edit.err; tail -c 400 $out/bench_edit.json; echo
+timeout 600 python bench.py --full > $out/bench_recon.json 2> $out/bench_recon.err; tail -c 600 $out/bench_recon.json; echo
+timeout 900 python bench.py --task edit --full > $out/bench_edit.json 2> $out/bench_edit.err; tail -c 400 $out/bench_edit.json; echo
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_recon -o bench -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/prof_recon.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_edit -o bench -- python3 bench.py --task edit --steps 10 --warmup 3 --no-cpu-baseline > $out/prof_edit.log 2>&1
 rm -f $out/prof_recon/bench_kernel_trace.csv $out/prof_edit/bench_kernel_trace.csv

@@ -1,7 +1,7 @@
 """the N > 1 code path on a ONE-GPU box.  Two fresh child ranks share device 0; their process group is gloo with every
 collective staged through host memory (customnerf_amd/_coll.py) — same call order and arithmetic as the RCCL run, no links.  (1) two
 data-parallel steps of the sharded exchange end in exactly the table / MLPs a single process reaches from the two views' mean gradient;
-(2) `bench.py --gpus 2` runs end to end through its own launcher — every leg, the variants, the strong-scaling and multi-view sub-records — which
+(2) `bench.py --gpus 2 --full` runs end to end through its own launcher — every leg, the variants, the strong-scaling and multi-view sub-records — which
 is what catches collective-order hangs (a rank that skips a leg leaves its peer waiting: ADVICE r3)."""
 import json
 import os
@@ -77,8 +77,8 @@ def test_two_ranks_on_one_device_match_the_mean_gradient_step(tmp_path):
 def test_bench_two_ranks_on_one_device_runs_every_leg():
     env = dict(os.environ, CNERF_DP_BACKEND="gloo", CNERF_SINGLE_DEVICE="1", CNERF_BENCH_WATCHDOG="420")      # (a hang ends in stack dumps, not in the suite's timeout)
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env=env,
-                         capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
+                         env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-4000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 2 and rec["rccl_ranks"] == 2 and "gloo" in rec["collective_backend"]
