@@ -228,6 +228,16 @@ static int fb_dims(uint32_t enc_dim, uint32_t n_hidden_geo, uint32_t n_rgb_out, 
     return CNERF_OK;
 }
 
+// the weight-gradient GEMM's partial rows (one per K split, ff_offsets layout) follow the [row][sample] matrices
+static inline size_t fb_part_off(const FieldDims &dm, uint32_t P_, int dtype) {
+    return ((size_t)fb_ws_layout(dm).rows * fb_ld(P_) * (dtype == CNERF_F16 ? 2 : 4) + 255) / 256 * 256;
+}
+static inline size_t fb_workspace_bytes(const FieldDims &dm, uint32_t P_, int dtype) {
+    uint32_t kps;
+    return fb_part_off(dm, P_, dtype) + (size_t)fb_dw_splits(cn_div_up(P_, FLD_TILE), kps) * ff_offsets(dm).total * sizeof(float) + 256;
+}
+void ff_reduce_partials(const float *partials, uint32_t n_partials, uint32_t total, uint32_t n_net, uint32_t n_den, float *g_net, float *g_den, float *g_rgb,
+                        hipStream_t st);
 
 template <bool H>
 static int fb_launch(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, const FieldDims &dm, const float *pnet,
@@ -269,24 +279,29 @@ static int fb_launch(const void *enc, const float *xyz, const float *dirs, uint3
     int rc = cn_launch_status();
     if (rc) return rc;
 
-    // weight gradients
+    // weight gradients: one partial row per K split (every entry of the ff_offsets layout written, padding as zeros), then the fixed-order
+    // reduction that adds them into the gradients and raises found_inf — no float atomics, so the same bits every run
     const FieldWs wo = fb_ws_layout(dm);
+    const FfOff po = ff_offsets(dm);
     DwPlan pl;
     pl.n_jobs = 0; pl.n_tiles = 0;
+    pl.part_base[0] = 0; pl.part_base[1] = po.d0; pl.part_base[2] = po.r0; pl.part_total = po.total;
     const uint32_t in_r0 = FLD_HID + FLD_DIR;
     fb_add_job(pl, wo.z1, 64, wo.enc, dm.enc_pad, 0, 0, dm.enc_pad, 0);                                        // n0
     uint32_t off = FLD_HID * dm.enc_pad;
     if (dm.n_hidden_geo == 2) { fb_add_job(pl, wo.z2, 64, wo.h1, 64, 0, off, 64, 0); off += 4096; }            // n1
     fb_add_job(pl, wo.z3, 64, dm.n_hidden_geo == 2 ? wo.h2 : wo.h1, 64, 0, off, 64, 0);                        // n2
     fb_add_job(pl, wo.zd, 64, wo.fea, 64, 1, 0, 64, 0);                                                        // d0
-    fb_add_job(pl, wo.zdo, 1, wo.hd, 64, 1, 4096, 64, 0);                                                      // do (row 0)
+    fb_add_job(pl, wo.zdo, 1, wo.hd, 64, 1, 4096, 64, 0, 16);                                                  // do (row 0; rows 1..15 padding)
     fb_add_job(pl, wo.zr, 64, wo.dir, FLD_NDIR, 2, 0, in_r0, 0);                                               // r0, direction columns
-    fb_add_job(pl, wo.zr, 64, wo.fea, 64, 2, 0, in_r0, FLD_NDIR);                                              // r0, feature columns
-    fb_add_job(pl, wo.zro, dm.n_rgb_out, wo.hr, 64, 2, FLD_HID * in_r0, 64, 0);                                // ro
-    uint32_t splits = n_tiles < 64 ? 1 : (n_tiles < 4096 ? 8 : 64);
-    pl.k_tiles_per_split = cn_div_up(cn_div_up(n_tiles, splits), DW_KB / 32) * (DW_KB / 32);     // whole 128-sample blocks
-    splits = cn_div_up(n_tiles, pl.k_tiles_per_split);
-    hipLaunchKernelGGL((k_field_bwd_dw<H>), dim3(pl.n_tiles, splits), dim3(FLD_THREADS), 0, st, workspace, ld, n_tiles, pl, g_net, g_den, g_rgb);
+    fb_add_job(pl, wo.zr, 64, wo.fea, 64, 2, 0, in_r0, FLD_NDIR, 0, in_r0 - FLD_NDIR);                         // r0, feature + padding columns
+    fb_add_job(pl, wo.zro, dm.n_rgb_out, wo.hr, 64, 2, FLD_HID * in_r0, 64, 0, 16);                            // ro (rows n_rgb_out..15 padding)
+    const uint32_t splits = fb_dw_splits(n_tiles, pl.k_tiles_per_split);
+    float *partials = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(workspace) + fb_part_off(dm, P_, H ? CNERF_F16 : CNERF_F32));
+    hipLaunchKernelGGL((k_field_bwd_dw<H>), dim3(pl.n_tiles, splits), dim3(FLD_THREADS), 0, st, workspace, ld, n_tiles, pl, g_net, g_den, g_rgb, partials);
+    rc = cn_launch_status();
+    if (rc) return rc;
+    ff_reduce_partials(partials, splits, po.total, po.d0, po.r0 - po.d0, g_net, g_den, g_rgb, st);
     return cn_launch_status();
 }
 
@@ -308,9 +323,8 @@ int cnerf_field_backward_workspace_bytes(uint32_t P_, uint32_t enc_dim, uint32_t
     int rc = fb_dims(enc_dim, n_hidden_geo, n_rgb_out, dm);
     if (rc) return rc;
     if (dtype != CNERF_F32 && dtype != CNERF_F16) return CNERF_EINVAL;
-    const FieldWs wo = fb_ws_layout(dm);
     if (fb_use_fused(dm, dtype)) *bytes = ff_workspace_bytes(dm);
-    else *bytes = (uint64_t)wo.rows * fb_ld(P_) * (dtype == CNERF_F16 ? 2 : 4) + 256;
+    else *bytes = fb_workspace_bytes(dm, P_, dtype);
     return CNERF_OK;
 }
 

@@ -5,7 +5,8 @@
 //                     layout, and spill every dz_l / layer input once as [row][sample] matrices;
 //   k_field_bwd_dw    dW_l = dz_l . a_{l-1}^T : MFMA GEMMs whose contraction runs over the samples, reading those
 //                     [row][sample] matrices with 16-byte per-lane loads; split-K over the sample axis, per-workgroup LDS
-//                     reduction, one float atomic per weight per split (24.5 k x splits — negligible).
+//                     reduction, one partial row per split (plain stores), summed in a fixed order by k_field_reduce_partials,
+//                     which also raises found_inf.
 // trunc_exp backward clamps the exponent to [-15, 15] (provider_utils.py:26-29).
 #pragma once
 #include "field_common.h"
@@ -266,3 +267,22 @@ __host__ __device__ __forceinline__ FieldLdsT fb_ldsT_layout(const FieldDims &d)
     return l;
 }
 
+
+// Flat [net | den | rgb] parameter space of the partial weight-gradient rows: one layout for every backward form that reduces partials with
+// k_field_reduce_partials (the four-wave kernel of field_bwd_fused.hip and the split-K GEMM of field_bwd.hip)
+struct FfOff {
+    uint32_t n0, n1, n2, d0, dO, r0, rO, total;
+};
+__host__ __device__ __forceinline__ FfOff ff_offsets(const FieldDims &dm) {
+    FfOff o;
+    uint32_t p = 0;
+    o.n0 = p; p += FLD_HID * dm.enc_pad;
+    o.n1 = p; p += (dm.n_hidden_geo == 2) ? 4096 : 0;
+    o.n2 = p; p += 4096;
+    o.d0 = p; p += 4096;
+    o.dO = p; p += 16 * 64;
+    o.r0 = p; p += 64 * 96;
+    o.rO = p; p += 16 * 64;
+    o.total = p;
+    return o;
+}

@@ -71,23 +71,7 @@ __device__ __forceinline__ void ff_tile_store(float *__restrict__ part, const Ff
     }
 }
 
-// ---- tile tables of the four phases (idx = slot * 4 + wave).  Offsets into the flat [net | den | rgb] parameter space.
-struct FfOff {
-    uint32_t n0, n1, n2, d0, dO, r0, rO, total;
-};
-__host__ __device__ __forceinline__ FfOff ff_offsets(const FieldDims &dm) {
-    FfOff o;
-    uint32_t p = 0;
-    o.n0 = p; p += FLD_HID * dm.enc_pad;
-    o.n1 = p; p += (dm.n_hidden_geo == 2) ? 4096 : 0;
-    o.n2 = p; p += 4096;
-    o.d0 = p; p += 4096;
-    o.dO = p; p += 16 * 64;
-    o.r0 = p; p += 64 * 96;
-    o.rO = p; p += 16 * 64;
-    o.total = p;
-    return o;
-}
+// ---- tile tables of the four phases (idx = slot * 4 + wave).  Offsets into the flat [net | den | rgb] parameter space (ff_offsets).
 
 // phase A staging rows: zro 0..7 | hr 8..71 | zr 72..135 | fea 136..199 | dir 200..231
 __device__ __forceinline__ FfTile ff_tile_A(uint32_t i, const FieldDims &dm, const FfOff &o) {

@@ -5,6 +5,7 @@
 // ------------------------------------------------------------------------------------------------ weight-gradient kernel
 struct DwJob {
     uint32_t z_row, M, a_row, N;         // rows of dz / rows of the layer input inside the workspace, and their counts
+    uint32_t Mw, Nw;                     // extent written into a partial row (>= M, N: the padding of the parameter matrix gets zeros)
     uint32_t dst_off, dst_stride, dst_col0, net;   // destination inside grad_params_{net 0, den 1, rgb 2}
     uint32_t tile0, nt_n;                // first global tile index of this job, tiles along N
 };
@@ -12,16 +13,20 @@ struct DwJob {
 struct DwPlan {
     DwJob job[FLD_MAX_JOBS];
     uint32_t n_jobs, n_tiles, k_tiles_per_split;     // K split in units of 32-sample tiles
+    uint32_t part_base[3], part_total;   // partial-row mode: where grad_params_{net, den, rgb} start inside one row, and the row length
 };
 
 // One workgroup = one 32x32 tile of one layer's dW over one K split.  Per step it stages a [32 rows x 128 samples] block of dz
 // and of the layer input into LDS with fully coalesced loads (a wave instruction reads 4 rows x 256 contiguous bytes), then
-// each wave contracts its own 32 of the 128 samples; partial tiles are reduced through LDS and added with one float atomic per
-// weight per split.  (Reading the MFMA fragments straight from HBM touches 32 rows x 32 B per instruction: 4x slower.)
+// each wave contracts its own 32 of the 128 samples; partial tiles are reduced through LDS.  With part == NULL the tile is added with
+// one float atomic per weight per split; otherwise split s stores it into partial row s (part[s * part_total + ...], plain stores, zeros
+// included: the last tile along M / N also covers the padding up to Mw / Nw) for a fixed-order reduction (k_field_reduce_partials) — same bits every run.
+// (Reading the MFMA fragments straight from HBM touches 32 rows x 32 B per instruction: 4x slower.)
 #define DW_KB 128                       // samples per staged block (4 waves x 32)
 template <bool H>
 __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_dw(const void *__restrict__ ws_, size_t ld, uint32_t n_ktiles, DwPlan plan,
-                                                              float *__restrict__ g_net, float *__restrict__ g_den, float *__restrict__ g_rgb) {
+                                                              float *__restrict__ g_net, float *__restrict__ g_den, float *__restrict__ g_rgb,
+                                                              float *__restrict__ part) {
     using PR = Prec<H>;
     using elem_t = typename PR::elem_t;
     using frag_t = typename PR::frag_t;
@@ -74,6 +79,18 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_dw(const void *__rest
 #pragma unroll
     for (int r = 0; r < 16; r++) red[wave][fld_rho(r, hi) * 32 + li] = acc[r];
     __syncthreads();
+    if (part) {
+        float *dst = part + (size_t)split * plan.part_total + plan.part_base[jb.net] + jb.dst_off;
+        const uint32_t nr = (32 * mt + 32 >= jb.M ? jb.Mw : 32 * mt + 32) - 32 * mt;          // <= 32 + padding (rows of do / ro, r0's last columns)
+        const uint32_t nc = (32 * nt + 32 >= jb.N ? jb.Nw : 32 * nt + 32) - 32 * nt;
+        for (uint32_t i = threadIdx.x; i < nr * nc; i += FLD_THREADS) {
+            const uint32_t r = i / nc, c = i % nc, row = 32 * mt + r, col = 32 * nt + c;
+            float v = 0.0f;
+            if (r < 32 && c < 32 && row < jb.M && col < jb.N) v = red[0][r * 32 + c] + red[1][r * 32 + c] + red[2][r * 32 + c] + red[3][r * 32 + c];
+            dst[(size_t)row * jb.dst_stride + jb.dst_col0 + col] = v;
+        }
+        return;
+    }
     float *dst = (jb.net == 0 ? g_net : (jb.net == 1 ? g_den : g_rgb)) + jb.dst_off;
     for (uint32_t i = threadIdx.x; i < 32 * 32; i += FLD_THREADS) {
         const uint32_t row = 32 * mt + i / 32, col = 32 * nt + (i & 31);
@@ -85,13 +102,22 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_dw(const void *__rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+// Mw, Nw (partial-row mode): the extent of the parameter matrix this job writes, padding included (0: M, N)
 static inline void fb_add_job(DwPlan &pl, uint32_t z_row, uint32_t M, uint32_t a_row, uint32_t N, uint32_t net, uint32_t dst_off, uint32_t dst_stride,
-                       uint32_t dst_col0) {
+                       uint32_t dst_col0, uint32_t Mw = 0, uint32_t Nw = 0) {
     DwJob &j = pl.job[pl.n_jobs++];
     j.z_row = z_row; j.M = M; j.a_row = a_row; j.N = N; j.net = net; j.dst_off = dst_off; j.dst_stride = dst_stride; j.dst_col0 = dst_col0;
+    j.Mw = Mw ? Mw : M; j.Nw = Nw ? Nw : N;
     j.tile0 = pl.n_tiles;
     j.nt_n = cn_div_up(N, 32);
     pl.n_tiles += cn_div_up(M, 32) * j.nt_n;
+}
+
+// K split of the weight-gradient GEMM over n_tiles 32-sample tiles (whole 128-sample blocks per split); returns the split count
+static inline uint32_t fb_dw_splits(uint32_t n_tiles, uint32_t &k_tiles_per_split) {
+    const uint32_t splits = n_tiles < 64 ? 1 : (n_tiles < 4096 ? 8 : 64);
+    k_tiles_per_split = cn_div_up(cn_div_up(n_tiles, splits), DW_KB / 32) * (DW_KB / 32);
+    return cn_div_up(n_tiles, k_tiles_per_split);
 }
 
 

@@ -318,7 +318,7 @@ static int mlp_launch_bwd(const void *x, uint32_t ldx, const float *params, cons
     uint32_t splits = n_tiles < 64 ? 1 : (n_tiles < 4096 ? 8 : 64);
     pl.k_tiles_per_split = cn_div_up(cn_div_up(n_tiles, splits), DW_KB / 32) * (DW_KB / 32);
     splits = cn_div_up(n_tiles, pl.k_tiles_per_split);
-    hipLaunchKernelGGL((k_field_bwd_dw<H>), dim3(pl.n_tiles, splits), dim3(FLD_THREADS), 0, st, workspace, ld, n_tiles, pl, gparams, gparams, gparams);
+    hipLaunchKernelGGL((k_field_bwd_dw<H>), dim3(pl.n_tiles, splits), dim3(FLD_THREADS), 0, st, workspace, ld, n_tiles, pl, gparams, gparams, gparams, nullptr);
     return cn_launch_status();
 }
 

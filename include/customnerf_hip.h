@@ -465,7 +465,8 @@ int cnerf_adam_step(float *p, float *g, float *m, float *v, void *p_half, uint64
  * ---------------------------------------------------------------------------------------------- */
 int cnerf_scaler_check(const float *g, uint64_t n, float *state, void *stream);
 /* Round 6: while a scaler state is WATCHED (state != NULL; NULL switches it off — the default), the two gradient-producing entry points of the
- * field raise its found_inf themselves on their launch stream: cnerf_field_backward* when a parameter gradient it writes is not finite,
+ * field raise its found_inf themselves on their launch stream: cnerf_field_backward* when a parameter gradient it writes is not finite (every
+ * form, the two-launch fallback of wide encodings and of float32 included: all of them add their partial weight gradients in one reduction that checks),
  * cnerf_grid_encode_backward* when an incoming feature gradient is not finite (the value it then also poisons the table gradient with).  A caller
  * whose gradients ALL come from these entry points may skip cnerf_scaler_check (a pass over every gradient: 9 us for the benchmark table, 30 us
  * for the reference field's).  One watched state per process; host-side switch, no launch. */

@@ -29,7 +29,7 @@ def make_case(L, n_geo, P, seed=0, scale=0.5):
     return ref, enc, x, d
 
 
-@pytest.mark.parametrize("L,n_geo", [(16, 2), (4, 1), (16, 1), (8, 2)])
+@pytest.mark.parametrize("L,n_geo", [(16, 2), (4, 1), (16, 1), (8, 2), (17, 1), (24, 2), (32, 1), (32, 2)])
 @pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
 def test_field_forward(L, n_geo, half):
     from customnerf_amd.field import field_forward_raw
@@ -56,8 +56,17 @@ def test_field_forward(L, n_geo, half):
 
 def test_field_forward_dir_group_and_rgb3():
     """one direction per group of samples (samples of a ray share rays_d) and the 3-channel colour head"""
+    _check_dir_group_and_rgb3(16)
+
+
+def test_field_forward_dir_group_and_rgb3_at_24_levels():
+    """the same with a 48-wide encoding (the forward's three-K-step first layer)"""
+    _check_dir_group_and_rgb3(24)
+
+
+def _check_dir_group_and_rgb3(L):
     from customnerf_amd.field import field_forward_raw
-    L, n_geo, rays, spr = 16, 2, 37, 24
+    n_geo, rays, spr = 2, 37, 24
     P = rays * spr
     ref, enc, x, d = make_case(L, n_geo, P, seed=3)
     d_ray = d[:rays]
@@ -70,10 +79,11 @@ def test_field_forward_dir_group_and_rgb3():
     np.testing.assert_allclose(s.cpu().numpy(), s_ref.numpy(), rtol=2e-5, atol=1e-6)
 
 
-@pytest.mark.parametrize("L,n_geo", [(16, 2), (4, 1)])
+@pytest.mark.parametrize("L,n_geo", [(16, 2), (4, 1), (17, 2), (24, 1), (32, 2)])
 @pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
 def test_field_backward(L, n_geo, half):
-    """d(sigma, rgbc)/d(grid table, MLP weights) through the fused backward + the grid scatter, against autograd on the oracle."""
+    """d(sigma, rgbc)/d(grid table, MLP weights) through the fused backward + the grid scatter, against autograd on the oracle (17..32 levels:
+    the two-launch form with its split-K weight-gradient GEMM, in both precisions)."""
     from customnerf_amd.field import field
     P = 2077
     ref, enc, x, d = make_case(L, n_geo, P, seed=5)
@@ -98,17 +108,22 @@ def test_field_backward(L, n_geo, half):
         err = np.abs(a - b).max() / scale
         assert err < (rt if name != "grid" else rt * 2), f"{name}: max|diff|/max|ref| = {err:.3e}"
         np.testing.assert_allclose(a, b, rtol=rt * 10, atol=max(at, rt * scale), err_msg=name)
-    # padded parameter rows/columns (tcnn pads 1 -> 16 outputs, 91 -> 96 inputs) must get exactly zero gradient
+    # padded parameter rows/columns (tcnn pads 1 -> 16 outputs, 91 -> 96 inputs, 2 L -> 16-multiple inputs) must get exactly zero gradient
     assert torch.all(pd.grad[4096 + 64:] == 0)
     assert torch.all(pr.grad[:64 * 96].view(64, 96)[:, 91:] == 0)
+    enc_pad = (2 * L + 15) // 16 * 16
+    assert torch.all(pn.grad[:64 * enc_pad].view(64, enc_pad)[:, 2 * L:] == 0)
 
 
 @pytest.mark.parametrize("n_geo,P,dir_group,L", [(2, 70003, 1, 16), (1, 4099, 1, 16), (2, 64 * 700, 64, 16), (1, 32 * 3 + 5, 32, 16), (2, 17, 1, 16),
-                                                 (2, 5000, 1, 12), (1, 2500, 128, 9)])
+                                                 (2, 5000, 1, 12), (1, 2500, 128, 9),
+                                                 (2, 17, 1, 24), (1, 3997, 1, 24), (2, 70003, 1, 32), (1, 64 * 700, 64, 32), (2, 4001, 1, 17),
+                                                 (1, 131101, 1, 24)])
 def test_field_backward_pipeline_shapes(n_geo, P, dir_group, L):
     """k_field_bwd_x2 (fp16, 9..16 levels = feature width padded to 32): several tiles per wave pair (the software pipeline really cycles), a ragged last tile, tile
     counts below the pipeline depth, one / two hidden layers, and one direction per group of samples (the per-tile direction path when the
-    group is a multiple of the 32-sample tile) — against autograd on the oracle field."""
+    group is a multiple of the 32-sample tile) — against autograd on the oracle field.  17..32 levels (48- / 64-wide encodings) take the two-launch
+    form: one, eight and 64 K splits of its weight-gradient GEMM (P = 17; ~4 000 and 70 003; 131 101), and a 64-sample direction group."""
     from customnerf_amd.field import field
     ref, enc, x, d = make_case(L, n_geo, P, seed=11)
     ref.half = True
@@ -139,23 +154,72 @@ def test_field_backward_pipeline_shapes(n_geo, P, dir_group, L):
 
 def test_field_backward_is_reproducible():
     """the per-pair partial sums and their reduction have a fixed order: two runs give the same bits"""
+    _check_reproducible(16, True)
+
+
+@pytest.mark.parametrize("L,half", [(24, True), (32, True), (16, False)], ids=["L24-f16", "L32-f16", "L16-f32"])
+def test_field_backward_is_reproducible_in_the_two_launch_form(L, half):
+    """the two-launch form (17..32 levels in fp16, every level count in fp32): its split-K partial rows and their reduction have a fixed order too"""
+    _check_reproducible(L, half)
+
+
+def _check_reproducible(L, half):
+    """two runs give the same bits — the second from a workspace filled with 0xFF bytes (NaN in both precisions): every entry a reduction reads
+    is written by the same call, so nothing of an earlier call's workspace reaches the sums"""
+    from customnerf_amd import field as fld
     from customnerf_amd.field import field
-    L, n_geo, P = 16, 2, 40000
+    n_geo, P = 2, 40000
     ref, enc, x, d = make_case(L, n_geo, P, seed=2)
     pn0, pd0, pr0 = ref.network, ref.density_network, ref.rgb_network
     g = torch.Generator().manual_seed(0)
     gs, gc = torch.randn(P, generator=g).cuda() * 0.05, torch.randn(P, 4, generator=g).cuda()
     outs = []
-    for _ in range(2):
+    for run in range(2):
         pn, pd, pr = (t.detach().clone().cuda().requires_grad_(True) for t in (pn0, pd0, pr0))
         with torch.no_grad():
-            e = enc.encode(cuda(x), bound=2.0, half=True)
+            e = enc.encode(cuda(x), bound=2.0, half=half)
         e.requires_grad_(True)
+        if run == 1:
+            assert fld._WS
+            for buf in fld._WS.values():
+                buf.fill_(0xFF)
         s, c = field(e, cuda(x), cuda(d), 1, 2 * L, n_geo, 4, pn, pd, pr)
         torch.autograd.backward([s, c], [gs, gc])
         outs.append((pn.grad.clone(), pd.grad.clone(), pr.grad.clone(), e.grad.clone()))
     for a, b in zip(*outs):
+        assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0
         assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("L", [4, 12, 16, 24, 32])
+def test_field_backward_raises_found_inf(L):
+    """cnerf_scaler_watch: every form of the fp16 field backward (four-wave kernel: 4 levels, x2 kernel: 12 / 16, two-launch form: 24 / 32)
+    raises the watched scaler's found_inf when a parameter gradient it writes is not finite, and only then — the trainer folds the inf check
+    into the producers on the strength of it.  The encoding is detached: only the field backward can raise the flag here."""
+    from customnerf_amd.field import field
+    from customnerf_amd.optim import DynamicLossScaler
+    n_geo, P = 2, 5003
+    ref, enc, x, d = make_case(L, n_geo, P, seed=4)
+    with torch.no_grad():
+        e = enc.encode(cuda(x), bound=2.0, half=True)
+    g = torch.Generator().manual_seed(3)
+    gs, gc = torch.randn(P, generator=g).cuda() * 0.05, torch.randn(P, 4, generator=g).cuda()
+    sclr = DynamicLossScaler(torch.device("cuda"))
+    for bad in (None, float("inf"), float("nan")):
+        gcb = gc.clone()
+        if bad is not None:
+            gcb[2345, 1] = bad
+        sclr.state[2] = 0.0
+        pn, pd, pr = (t.detach().clone().cuda().requires_grad_(True) for t in (ref.network, ref.density_network, ref.rgb_network))
+        s, c = field(e, cuda(x), cuda(d), 1, 2 * L, n_geo, 4, pn, pd, pr)
+        sclr.watch(True)
+        try:
+            torch.autograd.backward([s, c], [gs, gcb])
+        finally:
+            sclr.watch(False)
+        finite = all(bool(torch.isfinite(t.grad).all()) for t in (pn, pd, pr))
+        assert float(sclr.state[2]) == (0.0 if bad is None else 1.0), (L, bad)
+        assert finite == (bad is None), (L, bad)
 
 
 # ---- packed weights (ABI 5: cnerf_field_pack_weights + the _img entry points) ----
@@ -171,11 +235,12 @@ def _field_run(enc_t, x, d, dir_group, L, n_geo, params, gs, gc, wimg):
     return s.detach(), c.detach(), e.grad, pn.grad, pd.grad, pr.grad
 
 
-@pytest.mark.parametrize("L,n_geo,P,dir_group", [(16, 2, 40000, 1), (16, 1, 64 * 300, 64), (12, 2, 5003, 1), (4, 1, 3000, 1)])
+@pytest.mark.parametrize("L,n_geo,P,dir_group", [(16, 2, 40000, 1), (16, 1, 64 * 300, 64), (12, 2, 5003, 1), (4, 1, 3000, 1), (24, 2, 40000, 1),
+                                                  (17, 1, 64 * 300, 64)])
 def test_packed_weights_are_bit_identical(L, n_geo, P, dir_group):
     """forward and backward reading the packed fp16 image (k_field_pack) against the same launches staging from the float32 parameters:
-    the image holds the very halves the kernels stage, so every output is the same bits ((4, 1): the narrow-encoding backward accepts an
-    image and ignores it)"""
+    the image holds the very halves the kernels stage, so every output is the same bits ((4, 1), 17 and 24 levels: the narrow-encoding and the
+    two-launch backward accept an image and ignore it; the forward reads it at every width)"""
     ref, enc, x, d = make_case(L, n_geo, P, seed=5)
     params = [t.detach().clone().cuda() for t in (ref.network, ref.density_network, ref.rgb_network)]
     n_dir = (P + dir_group - 1) // dir_group

@@ -41,7 +41,16 @@ CONFIGS = [
     ("tiled_tiny_T4", dict(input_dim=3, num_levels=5, level_dim=2, base_resolution=8, log2_hashmap_size=4, per_level_scale=1.6, gridtype='tiled')),
     ("hash_tiny_T6", dict(input_dim=3, num_levels=6, level_dim=2, base_resolution=8, log2_hashmap_size=6, per_level_scale=1.6, gridtype='hash')),
     ("hash_tiny_T2", dict(input_dim=3, num_levels=4, level_dim=2, base_resolution=8, log2_hashmap_size=2, per_level_scale=1.6, gridtype='hash')),
+    # 17..32 levels (GE_MAX_LEVELS = 32): the level-major gather's XCD balance over more than 16 levels, an odd level count, the widest table
+    ("hash_L24_T19", dict(input_dim=3, num_levels=24, level_dim=2, base_resolution=16, log2_hashmap_size=19, desired_resolution=2048, gridtype='hash')),
+    ("hash_L17_T16", dict(input_dim=3, num_levels=17, level_dim=2, base_resolution=16, log2_hashmap_size=16, desired_resolution=2048, gridtype='hash')),
+    ("tiled_L32_T17", dict(input_dim=3, num_levels=32, level_dim=2, base_resolution=16, log2_hashmap_size=17, desired_resolution=4096, gridtype='tiled')),
 ]
+WIDE_CONFIGS = [c for c in CONFIGS if c[1]['num_levels'] > 16]
+
+
+def config(name):
+    return next(kw for n, kw in CONFIGS if n == name)
 
 
 def build(kw, scale=1.0, seed=0):
@@ -90,7 +99,7 @@ def test_forward_max_level_and_empty():
     assert out.shape == (0, 32)
 
 
-@pytest.mark.parametrize("name,kw", CONFIGS[:6], ids=[c[0] for c in CONFIGS[:6]])
+@pytest.mark.parametrize("name,kw", CONFIGS[:6] + WIDE_CONFIGS, ids=[c[0] for c in CONFIGS[:6] + WIDE_CONFIGS])
 @pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
 def test_dy_dx_and_input_grad(name, kw, half):
     from customnerf_amd.gridencoder.grid import _grid_encode
@@ -159,7 +168,11 @@ BINNED_CONFIGS = [CONFIGS[0], CONFIGS[1],
                   # hashed levels smaller than one 4096-entry bin: single-bin levels of the third form (round 6; the second form, which used to serve
                   # them — and the align_corners tables above, whose dense levels have odd sizes — was removed)
                   ("hash_L16_T10_small", dict(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=10,
-                                              desired_resolution=512, gridtype='hash'))]
+                                              desired_resolution=512, gridtype='hash')),
+                  # more than 16 levels: the plan's per-level slots beyond 16, and the bear table's 512-bin levels at 24 levels
+                  ("hash_L24_T19", config("hash_L24_T19")),
+                  ("tiled_L24_T21_8192_bear", dict(input_dim=3, num_levels=24, level_dim=2, base_resolution=16, log2_hashmap_size=21,
+                                                   desired_resolution=8192, gridtype='tiled'))]
 
 
 @pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
@@ -322,13 +335,14 @@ def test_scatter_skips_zero_rows_and_recomputes_overflowing_bins():
     assert scale > 100.0 and float((r1 - ra).abs().max()) < 2e-3 * scale
 
 
-@pytest.mark.parametrize("max_level", [1, 6, 9])
+@pytest.mark.parametrize("max_level", [1, 6, 9, 17, 23])
 def test_binned_scatter_with_fewer_active_levels(max_level):
     """coarse-to-fine training hands `max_level < L` to the backward (grid.py: only the first max_level levels receive gradient): the histogram-free
-    scatter plans its slots for those levels only — same table gradient as the atomic kernel, the inactive levels' rows untouched, bit-reproducible"""
+    scatter plans its slots for those levels only — same table gradient as the atomic kernel, the inactive levels' rows untouched, bit-reproducible
+    (a 16-level table up to 9 active levels, a 24-level one above 16)"""
     from customnerf_amd._lib import lib, ptr, stream, check
     import ctypes
-    enc = build(CONFIGS[0][1])
+    enc = build(CONFIGS[0][1] if max_level < 16 else config("hash_L24_T19"))
     L, C = enc.num_levels, enc.level_dim
     S = float(np.log2(enc.per_level_scale))
     B = 90001
@@ -391,12 +405,13 @@ def test_rejects_bad_arguments():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("bad", [float("inf"), float("-inf"), float("nan")])
-def test_backward_propagates_non_finite_gradients(bad):
+@pytest.mark.parametrize("bad,level", [pytest.param(float("inf"), 8, id="inf"), pytest.param(float("-inf"), 8, id="-inf"), pytest.param(float("nan"), 8, id="nan"),
+                                       pytest.param(float("inf"), 17, id="inf-level17"), pytest.param(float("nan"), 23, id="nan-level23")])
+def test_backward_propagates_non_finite_gradients(bad, level):
     """The loss scaler detects overflow by looking for inf / NaN in the gradients (GradScaler; the reference's half2 atomics propagate them,
     gridencoder.cu:324-337).  The binned fp16 backward sums in fixed point, which cannot carry them: a non-finite incoming gradient must still
-    leave a non-finite entry in the table gradient."""
-    kw = CONFIGS[0][1]
+    leave a non-finite entry in the table gradient — in a level of the first 16 (16-level table) and in a level above 16 (24-level table)."""
+    kw = CONFIGS[0][1] if level < 16 else config("hash_L24_T19")
     enc = build(kw)
     B = 70001                                                 # B x levels >= 2^20: the binned (fixed-point) path, not the atomic kernel
     x = torch.from_numpy(make_inputs(B, 3)).cuda()
@@ -404,7 +419,7 @@ def test_backward_propagates_non_finite_gradients(bad):
         out = enc(x * 2 - 1, bound=1.0)
     assert out.dtype == torch.float16
     g = torch.randn(out.shape, device='cuda').half() * 1e-3
-    g[1234, 17] = bad
+    g[1234, 2 * level + 1] = bad
     out.backward(g)
     grad = enc.embeddings.grad
     assert not bool(torch.isfinite(grad).all()), "a non-finite output gradient vanished in the scatter"
@@ -491,13 +506,14 @@ def _adam_reference_and_fused(enc, x, g_lbc, scaler_state, p_half, max_level=Non
     return outs[0], outs[1], consumed
 
 
-@pytest.mark.parametrize("case", ["uniform", "corner", "overflow_skip", "accumulated_grad", "no_shadow_keep_grad"])
+@pytest.mark.parametrize("case", ["uniform", "corner", "overflow_skip", "accumulated_grad", "no_shadow_keep_grad", "uniform_L24"])
 def test_table_adam_inside_the_scatter_is_bit_identical(case):
     """cnerf_grid_backward_adam: the Adam update applied by the scatter's flush (sole-owner bins, the split bins' reduction, bins without a single record)
     leaves parameter, moments, gradient table and fp16 shadow exactly as the backward pass followed by cnerf_adam_step_scaled does — uniform samples,
     samples confined to a corner of the volume (most bins of the dense levels see no record; a few are crowded and split), a step the loss scaler
-    skips (found_inf set: no update, gradients cleared), a gradient table that already holds a contribution, and without shadow / without clearing"""
-    enc = build(CONFIGS[0][1], scale=0.5)
+    skips (found_inf set: no update, gradients cleared), a gradient table that already holds a contribution, without shadow / without clearing,
+    and a 24-level table"""
+    enc = build(config("hash_L24_T19") if case == "uniform_L24" else CONFIGS[0][1], scale=0.5)
     L, C = enc.num_levels, enc.level_dim
     B = 150001
     rng = np.random.default_rng(31)

@@ -779,15 +779,19 @@ _HEADLINE_F16_PIN = {            # geometry -> {quantity: 3 x measured max abs e
     "hash_T19": dict(image=7e-5, depth=1.2e-5, weights_sum=4e-6, grid=8.1e-2, net=0.23, den=0.19, rgb=1.7e-2),
     # measured: image 4.55e-5, depth 2.28e-5, weights_sum 1.85e-6, grid 4.78e-2, net 3.20e-2, den 1.18e-1, rgb 1.34e-2
     "bear_tiled_T21": dict(image=1.4e-4, depth=7e-5, weights_sum=6e-6, grid=0.145, net=0.1, den=0.36, rgb=4.1e-2),
+    # 24 levels (the two-launch field backward).  measured: image 3.91e-5, depth 3.46e-6, weights_sum 1.19e-6, grid 7.42e-2, net 5.20e-2,
+    # den 1.06e-1 (3x would exceed the loose bound: den stays at _HEADLINE_F16_LOOSE), rgb 8.09e-3
+    "hash_L24_T19": dict(image=1.2e-4, depth=1.1e-5, weights_sum=3.6e-6, grid=0.223, net=0.156, den=None, rgb=2.5e-2),
 }
 _HEADLINE_F16_LOOSE = dict(image=3e-2, depth=6e-2, weights_sum=3e-2, grid=0.25, net=0.25, den=0.25, rgb=0.25)   # used for a quantity whose pin is None
 
 
 @pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
-@pytest.mark.parametrize("geom", ["hash_T19", "bear_tiled_T21"])
+@pytest.mark.parametrize("geom", ["hash_T19", "bear_tiled_T21", "hash_L24_T19"])
 def test_run_end_to_end_vs_oracle_headline(geom, half):
     """1024 rays of a cfg2 view through run() + the reconstruction loss + backward with the headline field (hash L16 T = 2^19 desired 2048, and the
-    reference field's own geometry: tiled L16 T = 2^21 desired 8192 — network_grid.py:89-96), 64 + 64 samples, two hidden geometry layers —
+    reference field's own geometry: tiled L16 T = 2^21 desired 8192 — network_grid.py:89-96 —, and hash L24 T = 2^19: a 48-wide encoding, whose
+    backward is the two-launch form), 64 + 64 samples, two hidden geometry layers —
     i.e. the fused samplers, BOTH gathers, the block-wise fused field, the indexed compositing, the fused field backward and the BINNED
     scatter (2.1 M (sample, level) pairs) in one piece, against oracle.torch_oracle.run on the CPU with the same parameters and RNG draws.
     renderer.py:278-474, network_grid.py:159-193."""
@@ -797,10 +801,12 @@ def test_run_end_to_end_vs_oracle_headline(geom, half):
     tcnn.set_default_dtype(torch.float16 if half else torch.float32)
     try:
         gkw = dict(grid_type='tiledgrid', log2_hashmap_size=21, desired_resolution=8192) if geom == "bear_tiled_T21" else {}
+        if geom == "hash_L24_T19":
+            gkw = dict(num_levels=24)
         opt = sc.make_opt(fp16=half, **gkw)
         torch.manual_seed(0)
         model = NeRFNetwork(opt).cuda()
-        ref = to.FieldRef(bound=opt.bound, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=opt.log2_hashmap_size,
+        ref = to.FieldRef(bound=opt.bound, num_levels=opt.num_levels, level_dim=2, base_resolution=16, log2_hashmap_size=opt.log2_hashmap_size,
                           desired_resolution=opt.desired_resolution, gridtype='tiled' if geom == "bear_tiled_T21" else 'hash', n_hidden_geo=2, half=half, seed=1)
         ref.pos_en.half = half
         g = torch.Generator().manual_seed(101)

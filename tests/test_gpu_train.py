@@ -318,6 +318,15 @@ def test_training_is_bit_reproducible():
     """Two identical fp16 trainings (same seed, full-size 128x128 views so that the binned fixed-point scatter, the wave-specialised field
     backward and the split-bin reduction all run) end in bit-identical parameters: every reduction on the path has a fixed order or is
     exact (the reference's half2 atomic scatter is not reproducible)."""
+    _check_training_is_bit_reproducible(16)
+
+
+def test_training_is_bit_reproducible_at_24_levels():
+    """the same with a 24-level table: the two-launch field backward and its split-K partial rows"""
+    _check_training_is_bit_reproducible(24)
+
+
+def _check_training_is_bit_reproducible(num_levels):
     from customnerf_amd import scene as sc, tcnn
     from customnerf_amd.nerf.network_grid import NeRFNetwork
     from customnerf_amd.trainer import ReconTrainer
@@ -325,7 +334,7 @@ def test_training_is_bit_reproducible():
 
     def train():
         torch.manual_seed(0)
-        opt = sc.make_opt(fp16=True)
+        opt = sc.make_opt(fp16=True, num_levels=num_levels)
         model = NeRFNetwork(opt).cuda()
         H = W = 128
         V = 2
@@ -413,6 +422,15 @@ def test_training_is_bit_identical_with_the_table_step_inside_the_scatter():
     """ReconTrainer arms the grid table's Adam update for its one backward pass (optim.FusedAdam.arm_in_backward -> cnerf_grid_backward_adam): eight
     steps — among them one the loss scaler skips (its scale is raised until the half-precision gradients overflow) — end in the parameters, Adam
     moments and scaler state of the same steps with `opt.fuse_table_adam = False`, bit for bit; and the fused run really took the fused path"""
+    _check_table_step_inside_the_scatter(16)
+
+
+def test_training_is_bit_identical_with_the_table_step_inside_the_scatter_at_24_levels():
+    """the same with a 24-level table (the field backward's two-launch form raises found_inf for the folded check)"""
+    _check_table_step_inside_the_scatter(24)
+
+
+def _check_table_step_inside_the_scatter(num_levels):
     from customnerf_amd import scene as sc, tcnn
     from customnerf_amd.nerf.network_grid import NeRFNetwork
     from customnerf_amd.trainer import ReconTrainer
@@ -420,7 +438,7 @@ def test_training_is_bit_identical_with_the_table_step_inside_the_scatter():
 
     def train(fuse):
         torch.manual_seed(0)
-        opt = sc.make_opt(fp16=True)
+        opt = sc.make_opt(fp16=True, num_levels=num_levels)
         opt.fuse_table_adam = fuse
         model = NeRFNetwork(opt).cuda()
         H = W = 64
@@ -834,13 +852,14 @@ def test_graphed_step_owns_its_buffers():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("fitted", [0, 1, 2], ids=["random_init", "fitted_sphere", "half_the_rays_without_loss"])
+@pytest.mark.parametrize("fitted", [0, 1, 2, 3], ids=["random_init", "fitted_sphere", "half_the_rays_without_loss", "random_init_L24"])
 def test_early_termination_leaves_every_gradient_bit_identical(fitted):
     """VERDICT r4 item 2 (north_star: "wavefront ballot/scan for ray compaction and early termination").  With the half-precision fused field the
     compositing backward writes exact zeros for rows whose gradients round to zero in the form k_field_bwd_x2 consumes them, reports the ray's dead
     32-row tiles by wave ballot, the field backward skips those tiles in place and the scatter emits no records for zero rows.  Skipped work adds
     exact zeros, so the table gradient (exact fixed-point sums) and the three MLP gradients (same tiles, same pipelines, same order) must be
-    torch.equal to the run without it — on a random-initialised field (nothing to skip) and on a field fitted to the sphere scene (most of it)."""
+    torch.equal to the run without it — on a random-initialised field (nothing to skip) and on a field fitted to the sphere scene (most of it);
+    random_init_L24: a 24-level table, whose two-launch field backward evaluates every tile (the flushed rows are exact zeros there too)."""
     from customnerf_amd import scene as sc, tcnn, field as fld
     from customnerf_amd.nerf.network_grid import NeRFNetwork
     from customnerf_amd.nerf.provider_utils import generate_rays
@@ -849,7 +868,7 @@ def test_early_termination_leaves_every_gradient_bit_identical(fitted):
     H = W = 64
     V = 4
     torch.manual_seed(0)
-    opt = sc.make_opt(fp16=True, num_steps=32, upsample_steps=32, iters=1000)
+    opt = sc.make_opt(fp16=True, num_steps=32, upsample_steps=32, iters=1000, num_levels=24 if fitted == 3 else 16)
     model = NeRFNetwork(opt).cuda()
     c2w = torch.from_numpy(sc.poses(V)).cuda()
     ro, rd = generate_rays(c2w, *sc.intrinsics(H, W), H, W, 1.0, 'nerfstudio')
@@ -980,11 +999,9 @@ def test_inf_check_is_folded_into_the_gradient_producers():
     trainer skips the pass over every gradient.  (1) the two producers raise the flag for a non-finite gradient — binned and atomic scatter sizes —
     and leave it alone otherwise; (2) a training step whose targets contain an infinity is skipped exactly as with the explicit check: parameters
     untouched, loss scale halved, gradients zeroed, the next clean step counts."""
-    from customnerf_amd import scene as sc, tcnn
+    from customnerf_amd import tcnn
     from customnerf_amd.gridencoder import GridEncoder
-    from customnerf_amd.nerf.network_grid import NeRFNetwork
     from customnerf_amd.optim import DynamicLossScaler
-    from customnerf_amd.trainer import ReconTrainer
     tcnn.set_default_dtype(torch.float16)
     try:
         # (1) the scatter
@@ -1007,31 +1024,49 @@ def test_inf_check_is_folded_into_the_gradient_producers():
                 assert float(sclr.state[2]) == (1.0 if bad else 0.0), (B, bad)
                 assert bool(torch.isfinite(enc.embeddings.grad).all()) == (not bad)
         # (2) the trainer
-        H = W = 128
-        o, d, rgb, mask = _target_scene(H, W, 2)
-        results = {}
-        for fold in (True, False):
-            torch.manual_seed(0)
-            opt = sc.make_opt(fp16=True, fold_inf_check=fold)
-            model = NeRFNetwork(opt).cuda()
-            tr = ReconTrainer(model, opt, fp16=True)
-            kw = dict(num_steps=opt.num_steps, upsample_steps=opt.upsample_steps)
-            tr.train_step(o[0], d[0], rgb[0], mask[0], **kw)
-            assert tr._inf_folded == fold
-            before = [p.detach().clone() for p in model.parameters()]
-            bad_rgb = rgb[1].clone()
-            bad_rgb[1234, 1] = float("inf")
-            loss, _ = tr.train_step(o[1], d[1], bad_rgb, mask[1], **kw)
-            st = tr.scaler.state.detach().cpu().tolist()
-            assert not np.isfinite(float(loss))
-            assert st[0] == 32768.0 and st[2] == 0.0 and st[3] == 1.0, st           # backed off, flag cleared, still one good step
-            for a, p in zip(before, model.parameters()):
-                assert torch.equal(a, p.detach())                                      # the optimiser step was skipped
-                assert bool((p.grad == 0).all())                                       # ... and the gradients were zeroed all the same
-            loss, _ = tr.train_step(o[0], d[0], rgb[0], mask[0], **kw)
-            assert np.isfinite(float(loss)) and tr.scaler.good_steps() == 2
-            results[fold] = [p.detach().clone() for p in model.parameters()]
-        for a, b in zip(results[True], results[False]):
-            assert torch.equal(a, b)                                                   # the folded check changes no bit of the training
+        _check_folded_inf_check_skips_a_step(16)
     finally:
         tcnn.set_default_dtype(torch.float32)
+
+
+@pytest.mark.gpu
+def test_inf_check_is_folded_into_the_gradient_producers_at_24_levels():
+    """part (2) of the test above with a 24-level table: the field backward's two-launch form must raise found_inf itself"""
+    from customnerf_amd import tcnn
+    tcnn.set_default_dtype(torch.float16)
+    try:
+        _check_folded_inf_check_skips_a_step(24)
+    finally:
+        tcnn.set_default_dtype(torch.float32)
+
+
+def _check_folded_inf_check_skips_a_step(num_levels):
+    from customnerf_amd import scene as sc
+    from customnerf_amd.nerf.network_grid import NeRFNetwork
+    from customnerf_amd.trainer import ReconTrainer
+    H = W = 128
+    o, d, rgb, mask = _target_scene(H, W, 2)
+    results = {}
+    for fold in (True, False):
+        torch.manual_seed(0)
+        opt = sc.make_opt(fp16=True, fold_inf_check=fold, num_levels=num_levels)
+        model = NeRFNetwork(opt).cuda()
+        tr = ReconTrainer(model, opt, fp16=True)
+        kw = dict(num_steps=opt.num_steps, upsample_steps=opt.upsample_steps)
+        tr.train_step(o[0], d[0], rgb[0], mask[0], **kw)
+        assert tr._inf_folded == fold
+        before = [p.detach().clone() for p in model.parameters()]
+        bad_rgb = rgb[1].clone()
+        bad_rgb[1234, 1] = float("inf")
+        loss, _ = tr.train_step(o[1], d[1], bad_rgb, mask[1], **kw)
+        st = tr.scaler.state.detach().cpu().tolist()
+        assert not np.isfinite(float(loss))
+        assert st[0] == 32768.0 and st[2] == 0.0 and st[3] == 1.0, st           # backed off, flag cleared, still one good step
+        for a, p in zip(before, model.parameters()):
+            assert torch.equal(a, p.detach())                                      # the optimiser step was skipped
+            assert bool((p.grad == 0).all())                                       # ... and the gradients were zeroed all the same
+        loss, _ = tr.train_step(o[0], d[0], rgb[0], mask[0], **kw)
+        assert np.isfinite(float(loss)) and tr.scaler.good_steps() == 2
+        results[fold] = [p.detach().clone() for p in model.parameters()]
+    for a, b in zip(results[True], results[False]):
+        assert torch.equal(a, b)                                                   # the folded check changes no bit of the training
