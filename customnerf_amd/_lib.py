@@ -100,6 +100,10 @@ SIGNATURES = {
     "cnerf_mesh_decimate_init": [vp, u32, vp, u32, vp, u64, vp, vp],
     "cnerf_mesh_decimate_round": [u32, u32, u32, vp, u64, vp, vp],
     "cnerf_mesh_decimate_emit": [vp, u32, u32, vp, u64, vp, vp, vp, vp, u32, u32, vp],
+    "cnerf_mesh_smooth_workspace_bytes": [u32, u32, vp],
+    "cnerf_mesh_smooth_init": [vp, u32, u32, vp, u64, vp, vp],
+    "cnerf_mesh_smooth_steps": [vp, u32, u32, u32, f32, f32, i32, vp, u64, vp, vp],
+    "cnerf_mesh_smooth_normals": [vp, vp, u32, vp, u32, vp, u64, vp, vp],
     "cnerf_mesh_atlas_layout": [u32, u32, vp, vp],
     "cnerf_mesh_atlas_uvs": [vp, u32, u32, u32, vp, u32, vp, vp],
     "cnerf_mesh_atlas_points": [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, vp, u32, vp],

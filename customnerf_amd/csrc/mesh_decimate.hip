@@ -139,20 +139,6 @@ DcPtr dc_ptr(void *ws, const DcLayout &l) {
 __device__ __forceinline__ uint32_t dc_next(uint32_t k) { return k == 2 ? 0 : k + 1; }
 __device__ __forceinline__ uint32_t dc_fv(const int32_t *fa, uint32_t f, uint32_t q) { return (uint32_t)fa[3 * (uint64_t)f + q]; }
 
-// exclusive prefix of v over the workgroup in thread order and its total; every thread of the block must call it.  `red` = LDS [MC_WAVES]
-__device__ __forceinline__ uint32_t dc_block_excl(uint32_t v, uint32_t *red, uint32_t &tot) {
-    const uint32_t incl = cn_wave_incl_scan(v), w = threadIdx.x / CN_WAVE;
-    if (cn_lane() == CN_WAVE - 1) red[w] = incl;
-    __syncthreads();
-    uint32_t pre = incl - v;
-    tot = 0;
-    for (uint32_t j = 0; j < MC_WAVES; ++j) {
-        if (j < w) pre += red[j];
-        tot += red[j];
-    }
-    return pre;
-}
-
 // ------------------------------------------------------------------------------------------------ vertex -> face lists
 __global__ __launch_bounds__(MC_BLOCK) void k_dc_clear(uint32_t V, DcPtr p) {
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
@@ -206,8 +192,8 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_vsum(uint32_t V, DcPtr p) {
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
     const uint32_t d = v < V ? p.deg[v] : 0;
     uint32_t td, tr;
-    dc_block_excl(d, red_d, td);
-    dc_block_excl(d ? 1u : 0u, red_r, tr);
+    mc_block_excl(d, red_d, td);
+    mc_block_excl(d ? 1u : 0u, red_r, tr);
     if (threadIdx.x == 0) p.sums[blockIdx.x] = make_uint2(td, tr);
 }
 
@@ -222,7 +208,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_offsets(uint32_t V, DcPtr p) {
     __shared__ uint32_t red[MC_WAVES];
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
     uint32_t tot;
-    const uint32_t start = p.sums[blockIdx.x].x + dc_block_excl(v < V ? p.deg[v] : 0, red, tot);
+    const uint32_t start = p.sums[blockIdx.x].x + mc_block_excl(v < V ? p.deg[v] : 0, red, tot);
     if (v < V) p.end[v] = start;                     // k_dc_fill advances it to start + degree
 }
 

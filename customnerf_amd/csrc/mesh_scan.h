@@ -1,5 +1,6 @@
 // Workgroup prefix sums and the one-workgroup scan of workgroup totals, shared by the mesh kernels (mesh.hip: marching cubes,
-// mesh_clean.hip: component removal and clustering).  Every grid these kernels scan is one thread per item, MC_BLOCK threads per workgroup;
+// mesh_clean.hip: component removal and clustering, mesh_decimate.hip and mesh_smooth.hip: vertex lists).  Every grid these kernels scan
+// is one thread per item, MC_BLOCK threads per workgroup;
 // a count pass stores each workgroup's two totals (uint2), mc_scan_totals turns them into exclusive offsets in place, and an emit pass adds
 // the in-workgroup prefix (ballot + mbcnt, LDS wave totals) to its workgroup's offset.  Order follows the thread index: no atomics.
 #pragma once
@@ -30,6 +31,20 @@ __device__ __forceinline__ uint32_t mc_block_prefix(uint32_t v, uint32_t *red) {
     if (cn_lane() == 0) red[w] = tot;
     __syncthreads();
     for (uint32_t j = 0; j < w; ++j) pre += red[j];
+    return pre;
+}
+
+// exclusive prefix of any v over the workgroup in thread order and its total; every thread of the block must call it.  `red` = LDS [MC_WAVES]
+__device__ __forceinline__ uint32_t mc_block_excl(uint32_t v, uint32_t *red, uint32_t &tot) {
+    const uint32_t incl = cn_wave_incl_scan(v), w = threadIdx.x / CN_WAVE;
+    if (cn_lane() == CN_WAVE - 1) red[w] = incl;
+    __syncthreads();
+    uint32_t pre = incl - v;
+    tot = 0;
+    for (uint32_t j = 0; j < MC_WAVES; ++j) {
+        if (j < w) pre += red[j];
+        tot += red[j];
+    }
     return pre;
 }
 

@@ -1,6 +1,7 @@
 """Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*), mesh cleanup on the GPU (csrc/mesh_clean.hip:
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
-face count), texture baking into a per-face-pair atlas on the GPU (csrc/mesh_texture.hip), a binary PLY writer and an OBJ + MTL + PNG writer.
+face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU
+(csrc/mesh_texture.hip), a binary PLY writer and an OBJ + MTL + PNG writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -8,6 +9,7 @@ The table is crack-free for any input (csrc/gen_mc_tables.py); it is not skimage
 from skimage's while describing the same isosurface.
 """
 import ctypes as C
+import math
 import os
 import struct
 import zlib
@@ -221,6 +223,65 @@ def decimate(verts, faces, target_faces, normals=None, rounds=None):
                                        ptr(no) if nv and no is not None else None, ptr(fo) if nf else None, ptr(old) if nv else None,
                                        nv, nf, stream()), "mesh_decimate_emit")
     return vo, fo, no, old
+
+
+def smooth_workspace_bytes(V, F):
+    out = C.c_uint64(0)
+    check(lib.cnerf_mesh_smooth_workspace_bytes(int(V), int(F), C.byref(out)), "mesh_smooth_workspace_bytes")
+    return out.value
+
+
+def _smooth_init(v, f, what):
+    """workspace of cnerf_mesh_smooth_* with the neighbour and face lists built, and its size"""
+    V, F = v.shape[0], f.shape[0]
+    nbytes = smooth_workspace_bytes(V, F)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=v.device)
+    flags = torch.empty(1, dtype=torch.int32, device=v.device)
+    check(lib.cnerf_mesh_smooth_init(ptr(f) if F else None, V, F, ptr(ws), nbytes, ptr(flags), stream()), "mesh_smooth_init")
+    if int(flags.cpu()[0]) & 1:                                                 # the one host read
+        raise ValueError(f"{what}: a face index lies outside [0, V)")
+    return ws, nbytes
+
+
+def _normals(v, f, n, ws, nbytes):
+    V, F = v.shape[0], f.shape[0]
+    no = torch.empty(V, 3, dtype=torch.float32, device=v.device)
+    check(lib.cnerf_mesh_smooth_normals(ptr(v) if V else None, ptr(n) if V and n is not None else None, V, ptr(f) if F else None, F,
+                                        ptr(ws), nbytes, ptr(no) if V else None, stream()), "mesh_smooth_normals")
+    return no
+
+
+def smooth(verts, faces, iterations=10, lamb=0.5, mu=-0.53, normals=None, pin_boundary=True):
+    """Taubin lambda|mu smoothing (Taubin 1995) with uniform weights on the device (csrc/mesh_smooth.hip; the rules are in
+    include/customnerf_hip.h, cnerf_mesh_smooth_*): each iteration moves every vertex by lamb, then by mu (when mu != 0), times the offset
+    from the mean of its neighbours (the distinct vertices sharing an edge with it).  The defaults are MeshLab's Taubin defaults; mu=0 is
+    plain Laplacian smoothing, which shrinks the mesh.  With pin_boundary, vertices on an edge with one face keep their position bit for
+    bit; a vertex no edge reaches never moves.  Any triangle mesh: CUDA tensors verts [V, 3], faces [F, 3] (int; need not be manifold),
+    normals [V, 3] or None.  -> (verts [V, 3] float32, normals [V, 3] float32): the faces are unchanged and the normals are vertex_normals()
+    of the smoothed positions (where a vertex's face normals sum to zero, its input normal, or zero without one).  Bad input raises
+    ValueError."""
+    v, f, n = _mesh_args(verts, faces, normals, "smooth")
+    it = int(iterations)
+    if it < 0 or it >= 2 ** 32:
+        raise ValueError(f"smooth: iterations must be in [0, 2^32), got {iterations}")
+    lamb, mu = float(lamb), float(mu)
+    if not (math.isfinite(lamb) and 0.0 < lamb <= 1.0 and math.isfinite(mu) and -1.0 <= mu <= 0.0):
+        raise ValueError(f"smooth: need 0 < lamb <= 1 and -1 <= mu <= 0, got lamb = {lamb}, mu = {mu}")
+    V, F = v.shape[0], f.shape[0]
+    ws, nbytes = _smooth_init(v, f, "smooth")
+    vo = torch.empty(V, 3, dtype=torch.float32, device=v.device)
+    check(lib.cnerf_mesh_smooth_steps(ptr(v) if V else None, V, F, it, lamb, mu, 1 if pin_boundary else 0, ptr(ws), nbytes,
+                                      ptr(vo) if V else None, stream()), "mesh_smooth_steps")
+    return vo, _normals(vo, f, n, ws, nbytes)
+
+
+def vertex_normals(verts, faces, normals=None):
+    """Area-weighted vertex normals on the device (csrc/mesh_smooth.hip): the normalised sum of (p1 - p0) x (p2 - p0) over the faces that hold
+    the vertex, in increasing face index, in float32; where that sum is zero, the vertex's normal from `normals`, or zero without them.  CUDA
+    tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None.  -> normals [V, 3] float32.  Bad input raises ValueError."""
+    v, f, n = _mesh_args(verts, faces, normals, "vertex_normals")
+    ws, nbytes = _smooth_init(v, f, "vertex_normals")
+    return _normals(v, f, n, ws, nbytes)
 
 
 def _host(a, dtype):

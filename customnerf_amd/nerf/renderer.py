@@ -486,16 +486,20 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
-                     min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0):
+                     min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
+                     smooth_mu=-0.53):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
         coordinates), faces [F, 3] int32 (wound outwards), normals [V, 3] (outward), colors [V, 3] uint8 or None, and the volume.
         Cleanup on the device (mesh.py, csrc/mesh_clean.hip), in this order, before the colours are sampled at the final vertices:
         min_component_faces > 0 drops the connected components with fewer faces (floaters); keep_largest=True keeps only the component with
-        the most faces; simplify=k >= 2 clusters the vertices in cells of k lattice steps from the lattice's lower corner (mesh.simplify);
-        target_faces > 0 decimates by quadric edge collapse to that many faces (mesh.decimate; not with simplify, whose output need not be
-        manifold).  The defaults return the marching-cubes mesh as it is.
+        the most faces; smooth=k > 0 runs k Taubin iterations (smooth_lambda, smooth_mu; mesh.smooth, csrc/mesh_smooth.hip: boundary vertices
+        stay, smooth_mu=0 is plain Laplacian smoothing), after which the normals are the area-weighted normals of the smoothed surface;
+        simplify=k >= 2 clusters the vertices in cells of k lattice steps from the lattice's lower corner (mesh.simplify); target_faces > 0
+        decimates by quadric edge collapse to that many faces (mesh.decimate; not with simplify, whose output need not be manifold).
+        simplify and decimate carry the normals along, and color / texture look along them.  The defaults return the marching-cubes mesh
+        as it is.
         texture=R > 0 bakes the field's colour, looking at the surface, into an R x R texture atlas of the final mesh (mesh.bake_texture,
         csrc/mesh_texture.hip): 'uvs' [F, 3, 2] float32 and 'texture' [R, R, 3] uint8 join the dict (both None with texture=0)."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
@@ -514,9 +518,14 @@ class NeRFRenderer(nn.Module):
         tex_r = int(texture)
         if tex_r < 0:
             raise ValueError(f"extract_mesh: texture must be 0 (off) or a texture resolution, got {texture}")
+        n_smooth = int(smooth)
+        if n_smooth < 0:
+            raise ValueError(f"extract_mesh: smooth must be 0 (off) or a number of iterations, got {smooth}")
         if int(min_component_faces) > 0 or keep_largest:
             verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
                                                                      largest=bool(keep_largest))
+        if n_smooth:
+            verts, normals = _mesh.smooth(verts, faces, n_smooth, smooth_lambda, smooth_mu, normals=normals)
         if k >= 2:
             g = (-(-(R - 1) // k),) * 3                                          # ceil((R - 1) / k) cells cover the lattice
             verts, faces, normals = _mesh.simplify(verts, faces, (step * k).tolist(), normals=normals, origin=lo.tolist(), grid=g)
@@ -539,7 +548,7 @@ class NeRFRenderer(nn.Module):
         """extract_mesh(**kw) written to `path` -> the mesh dict.  A path ending in .obj writes a Wavefront OBJ (mesh.write_obj: positions,
         normals, and with texture=R the UVs, <stem>.mtl and the R x R <stem>.png beside it; vertex colours are not written to OBJ); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
-        extract_mesh (min_component_faces, keep_largest, simplify, target_faces) pass through."""
+        extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces) pass through."""
         obj = str(path).lower().endswith(".obj")
         if int(kw.get('texture', 0) or 0) and not obj:
             raise ValueError(f"save_mesh: texture= needs an .obj path (PLY carries no texture), got {path!r}")

@@ -38,7 +38,8 @@ extern "C" {
  * 7: mesh extraction — cnerf_marching_cubes_workspace_bytes / _count / _emit; mesh cleanup (additive, same version: a binding that
  *    needs them fails at load on the missing symbol) — cnerf_mesh_components_* and cnerf_mesh_cluster_* (workspace_bytes / _count / _emit);
  *    quadric decimation (additive, same version) — cnerf_mesh_decimate_workspace_bytes / _init / _round / _emit; texture baking (additive,
- *    same version) — cnerf_mesh_atlas_layout / _uvs / _points / _store / _fill. */
+ *    same version) — cnerf_mesh_atlas_layout / _uvs / _points / _store / _fill; smoothing and normals (additive, same version) —
+ *    cnerf_mesh_smooth_workspace_bytes / _init / _steps / _normals. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -637,6 +638,33 @@ int cnerf_mesh_atlas_points(const float *verts, const float *normals, uint32_t V
 int cnerf_mesh_atlas_store(uint32_t F, uint32_t R, uint32_t t0, uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host,
                            const uint32_t *flags, uint8_t *image, void *stream);
 int cnerf_mesh_atlas_fill(uint32_t F, uint32_t R, const uint8_t *fill_host, uint8_t *image, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Taubin lambda|mu smoothing with uniform weights and area-weighted vertex normals (customnerf_amd/mesh.py smooth / vertex_normals;
+ * csrc/mesh_smooth.hip; Taubin 1995).  Any triangle mesh: verts float32 [V][3], faces int32 [F][3] (need not be manifold; a face repeating an
+ * index adds only its distinct edges), optional normals float32 [V][3] (NULL: none).  V < 2^31 and F <= 0x2AAAAAAA (6 F neighbour records
+ * fit 32 bits), else CNERF_EINVAL; ws 16-byte aligned and >= workspace_bytes(V, F), else CNERF_EINVAL.  The caller's stream and workspace;
+ * no allocation, no host sync, integer atomics only (every list is sorted before it is read): the output is bit-reproducible.
+ *   init    : from the faces alone: each vertex's neighbours (the distinct vertices sharing an edge with it, in increasing index), its faces
+ *             (each once, in increasing index) and its boundary mark (one of its edges lies in exactly one face).  flags[0] (device uint32)
+ *             = bit 0 when an index lies outside [0, V): the one host read; after it steps and normals write nothing.
+ *   steps   : after init on the same stream with the same ws, V and F.  `iterations` of a lambda step and, when mu != 0, a mu step (lambda and
+ *             mu finite, else CNERF_EINVAL); Jacobi: each step reads the previous positions only.  Step with factor s: a vertex with n > 0
+ *             neighbours that is not pinned (pin_boundary != 0 pins boundary vertices) gets x + s * (m - x), m = sum / (float) n, sum = the
+ *             neighbours' positions added in float32 in list order from the first, three rounded operations; every other vertex keeps x
+ *             bit for bit.  The last step writes verts_out [V][3] (iterations = 0: a copy of verts_in), which must not overlap verts_in.
+ *   normals : after init, from `verts` (any positions over the same faces): c = (p1 - p0) x (p2 - p0) per face in float32,
+ *             (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x); a = (0, 0, 0) + c of each of the vertex's faces in increasing face
+ *             index; q = ax ax + ay ay + az az; 0 < q < inf: normals_out = a / sqrt(q) (correctly rounded), otherwise normals_in of the
+ *             vertex, or (0, 0, 0) when normals_in is NULL.
+ *   workspace_bytes : about 48 bytes per vertex + 36 per face.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_smooth_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_smooth_init(const int32_t *faces, uint32_t V, uint32_t F, void *ws, uint64_t ws_bytes, uint32_t *flags, void *stream);
+int cnerf_mesh_smooth_steps(const float *verts_in, uint32_t V, uint32_t F, uint32_t iterations, float lambda, float mu, int pin_boundary,
+                            void *ws, uint64_t ws_bytes, float *verts_out, void *stream);
+int cnerf_mesh_smooth_normals(const float *verts, const float *normals_in, uint32_t V, const int32_t *faces, uint32_t F, void *ws,
+                              uint64_t ws_bytes, float *normals_out, void *stream);
 
 #ifdef __cplusplus
 }
