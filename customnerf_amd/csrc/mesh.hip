@@ -12,24 +12,26 @@
 // scheduling.  Workspace: header (overflow flag) | case bytes [N] | mask bytes [N] | vertex bases uint32 [N] | workgroup totals uint2 [N/256].
 #include "common.h"
 #include "mc_tables.h"
-#include "mesh_scan.h"          // MC_BLOCK, mc_block_prefix / mc_block_total, mc_scan_totals
+#include "mesh_common.h"        // MC_BLOCK, mc_block_prefix / mc_block_total, mc_scan_totals, MeshCarve
 
 namespace {
 
-struct McLayout {
-    uint64_t cases, masks, vbase, sums, total;
+struct McPtr {
+    uint32_t *flag;                                  // header: the overflow flag
+    uint8_t *cases, *masks;
+    uint32_t *vbase;
+    uint2 *sums;
 };
 
-inline uint64_t mc_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
-McLayout mc_layout(uint64_t n) {
-    McLayout l;
-    l.cases = 256;                                   // [0, 256): uint32 overflow flag
-    l.masks = l.cases + mc_align(n);
-    l.vbase = l.masks + mc_align(n);
-    l.sums = l.vbase + mc_align(4 * n);
-    l.total = l.sums + mc_align(8 * cn_div_up64(n, MC_BLOCK));
-    return l;
+// the workspace of n grid points: its regions in order -> total bytes (ws == nullptr: the size only)
+uint64_t mc_carve(void *ws, uint64_t n, McPtr &p) {
+    MeshCarve c(ws);
+    p.flag = c.header();
+    p.cases = c.take<uint8_t>(n);
+    p.masks = c.take<uint8_t>(n);
+    p.vbase = c.take<uint32_t>(n);
+    p.sums = c.take<uint2>(cn_div_up64(n, MC_BLOCK));
+    return c.total();
 }
 
 struct McGeom {
@@ -187,7 +189,8 @@ extern "C" {
 int cnerf_marching_cubes_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz, uint64_t *bytes_host) {
     if (const int rc = mc_check_dims(nx, ny, nz)) return rc;
     if (!bytes_host) return CNERF_ENULL;
-    *bytes_host = mc_layout((uint64_t)nx * ny * nz).total;
+    McPtr p;
+    *bytes_host = mc_carve(nullptr, (uint64_t)nx * ny * nz, p);
     return CNERF_OK;
 }
 
@@ -196,13 +199,10 @@ int cnerf_marching_cubes_count(const float *vol, uint32_t nx, uint32_t ny, uint3
     if (const int rc = mc_check_dims(nx, ny, nz)) return rc;
     if (!vol || !ws || !counts) return CNERF_ENULL;
     const uint32_t n = nx * ny * nz;
-    const McLayout l = mc_layout(n);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return CNERF_EINVAL;
-    uint8_t *w = (uint8_t *)ws;
-    const uint32_t nblk = cn_div_up(n, MC_BLOCK);
-    hipLaunchKernelGGL(k_mc_count, dim3(nblk), dim3(MC_BLOCK), 0, CN_STREAM(stream), vol, nx, ny, nz, level, w + l.cases, w + l.masks,
-                       (uint2 *)(w + l.sums));
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, CN_STREAM(stream), (uint2 *)(w + l.sums), nblk, counts, (uint32_t *)w);
+    McPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, mc_carve(ws, n, p))) return rc;
+    hipLaunchKernelGGL(k_mc_count, mesh_grid(n), dim3(MC_BLOCK), 0, CN_STREAM(stream), vol, nx, ny, nz, level, p.cases, p.masks, p.sums);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, CN_STREAM(stream), p.sums, cn_div_up(n, MC_BLOCK), counts, p.flag);
     return cn_launch_status();
 }
 
@@ -212,21 +212,18 @@ int cnerf_marching_cubes_emit(const float *vol, uint32_t nx, uint32_t ny, uint32
     if (const int rc = mc_check_dims(nx, ny, nz)) return rc;
     if (!vol || !origin_host || !spacing_host || !ws || (max_verts && !verts) || (max_faces && !faces)) return CNERF_ENULL;
     const uint32_t n = nx * ny * nz;
-    const McLayout l = mc_layout(n);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return CNERF_EINVAL;
+    McPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, mc_carve(ws, n, p))) return rc;
     McGeom g;
     for (int b = 0; b < 3; ++b) {
         g.org[b] = origin_host[b];
         g.sp[b] = spacing_host[b];
     }
-    uint8_t *w = (uint8_t *)ws;
-    const uint32_t nblk = cn_div_up(n, MC_BLOCK);
-    hipLaunchKernelGGL(k_mc_verts, dim3(nblk), dim3(MC_BLOCK), 0, CN_STREAM(stream), vol, nx, ny, nz, level, g, (const uint8_t *)(w + l.masks),
-                       (const uint2 *)(w + l.sums), (const uint32_t *)w, (uint32_t *)(w + l.vbase), verts, max_verts ? normals : nullptr,
-                       max_verts);
-    hipLaunchKernelGGL(k_mc_faces, dim3(nblk), dim3(MC_BLOCK), 0, CN_STREAM(stream), nx, ny, nz, (const uint8_t *)(w + l.cases),
-                       (const uint8_t *)(w + l.masks), (const uint2 *)(w + l.sums), (const uint32_t *)w, (const uint32_t *)(w + l.vbase),
-                       faces, max_faces);
+    hipLaunchKernelGGL(k_mc_verts, mesh_grid(n), dim3(MC_BLOCK), 0, CN_STREAM(stream), vol, nx, ny, nz, level, g, (const uint8_t *)p.masks,
+                       (const uint2 *)p.sums, (const uint32_t *)p.flag, p.vbase, verts, max_verts ? normals : nullptr, max_verts);
+    hipLaunchKernelGGL(k_mc_faces, mesh_grid(n), dim3(MC_BLOCK), 0, CN_STREAM(stream), nx, ny, nz, (const uint8_t *)p.cases,
+                       (const uint8_t *)p.masks, (const uint2 *)p.sums, (const uint32_t *)p.flag, (const uint32_t *)p.vbase, faces,
+                       max_faces);
     return cn_launch_status();
 }
 

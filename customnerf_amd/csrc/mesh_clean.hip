@@ -1,7 +1,7 @@
 // Mesh cleanup on the device (cnerf_mesh_components_*, cnerf_mesh_cluster_*): removal of small connected components and simplification by
 // vertex clustering, for any triangle mesh (marching-cubes output of mesh.hip or another).  Same conventions as mesh.hip: the caller's stream,
 // caller-owned buffers and workspace, a count pass whose counts[3] = (vertices, faces, flags) are the only host read, then an emit pass.
-// Output order never depends on scheduling: compaction is an exclusive scan of keep flags (mesh_scan.h), and the only atomics are integer
+// Output order never depends on scheduling: compaction is an exclusive scan of keep flags (mesh_common.h), and the only atomics are integer
 // ones whose result does not depend on their order (min-root hooking, counts, 64-bit fixed-point sums, atomicMin).  NumPy restatement:
 // tests/mesh_clean_restatement.py.  flags bit 0 (CC_BAD_INDEX): a face index outside [0, V); emit then writes nothing.
 //
@@ -36,7 +36,7 @@
 //     cluster's frame.  Exact while, per cluster, the sum over its faces of a * max(1, |d|) stays below 2^30 (about 10^9 cells^2) => |sum| < 2^62.
 //     A marching-cubes face under cells of >= 2 lattice steps has a < 1 and |d| < 3; a cluster collects a few hundred of them.
 #include "common.h"
-#include "mesh_scan.h"
+#include "mesh_common.h"
 #include "mesh_qef.h"
 
 #define CC_BAD_INDEX 1u
@@ -48,38 +48,31 @@
 
 namespace {
 
-inline uint64_t mcl_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
 __device__ __forceinline__ uint32_t ld_rlx(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_rlx(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void add_i64(int64_t *p, int64_t v) {
     if (v) __hip_atomic_fetch_add((unsigned long long *)p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ bool face_ok(const int32_t *__restrict__ faces, uint32_t f, uint32_t V, uint32_t t[3]) {
-    bool ok = true;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        t[q] = (uint32_t)faces[3 * (uint64_t)f + q];
-        ok &= t[q] < V;                              // a negative int32 is >= 2^31 > V here
-    }
-    return ok;
-}
-
 // ------------------------------------------------------------------------------------------------ components
-struct CcLayout {
-    uint64_t parent, fcount, remap, sums, total;
+struct CcPtr {
+    uint32_t *hdr;                                   // flags, largest label, its face count, kept vertices
+    uint32_t *parent, *fcount, *remap;
+    uint2 *sums;
+    uint32_t n;                                      // threads of the count and emit passes: max(V, F), one workgroup at least
 };
 
-CcLayout cc_layout(uint64_t V, uint64_t F) {
-    CcLayout l;
-    l.parent = 256;                                  // [0, 256): uint32 flags, largest label, its face count
-    l.fcount = l.parent + mcl_align(4 * V);
-    l.remap = l.fcount + mcl_align(4 * V);
-    l.sums = l.remap + mcl_align(4 * V);
-    const uint64_t n = V > F ? V : F;
-    l.total = l.sums + mcl_align(8 * cn_div_up64(n ? n : 1, MC_BLOCK));     // one workgroup at least, also for an empty mesh
-    return l;
+// the workspace: its regions in order -> total bytes (ws == nullptr: the size only)
+uint64_t cc_carve(void *ws, uint32_t V, uint32_t F, CcPtr &p) {
+    MeshCarve c(ws);
+    p.hdr = c.header();
+    p.parent = c.take<uint32_t>(V);
+    p.fcount = c.take<uint32_t>(V);
+    p.remap = c.take<uint32_t>(V);
+    p.n = V > F ? V : F;
+    if (!p.n) p.n = 1;                               // also for an empty mesh
+    p.sums = c.take<uint2>(cn_div_up64(p.n, MC_BLOCK));
+    return c.total();
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void k_cc_init(uint32_t V, uint32_t *__restrict__ parent, uint32_t *__restrict__ fcount,
@@ -125,7 +118,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cc_hook(const int32_t *__restrict_
     const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (f >= F) return;
     uint32_t t[3];
-    if (!face_ok(faces, f, V, t)) {
+    if (!mesh_face(faces, f, V, t)) {
         atomicOr(hdr, CC_BAD_INDEX);
         return;
     }
@@ -148,7 +141,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cc_size(const int32_t *__restrict_
                                                       const uint32_t *__restrict__ label, uint32_t *__restrict__ fcount) {
     const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
     uint32_t t[3];
-    const bool ok = f < F && face_ok(faces, f, V, t);
+    const bool ok = f < F && mesh_face(faces, f, V, t);
     const uint32_t lab = ok ? label[t[0]] : CL_NONE;
     uint64_t todo = __ballot(ok);                    // wave-uniform
     while (todo) {
@@ -194,7 +187,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cc_count(const int32_t *__restrict
     const uint32_t i = blockIdx.x * MC_BLOCK + threadIdx.x;
     uint32_t t[3];
     const uint32_t kv = i < V && cc_keep(label[i], fcount, min_faces, largest, hdr);
-    const uint32_t kf = i < F && face_ok(faces, i, V, t) && cc_keep(label[t[0]], fcount, min_faces, largest, hdr);
+    const uint32_t kf = i < F && mesh_face(faces, i, V, t) && cc_keep(label[t[0]], fcount, min_faces, largest, hdr);
     const uint32_t tv = mc_block_total<1>(kv, red_v);
     const uint32_t tf = mc_block_total<1>(kf, red_f);
     if (threadIdx.x == 0) sums[blockIdx.x] = make_uint2(tv, tf);
@@ -225,15 +218,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cc_verts(const float *__restrict__
     const uint32_t k = sums[blockIdx.x].x + mc_block_prefix<1>(kv, red);
     if (i >= V) return;
     remap[i] = kv ? k : CL_NONE;
-    if (!kv || k >= max_verts) return;
-    const uint64_t s = 3 * (uint64_t)i, d = 3 * (uint64_t)k;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) verts_out[d + q] = verts[s + q];
-    if (normals && normals_out) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) normals_out[d + q] = normals[s + q];
-    }
-    if (old_index) old_index[k] = (int32_t)i;
+    if (kv) mesh_emit_vertex(verts, normals, i, k, verts_out, normals_out, old_index, max_verts);
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void k_cc_faces(const int32_t *__restrict__ faces, uint32_t V, uint32_t F, const uint32_t *__restrict__ label,
@@ -244,7 +229,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cc_faces(const int32_t *__restrict
     if (hdr[0]) return;
     const uint32_t i = blockIdx.x * MC_BLOCK + threadIdx.x;
     uint32_t t[3];
-    const uint32_t kf = i < F && face_ok(faces, i, V, t) && cc_keep(label[t[0]], fcount, min_faces, largest, hdr);
+    const uint32_t kf = i < F && mesh_face(faces, i, V, t) && cc_keep(label[t[0]], fcount, min_faces, largest, hdr);
     const uint32_t k = sums[blockIdx.x].y + mc_block_prefix<1>(kf, red);
     if (!kf || k >= max_faces) return;
     const uint64_t d = 3 * (uint64_t)k;
@@ -260,26 +245,34 @@ struct ClGeom {
     uint32_t g[3];
 };
 
-struct ClLayout {
-    uint64_t vcell, occ, cid, ccell, table, fslot, sums, acc, total, H;
+struct ClPtr {
+    uint32_t *hdr;                                   // flags, -, -, cluster count
+    uint32_t *vcell;
+    uint8_t *occ;
+    uint32_t *cid, *ccell, *table, *fslot;
+    uint2 *sums;
+    int64_t *acc;
+    uint64_t H;                                      // slots of the face hash
+    uint32_t n;                                      // threads of the count and emit passes: max(G, F)
 };
 
-ClLayout cl_layout(uint64_t V, uint64_t F, uint64_t G) {
-    ClLayout l;
-    uint64_t H = 64;
-    while (H < 2 * F) H <<= 1;                       // load factor <= 1/2; F < 2^31 => H <= 2^32, slot indices fit a uint32 mask
-    l.H = H;
+// the workspace: its regions in order -> total bytes (ws == nullptr: the size only)
+uint64_t cl_carve(void *ws, uint64_t V, uint64_t F, uint64_t G, ClPtr &p) {
+    p.H = 64;
+    while (p.H < 2 * F) p.H <<= 1;                   // load factor <= 1/2; F < 2^31 => H <= 2^32, slot indices fit a uint32 mask
     const uint64_t K = V < G ? V : G;
-    l.vcell = 256;                                   // [0, 256): uint32 flags, -, -, cluster count
-    l.occ = l.vcell + mcl_align(4 * V);
-    l.cid = l.occ + mcl_align(G);
-    l.ccell = l.cid + mcl_align(4 * G);
-    l.table = l.ccell + mcl_align(4 * K);
-    l.fslot = l.table + mcl_align(4 * H);
-    l.sums = l.fslot + mcl_align(4 * F);
-    l.acc = l.sums + mcl_align(8 * cn_div_up64(G > F ? G : F, MC_BLOCK));
-    l.total = l.acc + mcl_align(8 * CL_ACC * K);
-    return l;
+    p.n = (uint32_t)(G > F ? G : F);
+    MeshCarve c(ws);
+    p.hdr = c.header();
+    p.vcell = c.take<uint32_t>(V);
+    p.occ = c.take<uint8_t>(G);
+    p.cid = c.take<uint32_t>(G);
+    p.ccell = c.take<uint32_t>(K);
+    p.table = c.take<uint32_t>(p.H);
+    p.fslot = c.take<uint32_t>(F);
+    p.sums = c.take<uint2>(cn_div_up64(p.n, MC_BLOCK));
+    p.acc = c.take<int64_t>(CL_ACC * K);
+    return c.total();
 }
 
 __device__ __forceinline__ uint32_t cl_cell(const float *__restrict__ verts, uint32_t v, const ClGeom &g, uint32_t c[3]) {
@@ -323,7 +316,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cl_hash(const int32_t *__restrict_
     const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (f >= F) return;
     uint32_t t[3], k[3];
-    if (!face_ok(faces, f, V, t)) {
+    if (!mesh_face(faces, f, V, t)) {
         atomicOr(hdr, CC_BAD_INDEX);
         fslot[f] = CL_NONE;
         return;
@@ -419,7 +412,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cl_fsum(const float *__restrict__ 
     if (hdr[0]) return;
     const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
     uint32_t t[3];
-    if (f >= F || !face_ok(faces, f, V, t)) return;
+    if (f >= F || !mesh_face(faces, f, V, t)) return;
     double p[3][3];
 #pragma unroll
     for (int q = 0; q < 3; ++q)
@@ -539,7 +532,8 @@ extern "C" {
 int cnerf_mesh_components_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host) {
     if (const int rc = cc_check_dims(V, F)) return rc;
     if (!bytes_host) return CNERF_ENULL;
-    *bytes_host = cc_layout(V, F).total;
+    CcPtr p;
+    *bytes_host = cc_carve(nullptr, V, F, p);
     return CNERF_OK;
 }
 
@@ -547,22 +541,19 @@ int cnerf_mesh_components_count(const int32_t *faces, uint32_t V, uint32_t F, ui
                                 uint32_t *counts, void *stream) {
     if (const int rc = cc_check_dims(V, F)) return rc;
     if ((F && !faces) || !ws || !counts) return CNERF_ENULL;
-    const CcLayout l = cc_layout(V, F);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return CNERF_EINVAL;
-    uint8_t *w = (uint8_t *)ws;
-    uint32_t *hdr = (uint32_t *)w, *parent = (uint32_t *)(w + l.parent), *fcount = (uint32_t *)(w + l.fcount);
+    CcPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, cc_carve(ws, V, F, p))) return rc;
     hipStream_t st = CN_STREAM(stream);
-    const uint32_t n = V > F ? V : F, nblk = cn_div_up(n ? n : 1, MC_BLOCK);
-    hipLaunchKernelGGL(k_cc_init, dim3(cn_div_up(V ? V : 1, MC_BLOCK)), dim3(MC_BLOCK), 0, st, V, parent, fcount, hdr);
+    hipLaunchKernelGGL(k_cc_init, mesh_grid(V ? V : 1), dim3(MC_BLOCK), 0, st, V, p.parent, p.fcount, p.hdr);
     if (F) {
-        hipLaunchKernelGGL(k_cc_hook, dim3(cn_div_up(F, MC_BLOCK)), dim3(MC_BLOCK), 0, st, faces, V, F, parent, hdr);
-        if (V) hipLaunchKernelGGL(k_cc_compress, dim3(cn_div_up(V, MC_BLOCK)), dim3(MC_BLOCK), 0, st, V, parent);
-        hipLaunchKernelGGL(k_cc_size, dim3(cn_div_up(F, MC_BLOCK)), dim3(MC_BLOCK), 0, st, faces, V, F, (const uint32_t *)parent, fcount);
+        hipLaunchKernelGGL(k_cc_hook, mesh_grid(F), dim3(MC_BLOCK), 0, st, faces, V, F, p.parent, p.hdr);
+        if (V) hipLaunchKernelGGL(k_cc_compress, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p.parent);
+        hipLaunchKernelGGL(k_cc_size, mesh_grid(F), dim3(MC_BLOCK), 0, st, faces, V, F, (const uint32_t *)p.parent, p.fcount);
     }
-    if (largest) hipLaunchKernelGGL(k_cc_largest, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, V, (const uint32_t *)fcount, hdr);
-    hipLaunchKernelGGL(k_cc_count, dim3(nblk), dim3(MC_BLOCK), 0, st, faces, V, F, (const uint32_t *)parent, (const uint32_t *)fcount, min_faces,
-                       largest, (const uint32_t *)hdr, (uint2 *)(w + l.sums));
-    hipLaunchKernelGGL(k_clean_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, (uint2 *)(w + l.sums), nblk, counts, hdr);
+    if (largest) hipLaunchKernelGGL(k_cc_largest, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, V, (const uint32_t *)p.fcount, p.hdr);
+    hipLaunchKernelGGL(k_cc_count, mesh_grid(p.n), dim3(MC_BLOCK), 0, st, faces, V, F, (const uint32_t *)p.parent, (const uint32_t *)p.fcount,
+                       min_faces, largest, (const uint32_t *)p.hdr, p.sums);
+    hipLaunchKernelGGL(k_clean_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, p.sums, cn_div_up(p.n, MC_BLOCK), counts, p.hdr);
     return cn_launch_status();
 }
 
@@ -571,18 +562,15 @@ int cnerf_mesh_components_emit(const float *verts, const float *normals, uint32_
                                int32_t *old_index, uint32_t max_verts, uint32_t max_faces, void *stream) {
     if (const int rc = cc_check_dims(V, F)) return rc;
     if ((V && !verts) || (F && !faces) || !ws || (max_verts && !verts_out) || (max_faces && !faces_out)) return CNERF_ENULL;
-    const CcLayout l = cc_layout(V, F);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return CNERF_EINVAL;
-    uint8_t *w = (uint8_t *)ws;
-    const uint32_t *hdr = (const uint32_t *)w, *label = (const uint32_t *)(w + l.parent), *fcount = (const uint32_t *)(w + l.fcount);
-    uint32_t *remap = (uint32_t *)(w + l.remap);
-    const uint2 *sums = (const uint2 *)(w + l.sums);
+    CcPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, cc_carve(ws, V, F, p))) return rc;
+    const uint32_t *hdr = p.hdr, *label = p.parent, *fcount = p.fcount;
+    const uint2 *sums = p.sums;
     hipStream_t st = CN_STREAM(stream);
-    const uint32_t n = V > F ? V : F, nblk = cn_div_up(n ? n : 1, MC_BLOCK);
-    hipLaunchKernelGGL(k_cc_verts, dim3(nblk), dim3(MC_BLOCK), 0, st, verts, normals, V, label, fcount, min_faces, largest, hdr, sums, remap,
-                       verts_out, max_verts ? normals_out : nullptr, max_verts ? old_index : nullptr, max_verts);
-    hipLaunchKernelGGL(k_cc_faces, dim3(nblk), dim3(MC_BLOCK), 0, st, faces, V, F, label, fcount, min_faces, largest, hdr, sums,
-                       (const uint32_t *)remap, faces_out, max_faces);
+    hipLaunchKernelGGL(k_cc_verts, mesh_grid(p.n), dim3(MC_BLOCK), 0, st, verts, normals, V, label, fcount, min_faces, largest, hdr, sums,
+                       p.remap, verts_out, max_verts ? normals_out : nullptr, max_verts ? old_index : nullptr, max_verts);
+    hipLaunchKernelGGL(k_cc_faces, mesh_grid(p.n), dim3(MC_BLOCK), 0, st, faces, V, F, label, fcount, min_faces, largest, hdr, sums,
+                       (const uint32_t *)p.remap, faces_out, max_faces);
     return cn_launch_status();
 }
 
@@ -590,7 +578,8 @@ int cnerf_mesh_cluster_workspace_bytes(uint32_t V, uint32_t F, const uint32_t *g
     uint64_t G;
     if (const int rc = cl_check(V, F, grid_host, &G)) return rc;
     if (!bytes_host) return CNERF_ENULL;
-    *bytes_host = cl_layout(V, F, G).total;
+    ClPtr p;
+    *bytes_host = cl_carve(nullptr, V, F, G, p);
     return CNERF_OK;
 }
 
@@ -601,22 +590,19 @@ int cnerf_mesh_cluster_count(const float *verts, uint32_t V, const int32_t *face
     if ((V && !verts) || (F && !faces) || !origin_host || !cell_host || !ws || !counts) return CNERF_ENULL;
     ClGeom g;
     if (const int rc = cl_geom(origin_host, cell_host, grid_host, &g)) return rc;
-    const ClLayout l = cl_layout(V, F, G);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return CNERF_EINVAL;
-    uint8_t *w = (uint8_t *)ws;
-    uint32_t *hdr = (uint32_t *)w, *vcell = (uint32_t *)(w + l.vcell), *table = (uint32_t *)(w + l.table), *fslot = (uint32_t *)(w + l.fslot);
+    ClPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, cl_carve(ws, V, F, G, p))) return rc;
     hipStream_t st = CN_STREAM(stream);
-    int rc = cn_memset(w, 0, 256, stream);
-    if (!rc) rc = cn_memset(w + l.occ, 0, G, stream);
-    if (!rc) rc = cn_memset(table, 0xff, 4ull * l.H, stream);
+    int rc = cn_memset(p.hdr, 0, 256, stream);
+    if (!rc) rc = cn_memset(p.occ, 0, G, stream);
+    if (!rc) rc = cn_memset(p.table, 0xff, 4ull * p.H, stream);
     if (rc) return rc;
-    const uint32_t n = (uint32_t)(G > F ? G : F), nblk = cn_div_up(n, MC_BLOCK);
-    if (V) hipLaunchKernelGGL(k_cl_assign, dim3(cn_div_up(V, MC_BLOCK)), dim3(MC_BLOCK), 0, st, verts, V, g, vcell, w + l.occ);
-    if (F) hipLaunchKernelGGL(k_cl_hash, dim3(cn_div_up(F, MC_BLOCK)), dim3(MC_BLOCK), 0, st, faces, V, F, (const uint32_t *)vcell, table, (uint32_t)(l.H - 1),
-                              fslot, hdr);
-    hipLaunchKernelGGL(k_cl_count, dim3(nblk), dim3(MC_BLOCK), 0, st, (uint32_t)G, F, (const uint8_t *)(w + l.occ), (const uint32_t *)table,
-                       (const uint32_t *)fslot, (uint2 *)(w + l.sums));
-    hipLaunchKernelGGL(k_clean_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, (uint2 *)(w + l.sums), nblk, counts, hdr);
+    if (V) hipLaunchKernelGGL(k_cl_assign, mesh_grid(V), dim3(MC_BLOCK), 0, st, verts, V, g, p.vcell, p.occ);
+    if (F) hipLaunchKernelGGL(k_cl_hash, mesh_grid(F), dim3(MC_BLOCK), 0, st, faces, V, F, (const uint32_t *)p.vcell, p.table, (uint32_t)(p.H - 1),
+                              p.fslot, p.hdr);
+    hipLaunchKernelGGL(k_cl_count, mesh_grid(p.n), dim3(MC_BLOCK), 0, st, (uint32_t)G, F, (const uint8_t *)p.occ, (const uint32_t *)p.table,
+                       (const uint32_t *)p.fslot, p.sums);
+    hipLaunchKernelGGL(k_clean_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, p.sums, cn_div_up(p.n, MC_BLOCK), counts, p.hdr);
     return cn_launch_status();
 }
 
@@ -629,23 +615,18 @@ int cnerf_mesh_cluster_emit(const float *verts, const float *normals, uint32_t V
         return CNERF_ENULL;
     ClGeom g;
     if (const int rc = cl_geom(origin_host, cell_host, grid_host, &g)) return rc;
-    const ClLayout l = cl_layout(V, F, G);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return CNERF_EINVAL;
-    uint8_t *w = (uint8_t *)ws;
-    const uint32_t *hdr = (const uint32_t *)w, *vcell = (const uint32_t *)(w + l.vcell), *cid = (const uint32_t *)(w + l.cid);
-    const uint32_t *table = (const uint32_t *)(w + l.table), *fslot = (const uint32_t *)(w + l.fslot);
-    const uint2 *sums = (const uint2 *)(w + l.sums);
-    int64_t *acc = (int64_t *)(w + l.acc);
+    ClPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, cl_carve(ws, V, F, G, p))) return rc;
+    const uint32_t *hdr = p.hdr, *vcell = p.vcell, *cid = p.cid, *table = p.table, *fslot = p.fslot;
+    const uint2 *sums = p.sums;
     hipStream_t st = CN_STREAM(stream);
-    const uint32_t n = (uint32_t)(G > F ? G : F), nblk = cn_div_up(n, MC_BLOCK);
-    hipLaunchKernelGGL(k_cl_ids, dim3(nblk), dim3(MC_BLOCK), 0, st, (uint32_t)G, (const uint8_t *)(w + l.occ), sums, hdr, (uint32_t *)(w + l.cid),
-                       (uint32_t *)(w + l.ccell), acc);
-    if (V) hipLaunchKernelGGL(k_cl_vsum, dim3(cn_div_up(V, MC_BLOCK)), dim3(MC_BLOCK), 0, st, verts, normals, V, g, vcell, cid, hdr, acc);
-    if (F) hipLaunchKernelGGL(k_cl_fsum, dim3(cn_div_up(F, MC_BLOCK)), dim3(MC_BLOCK), 0, st, verts, faces, V, F, g, vcell, cid, hdr, acc);
+    hipLaunchKernelGGL(k_cl_ids, mesh_grid(p.n), dim3(MC_BLOCK), 0, st, (uint32_t)G, (const uint8_t *)p.occ, sums, hdr, p.cid, p.ccell, p.acc);
+    if (V) hipLaunchKernelGGL(k_cl_vsum, mesh_grid(V), dim3(MC_BLOCK), 0, st, verts, normals, V, g, vcell, cid, hdr, p.acc);
+    if (F) hipLaunchKernelGGL(k_cl_fsum, mesh_grid(F), dim3(MC_BLOCK), 0, st, verts, faces, V, F, g, vcell, cid, hdr, p.acc);
     if (max_verts)
-        hipLaunchKernelGGL(k_cl_solve, dim3(cn_div_up(max_verts, MC_BLOCK)), dim3(MC_BLOCK), 0, st, g, (const uint32_t *)(w + l.ccell),
-                           (const int64_t *)acc, hdr, normals ? 1 : 0, verts_out, normals_out, max_verts);
-    hipLaunchKernelGGL(k_cl_faces, dim3(nblk), dim3(MC_BLOCK), 0, st, faces, F, table, fslot, vcell, cid, hdr, sums, faces_out, max_faces);
+        hipLaunchKernelGGL(k_cl_solve, mesh_grid(max_verts), dim3(MC_BLOCK), 0, st, g, (const uint32_t *)p.ccell, (const int64_t *)p.acc, hdr,
+                           normals ? 1 : 0, verts_out, normals_out, max_verts);
+    hipLaunchKernelGGL(k_cl_faces, mesh_grid(p.n), dim3(MC_BLOCK), 0, st, faces, F, table, fslot, vcell, cid, hdr, sums, faces_out, max_faces);
     return cn_launch_status();
 }
 

@@ -1,0 +1,180 @@
+// What the mesh passes share (mesh.hip: marching cubes, mesh_clean.hip: component removal and clustering, mesh_decimate.hip, mesh_smooth.hip).
+// Host: the 256-byte alignment, the launch grid and the bump carver every pass describes its workspace with, once.  Device: workgroup
+// prefix sums and the one-workgroup scan of workgroup totals, the range-checked face load, the vertex -> list offset steps, the per-vertex
+// insertion sort and the compacted vertex store.
+// Every grid these kernels scan is one thread per item, MC_BLOCK threads per workgroup;
+// a count pass stores each workgroup's two totals (uint2), mc_scan_totals turns them into exclusive offsets in place, and an emit pass adds
+// the in-workgroup prefix (ballot + mbcnt, LDS wave totals) to its workgroup's offset.  Order follows the thread index: no atomics.
+#pragma once
+#include "common.h"
+
+#define MC_BLOCK 256
+#define MC_WAVES (MC_BLOCK / CN_WAVE)
+#define MC_SCAN_BLOCK 1024
+#define MC_SCAN_PER_THREAD 4
+
+namespace {
+
+inline uint64_t mesh_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+inline dim3 mesh_grid(uint64_t n) { return dim3((uint32_t)cn_div_up64(n, MC_BLOCK)); }      // one thread per item
+inline int mesh_check_ws(const void *ws, uint64_t ws_bytes, uint64_t total) {
+    return (ws_bytes < total || ((uintptr_t)ws & 15)) ? CNERF_EINVAL : CNERF_OK;
+}
+
+// A workspace is a 256-byte header of uint32 slots, then regions of 256-byte-aligned size.  Each pass has one function that takes its
+// regions in order and returns total(); without a base (the size query) the pointers are null.
+struct MeshCarve {
+    uint8_t *base;
+    uint64_t off;
+    explicit MeshCarve(void *ws) : base((uint8_t *)ws), off(0) {}
+    template <class T>
+    T *take(uint64_t count) {
+        T *p = base ? (T *)(base + off) : nullptr;
+        off += mesh_align(sizeof(T) * count);
+        return p;
+    }
+    uint32_t *header() { return take<uint32_t>(64); }
+    uint64_t total() const { return off; }
+};
+
+__device__ __forceinline__ uint32_t mc_rank(uint64_t ballot) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+
+// exclusive prefix of v (< 2^BITS) over the workgroup in thread order; every thread of the block must call it.  `red` = LDS [MC_WAVES]
+template <int BITS>
+__device__ __forceinline__ uint32_t mc_block_prefix(uint32_t v, uint32_t *red) {
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < BITS; ++k) {
+        const uint64_t b = __ballot((v >> k) & 1u);
+        pre += mc_rank(b) << k;
+        tot += (uint32_t)__popcll(b) << k;
+    }
+    const uint32_t w = threadIdx.x / CN_WAVE;
+    if (cn_lane() == 0) red[w] = tot;
+    __syncthreads();
+    for (uint32_t j = 0; j < w; ++j) pre += red[j];
+    return pre;
+}
+
+// exclusive prefix of any v over the workgroup in thread order and its total; every thread of the block must call it.  `red` = LDS [MC_WAVES]
+__device__ __forceinline__ uint32_t mc_block_excl(uint32_t v, uint32_t *red, uint32_t &tot) {
+    const uint32_t incl = cn_wave_incl_scan(v), w = threadIdx.x / CN_WAVE;
+    if (cn_lane() == CN_WAVE - 1) red[w] = incl;
+    __syncthreads();
+    uint32_t pre = incl - v;
+    tot = 0;
+    for (uint32_t j = 0; j < MC_WAVES; ++j) {
+        if (j < w) pre += red[j];
+        tot += red[j];
+    }
+    return pre;
+}
+
+template <int BITS>
+__device__ __forceinline__ uint32_t mc_block_total(uint32_t v, uint32_t *red) {
+    uint32_t tot = 0;
+#pragma unroll
+    for (int k = 0; k < BITS; ++k) tot += (uint32_t)__popcll(__ballot((v >> k) & 1u)) << k;
+    if (cn_lane() == 0) red[threadIdx.x / CN_WAVE] = tot;
+    __syncthreads();
+    uint32_t s = 0;
+    for (int j = 0; j < MC_WAVES; ++j) s += red[j];
+    return s;
+}
+
+// Body of a one-workgroup (MC_SCAN_BLOCK threads) scan: sums[0..nblk) -> exclusive offsets in place, component-wise; cv / ct = the two
+// totals (exact in 64 bits; every thread gets them).  Every thread of the block must call it.
+__device__ __forceinline__ void mc_scan_totals(uint2 *__restrict__ sums, uint32_t nblk, uint64_t &cv, uint64_t &ct) {
+    __shared__ uint32_t wv[MC_SCAN_BLOCK / CN_WAVE], wt[MC_SCAN_BLOCK / CN_WAVE];
+    const uint32_t nw = MC_SCAN_BLOCK / CN_WAVE, w = threadIdx.x / CN_WAVE, lane = cn_lane();
+    cv = 0;                                          // carry: totals of the tiles before this one
+    ct = 0;
+    for (uint32_t base = 0; base < nblk; base += MC_SCAN_BLOCK * MC_SCAN_PER_THREAD) {
+        const uint32_t j0 = base + threadIdx.x * MC_SCAN_PER_THREAD;
+        uint2 e[MC_SCAN_PER_THREAD];
+        uint32_t sv = 0, st = 0;
+#pragma unroll
+        for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
+            e[k] = j0 + k < nblk ? sums[j0 + k] : make_uint2(0, 0);
+            sv += e[k].x;
+            st += e[k].y;
+        }
+        const uint32_t iv = cn_wave_incl_scan(sv), it = cn_wave_incl_scan(st);
+        if (lane == CN_WAVE - 1) { wv[w] = iv; wt[w] = it; }
+        __syncthreads();
+        uint32_t ov = iv - sv, ot = it - st, tile_v = 0, tile_t = 0;
+        for (uint32_t j = 0; j < nw; ++j) {
+            if (j < w) { ov += wv[j]; ot += wt[j]; }
+            tile_v += wv[j];
+            tile_t += wt[j];
+        }
+        __syncthreads();                             // wv / wt are rewritten by the next tile
+        uint64_t pv = cv + ov, pt = ct + ot;
+#pragma unroll
+        for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
+            if (j0 + k < nblk) sums[j0 + k] = make_uint2((uint32_t)pv, (uint32_t)pt);
+            pv += e[k].x;
+            pt += e[k].y;
+        }
+        cv += tile_v;
+        ct += tile_t;
+    }
+}
+
+__device__ __forceinline__ uint32_t mesh_fv(const int32_t *fa, uint32_t f, uint32_t q) { return (uint32_t)fa[3 * (uint64_t)f + q]; }
+
+// the three indices of face f; false when one lies outside [0, V)
+__device__ __forceinline__ bool mesh_face(const int32_t *__restrict__ faces, uint32_t f, uint32_t V, uint32_t t[3]) {
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        t[q] = mesh_fv(faces, f, q);
+        ok &= t[q] < V;                              // a negative int32 is >= 2^31 > V here
+    }
+    return ok;
+}
+
+// Vertex -> list offsets for two counters per vertex (a, b), one thread per vertex; every thread of the block must call them.
+// Count pass: this workgroup's two totals, which a one-workgroup mc_scan_totals turns into offsets.
+__device__ __forceinline__ void mesh_csr_totals(uint32_t a, uint32_t b, uint2 *__restrict__ sums) {
+    __shared__ uint32_t red_a[MC_WAVES], red_b[MC_WAVES];
+    uint32_t ta, tb;
+    mc_block_excl(a, red_a, ta);
+    mc_block_excl(b, red_b, tb);
+    if (threadIdx.x == 0) sums[blockIdx.x] = make_uint2(ta, tb);
+}
+
+// Offset pass, per counter: this thread's list start = its workgroup's offset + the in-workgroup exclusive prefix.  `red` = LDS [MC_WAVES]
+__device__ __forceinline__ uint32_t mesh_csr_start(uint32_t wg_offset, uint32_t v, uint32_t *red) {
+    uint32_t tot;
+    return wg_offset + mc_block_excl(v, red, tot);
+}
+
+// increasing order, in place; the lists are short (a vertex's faces or edge records)
+__device__ __forceinline__ void mesh_isort(uint32_t *l, uint32_t n) {
+    for (uint32_t i = 1; i < n; ++i) {
+        const uint32_t x = l[i];
+        uint32_t j = i;
+        for (; j > 0 && l[j - 1] > x; --j) l[j] = l[j - 1];
+        l[j] = x;
+    }
+}
+
+// input vertex i becomes output vertex k (its slot in the scan of the keep flags): position, normal when both sides have one, old_index
+__device__ __forceinline__ void mesh_emit_vertex(const float *__restrict__ pos, const float *__restrict__ normals, uint32_t i, uint32_t k,
+                                                 float *__restrict__ verts_out, float *__restrict__ normals_out,
+                                                 int32_t *__restrict__ old_index, uint32_t max_verts) {
+    if (k >= max_verts) return;
+    const uint64_t s = 3 * (uint64_t)i, d = 3 * (uint64_t)k;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) verts_out[d + q] = pos[s + q];
+    if (normals && normals_out) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) normals_out[d + q] = normals[s + q];
+    }
+    if (old_index) old_index[k] = (int32_t)i;
+}
+
+}  // namespace

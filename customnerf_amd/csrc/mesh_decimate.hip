@@ -46,7 +46,7 @@
 //   k_dc_apply   : the winners under the limit write position, quadric, remap and the two dropped faces
 //   k_dc_fcount / k_dc_fscan / k_dc_compact : surviving faces, counts, compaction into the persistent faces
 #include "common.h"
-#include "mesh_scan.h"
+#include "mesh_common.h"
 #include "mesh_qef.h"
 
 #define DC_BAD_INDEX 1u
@@ -61,37 +61,6 @@
 namespace {
 
 enum { H_FLAGS = 0, H_REFS = 1, H_NPRE = 2, H_NWIN = 3, H_NAPPLY = 4, H64_LIM = 4 };     // uint32 slots of the header; H64_LIM: uint64 slot
-
-inline uint64_t dc_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
-struct DcLayout {
-    uint64_t pos, quad, deg, end, bnd, remap, vkey, nkey, faces, work, list, twin, ekey, dead, sums, pre, win, total, cap;
-};
-
-DcLayout dc_layout(uint64_t V, uint64_t F) {
-    DcLayout l;
-    l.cap = V / 2 + 1;                               // pre-winners hold both endpoints' minima: a matching, at most V / 2 edges
-    l.pos = 256;
-    l.quad = l.pos + dc_align(12 * V);
-    l.deg = l.quad + dc_align(80 * V);
-    l.end = l.deg + dc_align(4 * V);
-    l.bnd = l.end + dc_align(4 * V);
-    l.remap = l.bnd + dc_align(V);
-    l.vkey = l.remap + dc_align(4 * V);
-    l.nkey = l.vkey + dc_align(8 * V);
-    l.faces = l.nkey + dc_align(8 * V);
-    l.work = l.faces + dc_align(12 * F);
-    l.list = l.work + dc_align(12 * F);
-    l.twin = l.list + dc_align(12 * F);
-    l.ekey = l.twin + dc_align(12 * F);
-    l.dead = l.ekey + dc_align(24 * F);
-    l.sums = l.dead + dc_align(F);
-    const uint64_t n = V > F ? V : F;
-    l.pre = l.sums + dc_align(8 * cn_div_up64(n ? n : 1, MC_BLOCK));
-    l.win = l.pre + dc_align(4 * l.cap);
-    l.total = l.win + dc_align(8 * l.cap);
-    return l;
-}
 
 struct DcPtr {
     uint32_t *hdr;
@@ -111,33 +80,34 @@ struct DcPtr {
     uint32_t cap;
 };
 
-DcPtr dc_ptr(void *ws, const DcLayout &l) {
-    uint8_t *w = (uint8_t *)ws;
-    DcPtr p;
-    p.hdr = (uint32_t *)w;
-    p.pos = (float *)(w + l.pos);
-    p.quad = (double *)(w + l.quad);
-    p.deg = (uint32_t *)(w + l.deg);
-    p.end = (uint32_t *)(w + l.end);
-    p.bnd = w + l.bnd;
-    p.remap = (uint32_t *)(w + l.remap);
-    p.vkey = (unsigned long long *)(w + l.vkey);
-    p.nkey = (unsigned long long *)(w + l.nkey);
-    p.faces = (int32_t *)(w + l.faces);
-    p.work = (int32_t *)(w + l.work);
-    p.list = (uint32_t *)(w + l.list);
-    p.twin = (uint32_t *)(w + l.twin);
-    p.ekey = (uint64_t *)(w + l.ekey);
-    p.dead = w + l.dead;
-    p.sums = (uint2 *)(w + l.sums);
-    p.pre = (uint32_t *)(w + l.pre);
-    p.win = (uint64_t *)(w + l.win);
-    p.cap = (uint32_t)l.cap;
-    return p;
+// the workspace: its regions in order -> total bytes (ws == nullptr: the size only).  The V-sized regions come first, so a round can pass
+// the live F and find them where init put them.
+uint64_t dc_carve(void *ws, uint64_t V, uint64_t F, DcPtr &p) {
+    MeshCarve c(ws);
+    p.cap = (uint32_t)(V / 2 + 1);                   // pre-winners hold both endpoints' minima: a matching, at most V / 2 edges
+    p.hdr = c.header();
+    p.pos = c.take<float>(3 * V);
+    p.quad = c.take<double>(10 * V);
+    p.deg = c.take<uint32_t>(V);
+    p.end = c.take<uint32_t>(V);
+    p.bnd = c.take<uint8_t>(V);
+    p.remap = c.take<uint32_t>(V);
+    p.vkey = c.take<unsigned long long>(V);
+    p.nkey = c.take<unsigned long long>(V);
+    p.faces = c.take<int32_t>(3 * F);
+    p.work = c.take<int32_t>(3 * F);
+    p.list = c.take<uint32_t>(3 * F);
+    p.twin = c.take<uint32_t>(3 * F);
+    p.ekey = c.take<uint64_t>(3 * F);
+    p.dead = c.take<uint8_t>(F);
+    const uint64_t n = V > F ? V : F;
+    p.sums = c.take<uint2>(cn_div_up64(n ? n : 1, MC_BLOCK));
+    p.pre = c.take<uint32_t>(p.cap);
+    p.win = c.take<uint64_t>(p.cap);
+    return c.total();
 }
 
 __device__ __forceinline__ uint32_t dc_next(uint32_t k) { return k == 2 ? 0 : k + 1; }
-__device__ __forceinline__ uint32_t dc_fv(const int32_t *fa, uint32_t f, uint32_t q) { return (uint32_t)fa[3 * (uint64_t)f + q]; }
 
 // ------------------------------------------------------------------------------------------------ vertex -> face lists
 __global__ __launch_bounds__(MC_BLOCK) void k_dc_clear(uint32_t V, DcPtr p) {
@@ -155,13 +125,9 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_load(const int32_t *__restrict_
     const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (f >= F) return;
     uint32_t t[3];
-    bool ok = true;
+    const bool ok = mesh_face(faces, f, V, t);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        t[q] = dc_fv(faces, f, q);
-        p.faces[3 * (uint64_t)f + q] = (int32_t)t[q];
-        ok &= t[q] < V;                              // a negative int32 is >= 2^31 > V here
-    }
+    for (int q = 0; q < 3; ++q) p.faces[3 * (uint64_t)f + q] = (int32_t)t[q];
     if (!ok) {
         atomicOr(p.hdr + H_FLAGS, DC_BAD_INDEX);
         return;
@@ -188,13 +154,9 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_deg(uint32_t F, DcPtr p) {
 
 // workgroup totals of (degree, referenced)
 __global__ __launch_bounds__(MC_BLOCK) void k_dc_vsum(uint32_t V, DcPtr p) {
-    __shared__ uint32_t red_d[MC_WAVES], red_r[MC_WAVES];
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
     const uint32_t d = v < V ? p.deg[v] : 0;
-    uint32_t td, tr;
-    mc_block_excl(d, red_d, td);
-    mc_block_excl(d ? 1u : 0u, red_r, tr);
-    if (threadIdx.x == 0) p.sums[blockIdx.x] = make_uint2(td, tr);
+    mesh_csr_totals(d, d ? 1u : 0u, p.sums);
 }
 
 // one workgroup: the shared scan of the workgroup totals.  refs != 0: the referenced vertices are the header's count (init)
@@ -207,8 +169,7 @@ __global__ __launch_bounds__(MC_SCAN_BLOCK) void k_dc_scan(uint32_t nblk, int re
 __global__ __launch_bounds__(MC_BLOCK) void k_dc_offsets(uint32_t V, DcPtr p) {
     __shared__ uint32_t red[MC_WAVES];
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
-    uint32_t tot;
-    const uint32_t start = p.sums[blockIdx.x].x + mc_block_excl(v < V ? p.deg[v] : 0, red, tot);
+    const uint32_t start = mesh_csr_start(p.sums[blockIdx.x].x, v < V ? p.deg[v] : 0, red);
     if (v < V) p.end[v] = start;                     // k_dc_fill advances it to start + degree
 }
 
@@ -217,7 +178,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_fill(const int32_t *__restrict_
     const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (f >= F) return;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) p.list[atomicAdd(p.end + dc_fv(fa, f, q), 1u)] = f;
+    for (int q = 0; q < 3; ++q) p.list[atomicAdd(p.end + mesh_fv(fa, f, q), 1u)] = f;
 }
 
 // init: each vertex sorts its own list (increasing face index: the order of the quadric sums)
@@ -225,14 +186,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_sort(uint32_t V, DcPtr p) {
     if (p.hdr[H_FLAGS] & DC_BAD_INDEX) return;
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (v >= V) return;
-    uint32_t *l = p.list + (p.end[v] - p.deg[v]);
-    const uint32_t n = p.deg[v];
-    for (uint32_t i = 1; i < n; ++i) {
-        const uint32_t x = l[i];
-        uint32_t j = i;
-        for (; j > 0 && l[j - 1] > x; --j) l[j] = l[j - 1];
-        l[j] = x;
-    }
+    mesh_isort(p.list + (p.end[v] - p.deg[v]), p.deg[v]);
 }
 
 // per half-edge (a, b) of face f: its twin, the half-edge (b, a) of another face; no twin marks a and b as boundary.  check (init, no face
@@ -242,13 +196,13 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_twin(const int32_t *__restrict_
     const uint32_t he = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (he >= 3 * F) return;
     const uint32_t f = he / 3, k = he - 3 * f;
-    const uint32_t a = dc_fv(fa, f, k), b = dc_fv(fa, f, dc_next(k));
+    const uint32_t a = mesh_fv(fa, f, k), b = mesh_fv(fa, f, dc_next(k));
     uint32_t tw = DC_NONE, ntw = 0;
     for (uint32_t i = p.end[b] - p.deg[b]; i < p.end[b]; ++i) {
         const uint32_t g = p.list[i];
 #pragma unroll
         for (uint32_t j = 0; j < 3; ++j)
-            if (dc_fv(fa, g, j) == b && dc_fv(fa, g, dc_next(j)) == a) {
+            if (mesh_fv(fa, g, j) == b && mesh_fv(fa, g, dc_next(j)) == a) {
                 tw = 3 * g + j;
                 ++ntw;
             }
@@ -263,7 +217,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_twin(const int32_t *__restrict_
         for (uint32_t i = p.end[a] - p.deg[a]; i < p.end[a]; ++i) {
             const uint32_t g = p.list[i];
 #pragma unroll
-            for (uint32_t j = 0; j < 3; ++j) same += dc_fv(fa, g, j) == a && dc_fv(fa, g, dc_next(j)) == b;
+            for (uint32_t j = 0; j < 3; ++j) same += mesh_fv(fa, g, j) == a && mesh_fv(fa, g, dc_next(j)) == b;
         }
         if (same != 1 || ntw > 1) atomicOr(p.hdr + H_FLAGS, DC_NON_MANIFOLD);
     }
@@ -275,7 +229,7 @@ __device__ __forceinline__ bool dc_face_quadric(const float *__restrict__ P, con
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int a = 0; a < 3; ++a) p[i][a] = (double)P[3 * (uint64_t)dc_fv(fa, g, i) + a];
+        for (int a = 0; a < 3; ++a) p[i][a] = (double)P[3 * (uint64_t)mesh_fv(fa, g, i) + a];
     double e1[3], e2[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -334,8 +288,8 @@ __global__ void k_dc_report(uint32_t F, DcPtr p, uint32_t *__restrict__ counts) 
 __device__ __forceinline__ uint32_t dc_nbr(const int32_t *__restrict__ fa, const DcPtr &p, uint32_t c, uint32_t e) {
     const uint32_t g = p.list[p.end[c] - p.deg[c] + (e >> 1)];
     uint32_t j = 0;
-    while (j < 2 && dc_fv(fa, g, j) != c) ++j;
-    return dc_fv(fa, g, (j + 1 + (e & 1)) % 3);
+    while (j < 2 && mesh_fv(fa, g, j) != c) ++j;
+    return mesh_fv(fa, g, (j + 1 + (e & 1)) % 3);
 }
 
 // link condition: u and v share exactly two neighbours
@@ -370,16 +324,16 @@ __device__ bool dc_distinct(const int32_t *__restrict__ fa, const DcPtr &p, uint
         const uint32_t h = dc_around(p, u, v, i, c);
         if (h == f || h == g) continue;
         uint32_t j = 0;
-        while (j < 2 && dc_fv(fa, h, j) != c) ++j;
-        uint32_t x0 = dc_fv(fa, h, (j + 1) % 3), x1 = dc_fv(fa, h, (j + 2) % 3);
+        while (j < 2 && mesh_fv(fa, h, j) != c) ++j;
+        uint32_t x0 = mesh_fv(fa, h, (j + 1) % 3), x1 = mesh_fv(fa, h, (j + 2) % 3);
         if (x0 > x1) { const uint32_t t = x0; x0 = x1; x1 = t; }
         for (uint32_t i2 = 0; i2 < i; ++i2) {
             uint32_t c2;
             const uint32_t h2 = dc_around(p, u, v, i2, c2);
             if (h2 == f || h2 == g) continue;
             uint32_t j2 = 0;
-            while (j2 < 2 && dc_fv(fa, h2, j2) != c2) ++j2;
-            uint32_t y0 = dc_fv(fa, h2, (j2 + 1) % 3), y1 = dc_fv(fa, h2, (j2 + 2) % 3);
+            while (j2 < 2 && mesh_fv(fa, h2, j2) != c2) ++j2;
+            uint32_t y0 = mesh_fv(fa, h2, (j2 + 1) % 3), y1 = mesh_fv(fa, h2, (j2 + 2) % 3);
             if (y0 > y1) { const uint32_t t = y0; y0 = y1; y1 = t; }
             if (x0 == y0 && x1 == y1) return false;
         }
@@ -445,7 +399,7 @@ __device__ bool dc_no_flip(const int32_t *__restrict__ fa, const DcPtr &p, uint3
         double po[3][3], pn[3][3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const uint32_t t = dc_fv(fa, h, q);
+            const uint32_t t = mesh_fv(fa, h, q);
             const bool moved = t == u || t == v;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -471,7 +425,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_cand(uint32_t F, DcPtr p) {
     if (he >= 3 * F) return;
     const int32_t *fa = p.work;
     const uint32_t f = he / 3, k = he - 3 * f;
-    const uint32_t u = dc_fv(fa, f, k), v = dc_fv(fa, f, dc_next(k)), tw = p.twin[he];
+    const uint32_t u = mesh_fv(fa, f, k), v = mesh_fv(fa, f, dc_next(k)), tw = p.twin[he];
     uint64_t key = DC_NOKEY;
     if (tw != DC_NONE && u < v && !(p.bnd[u] && p.bnd[v]) && p.deg[u] <= DC_MAX_DEG && p.deg[v] <= DC_MAX_DEG && dc_link(fa, p, u, v) &&
         dc_distinct(fa, p, u, v, f, tw / 3)) {
@@ -495,14 +449,14 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_pre(uint32_t F, DcPtr p) {
     if (key == DC_NOKEY) return;
     const int32_t *fa = p.work;
     const uint32_t f = he / 3, k = he - 3 * f;
-    const uint32_t u = dc_fv(fa, f, k), v = dc_fv(fa, f, dc_next(k));
+    const uint32_t u = mesh_fv(fa, f, k), v = mesh_fv(fa, f, dc_next(k));
     if (p.vkey[u] != key || p.vkey[v] != key) return;
     const uint32_t n = p.deg[u] + p.deg[v];
     for (uint32_t i = 0; i < n; ++i) {
         uint32_t c;
         const uint32_t h = dc_around(p, u, v, i, c);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) atomicMin(p.nkey + dc_fv(fa, h, q), (unsigned long long)key);
+        for (int q = 0; q < 3; ++q) atomicMin(p.nkey + mesh_fv(fa, h, q), (unsigned long long)key);
     }
     const uint32_t slot = atomicAdd(p.hdr + H_NPRE, 1u);
     if (slot < p.cap) p.pre[slot] = he;
@@ -516,14 +470,14 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_win(DcPtr p) {
     const uint32_t he = p.pre[i];
     const uint64_t key = p.ekey[he];
     const uint32_t f = he / 3, k = he - 3 * f;
-    const uint32_t u = dc_fv(fa, f, k), v = dc_fv(fa, f, dc_next(k));
+    const uint32_t u = mesh_fv(fa, f, k), v = mesh_fv(fa, f, dc_next(k));
     const uint32_t n = p.deg[u] + p.deg[v];
     for (uint32_t j = 0; j < n; ++j) {
         uint32_t c;
         const uint32_t h = dc_around(p, u, v, j, c);
 #pragma unroll
         for (int q = 0; q < 3; ++q)
-            if (p.nkey[dc_fv(fa, h, q)] != key) return;
+            if (p.nkey[mesh_fv(fa, h, q)] != key) return;
     }
     const uint32_t slot = atomicAdd(p.hdr + H_NWIN, 1u);
     if (slot < p.cap) p.win[slot] = key;
@@ -579,7 +533,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_apply(DcPtr p) {
     if (key >= ((const uint64_t *)p.hdr)[H64_LIM]) return;
     const int32_t *fa = p.work;
     const uint32_t he = (uint32_t)key, f = he / 3, k = he - 3 * f;
-    const uint32_t u = dc_fv(fa, f, k), v = dc_fv(fa, f, dc_next(k));
+    const uint32_t u = mesh_fv(fa, f, k), v = mesh_fv(fa, f, dc_next(k));
     DcPlace r;
     dc_place(p, u, v, r);                            // as k_dc_cand computed it: the neighbourhood is the winner's alone
 #pragma unroll
@@ -659,15 +613,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_everts(uint32_t V, DcPtr p, con
     const uint32_t k = p.sums[blockIdx.x].x + mc_block_prefix<1>(ref, red);
     if (!ref) return;
     p.end[v] = k;                                    // new index
-    if (k >= max_verts) return;
-    const uint64_t s = 3 * (uint64_t)v, d = 3 * (uint64_t)k;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) verts_out[d + a] = p.pos[s + a];
-    if (normals && normals_out) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) normals_out[d + a] = normals[s + a];
-    }
-    if (old_index) old_index[k] = (int32_t)v;
+    mesh_emit_vertex(p.pos, normals, v, k, verts_out, normals_out, old_index, max_verts);
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void k_dc_efaces(uint32_t F, DcPtr p, int32_t *__restrict__ faces_out, uint32_t max_faces) {
@@ -680,21 +626,14 @@ __global__ __launch_bounds__(MC_BLOCK) void k_dc_efaces(uint32_t F, DcPtr p, int
 
 int dc_check_dims(uint32_t V, uint32_t F) { return (V >= (1u << 31) || F >= (1u << 31) || F > DC_MAX_F) ? CNERF_EINVAL : CNERF_OK; }
 
-int dc_check_ws(uint32_t V, uint32_t F, const void *ws, uint64_t ws_bytes, DcLayout &l) {
-    l = dc_layout(V, F);
-    return (ws_bytes < l.total || ((uintptr_t)ws & 15)) ? CNERF_EINVAL : CNERF_OK;
-}
-
-inline dim3 dc_grid(uint64_t n) { return dim3((uint32_t)cn_div_up64(n, MC_BLOCK)); }
-
 // vertex -> face lists of the faces `fa` (F of them): degrees already counted; init sorts the lists and checks the edges
 void dc_lists(const int32_t *fa, uint32_t V, uint32_t F, int init, const DcPtr &p, hipStream_t st) {
-    hipLaunchKernelGGL(k_dc_vsum, dc_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+    hipLaunchKernelGGL(k_dc_vsum, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
     hipLaunchKernelGGL(k_dc_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, (uint32_t)cn_div_up64(V, MC_BLOCK), init, p);
-    hipLaunchKernelGGL(k_dc_offsets, dc_grid(V), dim3(MC_BLOCK), 0, st, V, p);
-    hipLaunchKernelGGL(k_dc_fill, dc_grid(F), dim3(MC_BLOCK), 0, st, fa, F, p);
-    if (init) hipLaunchKernelGGL(k_dc_sort, dc_grid(V), dim3(MC_BLOCK), 0, st, V, p);
-    hipLaunchKernelGGL(k_dc_twin, dc_grid(3ull * F), dim3(MC_BLOCK), 0, st, fa, F, init, p);
+    hipLaunchKernelGGL(k_dc_offsets, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+    hipLaunchKernelGGL(k_dc_fill, mesh_grid(F), dim3(MC_BLOCK), 0, st, fa, F, p);
+    if (init) hipLaunchKernelGGL(k_dc_sort, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+    hipLaunchKernelGGL(k_dc_twin, mesh_grid(3ull * F), dim3(MC_BLOCK), 0, st, fa, F, init, p);
 }
 
 }  // namespace
@@ -704,7 +643,8 @@ extern "C" {
 int cnerf_mesh_decimate_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host) {
     if (const int rc = dc_check_dims(V, F)) return rc;
     if (!bytes_host) return CNERF_ENULL;
-    *bytes_host = dc_layout(V, F).total;
+    DcPtr p;
+    *bytes_host = dc_carve(nullptr, V, F, p);
     return CNERF_OK;
 }
 
@@ -712,17 +652,16 @@ int cnerf_mesh_decimate_init(const float *verts, uint32_t V, const int32_t *face
                              void *stream) {
     if (const int rc = dc_check_dims(V, F)) return rc;
     if ((V && !verts) || (F && !faces) || !ws || !counts) return CNERF_ENULL;
-    DcLayout l;
-    if (const int rc = dc_check_ws(V, F, ws, ws_bytes, l)) return rc;
-    const DcPtr p = dc_ptr(ws, l);
+    DcPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, dc_carve(ws, V, F, p))) return rc;
     hipStream_t st = CN_STREAM(stream);
     if (const int rc = (int)hipMemsetAsync(ws, 0, 256, st)) return rc;
-    if (V) hipLaunchKernelGGL(k_dc_clear, dc_grid(V), dim3(MC_BLOCK), 0, st, V, p);
-    if (F) hipLaunchKernelGGL(k_dc_load, dc_grid(F), dim3(MC_BLOCK), 0, st, faces, V, F, p);
+    if (V) hipLaunchKernelGGL(k_dc_clear, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+    if (F) hipLaunchKernelGGL(k_dc_load, mesh_grid(F), dim3(MC_BLOCK), 0, st, faces, V, F, p);
     if (V) {
         if (F) dc_lists(p.faces, V, F, 1, p, st);
         else hipLaunchKernelGGL(k_dc_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, 0u, 1, p);    // (no degrees: no referenced vertex)
-        hipLaunchKernelGGL(k_dc_quadric, dc_grid(V), dim3(MC_BLOCK), 0, st, verts, V, p);
+        hipLaunchKernelGGL(k_dc_quadric, mesh_grid(V), dim3(MC_BLOCK), 0, st, verts, V, p);
     }
     hipLaunchKernelGGL(k_dc_report, dim3(1), dim3(1), 0, st, F, p, counts);
     return cn_launch_status();
@@ -731,25 +670,24 @@ int cnerf_mesh_decimate_init(const float *verts, uint32_t V, const int32_t *face
 int cnerf_mesh_decimate_round(uint32_t V, uint32_t F, uint32_t target_faces, void *ws, uint64_t ws_bytes, uint32_t *counts, void *stream) {
     if (const int rc = dc_check_dims(V, F)) return rc;
     if (!ws || !counts) return CNERF_ENULL;
-    DcLayout l;
-    if (const int rc = dc_check_ws(V, F, ws, ws_bytes, l)) return rc;
-    const DcPtr p = dc_ptr(ws, l);
+    DcPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, dc_carve(ws, V, F, p))) return rc;
     hipStream_t st = CN_STREAM(stream);
     if (!F || !V) {
         hipLaunchKernelGGL(k_dc_report, dim3(1), dim3(1), 0, st, F, p, counts);
         return cn_launch_status();
     }
-    hipLaunchKernelGGL(k_dc_clear, dc_grid(V), dim3(MC_BLOCK), 0, st, V, p);
-    hipLaunchKernelGGL(k_dc_deg, dc_grid(F), dim3(MC_BLOCK), 0, st, F, p);
+    hipLaunchKernelGGL(k_dc_clear, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+    hipLaunchKernelGGL(k_dc_deg, mesh_grid(F), dim3(MC_BLOCK), 0, st, F, p);
     dc_lists(p.work, V, F, 0, p, st);
-    hipLaunchKernelGGL(k_dc_cand, dc_grid(3ull * F), dim3(MC_BLOCK), 0, st, F, p);
-    hipLaunchKernelGGL(k_dc_pre, dc_grid(3ull * F), dim3(MC_BLOCK), 0, st, F, p);
-    hipLaunchKernelGGL(k_dc_win, dc_grid(l.cap), dim3(MC_BLOCK), 0, st, p);
+    hipLaunchKernelGGL(k_dc_cand, mesh_grid(3ull * F), dim3(MC_BLOCK), 0, st, F, p);
+    hipLaunchKernelGGL(k_dc_pre, mesh_grid(3ull * F), dim3(MC_BLOCK), 0, st, F, p);
+    hipLaunchKernelGGL(k_dc_win, mesh_grid(p.cap), dim3(MC_BLOCK), 0, st, p);
     hipLaunchKernelGGL(k_dc_select, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, F, target_faces, p);
-    hipLaunchKernelGGL(k_dc_apply, dc_grid(l.cap), dim3(MC_BLOCK), 0, st, p);
-    hipLaunchKernelGGL(k_dc_fcount, dc_grid(F), dim3(MC_BLOCK), 0, st, F, p);
+    hipLaunchKernelGGL(k_dc_apply, mesh_grid(p.cap), dim3(MC_BLOCK), 0, st, p);
+    hipLaunchKernelGGL(k_dc_fcount, mesh_grid(F), dim3(MC_BLOCK), 0, st, F, p);
     hipLaunchKernelGGL(k_dc_fscan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, F, (uint32_t)cn_div_up64(F, MC_BLOCK), p, counts);
-    hipLaunchKernelGGL(k_dc_compact, dc_grid(F), dim3(MC_BLOCK), 0, st, F, p);
+    hipLaunchKernelGGL(k_dc_compact, mesh_grid(F), dim3(MC_BLOCK), 0, st, F, p);
     return cn_launch_status();
 }
 
@@ -757,18 +695,17 @@ int cnerf_mesh_decimate_emit(const float *normals, uint32_t V, uint32_t F, void 
                              int32_t *faces_out, int32_t *old_index, uint32_t max_verts, uint32_t max_faces, void *stream) {
     if (const int rc = dc_check_dims(V, F)) return rc;
     if (!ws || (max_verts && !verts_out) || (max_faces && !faces_out)) return CNERF_ENULL;
-    DcLayout l;
-    if (const int rc = dc_check_ws(V, F, ws, ws_bytes, l)) return rc;
-    const DcPtr p = dc_ptr(ws, l);
+    DcPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, dc_carve(ws, V, F, p))) return rc;
     hipStream_t st = CN_STREAM(stream);
     if (!V) return CNERF_OK;
-    hipLaunchKernelGGL(k_dc_clear, dc_grid(V), dim3(MC_BLOCK), 0, st, V, p);
-    if (F) hipLaunchKernelGGL(k_dc_emark, dc_grid(F), dim3(MC_BLOCK), 0, st, F, p);
-    hipLaunchKernelGGL(k_dc_ecount, dc_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+    hipLaunchKernelGGL(k_dc_clear, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+    if (F) hipLaunchKernelGGL(k_dc_emark, mesh_grid(F), dim3(MC_BLOCK), 0, st, F, p);
+    hipLaunchKernelGGL(k_dc_ecount, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
     hipLaunchKernelGGL(k_dc_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, (uint32_t)cn_div_up64(V, MC_BLOCK), 0, p);
-    hipLaunchKernelGGL(k_dc_everts, dc_grid(V), dim3(MC_BLOCK), 0, st, V, p, normals, max_verts ? verts_out : nullptr,
+    hipLaunchKernelGGL(k_dc_everts, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p, normals, max_verts ? verts_out : nullptr,
                        max_verts ? normals_out : nullptr, max_verts ? old_index : nullptr, max_verts);
-    if (F) hipLaunchKernelGGL(k_dc_efaces, dc_grid(F), dim3(MC_BLOCK), 0, st, F, p, faces_out, max_faces);
+    if (F) hipLaunchKernelGGL(k_dc_efaces, mesh_grid(F), dim3(MC_BLOCK), 0, st, F, p, faces_out, max_faces);
     return cn_launch_status();
 }
 

@@ -28,13 +28,13 @@
 // init (faces only):
 //   k_sm_clear   : per vertex: degrees reset
 //   k_sm_deg     : per face: index check (flags bit 0), degrees (atomicAdd): two records per distinct edge, one list slot per distinct vertex
-//   k_sm_vsum / k_sm_scan / k_sm_offsets : exclusive scan of both degrees (mesh_scan.h)
+//   k_sm_vsum / k_sm_scan / k_sm_offsets : exclusive scan of both degrees (mesh_common.h)
 //   k_sm_fill    : per face: the records and the face list entries (atomicAdd on the list ends, which end at start + degree)
 //   k_sm_sort    : per vertex: both lists sorted; neighbour runs collapsed to their first entry, boundary mark; flags out
 // steps: k_sm_step per step, ping-pong between the two buffers, the last one into verts_out (k_sm_copy for zero iterations)
 // normals: k_sm_normals per vertex, its faces' normals recomputed from `verts`
 #include "common.h"
-#include "mesh_scan.h"
+#include "mesh_common.h"
 
 #define SM_BAD_INDEX 1u
 #define SM_MAX_F 0x2AAAAAAAu                         // 6 F records fit a u32
@@ -43,27 +43,6 @@
 namespace {
 
 enum { H_FLAGS = 0 };                                // uint32 slots of the header
-
-inline uint64_t sm_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
-struct SmLayout {
-    uint64_t nbr, deg, end, fdeg, fend, sums, rec, flist, pos, total;
-};
-
-SmLayout sm_layout(uint64_t V, uint64_t F) {
-    SmLayout l;
-    l.nbr = 256;
-    l.deg = l.nbr + sm_align(8 * V);
-    l.end = l.deg + sm_align(4 * V);
-    l.fdeg = l.end + sm_align(4 * V);
-    l.fend = l.fdeg + sm_align(4 * V);
-    l.sums = l.fend + sm_align(4 * V);
-    l.rec = l.sums + sm_align(8 * cn_div_up64(V ? V : 1, MC_BLOCK));
-    l.flist = l.rec + sm_align(24 * F);
-    l.pos = l.flist + sm_align(12 * F);
-    l.total = l.pos + 2 * sm_align(12 * V);
-    return l;
-}
 
 struct SmPtr {
     uint32_t *hdr;
@@ -74,24 +53,22 @@ struct SmPtr {
     float *pos[2];
 };
 
-SmPtr sm_ptr(void *ws, const SmLayout &l, uint64_t V) {
-    uint8_t *w = (uint8_t *)ws;
-    SmPtr p;
-    p.hdr = (uint32_t *)w;
-    p.nbr = (uint2 *)(w + l.nbr);
-    p.deg = (uint32_t *)(w + l.deg);
-    p.end = (uint32_t *)(w + l.end);
-    p.fdeg = (uint32_t *)(w + l.fdeg);
-    p.fend = (uint32_t *)(w + l.fend);
-    p.sums = (uint2 *)(w + l.sums);
-    p.rec = (uint32_t *)(w + l.rec);
-    p.flist = (uint32_t *)(w + l.flist);
-    p.pos[0] = (float *)(w + l.pos);
-    p.pos[1] = (float *)(w + l.pos + sm_align(12 * V));
-    return p;
+// the workspace: its regions in order -> total bytes (ws == nullptr: the size only)
+uint64_t sm_carve(void *ws, uint64_t V, uint64_t F, SmPtr &p) {
+    MeshCarve c(ws);
+    p.hdr = c.header();
+    p.nbr = c.take<uint2>(V);
+    p.deg = c.take<uint32_t>(V);
+    p.end = c.take<uint32_t>(V);
+    p.fdeg = c.take<uint32_t>(V);
+    p.fend = c.take<uint32_t>(V);
+    p.sums = c.take<uint2>(cn_div_up64(V ? V : 1, MC_BLOCK));
+    p.rec = c.take<uint32_t>(6 * F);
+    p.flist = c.take<uint32_t>(3 * F);
+    p.pos[0] = c.take<float>(3 * V);
+    p.pos[1] = c.take<float>(3 * V);
+    return c.total();
 }
-
-__device__ __forceinline__ uint32_t sm_fv(const int32_t *fa, uint32_t f, uint32_t q) { return (uint32_t)fa[3 * (uint64_t)f + q]; }
 
 // calls vert(u) for each distinct vertex u of face t and edge(a, b) for each of its distinct undirected edges: all three with three
 // distinct vertices, the one between them with two, none with one
@@ -124,13 +101,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_sm_deg(const int32_t *__restrict__
     const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (f >= F) return;
     uint32_t t[3];
-    bool ok = true;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        t[q] = sm_fv(fa, f, q);
-        ok &= t[q] < V;                              // a negative int32 is >= 2^31 > V here
-    }
-    if (!ok) {
+    if (!mesh_face(fa, f, V, t)) {
         atomicOr(p.hdr + H_FLAGS, SM_BAD_INDEX);
         return;
     }
@@ -142,12 +113,8 @@ __global__ __launch_bounds__(MC_BLOCK) void k_sm_deg(const int32_t *__restrict__
 
 // workgroup totals of (record degree, face degree)
 __global__ __launch_bounds__(MC_BLOCK) void k_sm_vsum(uint32_t V, SmPtr p) {
-    __shared__ uint32_t red_d[MC_WAVES], red_f[MC_WAVES];
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
-    uint32_t td, tf;
-    mc_block_excl(v < V ? p.deg[v] : 0, red_d, td);
-    mc_block_excl(v < V ? p.fdeg[v] : 0, red_f, tf);
-    if (threadIdx.x == 0) p.sums[blockIdx.x] = make_uint2(td, tf);
+    mesh_csr_totals(v < V ? p.deg[v] : 0, v < V ? p.fdeg[v] : 0, p.sums);
 }
 
 __global__ __launch_bounds__(MC_SCAN_BLOCK) void k_sm_scan(uint32_t nblk, SmPtr p) {
@@ -158,9 +125,8 @@ __global__ __launch_bounds__(MC_SCAN_BLOCK) void k_sm_scan(uint32_t nblk, SmPtr 
 __global__ __launch_bounds__(MC_BLOCK) void k_sm_offsets(uint32_t V, SmPtr p) {
     __shared__ uint32_t red_d[MC_WAVES], red_f[MC_WAVES];
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
-    uint32_t td, tf;
-    const uint32_t sd = p.sums[blockIdx.x].x + mc_block_excl(v < V ? p.deg[v] : 0, red_d, td);
-    const uint32_t sf = p.sums[blockIdx.x].y + mc_block_excl(v < V ? p.fdeg[v] : 0, red_f, tf);
+    const uint32_t sd = mesh_csr_start(p.sums[blockIdx.x].x, v < V ? p.deg[v] : 0, red_d);
+    const uint32_t sf = mesh_csr_start(p.sums[blockIdx.x].y, v < V ? p.fdeg[v] : 0, red_f);
     if (v >= V) return;
     p.end[v] = sd;                                   // k_sm_fill advances both to start + degree
     p.fend[v] = sf;
@@ -172,20 +138,11 @@ __global__ __launch_bounds__(MC_BLOCK) void k_sm_fill(const int32_t *__restrict_
     if (f >= F) return;
     uint32_t t[3];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) t[q] = sm_fv(fa, f, q);
+    for (int q = 0; q < 3; ++q) t[q] = mesh_fv(fa, f, q);
     sm_face(t, [&](uint32_t u) { p.flist[atomicAdd(p.fend + u, 1u)] = f; }, [&](uint32_t a, uint32_t b) {
         p.rec[atomicAdd(p.end + a, 1u)] = b;
         p.rec[atomicAdd(p.end + b, 1u)] = a;
     });
-}
-
-__device__ __forceinline__ void sm_isort(uint32_t *l, uint32_t n) {
-    for (uint32_t i = 1; i < n; ++i) {
-        const uint32_t x = l[i];
-        uint32_t j = i;
-        for (; j > 0 && l[j - 1] > x; --j) l[j] = l[j - 1];
-        l[j] = x;
-    }
 }
 
 // each vertex sorts its records and its faces; a run of equal records is one neighbour (its length: the faces on that edge)
@@ -195,7 +152,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_sm_sort(uint32_t V, SmPtr p, uint3
     if (v >= V || (p.hdr[H_FLAGS] & SM_BAD_INDEX)) return;
     const uint32_t d = p.deg[v], start = p.end[v] - d;
     uint32_t *l = p.rec + start;
-    sm_isort(l, d);
+    mesh_isort(l, d);
     uint32_t n = 0, bnd = 0;
     for (uint32_t i = 0; i < d;) {
         const uint32_t w = l[i];
@@ -206,7 +163,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_sm_sort(uint32_t V, SmPtr p, uint3
         i = j;
     }
     p.nbr[v] = make_uint2(start, n | (bnd ? SM_BOUNDARY : 0u));
-    sm_isort(p.flist + (p.fend[v] - p.fdeg[v]), p.fdeg[v]);
+    mesh_isort(p.flist + (p.fend[v] - p.fdeg[v]), p.fdeg[v]);
 }
 
 // ------------------------------------------------------------------------------------------------ steps
@@ -258,7 +215,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_sm_normals(const float *__restrict
     const uint32_t e = p.fend[v];
     for (uint32_t i = e - p.fdeg[v]; i < e; ++i) {
         const uint32_t g = p.flist[i];
-        const uint64_t i0 = 3 * (uint64_t)sm_fv(fa, g, 0), i1 = 3 * (uint64_t)sm_fv(fa, g, 1), i2 = 3 * (uint64_t)sm_fv(fa, g, 2);
+        const uint64_t i0 = 3 * (uint64_t)mesh_fv(fa, g, 0), i1 = 3 * (uint64_t)mesh_fv(fa, g, 1), i2 = 3 * (uint64_t)mesh_fv(fa, g, 2);
         const float e1x = P[i1] - P[i0], e1y = P[i1 + 1] - P[i0 + 1], e1z = P[i1 + 2] - P[i0 + 2];
         const float e2x = P[i2] - P[i0], e2y = P[i2 + 1] - P[i0 + 1], e2z = P[i2 + 2] - P[i0 + 2];
         a0 += e1y * e2z - e1z * e2y;
@@ -278,14 +235,11 @@ __global__ __launch_bounds__(MC_BLOCK) void k_sm_normals(const float *__restrict
     }
 }
 
-int sm_check(uint32_t V, uint32_t F, const void *ws, uint64_t ws_bytes, SmLayout &l) {
+int sm_check(uint32_t V, uint32_t F, void *ws, uint64_t ws_bytes, SmPtr &p) {
     if (V >= (1u << 31) || F > SM_MAX_F) return CNERF_EINVAL;
     if (!ws) return CNERF_ENULL;
-    l = sm_layout(V, F);
-    return (ws_bytes < l.total || ((uintptr_t)ws & 15)) ? CNERF_EINVAL : CNERF_OK;
+    return mesh_check_ws(ws, ws_bytes, sm_carve(ws, V, F, p));
 }
-
-inline dim3 sm_grid(uint64_t n) { return dim3((uint32_t)cn_div_up64(n, MC_BLOCK)); }
 
 }  // namespace
 
@@ -294,48 +248,47 @@ extern "C" {
 int cnerf_mesh_smooth_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host) {
     if (V >= (1u << 31) || F > SM_MAX_F) return CNERF_EINVAL;
     if (!bytes_host) return CNERF_ENULL;
-    *bytes_host = sm_layout(V, F).total;
+    SmPtr p;
+    *bytes_host = sm_carve(nullptr, V, F, p);
     return CNERF_OK;
 }
 
 int cnerf_mesh_smooth_init(const int32_t *faces, uint32_t V, uint32_t F, void *ws, uint64_t ws_bytes, uint32_t *flags, void *stream) {
-    SmLayout l;
-    if (const int rc = sm_check(V, F, ws, ws_bytes, l)) return rc;
+    SmPtr p;
+    if (const int rc = sm_check(V, F, ws, ws_bytes, p)) return rc;
     if ((F && !faces) || !flags) return CNERF_ENULL;
-    const SmPtr p = sm_ptr(ws, l, V);
     hipStream_t st = CN_STREAM(stream);
     if (const int rc = (int)hipMemsetAsync(ws, 0, 256, st)) return rc;
-    if (V) hipLaunchKernelGGL(k_sm_clear, sm_grid(V), dim3(MC_BLOCK), 0, st, V, p);
-    if (F) hipLaunchKernelGGL(k_sm_deg, sm_grid(F), dim3(MC_BLOCK), 0, st, faces, V, F, p);
+    if (V) hipLaunchKernelGGL(k_sm_clear, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+    if (F) hipLaunchKernelGGL(k_sm_deg, mesh_grid(F), dim3(MC_BLOCK), 0, st, faces, V, F, p);
     if (V) {
-        hipLaunchKernelGGL(k_sm_vsum, sm_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+        hipLaunchKernelGGL(k_sm_vsum, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
         hipLaunchKernelGGL(k_sm_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, (uint32_t)cn_div_up64(V, MC_BLOCK), p);
-        hipLaunchKernelGGL(k_sm_offsets, sm_grid(V), dim3(MC_BLOCK), 0, st, V, p);
-        if (F) hipLaunchKernelGGL(k_sm_fill, sm_grid(F), dim3(MC_BLOCK), 0, st, faces, F, p);
+        hipLaunchKernelGGL(k_sm_offsets, mesh_grid(V), dim3(MC_BLOCK), 0, st, V, p);
+        if (F) hipLaunchKernelGGL(k_sm_fill, mesh_grid(F), dim3(MC_BLOCK), 0, st, faces, F, p);
     }
-    hipLaunchKernelGGL(k_sm_sort, sm_grid(V ? V : 1), dim3(MC_BLOCK), 0, st, V, p, flags);
+    hipLaunchKernelGGL(k_sm_sort, mesh_grid(V ? V : 1), dim3(MC_BLOCK), 0, st, V, p, flags);
     return cn_launch_status();
 }
 
 int cnerf_mesh_smooth_steps(const float *verts_in, uint32_t V, uint32_t F, uint32_t iterations, float lambda, float mu, int pin_boundary,
                             void *ws, uint64_t ws_bytes, float *verts_out, void *stream) {
-    SmLayout l;
-    if (const int rc = sm_check(V, F, ws, ws_bytes, l)) return rc;
+    SmPtr p;
+    if (const int rc = sm_check(V, F, ws, ws_bytes, p)) return rc;
     if (!__builtin_isfinite(lambda) || !__builtin_isfinite(mu)) return CNERF_EINVAL;
     if (V && (!verts_in || !verts_out)) return CNERF_ENULL;
     if (!V) return CNERF_OK;
-    const SmPtr p = sm_ptr(ws, l, V);
     hipStream_t st = CN_STREAM(stream);
     const uint64_t per = mu != 0.0f ? 2 : 1, T = per * iterations;
     if (!T) {
-        hipLaunchKernelGGL(k_sm_copy, sm_grid(V), dim3(MC_BLOCK), 0, st, verts_in, verts_out, V, p);
+        hipLaunchKernelGGL(k_sm_copy, mesh_grid(V), dim3(MC_BLOCK), 0, st, verts_in, verts_out, V, p);
         return cn_launch_status();
     }
     const float *src = verts_in;
     for (uint64_t t = 0; t < T; ++t) {
         float *dst = t + 1 == T ? verts_out : p.pos[t & 1];
         const float s = (t % per) ? mu : lambda;
-        hipLaunchKernelGGL(k_sm_step, sm_grid(V), dim3(MC_BLOCK), 0, st, src, dst, V, s, pin_boundary ? 1 : 0, p);
+        hipLaunchKernelGGL(k_sm_step, mesh_grid(V), dim3(MC_BLOCK), 0, st, src, dst, V, s, pin_boundary ? 1 : 0, p);
         src = dst;
     }
     return cn_launch_status();
@@ -343,13 +296,12 @@ int cnerf_mesh_smooth_steps(const float *verts_in, uint32_t V, uint32_t F, uint3
 
 int cnerf_mesh_smooth_normals(const float *verts, const float *normals_in, uint32_t V, const int32_t *faces, uint32_t F, void *ws,
                               uint64_t ws_bytes, float *normals_out, void *stream) {
-    SmLayout l;
-    if (const int rc = sm_check(V, F, ws, ws_bytes, l)) return rc;
+    SmPtr p;
+    if (const int rc = sm_check(V, F, ws, ws_bytes, p)) return rc;
     if (V && (!verts || !normals_out)) return CNERF_ENULL;
     if (F && !faces) return CNERF_ENULL;
     if (!V) return CNERF_OK;
-    const SmPtr p = sm_ptr(ws, l, V);
-    hipLaunchKernelGGL(k_sm_normals, sm_grid(V), dim3(MC_BLOCK), 0, CN_STREAM(stream), verts, normals_in, faces, V, p, normals_out);
+    hipLaunchKernelGGL(k_sm_normals, mesh_grid(V), dim3(MC_BLOCK), 0, CN_STREAM(stream), verts, normals_in, faces, V, p, normals_out);
     return cn_launch_status();
 }
 

@@ -27,11 +27,46 @@ def _triple(v, name):
     return (C.c_float * 3)(*t)
 
 
-def workspace_bytes(shape):
-    nx, ny, nz = (int(s) for s in shape)
+def _bytes(name, *args):
+    """cnerf_<name>_workspace_bytes(*args): the size of a pass's workspace"""
     out = C.c_uint64(0)
-    check(lib.cnerf_marching_cubes_workspace_bytes(nx, ny, nz, C.byref(out)), "marching_cubes_workspace_bytes")
+    check(getattr(lib, f"cnerf_{name}_workspace_bytes")(*args, C.byref(out)), f"{name}_workspace_bytes")
     return out.value
+
+
+def _workspace(dev, name, *args):
+    nbytes = _bytes(name, *args)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def _p(t):
+    """pointer of a tensor, None for no tensor or an empty one"""
+    return ptr(t) if t is not None and t.numel() else None
+
+
+_BAD_INDEX = ((1, "a face index lies outside [0, V)"),)
+_DECIMATE_FLAGS = _BAD_INDEX + ((2, "an edge lies in more than two faces or two faces use it in one direction"),
+                                (4, "a face repeats a vertex index"))
+
+
+def _read(counts, what, flags):
+    """The one host read of a call: the device counts as unsigned ints; their last entry holds the flag bits, and the first set one of
+    `flags` ((bit, message), ...) raises ValueError."""
+    r = [int(c) & 0xffffffff for c in counts.cpu()]
+    for bit, msg in flags:
+        if r[-1] & bit:
+            raise ValueError(f"{what}: {msg}")
+    return r
+
+
+def _outputs(dev, V, F, normals, old_index=True):
+    """(verts [V, 3], normals [V, 3] or None, faces [F, 3], old_index [V] or None), uninitialised"""
+    return (torch.empty(V, 3, dtype=torch.float32, device=dev), torch.empty(V, 3, dtype=torch.float32, device=dev) if normals else None,
+            torch.empty(F, 3, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev) if old_index else None)
+
+
+def workspace_bytes(shape):
+    return _bytes("marching_cubes", *(int(s) for s in shape))
 
 
 def marching_cubes(volume, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), normals=True):
@@ -46,19 +81,16 @@ def marching_cubes(volume, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0
     nx, ny, nz = vol.shape
     sp, org = _triple(spacing, "spacing"), _triple(origin, "origin")
     dev = vol.device
-    nbytes = workspace_bytes(vol.shape)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "marching_cubes", nx, ny, nz)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     level = float(level)
     check(lib.cnerf_marching_cubes_count(ptr(vol), nx, ny, nz, level, ptr(ws), nbytes, ptr(counts), stream()), "marching_cubes_count")
     V, F = (int(c) & 0xffffffff for c in counts.cpu())                         # the one host read
     if V == 0xffffffff:
         raise ValueError(f"marching_cubes: the mesh of a {nx}x{ny}x{nz} volume has more than 2^31 - 1 vertices or triangles")
-    verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    nrm = torch.empty(V, 3, dtype=torch.float32, device=dev) if normals else None
-    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
-    check(lib.cnerf_marching_cubes_emit(ptr(vol), nx, ny, nz, level, org, sp, ptr(ws), nbytes, ptr(verts) if V else None,
-                                        ptr(nrm) if V else None, ptr(faces) if F else None, V, F, stream()), "marching_cubes_emit")
+    verts, nrm, faces, _ = _outputs(dev, V, F, normals, old_index=False)
+    check(lib.cnerf_marching_cubes_emit(ptr(vol), nx, ny, nz, level, org, sp, ptr(ws), nbytes, _p(verts), _p(nrm), _p(faces), V, F, stream()),
+          "marching_cubes_emit")
     return verts, faces, nrm
 
 
@@ -74,17 +106,8 @@ def _mesh_args(verts, faces, normals, what):
     return v, f, n
 
 
-def _counts(counts, what):
-    V, F, flags = (int(c) & 0xffffffff for c in counts.cpu())                  # the one host read
-    if flags & 1:
-        raise ValueError(f"{what}: a face index lies outside [0, V)")
-    return V, F
-
-
 def components_workspace_bytes(V, F):
-    out = C.c_uint64(0)
-    check(lib.cnerf_mesh_components_workspace_bytes(int(V), int(F), C.byref(out)), "mesh_components_workspace_bytes")
-    return out.value
+    return _bytes("mesh_components", int(V), int(F))
 
 
 def remove_small_components(verts, faces, normals=None, min_faces=1, largest=False):
@@ -99,20 +122,14 @@ def remove_small_components(verts, faces, normals=None, min_faces=1, largest=Fal
     if mf < 0 or mf >= 2 ** 32:
         raise ValueError(f"remove_small_components: min_faces must be in [0, 2^32), got {min_faces}")
     dev = v.device
-    nbytes = components_workspace_bytes(V, F)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "mesh_components", V, F)
     counts = torch.empty(3, dtype=torch.int32, device=dev)
     lg = 1 if largest else 0
-    check(lib.cnerf_mesh_components_count(ptr(f) if F else None, V, F, mf, lg, ptr(ws), nbytes, ptr(counts), stream()),
-          "mesh_components_count")
-    V2, F2 = _counts(counts, "remove_small_components")
-    vo = torch.empty(V2, 3, dtype=torch.float32, device=dev)
-    no = torch.empty(V2, 3, dtype=torch.float32, device=dev) if n is not None else None
-    fo = torch.empty(F2, 3, dtype=torch.int32, device=dev)
-    old = torch.empty(V2, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_components_emit(ptr(v) if V else None, ptr(n) if V and n is not None else None, V, ptr(f) if F else None, F, mf, lg,
-                                         ptr(ws), nbytes, ptr(vo) if V2 else None, ptr(no) if V2 and no is not None else None,
-                                         ptr(fo) if F2 else None, ptr(old) if V2 else None, V2, F2, stream()), "mesh_components_emit")
+    check(lib.cnerf_mesh_components_count(_p(f), V, F, mf, lg, ptr(ws), nbytes, ptr(counts), stream()), "mesh_components_count")
+    V2, F2, _ = _read(counts, "remove_small_components", _BAD_INDEX)
+    vo, no, fo, old = _outputs(dev, V2, F2, n is not None)
+    check(lib.cnerf_mesh_components_emit(_p(v), _p(n), V, _p(f), F, mf, lg, ptr(ws), nbytes, _p(vo), _p(no), _p(fo), _p(old), V2, F2,
+                                         stream()), "mesh_components_emit")
     return vo, fo, no, old
 
 
@@ -135,9 +152,7 @@ def cluster_grid(verts, cell, origin=None):
 
 
 def cluster_workspace_bytes(V, F, grid):
-    out = C.c_uint64(0)
-    check(lib.cnerf_mesh_cluster_workspace_bytes(int(V), int(F), (C.c_uint32 * 3)(*grid), C.byref(out)), "mesh_cluster_workspace_bytes")
-    return out.value
+    return _bytes("mesh_cluster", int(V), int(F), (C.c_uint32 * 3)(*grid))
 
 
 def simplify(verts, faces, cell, normals=None, origin=None, grid=None):
@@ -155,29 +170,18 @@ def simplify(verts, faces, cell, normals=None, origin=None, grid=None):
         raise ValueError(f"simplify: the grid {g} needs 1 <= g and gx * gy * gz < 2^31 (a larger cell)")
     dev = v.device
     og, cg, gg = (C.c_float * 3)(*o.tolist()), (C.c_float * 3)(*c.tolist()), (C.c_uint32 * 3)(*g)
-    nbytes = cluster_workspace_bytes(V, F, g)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "mesh_cluster", V, F, gg)
     counts = torch.empty(3, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_cluster_count(ptr(v) if V else None, V, ptr(f) if F else None, F, og, cg, gg, ptr(ws), nbytes, ptr(counts), stream()),
-          "mesh_cluster_count")
-    K, F2 = _counts(counts, "simplify")
-    vo = torch.empty(K, 3, dtype=torch.float32, device=dev)
-    no = torch.empty(K, 3, dtype=torch.float32, device=dev) if n is not None else None
-    fo = torch.empty(F2, 3, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_cluster_emit(ptr(v) if V else None, ptr(n) if V and n is not None else None, V, ptr(f) if F else None, F, og, cg, gg,
-                                      ptr(ws), nbytes, ptr(vo) if K else None, ptr(no) if K and no is not None else None,
-                                      ptr(fo) if F2 else None, K, F2, stream()), "mesh_cluster_emit")
+    check(lib.cnerf_mesh_cluster_count(_p(v), V, _p(f), F, og, cg, gg, ptr(ws), nbytes, ptr(counts), stream()), "mesh_cluster_count")
+    K, F2, _ = _read(counts, "simplify", _BAD_INDEX)
+    vo, no, fo, _ = _outputs(dev, K, F2, n is not None, old_index=False)
+    check(lib.cnerf_mesh_cluster_emit(_p(v), _p(n), V, _p(f), F, og, cg, gg, ptr(ws), nbytes, _p(vo), _p(no), _p(fo), K, F2, stream()),
+          "mesh_cluster_emit")
     return vo, fo, no
 
 
 def decimate_workspace_bytes(V, F):
-    out = C.c_uint64(0)
-    check(lib.cnerf_mesh_decimate_workspace_bytes(int(V), int(F), C.byref(out)), "mesh_decimate_workspace_bytes")
-    return out.value
-
-
-_DECIMATE_FLAGS = ((1, "a face index lies outside [0, V)"), (2, "an edge lies in more than two faces or two faces use it in one direction"),
-                   (4, "a face repeats a vertex index"))
+    return _bytes("mesh_decimate", int(V), int(F))
 
 
 def decimate(verts, faces, target_faces, normals=None, rounds=None):
@@ -194,60 +198,40 @@ def decimate(verts, faces, target_faces, normals=None, rounds=None):
     if target < 0 or target >= 2 ** 32:
         raise ValueError(f"decimate: target_faces must be in [0, 2^32), got {target_faces}")
     dev = v.device
-    nbytes = decimate_workspace_bytes(V, F)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "mesh_decimate", V, F)
     counts = torch.empty(4, dtype=torch.int32, device=dev)
-
-    def read():
-        r = [int(c) & 0xffffffff for c in counts.cpu()]                         # the one host read per call
-        for bit, what in _DECIMATE_FLAGS:
-            if r[3] & bit:
-                raise ValueError(f"decimate: {what}")
-        return r
-
-    check(lib.cnerf_mesh_decimate_init(ptr(v) if V else None, V, ptr(f) if F else None, F, ptr(ws), nbytes, ptr(counts), stream()),
-          "mesh_decimate_init")
-    nv, nf, _, _ = read()
+    check(lib.cnerf_mesh_decimate_init(_p(v), V, _p(f), F, ptr(ws), nbytes, ptr(counts), stream()), "mesh_decimate_init")
+    nv, nf, _, _ = _read(counts, "decimate", _DECIMATE_FLAGS)                   # one host read after init and after each round
     while nf > target:
         check(lib.cnerf_mesh_decimate_round(V, nf, target, ptr(ws), nbytes, ptr(counts), stream()), "mesh_decimate_round")
-        nv, nf, done, _ = read()
+        nv, nf, done, _ = _read(counts, "decimate", _DECIMATE_FLAGS)
         if rounds is not None:
             rounds.append((nv, nf, done))
         if done == 0:
             break
-    vo = torch.empty(nv, 3, dtype=torch.float32, device=dev)
-    no = torch.empty(nv, 3, dtype=torch.float32, device=dev) if n is not None else None
-    fo = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-    old = torch.empty(nv, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_decimate_emit(ptr(n) if V and n is not None else None, V, nf, ptr(ws), nbytes, ptr(vo) if nv else None,
-                                       ptr(no) if nv and no is not None else None, ptr(fo) if nf else None, ptr(old) if nv else None,
-                                       nv, nf, stream()), "mesh_decimate_emit")
+    vo, no, fo, old = _outputs(dev, nv, nf, n is not None)
+    check(lib.cnerf_mesh_decimate_emit(_p(n), V, nf, ptr(ws), nbytes, _p(vo), _p(no), _p(fo), _p(old), nv, nf, stream()), "mesh_decimate_emit")
     return vo, fo, no, old
 
 
 def smooth_workspace_bytes(V, F):
-    out = C.c_uint64(0)
-    check(lib.cnerf_mesh_smooth_workspace_bytes(int(V), int(F), C.byref(out)), "mesh_smooth_workspace_bytes")
-    return out.value
+    return _bytes("mesh_smooth", int(V), int(F))
 
 
 def _smooth_init(v, f, what):
     """workspace of cnerf_mesh_smooth_* with the neighbour and face lists built, and its size"""
     V, F = v.shape[0], f.shape[0]
-    nbytes = smooth_workspace_bytes(V, F)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=v.device)
+    ws, nbytes = _workspace(v.device, "mesh_smooth", V, F)
     flags = torch.empty(1, dtype=torch.int32, device=v.device)
-    check(lib.cnerf_mesh_smooth_init(ptr(f) if F else None, V, F, ptr(ws), nbytes, ptr(flags), stream()), "mesh_smooth_init")
-    if int(flags.cpu()[0]) & 1:                                                 # the one host read
-        raise ValueError(f"{what}: a face index lies outside [0, V)")
+    check(lib.cnerf_mesh_smooth_init(_p(f), V, F, ptr(ws), nbytes, ptr(flags), stream()), "mesh_smooth_init")
+    _read(flags, what, _BAD_INDEX)
     return ws, nbytes
 
 
 def _normals(v, f, n, ws, nbytes):
     V, F = v.shape[0], f.shape[0]
     no = torch.empty(V, 3, dtype=torch.float32, device=v.device)
-    check(lib.cnerf_mesh_smooth_normals(ptr(v) if V else None, ptr(n) if V and n is not None else None, V, ptr(f) if F else None, F,
-                                        ptr(ws), nbytes, ptr(no) if V else None, stream()), "mesh_smooth_normals")
+    check(lib.cnerf_mesh_smooth_normals(_p(v), _p(n), V, _p(f), F, ptr(ws), nbytes, _p(no), stream()), "mesh_smooth_normals")
     return no
 
 
@@ -270,8 +254,8 @@ def smooth(verts, faces, iterations=10, lamb=0.5, mu=-0.53, normals=None, pin_bo
     V, F = v.shape[0], f.shape[0]
     ws, nbytes = _smooth_init(v, f, "smooth")
     vo = torch.empty(V, 3, dtype=torch.float32, device=v.device)
-    check(lib.cnerf_mesh_smooth_steps(ptr(v) if V else None, V, F, it, lamb, mu, 1 if pin_boundary else 0, ptr(ws), nbytes,
-                                      ptr(vo) if V else None, stream()), "mesh_smooth_steps")
+    check(lib.cnerf_mesh_smooth_steps(_p(v), V, F, it, lamb, mu, 1 if pin_boundary else 0, ptr(ws), nbytes, _p(vo), stream()),
+          "mesh_smooth_steps")
     return vo, _normals(vo, f, n, ws, nbytes)
 
 
@@ -361,9 +345,8 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
     dev = v.device
     uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
     flags = torch.empty(1, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_atlas_uvs(ptr(f) if F else None, V, F, R, ptr(uvs) if F else None, F, ptr(flags), stream()), "mesh_atlas_uvs")
-    if int(flags.cpu()[0]) & 1:                                                 # the one host read
-        raise ValueError("bake_texture: a face index lies outside [0, V)")
+    check(lib.cnerf_mesh_atlas_uvs(_p(f), V, F, R, _p(uvs), F, ptr(flags), stream()), "mesh_atlas_uvs")
+    _read(flags, "bake_texture", _BAD_INDEX)
     tex = torch.empty(R, R, 3, dtype=torch.uint8, device=dev)
     check(lib.cnerf_mesh_atlas_fill(F, R, fill_c, ptr(tex), stream()), "mesh_atlas_fill")
     total = (F + 1) // 2 * s * s
@@ -373,7 +356,7 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
     for t0 in range(0, total, m):
         t1 = min(t0 + m, total)
         k = t1 - t0
-        check(lib.cnerf_mesh_atlas_points(ptr(v), ptr(n) if n is not None else None, V, ptr(f), F, R, t0, t1, ptr(flags), ptr(x), ptr(d), k,
+        check(lib.cnerf_mesh_atlas_points(ptr(v), _p(n), V, ptr(f), F, R, t0, t1, ptr(flags), ptr(x), ptr(d), k,
                                           stream()), "mesh_atlas_points")
         rgb = color_fn(x[:k], d[:k])
         if not torch.is_tensor(rgb) or rgb.dim() != 2 or rgb.shape[0] != k or rgb.shape[1] < 3 or not rgb.is_floating_point():

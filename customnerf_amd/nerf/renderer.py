@@ -505,8 +505,6 @@ class NeRFRenderer(nn.Module):
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
-        vol = self.density_volume(R, aabb, chunk, part, view_dir)
-        verts, faces, normals = _mesh.marching_cubes(vol, threshold, spacing=step.tolist(), origin=lo.tolist())
         k = int(simplify)
         if k == 1 or k < 0:
             raise ValueError(f"extract_mesh: simplify must be 0 (off) or a cluster size >= 2 lattice steps, got {simplify}")
@@ -521,6 +519,8 @@ class NeRFRenderer(nn.Module):
         n_smooth = int(smooth)
         if n_smooth < 0:
             raise ValueError(f"extract_mesh: smooth must be 0 (off) or a number of iterations, got {smooth}")
+        vol = self.density_volume(R, aabb, chunk, part, view_dir)
+        verts, faces, normals = _mesh.marching_cubes(vol, threshold, spacing=step.tolist(), origin=lo.tolist())
         if int(min_component_faces) > 0 or keep_largest:
             verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
                                                                      largest=bool(keep_largest))

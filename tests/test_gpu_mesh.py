@@ -1,6 +1,5 @@
 """GPU: marching cubes (csrc/mesh.hip) against its NumPy restatement (tests/mc_restatement.py) — same faces, bit-equal vertices — and mesh
 export end to end through NeRFNetwork (NeRFRenderer.extract_mesh / save_mesh)."""
-import math
 import os
 import sys
 
@@ -14,11 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import mc_restatement as R  # noqa: E402
-
-
-def lattice(shape, lo, hi):
-    axes = [np.linspace(lo, hi, n, dtype=np.float32) for n in shape]
-    return np.meshgrid(*axes, indexing="ij"), [float(a[1] - a[0]) for a in axes]
+from mesh_testlib import R_SPHERE, dtype_guard, gaussian_model, lattice  # noqa: E402,F401
 
 
 def volumes():
@@ -94,28 +89,6 @@ def test_emit_respects_capacity():
 
 
 # ------------------------------------------------------------------------------------------------ end to end through NeRFNetwork
-R_SPHERE = math.sqrt(-0.08 * math.log(math.log(10.0) / 5.0))                  # trunc_exp(5 exp(-|x|^2 / 0.08)) == 10
-
-
-@pytest.fixture
-def dtype_guard():
-    from customnerf_amd import tcnn
-    prev = tcnn._DEFAULT_DTYPE
-    yield tcnn
-    tcnn.set_default_dtype(prev)
-
-
-def gaussian_model(tcnn, fp16, **kw):
-    from customnerf_amd import scene as sc
-    from customnerf_amd.nerf.network_grid import NeRFNetwork
-    tcnn.set_default_dtype(torch.float16 if fp16 else torch.float32)
-    opt = sc.make_opt(num_levels=4, n_hidden_geo=1, **kw)
-    model = NeRFNetwork(opt).cuda().eval()
-    with torch.no_grad():
-        model.density_network.params.zero_()                                   # sigma = trunc_exp(gaussian(x)) exactly
-    return model
-
-
 @pytest.mark.parametrize("fp16", [False, True], ids=["fp32", "fp16"])
 def test_extract_mesh_gaussian_sphere(dtype_guard, fp16):
     model = gaussian_model(dtype_guard, fp16)

@@ -15,24 +15,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import mc_restatement as R  # noqa: E402
 import mesh_clean_restatement as MC  # noqa: E402
-
-
-def lattice(shape, lo, hi):
-    axes = [np.linspace(lo, hi, n, dtype=np.float32) for n in shape]
-    return np.meshgrid(*axes, indexing="ij"), [float(a[1] - a[0]) for a in axes]
-
-
-BLOBS = [(0.85, 0.0, 0.0, 0.08), (-0.8, 0.5, 0.3, 0.06), (0.1, -0.85, -0.6, 0.1), (-0.7, -0.75, 0.75, 0.07), (0.6, 0.7, -0.7, 0.05)]
-
-
-def speckled_sphere(n=56):
-    """(sphere-only volume, sphere + speckle volume, spacing, origin): the blobs sit >= 3 voxels away from the sphere's surface"""
-    (X, Y, Z), sp = lattice((n, n, n), -1.0, 1.0)
-    sphere = (0.55 - np.sqrt(X ** 2 + Y ** 2 + Z ** 2)).astype(np.float32)
-    vol = sphere.copy()
-    for cx, cy, cz, r in BLOBS:
-        vol = np.maximum(vol, (r - np.sqrt((X - cx) ** 2 + (Y - cy) ** 2 + (Z - cz) ** 2)).astype(np.float32))
-    return sphere, vol, sp, (-1.0, -1.0, -1.0)
+from mesh_testlib import AABB, R_SPHERE, cuda, dtype_guard, gaussian_model, host, lattice, speckled_sphere  # noqa: E402,F401
 
 
 def mc_meshes():
@@ -59,14 +42,6 @@ def hand_meshes():
 
 MESHES = [(name, v, f, n) for name, v, f, n in mc_meshes()] + list(hand_meshes())
 IDS = [m[0] for m in MESHES]
-
-
-def cuda(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
 
 
 @pytest.mark.parametrize("name,v,f,n", MESHES, ids=IDS)
@@ -149,28 +124,6 @@ def test_largest_of_speckled_sphere_is_the_sphere():
 
 
 # ------------------------------------------------------------------------------------------------ end to end through NeRFNetwork
-R_SPHERE = math.sqrt(-0.08 * math.log(math.log(10.0) / 5.0))                  # trunc_exp(5 exp(-|x|^2 / 0.08)) == 10
-AABB = [-0.5, -0.5, -0.5, 0.5, 0.5, 0.5]
-
-
-@pytest.fixture
-def dtype_guard():
-    from customnerf_amd import tcnn
-    prev = tcnn._DEFAULT_DTYPE
-    yield tcnn
-    tcnn.set_default_dtype(prev)
-
-
-def gaussian_model(tcnn, fp16):
-    from customnerf_amd import scene as sc
-    from customnerf_amd.nerf.network_grid import NeRFNetwork
-    tcnn.set_default_dtype(torch.float16 if fp16 else torch.float32)
-    model = NeRFNetwork(sc.make_opt(num_levels=4, n_hidden_geo=1)).cuda().eval()
-    with torch.no_grad():
-        model.density_network.params.zero_()                                   # sigma = trunc_exp(gaussian(x)) exactly
-    return model
-
-
 @pytest.mark.parametrize("fp16", [False, True], ids=["fp32", "fp16"])
 def test_extract_mesh_cleanup(dtype_guard, fp16):
     model = gaussian_model(dtype_guard, fp16)

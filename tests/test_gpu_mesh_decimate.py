@@ -16,41 +16,9 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import mc_restatement as R  # noqa: E402
 import qem_restatement as Q  # noqa: E402
-from test_gpu_mesh_clean import AABB, R_SPHERE, dtype_guard, gaussian_model, lattice  # noqa: E402,F401
-from test_mesh_decimate_host import grid  # noqa: E402
+from mesh_testlib import AABB, R_SPHERE, cuda, decimate_meshes, dtype_guard, gaussian_model, host, lattice  # noqa: E402,F401
 
-
-def cuda(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
-
-
-def mc_meshes():
-    rng = np.random.default_rng(23)
-    (X, Y, Z), sp = lattice((24, 24, 24), -1.0, 1.0)
-    r = np.sqrt(X ** 2 + Y ** 2 + Z ** 2)
-    vol = (0.7 - r + 0.04 * rng.standard_normal(r.shape)).astype(np.float32)                 # jittered sphere
-    yield ("jittered_sphere",) + R.marching_cubes(vol, 0.0, sp, (-1.0, -1.0, -1.0))
-    (X, Y, Z), sp = lattice((40, 30, 26), -1.0, 1.0)
-    t1 = 0.15 - np.sqrt((np.sqrt((X + 0.45) ** 2 + Y ** 2) - 0.35) ** 2 + Z ** 2)
-    t2 = 0.1 - np.sqrt((np.sqrt((X - 0.5) ** 2 + Z ** 2) - 0.3) ** 2 + Y ** 2)
-    yield ("two_tori",) + R.marching_cubes(np.maximum(t1, t2).astype(np.float32), 0.0, sp, (-1.0, -1.0, -1.0))
-    rng = np.random.default_rng(17)
-    yield ("noise",) + R.marching_cubes(rng.random((16, 16, 16), dtype=np.float32), 0.55, (0.5, 0.25, 1.0), (3.0, -2.0, 0.5))
-    (X, Y, Z), sp = lattice((26, 26, 20), -1.0, 1.0)
-    cut = (0.8 - np.sqrt(X ** 2 + Y ** 2 + (Z + 0.5) ** 2)).astype(np.float32)               # cut open by the volume's z = -1 face
-    yield ("cut_sphere",) + R.marching_cubes(cut, 0.0, sp, (-1.0, -1.0, -1.0))
-
-
-def hand_meshes():
-    v, f = grid(16)
-    yield "planar_grid", v, f, None
-
-
-MESHES = list(mc_meshes()) + list(hand_meshes())
+MESHES = decimate_meshes()
 IDS = [m[0] for m in MESHES]
 
 

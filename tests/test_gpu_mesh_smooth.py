@@ -15,18 +15,11 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import mc_restatement as R  # noqa: E402
 import smooth_restatement as S  # noqa: E402
-from test_gpu_mesh_clean import AABB, dtype_guard, gaussian_model, lattice  # noqa: E402,F401
-from test_gpu_mesh_decimate import MESHES as DECIMATE_MESHES  # noqa: E402
+from mesh_testlib import AABB, cuda, decimate_meshes, dtype_guard, gaussian_model, host, lattice  # noqa: E402,F401
+
+DECIMATE_MESHES = decimate_meshes()
 
 PARAMS = [(1, 0.5, -0.53, True), (10, 0.5, -0.53, True), (7, 0.33, 0.0, False), (4, 1.0, -1.0, True), (3, 0.6307, -0.6732, False)]
-
-
-def cuda(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def simplified_mesh():

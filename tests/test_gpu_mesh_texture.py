@@ -16,11 +16,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import atlas_restatement as A  # noqa: E402
 import mc_restatement as R  # noqa: E402
-from test_gpu_mesh_clean import AABB, dtype_guard, gaussian_model, lattice  # noqa: E402,F401
-
-
-def cuda(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+from mesh_testlib import AABB, cuda, dtype_guard, gaussian_model, lattice  # noqa: E402,F401
 
 
 def sphere_mesh(n=40, r=0.9):

@@ -43,6 +43,13 @@ def test_workspace_bytes():
         G, K = g[0] * g[1] * g[2], min(V, g[0] * g[1] * g[2])
         b = mesh.cluster_workspace_bytes(V, F, g)
         assert 4 * V + 5 * G + 12 * F + 132 * K <= b <= 4 * V + 5 * G + 20 * F + 132 * K + 8 * (max(G, F) // 256 + 1) + 10 * 256 + 64 * 4
+    M = (1 << 31) - 1                                                                      # pinned sizes, up to the largest V and F accepted
+    for V, F, b in ((0, 0, 512), (3, 1, 1280), (1000, 2000, 12800), (1 << 20, 1 << 21, 12648704), (M, M, 25836912896), (5, M, 67109888)):
+        assert mesh.components_workspace_bytes(V, F) == b
+    for V, F, g, b in ((0, 0, (1, 1, 1), 1280), (3, 1, (1, 1, 1), 2304), (100, 200, (4, 5, 6), 18176), (1000, 2000, (7, 1, 13), 42240),
+                       (1 << 20, 1 << 21, (128, 128, 128), 178323712), (824914, 1670112, (128, 128, 128), 146198016),
+                       (M, M, (1024, 1024, 2047), 328488452352), (3, 1, (1024, 1024, 2047), 10799253248)):
+        assert mesh.cluster_workspace_bytes(V, F, g) == b
     lib = mesh.lib
     out = C.c_uint64(0)
     assert lib.cnerf_mesh_components_workspace_bytes(1 << 31, 0, C.byref(out)) == EINVAL

@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import qem_restatement as Q  # noqa: E402
+from mesh_testlib import grid, octahedron_sphere  # noqa: E402
 
 ROOT = os.path.dirname(HERE)
 EINVAL, ENULL = -1, -2
@@ -40,6 +41,9 @@ def test_workspace_bytes_grows():
         prev = b
     assert mesh.decimate_workspace_bytes(1000, 3000) > mesh.decimate_workspace_bytes(1000, 2000)
     assert mesh.decimate_workspace_bytes(2000, 2000) > mesh.decimate_workspace_bytes(1000, 2000)
+    for V, F, b in ((0, 0, 1024), (3, 1, 4608), (1000, 2000, 274944), (1 << 20, 1 << 21, 286327552),
+                    ((1 << 31) - 1, 0x55555555, 377308403456), (3, 0x55555555, 104555613184)):       # pinned, up to the largest accepted
+        assert mesh.decimate_workspace_bytes(V, F) == b
     lib = mesh.lib
     out = C.c_uint64(0)
     wsb = lib.cnerf_mesh_decimate_workspace_bytes
@@ -87,43 +91,10 @@ def test_argument_checks_reject_before_launch():
 
 
 # ------------------------------------------------------------------------------------------------ restatement on hand meshes
-def grid(n):
-    """planar integer grid of n x n quads in z = 0, wound counter-clockwise (normals +z)"""
-    i, j = np.meshgrid(np.arange(n + 1), np.arange(n + 1), indexing="ij")
-    v = np.stack([i.ravel(), j.ravel(), np.zeros(i.size)], 1).astype(np.float32)
-    idx = lambda a, b: a * (n + 1) + b                                             # noqa: E731
-    f = []
-    for a in range(n):
-        for b in range(n):
-            f += [[idx(a, b), idx(a + 1, b), idx(a + 1, b + 1)], [idx(a, b), idx(a + 1, b + 1), idx(a, b + 1)]]
-    return v, np.array(f, np.int32)
-
-
 def tetrahedron():
     v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32)
     f = np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]], np.int32)
     return v, f
-
-
-def octahedron_sphere(level=2):
-    """subdivided octahedron projected to the unit sphere: closed, genus 0"""
-    v = [np.array(p, float) for p in ([1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1])]
-    f = [[0, 2, 4], [2, 1, 4], [1, 3, 4], [3, 0, 4], [2, 0, 5], [1, 2, 5], [3, 1, 5], [0, 3, 5]]
-    for _ in range(level):
-        mid, nf = {}, []
-
-        def m(a, b):
-            k = (min(a, b), max(a, b))
-            if k not in mid:
-                p = v[a] + v[b]
-                v.append(p / np.linalg.norm(p))
-                mid[k] = len(v) - 1
-            return mid[k]
-        for a, b, c in f:
-            ab, bc, ca = m(a, b), m(b, c), m(c, a)
-            nf += [[a, ab, ca], [ab, b, bc], [ca, bc, c], [ab, bc, ca]]
-        f = nf
-    return np.array(v, np.float32), np.array(f, np.int32)
 
 
 def test_planar_grid_zero_costs():

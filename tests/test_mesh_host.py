@@ -170,6 +170,10 @@ def test_workspace_bytes():
         assert mesh.workspace_bytes((n, n, n)) <= 6.1 * n ** 3 + 5 * 256          # (sections are 256-byte aligned)
     assert mesh.workspace_bytes((512, 512, 512)) / 512 ** 3 <= 6.1
     assert mesh.workspace_bytes((33, 17, 9)) >= 6 * 33 * 17 * 9
+    # pinned: callers size their buffers by these (the last shape is the largest accepted)
+    for shape, b in (((2, 2, 2), 1280), ((33, 17, 9), 30976), ((33, 33, 33), 217600), ((512, 512, 512), 809500928),
+                     ((2047, 1024, 1024), 12945686784)):
+        assert mesh.workspace_bytes(shape) == b
 
 
 def test_argument_checks_reject_before_launch():

@@ -13,8 +13,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import mc_restatement as R  # noqa: E402
 import smooth_restatement as S  # noqa: E402
-from test_gpu_mesh_clean import lattice  # noqa: E402
-from test_mesh_decimate_host import grid, octahedron_sphere  # noqa: E402
+from mesh_testlib import grid, lattice, octahedron_sphere  # noqa: E402
 
 ROOT = os.path.dirname(HERE)
 EINVAL, ENULL = -1, -2
@@ -43,6 +42,9 @@ def test_workspace_bytes_grows():
         prev = b
     assert mesh.smooth_workspace_bytes(1000, 3000) > mesh.smooth_workspace_bytes(1000, 2000)
     assert mesh.smooth_workspace_bytes(2000, 2000) > mesh.smooth_workspace_bytes(1000, 2000)
+    for V, F, b in ((0, 0, 512), (3, 1, 2816), (1000, 2000, 121344), (1 << 20, 1 << 21, 125862144),
+                    ((1 << 31) - 1, 0x2AAAAAAA, 128916128000), (3, 0x2AAAAAAA, 25769806080)):         # pinned, up to the largest accepted
+        assert mesh.smooth_workspace_bytes(V, F) == b
     lib = mesh.lib
     out = C.c_uint64(0)
     wsb = lib.cnerf_mesh_smooth_workspace_bytes
