@@ -4,36 +4,6 @@
 #include "field_common.h"
 
 // ------------------------------------------------------------------------------------------------ weight staging
-// Copy one layer's [rows, in_stride] float32 matrix into LDS in A-fragment order:
-//   dst[((t * S + s) * 64 + lane) * J + j] = W[32 t + (lane & 31)][col(s, lane >> 5, j)]      (0 where out of range)
-// KIND 0: natural column order (grid features).  KIND 1: C-register order (hidden activations).
-// KIND 2: rgb layer 0 = [C-ordered fea at column 27.., then natural dir features at column 0..26].
-template <bool H, int KIND>
-__device__ __forceinline__ void fld_stage_layer(typename Prec<H>::elem_t *dst, const float *__restrict__ W, uint32_t rows, uint32_t in_stride,
-                                                uint32_t T, uint32_t S, uint32_t n_valid_cols, uint32_t i0 = threadIdx.x, uint32_t istride = FLD_THREADS) {
-    using P = Prec<H>;
-    const uint32_t total = T * S * 64 * P::J;
-    for (uint32_t i = i0; i < total; i += istride) {
-        const uint32_t j = i % P::J, lane = (i / P::J) % 64, ts = i / (P::J * 64);
-        const uint32_t s = ts % S, t = ts / S;
-        const uint32_t row = 32 * t + (lane & 31), hi = lane >> 5;
-        int col;
-        if (KIND == 0) col = fld_col_natural<H>(s, hi, j);
-        else if (KIND == 1) col = fld_col_clayout<H>(s, hi, j);
-        else {
-            const uint32_t s_fea = FLD_HID / P::KS;
-            if (s < s_fea) col = FLD_NDIR + fld_col_clayout<H>(s, hi, j);
-            else {
-                col = fld_col_natural<H>(s - s_fea, hi, j);
-                if (col >= FLD_NDIR) col = -1;
-            }
-        }
-        float v = 0.0f;
-        if (row < rows && col >= 0 && (uint32_t)col < n_valid_cols) v = W[(size_t)row * in_stride + col];
-        dst[i] = (typename P::elem_t)v;
-    }
-}
-
 template <bool H>
 __device__ __forceinline__ void fld_stage_all(typename Prec<H>::elem_t *lds, const FieldDims &dm, const FieldLds &lo, const float *__restrict__ pnet,
                                               const float *__restrict__ pden, const float *__restrict__ prgb, bool with_rgb,
@@ -72,24 +42,9 @@ __device__ __forceinline__ void fld_copy_image(_Float16 *lds, const void *__rest
 }
 
 // ------------------------------------------------------------------------------------------------ per-wave building blocks
-template <bool H>
-__device__ __forceinline__ typename Prec<H>::frag_t fld_load_frag(const typename Prec<H>::elem_t *base, uint32_t t, uint32_t S, uint32_t s, uint32_t lane) {
-    using P = Prec<H>;
-    return *reinterpret_cast<const typename P::frag_t *>(base + ((size_t)(t * S + s) * 64 + lane) * P::J);
-}
-
-// acc[t] = sum_s A(t, s) * b[s]    for t < T, s in [s0, s0 + NS) of a layer whose fragment store has S K-steps per tile
-template <bool H, int T, int NS>
-__device__ __forceinline__ void fld_gemm(const typename Prec<H>::elem_t *wf, uint32_t S, uint32_t s0, const typename Prec<H>::frag_t *b, uint32_t lane,
-                                         cn_f16v (&acc)[T]) {
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-#pragma unroll
-        for (int t = 0; t < T; t++) acc[t] = Prec<H>::mfma(fld_load_frag<H>(wf, t, S, s0 + s, lane), b[s], acc[t]);
-    }
-}
-
-// C registers of two 32-row tiles -> the B fragments of the next layer (optionally through ReLU); fp16 mode rounds to half here
+// C registers of two 32-row tiles -> the B fragments of the next layer (optionally through ReLU); fp16 mode rounds to half here.
+// The forward's form (k_field_fwd): convert, then a packed max.  fb_c_to_b (field_bwd_common.h) and x4_c_to_b (field_bwd_x2.hip) give the
+// same values with other instructions; each kernel keeps the one it was measured with.
 template <bool H, bool RELU>
 __device__ __forceinline__ void fld_c_to_b(const cn_f16v (&acc)[2], typename Prec<H>::frag_t *b) {
     using P = Prec<H>;
@@ -118,62 +73,15 @@ __device__ __forceinline__ void fld_c_to_b(const cn_f16v (&acc)[2], typename Pre
     }
 }
 
-template <int T>
-__device__ __forceinline__ void fld_zero(cn_f16v (&acc)[T]) {
-#pragma unroll
-    for (int t = 0; t < T; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[t][r] = 0.0f;
-}
-
-// grid features of one sample as B fragments (natural order): lane (p, hi) reads levels per K-step from enc [L, P, 2]
-template <bool H, int SENC>
-__device__ __forceinline__ void fld_load_enc(const void *__restrict__ enc, uint32_t P_, uint32_t L, uint32_t p, bool valid, uint32_t hi,
-                                             typename Prec<H>::frag_t (&b)[SENC]) {
-    if constexpr (H) {
-        const uint32_t *e = reinterpret_cast<const uint32_t *>(enc);      // one half2 per (level, sample)
-#pragma unroll
-        for (int s = 0; s < SENC; s++) {
-            union { cn_h8 h; uint32_t u[4]; } f;
-#pragma unroll
-            for (int jj = 0; jj < 4; jj++) {
-                const uint32_t level = 8 * s + 4 * hi + jj;
-                f.u[jj] = (valid && level < L) ? e[(size_t)level * P_ + p] : 0u;
-            }
-            b[s] = f.h;
-        }
-    } else {
-        const float *e = reinterpret_cast<const float *>(enc);
-#pragma unroll
-        for (int s = 0; s < SENC; s++) {
-            const uint32_t feat = 2 * s + hi, level = feat >> 1;          // K-step s holds features (2s, 2s+1) = (level s, c = hi)
-            b[s] = (valid && level < L) ? e[((size_t)level * P_ + p) * 2 + (feat & 1)] : 0.0f;
-        }
-    }
-}
-
 template <bool H>
 __device__ __forceinline__ void fld_dir_frags(const float *__restrict__ dirs, uint32_t dir_group, uint32_t p, bool valid, uint32_t hi,
                                               typename Prec<H>::frag_t *b) {
-    float e[FLD_DIR];
     float dx = 0, dy = 0, dz = 0;
     if (valid) {
         const float *d = dirs + (size_t)(p / dir_group) * 3;
         dx = d[0]; dy = d[1]; dz = d[2];
     }
-    fld_dir_features<H>(dx, dy, dz, e);
-    if constexpr (H) {
-#pragma unroll
-        for (int s = 0; s < FLD_DIR / 16; s++) {
-            cn_h8 f;
-#pragma unroll
-            for (int j = 0; j < 8; j++) f[j] = (_Float16)(hi ? e[16 * s + 8 + j] : e[16 * s + j]);
-            b[s] = f;
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < FLD_DIR / 2; s++) b[s] = hi ? e[2 * s + 1] : e[2 * s];
-    }
+    fld_dir_frags_from<H>(dx, dy, dz, true, hi, b);
 }
 
 __device__ __forceinline__ float fld_round_half(float v) { return (float)(_Float16)v; }
@@ -291,56 +199,24 @@ __global__ void __launch_bounds__(FLD_THREADS, H ? 2 : 1) k_field_fwd(const void
 template <bool H>
 static int fld_launch_fwd(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, const FieldDims &dm,
                           const float *pnet, const float *pden, const float *prgb, float *sigma, float *rgbc, hipStream_t st, uint32_t enc_stride,
-                          const void *wimg = nullptr) {
+                          const void *wimg) {
     const FieldLds lo = fld_lds_layout<H>(dm);
     const uint32_t lds_bytes = lo.off[7] * sizeof(typename Prec<H>::elem_t) + FLD_WAVES * 64;       // weight fragments + per-wave direction scratch
     const uint32_t n_tiles = cn_div_up(P_, FLD_TILE);
     uint32_t blocks = cn_div_up(n_tiles, FLD_WAVES);
     const uint32_t max_blocks = H ? 768 : 256;            // persistent: LDS allows 3 (fp16) / 1 (fp32) workgroups per CU
     if (blocks > max_blocks) blocks = max_blocks;
-    const uint32_t senc = dm.enc_pad / Prec<H>::KS;
 #ifdef CNERF_TUNING
     static const int nostage = cn_tune_env("CNERF_FLD_NOSTAGE", 0);
     if (nostage) dir_group |= 0x80000000u;
 #endif
-#define FLD_FWD_CASE(SE, NG)                                                                                                           \
-    {                                                                                                                                  \
-        auto kern = k_field_fwd<H, SE, NG>;                                                                                            \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);        \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(FLD_THREADS), lds_bytes, st, enc, xyz, dirs, dir_group, P_, dm, pnet, pden, prgb, sigma, rgbc, enc_stride, wimg); \
-    }
-    const uint32_t se16 = dm.enc_pad / 16;               // 1..4
-    if (dm.n_hidden_geo == 1) {
-        switch (se16) {
-            case 1: FLD_FWD_CASE(16 / Prec<H>::KS, 1) break;
-            case 2: FLD_FWD_CASE(32 / Prec<H>::KS, 1) break;
-            case 3: FLD_FWD_CASE(48 / Prec<H>::KS, 1) break;
-            case 4: FLD_FWD_CASE(64 / Prec<H>::KS, 1) break;
-            default: return CNERF_EINVAL;
-        }
-    } else {
-        switch (se16) {
-            case 1: FLD_FWD_CASE(16 / Prec<H>::KS, 2) break;
-            case 2: FLD_FWD_CASE(32 / Prec<H>::KS, 2) break;
-            case 3: FLD_FWD_CASE(48 / Prec<H>::KS, 2) break;
-            case 4: FLD_FWD_CASE(64 / Prec<H>::KS, 2) break;
-            default: return CNERF_EINVAL;
-        }
-    }
-    (void)senc;
+    const bool ok = fld_dispatch(dm, [&](auto se16, auto ng) {
+        auto kern = k_field_fwd<H, se16 * 16 / Prec<H>::KS, ng>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(FLD_THREADS), lds_bytes, st, enc, xyz, dirs, dir_group, P_, dm, pnet, pden, prgb, sigma, rgbc, enc_stride, wimg);
+    });
+    if (!ok) return CNERF_EINVAL;
     return cn_launch_status();
-}
-
-static int fld_dims(uint32_t enc_dim, uint32_t n_hidden_geo, uint32_t n_rgb_out, FieldDims &dm) {
-    if (enc_dim == 0 || enc_dim > 64 || (enc_dim & 1)) return CNERF_EINVAL;
-    if (n_hidden_geo < 1 || n_hidden_geo > 2) return CNERF_EINVAL;
-    if (n_rgb_out != 3 && n_rgb_out != 4) return CNERF_EINVAL;
-    dm.enc_dim = enc_dim;
-    dm.enc_pad = (enc_dim + 15) / 16 * 16;
-    dm.n_hidden_geo = n_hidden_geo;
-    dm.n_rgb_out = n_rgb_out;
-    dm.L = enc_dim / 2;
-    return CNERF_OK;
 }
 
 extern "C" {
@@ -374,9 +250,8 @@ int cnerf_field_forward_img(const void *enc, const float *xyz, const float *dirs
     FieldDims dm;
     int rc = fld_dims(enc_dim, n_hidden_geo, n_rgb_out, dm);
     if (rc) return rc;
-    if (!weight_image || dtype != CNERF_F16)
-        return cnerf_field_forward_strided(enc, xyz, dirs, dir_group, P_, enc_dim, n_hidden_geo, n_rgb_out, params_net, params_den, params_rgb, sigma, rgbc,
-                                           dtype, enc_level_stride, stream);
+    if (dtype != CNERF_F32 && dtype != CNERF_F16) return CNERF_EINVAL;
+    if (dtype != CNERF_F16) weight_image = nullptr;             // the image is fp16: float32 mode stages from the parameters and ignores it
     if (((uintptr_t)weight_image) & 15) return CNERF_EINVAL;
     if (enc_level_stride == 0) enc_level_stride = P_;
     if (enc_level_stride < P_) return CNERF_EINVAL;
@@ -384,26 +259,18 @@ int cnerf_field_forward_img(const void *enc, const float *xyz, const float *dirs
     if (!enc || !xyz || !params_net || !params_den || !sigma) return CNERF_ENULL;
     if (rgbc && (!dirs || !params_rgb || dir_group == 0)) return CNERF_ENULL;
     if (rgbc && (((uintptr_t)rgbc) & 15)) return CNERF_EINVAL;
-    return fld_launch_fwd<true>(enc, xyz, dirs, dir_group, P_, dm, params_net, params_den, params_rgb, sigma, rgbc, CN_STREAM(stream), enc_level_stride,
-                                weight_image);
+    if (dtype == CNERF_F16)
+        return fld_launch_fwd<true>(enc, xyz, dirs, dir_group, P_, dm, params_net, params_den, params_rgb, sigma, rgbc, CN_STREAM(stream), enc_level_stride,
+                                    weight_image);
+    return fld_launch_fwd<false>(enc, xyz, dirs, dir_group, P_, dm, params_net, params_den, params_rgb, sigma, rgbc, CN_STREAM(stream), enc_level_stride,
+                                 nullptr);
 }
 
 int cnerf_field_forward_strided(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, uint32_t enc_dim,
                                 uint32_t n_hidden_geo, uint32_t n_rgb_out, const float *params_net, const float *params_den, const float *params_rgb,
                                 float *sigma, float *rgbc, int dtype, uint32_t enc_level_stride, void *stream) {
-    FieldDims dm;
-    int rc = fld_dims(enc_dim, n_hidden_geo, n_rgb_out, dm);
-    if (rc) return rc;
-    if (dtype != CNERF_F32 && dtype != CNERF_F16) return CNERF_EINVAL;
-    if (enc_level_stride == 0) enc_level_stride = P_;
-    if (enc_level_stride < P_) return CNERF_EINVAL;
-    if (P_ == 0) return CNERF_OK;
-    if (!enc || !xyz || !params_net || !params_den || !sigma) return CNERF_ENULL;
-    if (rgbc && (!dirs || !params_rgb || dir_group == 0)) return CNERF_ENULL;
-    if (rgbc && (((uintptr_t)rgbc) & 15)) return CNERF_EINVAL;
-    if (dtype == CNERF_F16)
-        return fld_launch_fwd<true>(enc, xyz, dirs, dir_group, P_, dm, params_net, params_den, params_rgb, sigma, rgbc, CN_STREAM(stream), enc_level_stride);
-    return fld_launch_fwd<false>(enc, xyz, dirs, dir_group, P_, dm, params_net, params_den, params_rgb, sigma, rgbc, CN_STREAM(stream), enc_level_stride);
+    return cnerf_field_forward_img(enc, xyz, dirs, dir_group, P_, enc_dim, n_hidden_geo, n_rgb_out, params_net, params_den, params_rgb, sigma, rgbc, dtype,
+                                   enc_level_stride, nullptr, stream);
 }
 
 int cnerf_field_forward(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, uint32_t enc_dim,

@@ -55,13 +55,13 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_data(const void *__re
     const float *r0 = prgb, *rO = prgb + FLD_HID * in_r0;
 
     // ---- stage weights
-    fb_stage_layer<H, 0>(wl + lo.off[0], n0, FLD_HID, dm.enc_pad, 2, SENC, dm.enc_pad);
-    if (NGEO == 2) fb_stage_layer<H, 1>(wl + lo.off[1], n1, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1>(wl + lo.off[2], n2, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1>(wl + lo.off[3], d0, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1>(wl + lo.off[4], dO, 16, FLD_HID, 1, S64, FLD_HID);
-    fb_stage_layer<H, 2>(wl + lo.off[5], r0, FLD_HID, in_r0, 2, SR0, in_r0);
-    fb_stage_layer<H, 1>(wl + lo.off[6], rO, 16, FLD_HID, 1, S64, FLD_HID);
+    fld_stage_layer<H, 0>(wl + lo.off[0], n0, FLD_HID, dm.enc_pad, 2, SENC, dm.enc_pad, threadIdx.x, blockDim.x);
+    if (NGEO == 2) fld_stage_layer<H, 1>(wl + lo.off[1], n1, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.off[2], n2, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.off[3], d0, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.off[4], dO, 16, FLD_HID, 1, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 2>(wl + lo.off[5], r0, FLD_HID, in_r0, 2, SR0, in_r0, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.off[6], rO, 16, FLD_HID, 1, S64, FLD_HID, threadIdx.x, blockDim.x);
     if constexpr (H) {
         fb_stage_layer_T<H>(wt + lt.off[0], n0, FLD_HID, dm.enc_pad, 0, dm.enc_pad, TENC, S64);
         if (NGEO == 2) fb_stage_layer_T<H>(wt + lt.off[1], n1, FLD_HID, FLD_HID, 0, FLD_HID, 2, S64);
@@ -84,43 +84,43 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_data(const void *__re
 
         // ================= forward recompute
         frag_t x0[SENC];
-        fb_load_enc<H, SENC>(enc, P_, dm.L, p, valid, hi, x0);
+        fld_load_enc<H, SENC>(enc, P_, dm.L, p, valid, hi, x0);
         cn_f16v acc[2];
         frag_t h1[2 * PR::FR], h2[2 * PR::FR], fea[2 * PR::FR], hd[2 * PR::FR], hr[2 * PR::FR];
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, SENC>(wl + lo.off[0], SENC, 0, x0, lane, acc);
         fb_dump_natural<H, SENC>(ws + (size_t)wo.enc * ld, ld, p, hi, x0, dm.enc_pad);     // spills happen as soon as a value is final
         fb_c_to_b<H, true>(acc, h1);
         fb_dump_clayout<H>(ws + (size_t)wo.h1 * ld, ld, p, hi, h1);
         if (NGEO == 2) {
-            fb_zero(acc);
+            fld_zero(acc);
             fb_gemm<H, 2, S64>(wl + lo.off[1], S64, 0, h1, lane, acc);
             fb_c_to_b<H, true>(acc, h2);
             fb_dump_clayout<H>(ws + (size_t)wo.h2 * ld, ld, p, hi, h2);
         }
         const frag_t *hlast = (NGEO == 2) ? h2 : h1;
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, S64>(wl + lo.off[2], S64, 0, hlast, lane, acc);
         fb_c_to_b<H, false>(acc, fea);
         fb_dump_clayout<H>(ws + (size_t)wo.fea * ld, ld, p, hi, fea);
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, S64>(wl + lo.off[3], S64, 0, fea, lane, acc);
         fb_c_to_b<H, true>(acc, hd);
         fb_dump_clayout<H>(ws + (size_t)wo.hd * ld, ld, p, hi, hd);
         cn_f16v out[1];
-        fb_zero(out);
+        fld_zero(out);
         fb_gemm<H, 1, S64>(wl + lo.off[4], S64, 0, hd, lane, out);
         float raw = out[0][0];
         if (H) raw = (float)(_Float16)raw;
         frag_t dfr[SDIR];
         fb_dir_frags<H>(dirs, dir_group, p, valid, hi, dfr);
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, S64>(wl + lo.off[5], SR0, 0, fea, lane, acc);
         fb_gemm<H, 2, SDIR>(wl + lo.off[5], SR0, S64, dfr, lane, acc);
         fb_dump_natural<H, SDIR>(ws + (size_t)wo.dir * ld, ld, p, hi, dfr, FLD_NDIR);
         fb_c_to_b<H, true>(acc, hr);
         fb_dump_clayout<H>(ws + (size_t)wo.hr * ld, ld, p, hi, hr);
-        fb_zero(out);
+        fld_zero(out);
         fb_gemm<H, 1, S64>(wl + lo.off[6], S64, 0, hr, lane, out);
 
         // ================= output-layer gradients (rows 0..3 live in registers 0..3 of the hi == 0 lanes)
@@ -156,15 +156,15 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_data(const void *__re
 
         // ================= colour head: dz_r = (W_ro^T dz_ro) * [hr > 0] ; dfea  = W_r0[:, fea]^T dz_r
         frag_t zr[2 * PR::FR], zd[2 * PR::FR], z3[2 * PR::FR], z2[2 * PR::FR], z1[2 * PR::FR];
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm_T<H, 2, (H ? 1 : 4)>(wt + lt.off[6], rO, 16, FLD_HID, 0, FLD_HID, S32, bro, lane, acc);
         fb_c_to_b_masked<H>(acc, hr, zr);
         fb_dump_clayout<H>(ws + (size_t)wo.zr * ld, ld, p, hi, zr);
         cn_f16v dfea[2];
-        fb_zero(dfea);
+        fld_zero(dfea);
         fb_gemm_T<H, 2, S64>(wt + lt.off[5], r0, FLD_HID, in_r0, FLD_NDIR, FLD_HID, S64, zr, lane, dfea);
         // ================= density head
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm_T<H, 2, (H ? 1 : 4)>(wt + lt.off[4], dO, 16, FLD_HID, 0, FLD_HID, S32, bdo, lane, acc);
         fb_c_to_b_masked<H>(acc, hd, zd);
         fb_dump_clayout<H>(ws + (size_t)wo.zd * ld, ld, p, hi, zd);
@@ -172,18 +172,18 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_data(const void *__re
         fb_c_to_b<H, false>(dfea, z3);                      // network output has no activation
         fb_dump_clayout<H>(ws + (size_t)wo.z3 * ld, ld, p, hi, z3);
         // ================= geometry network
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm_T<H, 2, S64>(wt + lt.off[2], n2, FLD_HID, FLD_HID, 0, FLD_HID, S64, z3, lane, acc);
         if (NGEO == 2) {
             fb_c_to_b_masked<H>(acc, h2, z2);
             fb_dump_clayout<H>(ws + (size_t)wo.z2 * ld, ld, p, hi, z2);
-            fb_zero(acc);
+            fld_zero(acc);
             fb_gemm_T<H, 2, S64>(wt + lt.off[1], n1, FLD_HID, FLD_HID, 0, FLD_HID, S64, z2, lane, acc);
         }
         fb_c_to_b_masked<H>(acc, h1, z1);
         fb_dump_clayout<H>(ws + (size_t)wo.z1 * ld, ld, p, hi, z1);
         cn_f16v denc[TENC];
-        fb_zero(denc);
+        fld_zero(denc);
         fb_gemm_T<H, TENC, S64>(wt + lt.off[0], n0, FLD_HID, dm.enc_pad, 0, dm.enc_pad, S64, z1, lane, denc);
 
         // ================= d(loss)/d(grid features) in the encoder's [L, P, 2] layout
@@ -216,18 +216,6 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_data(const void *__re
     }
 }
 
-static int fb_dims(uint32_t enc_dim, uint32_t n_hidden_geo, uint32_t n_rgb_out, FieldDims &dm) {
-    if (enc_dim == 0 || enc_dim > 64 || (enc_dim & 1)) return CNERF_EINVAL;
-    if (n_hidden_geo < 1 || n_hidden_geo > 2) return CNERF_EINVAL;
-    if (n_rgb_out != 3 && n_rgb_out != 4) return CNERF_EINVAL;
-    dm.enc_dim = enc_dim;
-    dm.enc_pad = (enc_dim + 15) / 16 * 16;
-    dm.n_hidden_geo = n_hidden_geo;
-    dm.n_rgb_out = n_rgb_out;
-    dm.L = enc_dim / 2;
-    return CNERF_OK;
-}
-
 // the weight-gradient GEMM's partial rows (one per K split, ff_offsets layout) follow the [row][sample] matrices
 static inline size_t fb_part_off(const FieldDims &dm, uint32_t P_, int dtype) {
     return ((size_t)fb_ws_layout(dm).rows * fb_ld(P_) * (dtype == CNERF_F16 ? 2 : 4) + 255) / 256 * 256;
@@ -236,8 +224,6 @@ static inline size_t fb_workspace_bytes(const FieldDims &dm, uint32_t P_, int dt
     uint32_t kps;
     return fb_part_off(dm, P_, dtype) + (size_t)fb_dw_splits(cn_div_up(P_, FLD_TILE), kps) * ff_offsets(dm).total * sizeof(float) + 256;
 }
-void ff_reduce_partials(const float *partials, uint32_t n_partials, uint32_t total, uint32_t n_net, uint32_t n_den, float *g_net, float *g_den, float *g_rgb,
-                        hipStream_t st);
 
 template <bool H>
 static int fb_launch(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, const FieldDims &dm, const float *pnet,
@@ -251,31 +237,13 @@ static int fb_launch(const void *enc, const float *xyz, const float *dirs, uint3
     const uint32_t n_tiles = cn_div_up(P_, FLD_TILE);
     uint32_t blocks = cn_div_up(n_tiles, FLD_WAVES);
     if (blocks > 256) blocks = 256;                       // one persistent workgroup per CU (LDS: 93 KiB fp16 / 96 KiB fp32)
-#define FLD_BWD_CASE(SE16, NG, TE)                                                                                                                \
-    {                                                                                                                                            \
-        auto kern = k_field_bwd_data<H, (SE16) * 16 / PR::KS, NG, TE>;                                                                            \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);                  \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(FLD_THREADS), lds_bytes, st, enc, xyz, dirs, dir_group, P_, dm, pnet, pden, prgb, g_sigma,   \
-                           g_rgbc, grad_enc, workspace, ld);                                                                                     \
-    }
-    const uint32_t se16 = dm.enc_pad / 16;
-    if (dm.n_hidden_geo == 1) {
-        switch (se16) {
-            case 1: FLD_BWD_CASE(1, 1, 1) break;
-            case 2: FLD_BWD_CASE(2, 1, 1) break;
-            case 3: FLD_BWD_CASE(3, 1, 2) break;
-            case 4: FLD_BWD_CASE(4, 1, 2) break;
-            default: return CNERF_EINVAL;
-        }
-    } else {
-        switch (se16) {
-            case 1: FLD_BWD_CASE(1, 2, 1) break;
-            case 2: FLD_BWD_CASE(2, 2, 1) break;
-            case 3: FLD_BWD_CASE(3, 2, 2) break;
-            case 4: FLD_BWD_CASE(4, 2, 2) break;
-            default: return CNERF_EINVAL;
-        }
-    }
+    const bool ok = fld_dispatch(dm, [&](auto se16, auto ng) {
+        auto kern = k_field_bwd_data<H, se16 * 16 / PR::KS, ng, (se16 + 1) / 2>;             // TENC: 32-row tiles of the encoding
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(FLD_THREADS), lds_bytes, st, enc, xyz, dirs, dir_group, P_, dm, pnet, pden, prgb, g_sigma, g_rgbc, grad_enc,
+                           workspace, ld);
+    });
+    if (!ok) return CNERF_EINVAL;
     int rc = cn_launch_status();
     if (rc) return rc;
 
@@ -305,11 +273,7 @@ static int fb_launch(const void *enc, const float *xyz, const float *dirs, uint3
     return cn_launch_status();
 }
 
-// single-launch fp16 form (field_bwd_fused.hip)
-uint64_t ff_workspace_bytes(const FieldDims &dm);
-int ff_launch(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, const FieldDims &dm, const float *pnet,
-              const float *pden, const float *prgb, const float *g_sigma, const float *g_rgbc, void *grad_enc, float *g_net, float *g_den,
-              float *g_rgb, void *workspace, const uint8_t *tile_live, hipStream_t st, const void *wimg);
+// single-launch fp16 form (ff_launch, field_bwd_fused.hip)
 static bool fb_use_fused(const FieldDims &dm, int dtype) {
     static const int env = cn_tune_env("CNERF_FIELD_FUSED_BWD", 1);
     return env && dtype == CNERF_F16 && dm.enc_pad <= 32;           // 92 KiB weight fragments + 64 KiB staging must fit the 160 KiB LDS
@@ -320,7 +284,7 @@ extern "C" {
 int cnerf_field_backward_workspace_bytes(uint32_t P_, uint32_t enc_dim, uint32_t n_hidden_geo, uint32_t n_rgb_out, int dtype, uint64_t *bytes) {
     if (!bytes) return CNERF_ENULL;
     FieldDims dm;
-    int rc = fb_dims(enc_dim, n_hidden_geo, n_rgb_out, dm);
+    int rc = fld_dims(enc_dim, n_hidden_geo, n_rgb_out, dm);
     if (rc) return rc;
     if (dtype != CNERF_F32 && dtype != CNERF_F16) return CNERF_EINVAL;
     if (fb_use_fused(dm, dtype)) *bytes = ff_workspace_bytes(dm);
@@ -350,7 +314,7 @@ int cnerf_field_backward_img(const void *enc, const float *xyz, const float *dir
                              float *grad_params_rgb, void *workspace, uint64_t workspace_bytes, int dtype, const uint8_t *tile_live,
                              const void *weight_image, void *stream) {
     FieldDims dm;
-    int rc = fb_dims(enc_dim, n_hidden_geo, n_rgb_out, dm);
+    int rc = fld_dims(enc_dim, n_hidden_geo, n_rgb_out, dm);
     if (rc) return rc;
     if (dtype != CNERF_F32 && dtype != CNERF_F16) return CNERF_EINVAL;
     if (P_ == 0) return CNERF_OK;

@@ -11,58 +11,15 @@
 #pragma once
 #include "field_common.h"
 
-// ---- re-declared helpers shared with field.hip (kept header-free on purpose: both TUs instantiate their own copies)
-template <bool H>
-__device__ __forceinline__ typename Prec<H>::frag_t fb_load_frag(const typename Prec<H>::elem_t *base, uint32_t t, uint32_t S, uint32_t s, uint32_t lane) {
-    using P = Prec<H>;
-    return *reinterpret_cast<const typename P::frag_t *>(base + ((size_t)(t * S + s) * 64 + lane) * P::J);
-}
+// Weight staging, fragment loads, the layer product, zeroing and the grid-feature load are the forward's (fld_*, field_common.h).
 
-template <int T>
-__device__ __forceinline__ void fb_zero(cn_f16v (&acc)[T]) {
-#pragma unroll
-    for (int t = 0; t < T; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[t][r] = 0.0f;
-}
-
+// The forward-order layer product of the backward kernels that run near the register limit (k_field_bwd_data, k_field_bwd_fused, k_mlp_*):
+// fld_gemm behind a scheduling fence that keeps this layer's fragment loads from being hoisted above the previous layer
 template <bool H, int T, int NS>
 __device__ __forceinline__ void fb_gemm(const typename Prec<H>::elem_t *wf, uint32_t S, uint32_t s0, const typename Prec<H>::frag_t *b, uint32_t lane,
                                         cn_f16v (&acc)[T]) {
-    asm volatile("" ::: "memory");      // scheduling fence: keeps this layer's fragment loads from being hoisted above the previous layer
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-#pragma unroll
-        for (int t = 0; t < T; t++) acc[t] = Prec<H>::mfma(fb_load_frag<H>(wf, t, S, s0 + s, lane), b[s], acc[t]);
-    }
-}
-
-// forward-order staging (same as field.hip).  SWZ: 16-byte fragment slots bank-swizzled for the transposing reads of field_bwd_x2.hip
-// (slot bits 2..3 ^= (K-step parity, half) — halves index i, i.e. byte offset 2 i; needs an even S)
-template <bool H, int KIND, bool SWZ = false>
-__device__ __forceinline__ void fb_stage_layer(typename Prec<H>::elem_t *dst, const float *__restrict__ W, uint32_t rows, uint32_t in_stride,
-                                               uint32_t T, uint32_t S, uint32_t n_valid_cols) {
-    using P = Prec<H>;
-    const uint32_t total = T * S * 64 * P::J;
-    for (uint32_t i = threadIdx.x; i < total; i += blockDim.x) {
-        const uint32_t j = i % P::J, lane = (i / P::J) % 64, ts = i / (P::J * 64);
-        const uint32_t s = ts % S, t = ts / S;
-        const uint32_t row = 32 * t + (lane & 31), hi = lane >> 5;
-        int col;
-        if (KIND == 0) col = fld_col_natural<H>(s, hi, j);
-        else if (KIND == 1) col = fld_col_clayout<H>(s, hi, j);
-        else {
-            const uint32_t s_fea = FLD_HID / P::KS;
-            if (s < s_fea) col = FLD_NDIR + fld_col_clayout<H>(s, hi, j);
-            else {
-                col = fld_col_natural<H>(s - s_fea, hi, j);
-                if (col >= FLD_NDIR) col = -1;
-            }
-        }
-        float v = 0.0f;
-        if (row < rows && col >= 0 && (uint32_t)col < n_valid_cols) v = W[(size_t)row * in_stride + col];
-        dst[SWZ ? (i ^ (((i >> 8) & 3u) << 5)) : i] = (typename P::elem_t)v;
-    }
+    asm volatile("" ::: "memory");
+    fld_gemm<H, T, NS>(wf, S, s0, b, lane, acc);
 }
 
 // transposed staging: A fragment of W^T.  tile t runs over the layer's INPUT features (col0 + 32 t + i), the K-slots over its
@@ -102,13 +59,15 @@ __device__ __forceinline__ void fb_gemm_T(const typename Prec<H>::elem_t *wt_lds
 #pragma unroll
         for (int t = 0; t < T; t++) {
             typename Prec<H>::frag_t a;
-            if constexpr (H) a = fb_load_frag<H>(wt_lds, t, S, s, lane);
+            if constexpr (H) a = fld_load_frag<H>(wt_lds, t, S, s, lane);
             else a = fb_frag_T_global(W, rows, in_stride, col0, n_in, t, s, lane);
             acc[t] = Prec<H>::mfma(a, b[s], acc[t]);
         }
     }
 }
 
+// C registers -> next layer's B fragments, the backward's form (k_field_bwd_data, k_field_bwd_fused, k_mlp_*): fmaxf on the accumulators, then
+// convert.  Same values as fld_c_to_b (field.hip), other instructions: swapping them changes the kernels' instruction streams.
 template <bool H, bool RELU>
 __device__ __forceinline__ void fb_c_to_b(const cn_f16v (&acc)[2], typename Prec<H>::frag_t *b) {
     using P = Prec<H>;
@@ -135,6 +94,7 @@ __device__ __forceinline__ void fb_c_to_b(const cn_f16v (&acc)[2], typename Prec
 }
 
 // dz = da * [act > 0]   (act = the forward's post-ReLU fragments, same register mapping as the C tiles)
+// (compare and select per half; x4_c_to_b_masked of field_bwd_x2.hip is the packed-integer form of k_field_bwd_x2)
 template <bool H>
 __device__ __forceinline__ void fb_c_to_b_masked(const cn_f16v (&acc)[2], const typename Prec<H>::frag_t *act, typename Prec<H>::frag_t *b) {
     using P = Prec<H>;
@@ -188,54 +148,7 @@ __device__ __forceinline__ void fb_dump_natural(typename Prec<H>::elem_t *__rest
     }
 }
 
-template <bool H, int SENC>
-__device__ __forceinline__ void fb_load_enc(const void *__restrict__ enc, uint32_t P_, uint32_t L, uint32_t p, bool valid, uint32_t hi,
-                                            typename Prec<H>::frag_t (&b)[SENC]) {
-    if constexpr (H) {
-        const uint32_t *e = reinterpret_cast<const uint32_t *>(enc);
-#pragma unroll
-        for (int s = 0; s < SENC; s++) {
-            union { cn_h8 h; uint32_t u[4]; } f;
-#pragma unroll
-            for (int jj = 0; jj < 4; jj++) {
-                const uint32_t level = 8 * s + 4 * hi + jj;
-                f.u[jj] = (valid && level < L) ? e[(size_t)level * P_ + p] : 0u;
-            }
-            b[s] = f.h;
-        }
-    } else {
-        const float *e = reinterpret_cast<const float *>(enc);
-#pragma unroll
-        for (int s = 0; s < SENC; s++) {
-            const uint32_t feat = 2 * s + hi, level = feat >> 1;
-            b[s] = (valid && level < L) ? e[((size_t)level * P_ + p) * 2 + (feat & 1)] : 0.0f;
-        }
-    }
-}
-
-// direction features from an already loaded direction (padded samples must spill zeros: cos(0) = 1 otherwise)
-template <bool H>
-__device__ __forceinline__ void fb_dir_frags_from(float dx, float dy, float dz, bool valid, uint32_t hi, typename Prec<H>::frag_t *b) {
-    float e[FLD_DIR];
-    fld_dir_features<H>(dx, dy, dz, e);
-    if (!valid) {
-#pragma unroll
-        for (int q = 0; q < FLD_DIR; q++) e[q] = 0.0f;
-    }
-    if constexpr (H) {
-#pragma unroll
-        for (int s = 0; s < FLD_DIR / 16; s++) {
-            cn_h8 f;
-#pragma unroll
-            for (int j = 0; j < 8; j++) f[j] = (_Float16)(hi ? e[16 * s + 8 + j] : e[16 * s + j]);
-            b[s] = f;
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < FLD_DIR / 2; s++) b[s] = hi ? e[2 * s + 1] : e[2 * s];
-    }
-}
-
+// direction features of sample p; padded samples give zero fragments (they are spilled)
 template <bool H>
 __device__ __forceinline__ void fb_dir_frags(const float *__restrict__ dirs, uint32_t dir_group, uint32_t p, bool valid, uint32_t hi,
                                              typename Prec<H>::frag_t *b) {
@@ -244,7 +157,7 @@ __device__ __forceinline__ void fb_dir_frags(const float *__restrict__ dirs, uin
         const float *d = dirs + (size_t)(p / dir_group) * 3;
         dx = d[0]; dy = d[1]; dz = d[2];
     }
-    fb_dir_frags_from<H>(dx, dy, dz, valid, hi, b);
+    fld_dir_frags_from<H>(dx, dy, dz, valid, hi, b);
 }
 
 // LDS layout of the backward kernel: forward fragment stores (as field.hip) then the transposed stores (fp16 only)
@@ -269,7 +182,7 @@ __host__ __device__ __forceinline__ FieldLdsT fb_ldsT_layout(const FieldDims &d)
 
 
 // Flat [net | den | rgb] parameter space of the partial weight-gradient rows: one layout for every backward form that reduces partials with
-// k_field_reduce_partials (the four-wave kernel of field_bwd_fused.hip and the split-K GEMM of field_bwd.hip)
+// k_field_reduce_partials (the four-wave kernel of field_bwd_fused.hip, k_field_bwd_x2 and the split-K GEMM of field_bwd.hip)
 struct FfOff {
     uint32_t n0, n1, n2, d0, dO, r0, rO, total;
 };
@@ -286,3 +199,17 @@ __host__ __device__ __forceinline__ FfOff ff_offsets(const FieldDims &dm) {
     o.total = p;
     return o;
 }
+
+// ---- host functions that cross translation units (each defining file includes this header and so sees the declaration it implements)
+// field_bwd_fused.hip: g += sum of the partial rows (fixed order, raises found_inf); the single-launch fp16 form
+void ff_reduce_partials(const float *partials, uint32_t n_partials, uint32_t total, uint32_t n_net, uint32_t n_den, float *g_net, float *g_den, float *g_rgb,
+                        hipStream_t st);
+uint64_t ff_workspace_bytes(const FieldDims &dm);
+int ff_launch(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, const FieldDims &dm, const float *pnet,
+              const float *pden, const float *prgb, const float *g_sigma, const float *g_rgbc, void *grad_enc, float *g_net, float *g_den,
+              float *g_rgb, void *workspace, const uint8_t *tile_live, hipStream_t st, const void *wimg);
+// field_bwd_x2.hip: the two-pipeline kernel for 32-wide encodings (9..16 levels); the four-wave kernel of field_bwd_fused.hip serves the narrower ones
+bool x2_eligible(const FieldDims &dm);
+int x2_launch(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, const FieldDims &dm, const float *pnet, const float *pden,
+              const float *prgb, const float *g_sigma, const float *g_rgbc, void *grad_enc, float *g_net, float *g_den, float *g_rgb, void *workspace,
+              uint32_t max_partials, const uint8_t *tile_live, hipStream_t st, const void *wimg);

@@ -132,13 +132,13 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_fused(const void *__r
     const float *d0 = pden, *dO = pden + FLD_HID * FLD_HID;
     const float *r0 = prgb, *rO = prgb + FLD_HID * in_r0;
 
-    fb_stage_layer<H, 0>(wl + lo.off[0], n0, FLD_HID, dm.enc_pad, 2, SENC, dm.enc_pad);
-    if (NGEO == 2) fb_stage_layer<H, 1>(wl + lo.off[1], n1, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1>(wl + lo.off[2], n2, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1>(wl + lo.off[3], d0, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1>(wl + lo.off[4], dO, 16, FLD_HID, 1, S64, FLD_HID);
-    fb_stage_layer<H, 2>(wl + lo.off[5], r0, FLD_HID, in_r0, 2, SR0, in_r0);
-    fb_stage_layer<H, 1>(wl + lo.off[6], rO, 16, FLD_HID, 1, S64, FLD_HID);
+    fld_stage_layer<H, 0>(wl + lo.off[0], n0, FLD_HID, dm.enc_pad, 2, SENC, dm.enc_pad, threadIdx.x, blockDim.x);
+    if (NGEO == 2) fld_stage_layer<H, 1>(wl + lo.off[1], n1, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.off[2], n2, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.off[3], d0, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.off[4], dO, 16, FLD_HID, 1, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 2>(wl + lo.off[5], r0, FLD_HID, in_r0, 2, SR0, in_r0, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.off[6], rO, 16, FLD_HID, 1, S64, FLD_HID, threadIdx.x, blockDim.x);
     fb_stage_layer_T<H>(wt + lt.off[0], n0, FLD_HID, dm.enc_pad, 0, dm.enc_pad, TENC, S64);
     if (NGEO == 2) fb_stage_layer_T<H>(wt + lt.off[1], n1, FLD_HID, FLD_HID, 0, FLD_HID, 2, S64);
     fb_stage_layer_T<H>(wt + lt.off[2], n2, FLD_HID, FLD_HID, 0, FLD_HID, 2, S64);
@@ -169,35 +169,35 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_fused(const void *__r
 
         // ================= forward recompute
         frag_t x0[SENC];
-        fb_load_enc<H, SENC>(enc, P_, dm.L, p, valid, hi, x0);
+        fld_load_enc<H, SENC>(enc, P_, dm.L, p, valid, hi, x0);
         cn_f16v acc[2];
         frag_t h1[4], h2[4], fea[4], hd[4], hr[4];
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, SENC>(wl + lo.off[0], SENC, 0, x0, lane, acc);
         fb_c_to_b<H, true>(acc, h1);
         if (NGEO == 2) {
-            fb_zero(acc);
+            fld_zero(acc);
             fb_gemm<H, 2, S64>(wl + lo.off[1], S64, 0, h1, lane, acc);
             fb_c_to_b<H, true>(acc, h2);
         }
         const frag_t *hlast = (NGEO == 2) ? h2 : h1;
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, S64>(wl + lo.off[2], S64, 0, hlast, lane, acc);
         fb_c_to_b<H, false>(acc, fea);
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, S64>(wl + lo.off[3], S64, 0, fea, lane, acc);
         fb_c_to_b<H, true>(acc, hd);
         cn_f16v out[1];
-        fb_zero(out);
+        fld_zero(out);
         fb_gemm<H, 1, S64>(wl + lo.off[4], S64, 0, hd, lane, out);
         const float raw = (float)(_Float16)out[0][0];
         frag_t dfr[SDIR];
         fb_dir_frags<H>(dirs, dir_group, p, valid, hi, dfr);
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, S64>(wl + lo.off[5], SR0, 0, fea, lane, acc);
         fb_gemm<H, 2, SDIR>(wl + lo.off[5], SR0, S64, dfr, lane, acc);
         fb_c_to_b<H, true>(acc, hr);
-        fb_zero(out);
+        fld_zero(out);
         fb_gemm<H, 1, S64>(wl + lo.off[6], S64, 0, hr, lane, out);
 
         // ================= output-layer gradients
@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_fused(const void *__r
         // ================= chain, interleaved with the four weight-gradient phases so that fragments die early
         // ---- colour head: dz_r, then phase A (dW_ro, dW_r0) — frees hr, dfr
         frag_t zr[4];
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm_T<H, 2, 1>(wt + lt.off[6], rO, 16, FLD_HID, 0, FLD_HID, S32, bro, lane, acc);
         fb_c_to_b_masked<H>(acc, hr, zr);
         FF_PIN(col, hi);
@@ -240,13 +240,13 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_fused(const void *__r
         ff_tile_mma(st, ff_tile_A(wave, dm, po), li, hi, wA0);
         ff_tile_mma(st, ff_tile_A(4 + wave, dm, po), li, hi, wA1);
         cn_f16v dfea[2];
-        fb_zero(dfea);
+        fld_zero(dfea);
         fb_gemm_T<H, 2, S64>(wt + lt.off[5], r0, FLD_HID, in_r0, FLD_NDIR, FLD_HID, S64, zr, lane, dfea);
         __syncthreads();
         // ---- density head: dz_d, then phase B (dW_do, dW_d0; fea stays at rows 136..199) — frees hd
         {
             frag_t zd[4];
-            fb_zero(acc);
+            fld_zero(acc);
             fb_gemm_T<H, 2, 1>(wt + lt.off[4], dO, 16, FLD_HID, 0, FLD_HID, S32, bdo, lane, acc);
             fb_c_to_b_masked<H>(acc, hd, zd);
             FF_PIN(col, hi);
@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_fused(const void *__r
         {
             frag_t z3[4], z2[4];
             fb_c_to_b<H, false>(dfea, z3);
-            fb_zero(acc);
+            fld_zero(acc);
             fb_gemm_T<H, 2, S64>(wt + lt.off[2], n2, FLD_HID, FLD_HID, 0, FLD_HID, S64, z3, lane, acc);
             FF_PIN(col, hi);
             ff_stage_clayout(st, 0, col, hi, z3);
@@ -280,7 +280,7 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_fused(const void *__r
                 ff_stage_clayout(st, 128, col, hi, z2);
                 FF_PIN(col, hi);
                 ff_stage_clayout(st, 192, col, hi, h1);
-                fb_zero(acc);
+                fld_zero(acc);
                 fb_gemm_T<H, 2, S64>(wt + lt.off[1], n1, FLD_HID, FLD_HID, 0, FLD_HID, S64, z2, lane, acc);
             }
             fb_c_to_b_masked<H>(acc, h1, z1);
@@ -295,14 +295,14 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_fused(const void *__r
         FF_PIN(col, hi);
         {
             frag_t x0b[SENC];                                               // re-read (L2 hit) rather than hold 8 VGPRs across the chain
-            fb_load_enc<H, SENC>(enc, P_, dm.L, p, valid, hi, x0b);
+            fld_load_enc<H, SENC>(enc, P_, dm.L, p, valid, hi, x0b);
             ff_stage_natural<SENC>(st, 64, col, hi, x0b);
         }
         __syncthreads();
         if (wave < 2) ff_tile_mma(st, ff_tile_D(wave, dm, po), li, hi, wX);
         {
             cn_f16v denc[TENC];
-            fb_zero(denc);
+            fld_zero(denc);
             fb_gemm_T<H, TENC, S64>(wt + lt.off[0], n0, FLD_HID, dm.enc_pad, 0, dm.enc_pad, S64, z1, lane, denc);
             if (valid) {
 #pragma unroll
@@ -365,12 +365,6 @@ __global__ void __launch_bounds__(256) k_field_reduce_partials(const float *__re
 #define FF_MAX_BLOCKS 512              // partial-gradient rows in the workspace (the wave-specialised kernel uses two per workgroup)
 uint64_t ff_workspace_bytes(const FieldDims &dm) { return (uint64_t)FF_MAX_BLOCKS * ff_offsets(dm).total * sizeof(float) + 256; }
 
-// field_bwd_x2.hip: the two-pipeline kernel for 32-wide encodings (9..16 levels); the four-wave kernel of this file serves the narrower ones
-bool x2_eligible(const FieldDims &dm);
-int x2_launch(const void *enc, const float *xyz, const float *dirs, uint32_t dir_group, uint32_t P_, const FieldDims &dm, const float *pnet, const float *pden,
-              const float *prgb, const float *g_sigma, const float *g_rgbc, void *grad_enc, float *g_net, float *g_den, float *g_rgb, void *workspace,
-              uint32_t max_partials, const uint8_t *tile_live, hipStream_t st, const void *wimg);
-
 void ff_reduce_partials(const float *partials, uint32_t n_partials, uint32_t total, uint32_t n_net, uint32_t n_den, float *g_net, float *g_den, float *g_rgb,
                         hipStream_t st) {
     hipLaunchKernelGGL(k_field_reduce_partials, dim3(cn_div_up(total, 64)), dim3(256), 0, st, partials, n_partials, total, n_net, n_den, g_net, g_den, g_rgb, g_cn_found_inf);
@@ -396,35 +390,15 @@ int ff_launch(const void *enc, const float *xyz, const float *dirs, uint32_t dir
     float *partials = reinterpret_cast<float *>(workspace);
     hipError_t e = hipMemsetAsync(partials, 0, (size_t)blocks * po.total * sizeof(float), st);
     if (e != hipSuccess) return (int)e;
-#define FF_CASE(SE16, NG, TE)                                                                                                                 \
-    {                                                                                                                                         \
-        auto kern = k_field_bwd_fused<(SE16), NG, TE>;                                                                                        \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);               \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(FLD_THREADS), lds_bytes, st, enc, xyz, dirs, dir_group, P_, dm, pnet, pden, prgb, g_sigma, \
-                           g_rgbc, grad_enc, partials);                                                                                       \
-    }
-    const uint32_t se16 = dm.enc_pad / 16;
-    if (dm.n_hidden_geo == 1) {
-        switch (se16) {
-            case 1: FF_CASE(1, 1, 1) break;
-            case 2: FF_CASE(2, 1, 1) break;
-            case 3: FF_CASE(3, 1, 2) break;
-            case 4: FF_CASE(4, 1, 2) break;
-            default: return CNERF_EINVAL;
-        }
-    } else {
-        switch (se16) {
-            case 1: FF_CASE(1, 2, 1) break;
-            case 2: FF_CASE(2, 2, 1) break;
-            case 3: FF_CASE(3, 2, 2) break;
-            case 4: FF_CASE(4, 2, 2) break;
-            default: return CNERF_EINVAL;
-        }
-    }
+    const bool ok = fld_dispatch(dm, [&](auto se16, auto ng) {
+        auto kern = k_field_bwd_fused<se16, ng, (se16 + 1) / 2>;                                 // TENC: 32-row tiles of the encoding
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(FLD_THREADS), lds_bytes, st, enc, xyz, dirs, dir_group, P_, dm, pnet, pden, prgb, g_sigma, g_rgbc, grad_enc,
+                           partials);
+    });
+    if (!ok) return CNERF_EINVAL;
     int rc = cn_launch_status();
     if (rc) return rc;
-    const uint32_t n_net = po.d0, n_den = po.r0 - po.d0;
-    hipLaunchKernelGGL(k_field_reduce_partials, dim3(cn_div_up(po.total, 64)), dim3(256), 0, st, partials, blocks, po.total, n_net, n_den, g_net,
-                       g_den, g_rgb, g_cn_found_inf);
+    ff_reduce_partials(partials, blocks, po.total, po.d0, po.r0 - po.d0, g_net, g_den, g_rgb, st);
     return cn_launch_status();
 }

@@ -18,34 +18,17 @@
 typedef short x4_s4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short x4_s2 __attribute__((ext_vector_type(2)));
 
-struct MmOff {
-    uint32_t n0, n1, n2, d0, dO, r0, rO, total;
-};
-__host__ __device__ __forceinline__ MmOff x4_offsets(const FieldDims &dm) {
-    MmOff o;
-    uint32_t p = 0;
-    o.n0 = p; p += FLD_HID * dm.enc_pad;
-    o.n1 = p; p += (dm.n_hidden_geo == 2) ? 4096 : 0;
-    o.n2 = p; p += 4096;
-    o.d0 = p; p += 4096;
-    o.dO = p; p += 16 * 64;
-    o.r0 = p; p += 64 * 96;
-    o.rO = p; p += 16 * 64;
-    o.total = p;
-    return o;
-}
-
 #define X4_K 1024                            // one K-step image: 64 lanes x 16 B (16 features x 32 samples)
 
 // A fragment of W^T for the data-gradient chain, read out of the FORWARD fragment store of the layer (dst[((t S + s) 64 + lane) 8 + j] =
-// W[32 t + (lane & 31)][col(s, lane >> 5, j)], field.hip) by two transposing reads.  Wanted: lane l = input feature 32 t' + (l & 31)
+// W[32 t + (lane & 31)][col(s, lane >> 5, j)], field_common.h) by two transposing reads.  Wanted: lane l = input feature 32 t' + (l & 31)
 // (natural order inside the tile), K-slot (s', hi' = l >> 5, j') = output feature clayout(s', hi', j') — the order in which dz arrives.
 // Those are the output rows li = 16 (s' & 1) + 8 c + 4 hi' + (j' & 3) (c = j' >> 2) of output tile t = s' >> 1: two runs of four
 // consecutive rows, one transposing read each; a read's 16-lane group G = (l >> 4) covers input features 16 (G & 1) .. + 15 in four 8-byte
 // chunks (address role of lane i = l & 15: row i >> 2, chunk q = i & 3), which for C-ordered columns sit at K-step 2 t' + (G & 1),
 // half q & 1, element offset 4 (q >> 1) and for natural columns (first layer) at half q >> 1, offset 4 (q & 1).
 // `lane_off` is that lane-dependent part (x4_lane_off_w), everything else is a compile-time immediate.
-// The store is bank-swizzled like the images below (fb_stage_layer<.., SWZ = true>, x4_img_swz): one lane offset per read.
+// The store is bank-swizzled like the images below (fld_stage_layer<.., SWZ = true>, x4_img_swz): one lane offset per read.
 struct X4Img { uint32_t c0, c1; };
 __device__ __forceinline__ uint32_t x4_img_swz(uint32_t byte_off) { return byte_off ^ (((byte_off >> 9) & 3u) << 6); }
 template <int S>
@@ -65,7 +48,7 @@ __device__ __forceinline__ X4Img x4_lane_off_w(uint32_t l, bool natural_cols) {
     o.c1 = x4_img_swz(base + 8 * 16) + j0 * 2;
     return o;
 }
-// forward-order A fragment out of the swizzled store
+// forward-order A fragment out of the swizzled store (k_field_bwd_x2 only: fld_load_frag reads the plain store)
 __device__ __forceinline__ cn_h8 x4_load_frag(const _Float16 *base, uint32_t t, uint32_t S, uint32_t s, uint32_t lane) {
     return *reinterpret_cast<const cn_h8 *>(reinterpret_cast<const unsigned char *>(base) + (t * S + s) * 1024 + ((lane * 16) ^ ((((s & 1) * 2 + (lane >> 5)) << 6))));
 }
@@ -226,6 +209,7 @@ __device__ __forceinline__ void x4_store(float *__restrict__ part, uint32_t dst,
         if (row < M && col < N) part[dst + (size_t)row * stride + col0 + col] = acc[r];
     }
 }
+// one persistent tile (fld_zero takes an array: zeroing the tile arrays through it orders the stores differently and with them this kernel's registers)
 __device__ __forceinline__ void x4_zero(cn_f16v &a) {
 #pragma unroll
     for (int r = 0; r < 16; r++) a[r] = 0.0f;
@@ -286,7 +270,7 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
     extern __shared__ __attribute__((aligned(16))) unsigned char fld_lds[];
     elem_t *wl = x2_w;
     const FieldLds lo = fld_lds_layout<H>(dm);
-    const MmOff po = x4_offsets(dm);
+    const FfOff po = ff_offsets(dm);
 
     constexpr uint32_t S64 = FLD_HID / PR::KS, SDIR = FLD_DIR / PR::KS, SR0 = S64 + SDIR;
     const uint32_t in_r0 = FLD_HID + FLD_DIR;
@@ -296,20 +280,20 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
     const float *r0 = prgb, *rO = prgb + FLD_HID * in_r0;
 
     if (wimg) {
-        // the packed fp16 image of the forward (field.hip: k_field_pack), 16-byte chunks into the bank-swizzled slots of fb_stage_layer<.., SWZ>:
+        // the packed fp16 image of the forward (field.hip: k_field_pack), 16-byte chunks into the bank-swizzled slots of fld_stage_layer<.., SWZ>:
         // half index i -> i ^ (((i >> 8) & 3) << 5), i.e. chunk c -> c ^ (((c >> 5) & 3) << 2) (every layer starts at a multiple of 2048 halves)
         const uint4 *src = reinterpret_cast<const uint4 *>(wimg);
         uint4 *dst = reinterpret_cast<uint4 *>(wl);
         for (uint32_t c = threadIdx.x; c < lo.off[7] / 8; c += FLD_THREADS) dst[c ^ (((c >> 5) & 3u) << 2)] = src[c];
     } else
     for (int rep = 0; rep < ((ablate & 64) ? 2 : 1); rep++) {                    // (bit 6: staged TWICE — the delta is the staging time)
-    fb_stage_layer<H, 0, true>(wl + lo.off[0], n0, FLD_HID, dm.enc_pad, 2, SENC, dm.enc_pad);
-    if (NGEO == 2) fb_stage_layer<H, 1, true>(wl + lo.off[1], n1, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1, true>(wl + lo.off[2], n2, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1, true>(wl + lo.off[3], d0, FLD_HID, FLD_HID, 2, S64, FLD_HID);
-    fb_stage_layer<H, 1, true>(wl + lo.off[4], dO, 16, FLD_HID, 1, S64, FLD_HID);
-    fb_stage_layer<H, 2, true>(wl + lo.off[5], r0, FLD_HID, in_r0, 2, SR0, in_r0);
-    fb_stage_layer<H, 1, true>(wl + lo.off[6], rO, 16, FLD_HID, 1, S64, FLD_HID);
+    fld_stage_layer<H, 0, true>(wl + lo.off[0], n0, FLD_HID, dm.enc_pad, 2, SENC, dm.enc_pad, threadIdx.x, blockDim.x);
+    if (NGEO == 2) fld_stage_layer<H, 1, true>(wl + lo.off[1], n1, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1, true>(wl + lo.off[2], n2, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1, true>(wl + lo.off[3], d0, FLD_HID, FLD_HID, 2, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1, true>(wl + lo.off[4], dO, 16, FLD_HID, 1, S64, FLD_HID, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 2, true>(wl + lo.off[5], r0, FLD_HID, in_r0, 2, SR0, in_r0, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1, true>(wl + lo.off[6], rO, 16, FLD_HID, 1, S64, FLD_HID, threadIdx.x, blockDim.x);
     if (ablate & 64) __syncthreads();
     }
     // the second K-step of the output-gradient images (features 16..31 of their padded 32-row tile) is never written: zero it once
@@ -439,7 +423,7 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
                 x4_publish<4>(my + X2_A_H1, lane, S.h1);
                 if (NGEO == 2) x4_publish<4>(my + X2_A_H2, lane, S.h2);
                 cn_f16v acc[2];
-                fb_zero(acc);
+                fld_zero(acc);
                 x4_gemm_T<2, S64, S64>(wb + off_n2, lw, z3, acc);
                 {   // dW_n2 = dz3 . hlast^T
                     const unsigned char *hl = my + ((NGEO == 2) ? X2_A_H2 : X2_A_H1);
@@ -453,7 +437,7 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
                     frag_t z2[4];
                     x4_c_to_b_masked(acc, S.h2, z2);
                     x4_publish<4>(my + X2_A_Z2, lane, z2);
-                    fb_zero(acc);
+                    fld_zero(acc);
                     x4_gemm_T<2, S64, S64>(wb + off_n1, lw, z2, acc);
                     cn_h8 z[2][2], a[2][2];
                     x4_load_block(my + X2_A_Z2, lc, 0, z[0]); x4_load_block(my + X2_A_Z2, lc, 1, z[1]);
@@ -463,7 +447,7 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
                 x4_c_to_b_masked(acc, S.h1, z1);
                 x4_publish<4>(my + X2_A_Z1, lane, z1);
                 cn_f16v denc[1];
-                fb_zero(denc);
+                fld_zero(denc);
                 x4_gemm_T<1, S64, SENC>(wb + off_n0, lwn, z1, denc);
                 {
                     cn_h8 z[2][2], a[2];
@@ -495,16 +479,16 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
             if (S.live) {
                 x4_enc_mask<SENC>(xcur, dm.L, S.v, hi, S.x0);
                 cn_f16v acc[2];
-                fb_zero(acc);
+                fld_zero(acc);
                 x4_gemm<2, SENC>(wl + lo.off[0], SENC, 0, S.x0, lane, acc);
                 x4_c_to_b<true>(acc, S.h1);
                 if (NGEO == 2) {
-                    fb_zero(acc);
+                    fld_zero(acc);
                     x4_gemm<2, S64>(wl + lo.off[1], S64, 0, S.h1, lane, acc);
                     x4_c_to_b<true>(acc, S.h2);
                 }
                 frag_t fea[4];
-                fb_zero(acc);
+                fld_zero(acc);
                 x4_gemm<2, S64>(wl + lo.off[2], S64, 0, (NGEO == 2) ? S.h2 : S.h1, lane, acc);
                 x4_c_to_b<false>(acc, fea);
                 x4_publish<4>(xch + X2_FEA + (k & 1) * 4 * X4_K, lane, fea);
@@ -572,24 +556,24 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
                 // one direction per tile (run() path): 27 lanes evaluate one feature each; the 64-byte scratch is the head of the dz_d image,
                 // which this wave rewrites later in the phase (its reads of the previous tile's image are already issued: in-order DS)
                 if (dir_uniform) fld_dir_frags_uniform(cur.dx, cur.dy, cur.dz, lane, hi, my + X2_B_ZD, dfr);
-                else fb_dir_frags_from<H>(cur.dx, cur.dy, cur.dz, valid, hi, dfr);
+                else fld_dir_frags_from<H>(cur.dx, cur.dy, cur.dz, valid, hi, dfr);
                 x4_publish<SDIR>(my + X2_B_DIR, lane, dfr);
                 // ---- forward of both heads
                 cn_f16v acc[2], out[1];
                 frag_t hd[4], hr[4];
-                fb_zero(acc);
+                fld_zero(acc);
                 x4_gemm<2, S64>(wl + lo.off[3], S64, 0, fea, lane, acc);
                 x4_c_to_b<true>(acc, hd);
                 x4_publish<4>(my + X2_B_HD, lane, hd);
-                fb_zero(out);
+                fld_zero(out);
                 x4_gemm<1, S64>(wl + lo.off[4], S64, 0, hd, lane, out);
                 const float raw = (float)(_Float16)out[0][0];
-                fb_zero(acc);
+                fld_zero(acc);
                 x4_gemm<2, S64>(wl + lo.off[5], SR0, 0, fea, lane, acc);
                 x4_gemm<2, SDIR>(wl + lo.off[5], SR0, S64, dfr, lane, acc);
                 x4_c_to_b<true>(acc, hr);
                 x4_publish<4>(my + X2_B_HR, lane, hr);
-                fb_zero(out);
+                fld_zero(out);
                 x4_gemm<1, S64>(wl + lo.off[6], S64, 0, hr, lane, out);
                 // ---- output-layer gradients (sigmoid', clamped exp': provider_utils.py:26-29)
                 frag_t bro[1], bdo[1];
@@ -611,11 +595,11 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
                 x4_publish<1>(my + X2_B_BRO, lane, bro);
                 x4_publish<1>(my + X2_B_BDO, lane, bdo);
                 cn_f16v dfea[2];
-                fb_zero(dfea);
+                fld_zero(dfea);
                 // ---- colour head
                 {
                     frag_t zr[4];
-                    fb_zero(acc);
+                    fld_zero(acc);
                     x4_gemm_T<2, 1, S64>(wb + off_rO, lw, bro, acc);
                     x4_c_to_b_masked(acc, hr, zr);
                     x4_publish<4>(my + X2_B_ZR, lane, zr);
@@ -636,7 +620,7 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
                 // ---- density head
                 {
                     frag_t zd[4];
-                    fb_zero(acc);
+                    fld_zero(acc);
                     x4_gemm_T<2, 1, S64>(wb + off_dO, lw, bdo, acc);
                     x4_c_to_b_masked(acc, hd, zd);
                     x4_publish<4>(my + X2_B_ZD, lane, zd);
@@ -693,9 +677,6 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
 }
 
 // ------------------------------------------------------------------------------------------------ host entry (called from field_bwd_fused.hip)
-void ff_reduce_partials(const float *partials, uint32_t n_partials, uint32_t total, uint32_t n_net, uint32_t n_den, float *g_net, float *g_den, float *g_rgb,
-                        hipStream_t st);
-
 bool x2_eligible(const FieldDims &dm) {
     static const int on = cn_tune_env("CNERF_FIELD_X2_BWD", 1);   // 0 (tuning builds): the four-wave kernel of field_bwd_fused.hip
     return on && dm.enc_pad == 32 && (dm.n_hidden_geo == 1 || dm.n_hidden_geo == 2);
@@ -711,7 +692,7 @@ int x2_launch(const void *enc, const float *xyz, const float *dirs, uint32_t dir
     uint32_t blocks = cn_div_up(n_tiles, 2);
     if (blocks > max_partials / 2) blocks = max_partials / 2;                   // two partial-gradient rows per workgroup
     if (blocks > 256) blocks = 256;
-    const MmOff po = x4_offsets(dm);
+    const FfOff po = ff_offsets(dm);
     float *partials = reinterpret_cast<float *>(workspace);
     // (every pipeline writes its whole partial row, padding included: no zero fill)
     // measurement aid of tuning builds only (bit 0 A-backward, 1 A-forward, 2 B switched off — results wrong —, 5 role timing); the release

@@ -68,9 +68,9 @@ __global__ void __launch_bounds__(FLD_THREADS) k_mlp_fwd(const void *__restrict_
     const MlpLds lo = mlp_lds<H>(dm, false);
     constexpr uint32_t S64 = FLD_HID / PR::KS;
     const float *w0 = params, *w1 = params + 64 * dm.in_pad16, *wo = w1 + (NH == 2 ? 4096 : 0);
-    fb_stage_layer<H, 0>(wl + lo.f0, w0, 64, dm.in_pad16, 2, SIN, dm.in_pad16);
-    if (NH == 2) fb_stage_layer<H, 1>(wl + lo.f1, w1, 64, 64, 2, S64, 64);
-    fb_stage_layer<H, 1>(wl + lo.fo, wo, dm.out_pad16, 64, TO, S64, 64);
+    fld_stage_layer<H, 0>(wl + lo.f0, w0, 64, dm.in_pad16, 2, SIN, dm.in_pad16, threadIdx.x, blockDim.x);
+    if (NH == 2) fld_stage_layer<H, 1>(wl + lo.f1, w1, 64, 64, 2, S64, 64, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.fo, wo, dm.out_pad16, 64, TO, S64, 64, threadIdx.x, blockDim.x);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hi = lane >> 5;
     const uint32_t n_tiles = (P_ + FLD_TILE - 1) / FLD_TILE;
@@ -82,16 +82,16 @@ __global__ void __launch_bounds__(FLD_THREADS) k_mlp_fwd(const void *__restrict_
         mlp_load_x<H, SIN>(x, ldx, dm.n_in, p, valid, hi, x0);
         cn_f16v acc[2];
         frag_t h[2 * PR::FR];
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, SIN>(wl + lo.f0, SIN, 0, x0, lane, acc);
         fb_c_to_b<H, true>(acc, h);
         if (NH == 2) {
-            fb_zero(acc);
+            fld_zero(acc);
             fb_gemm<H, 2, S64>(wl + lo.f1, S64, 0, h, lane, acc);
             fb_c_to_b<H, true>(acc, h);
         }
         cn_f16v out[TO];
-        fb_zero(out);
+        fld_zero(out);
         fb_gemm<H, TO, S64>(wl + lo.fo, S64, 0, h, lane, out);
         if (valid) {
             elem_t *yr = reinterpret_cast<elem_t *>(y) + (size_t)p * ldy;
@@ -137,9 +137,9 @@ __global__ void __launch_bounds__(FLD_THREADS) k_mlp_bwd_data(const void *__rest
     elem_t *ws = reinterpret_cast<elem_t *>(ws_);
     constexpr uint32_t S64 = FLD_HID / PR::KS, S32 = 32 / PR::KS;
     const float *w0 = params, *w1 = params + 64 * dm.in_pad16, *wo = w1 + (NH == 2 ? 4096 : 0);
-    fb_stage_layer<H, 0>(wl + lo.f0, w0, 64, dm.in_pad16, 2, SIN, dm.in_pad16);
-    if (NH == 2) fb_stage_layer<H, 1>(wl + lo.f1, w1, 64, 64, 2, S64, 64);
-    fb_stage_layer<H, 1>(wl + lo.fo, wo, dm.out_pad16, 64, TO, S64, 64);
+    fld_stage_layer<H, 0>(wl + lo.f0, w0, 64, dm.in_pad16, 2, SIN, dm.in_pad16, threadIdx.x, blockDim.x);
+    if (NH == 2) fld_stage_layer<H, 1>(wl + lo.f1, w1, 64, 64, 2, S64, 64, threadIdx.x, blockDim.x);
+    fld_stage_layer<H, 1>(wl + lo.fo, wo, dm.out_pad16, 64, TO, S64, 64, threadIdx.x, blockDim.x);
     if constexpr (H) {
         fb_stage_layer_T<H>(wl + lo.t0, w0, 64, dm.in_pad16, 0, dm.in_pad16, TIN, S64);
         if (NH == 2) fb_stage_layer_T<H>(wl + lo.t1, w1, 64, 64, 0, 64, 2, S64);
@@ -158,19 +158,19 @@ __global__ void __launch_bounds__(FLD_THREADS) k_mlp_bwd_data(const void *__rest
         fb_dump_natural<H, SIN>(ws + (size_t)wo_.x * ld, ld, p, hi, x0, dm.kp);
         cn_f16v acc[2];
         frag_t h1[2 * PR::FR], h2[2 * PR::FR];
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm<H, 2, SIN>(wl + lo.f0, SIN, 0, x0, lane, acc);
         fb_c_to_b<H, true>(acc, h1);
         fb_dump_clayout<H>(ws + (size_t)wo_.h1 * ld, ld, p, hi, h1);
         if (NH == 2) {
-            fb_zero(acc);
+            fld_zero(acc);
             fb_gemm<H, 2, S64>(wl + lo.f1, S64, 0, h1, lane, acc);
             fb_c_to_b<H, true>(acc, h2);
             fb_dump_clayout<H>(ws + (size_t)wo_.h2 * ld, ld, p, hi, h2);
         }
         const frag_t *hlast = (NH == 2) ? h2 : h1;
         cn_f16v out[TO];
-        fb_zero(out);
+        fld_zero(out);
         fb_gemm<H, TO, S64>(wl + lo.fo, S64, 0, hlast, lane, out);
         // ---- output gradient: the rows this lane owns, turned in place into the B fragments of the transposed output layer
         {
@@ -207,19 +207,19 @@ __global__ void __launch_bounds__(FLD_THREADS) k_mlp_bwd_data(const void *__rest
             }
         // ---- chain
         frag_t z1[2 * PR::FR], z0[2 * PR::FR];
-        fb_zero(acc);
+        fld_zero(acc);
         fb_gemm_T<H, 2, TO * PR::FR>(wl + lo.to, wo, dm.out_pad16, 64, 0, 64, TO * S32, bo, lane, acc);
         if (NH == 2) {
             fb_c_to_b_masked<H>(acc, h2, z1);
             fb_dump_clayout<H>(ws + (size_t)wo_.z1 * ld, ld, p, hi, z1);
-            fb_zero(acc);
+            fld_zero(acc);
             fb_gemm_T<H, 2, S64>(wl + lo.t1, w1, 64, 64, 0, 64, S64, z1, lane, acc);
         }
         fb_c_to_b_masked<H>(acc, h1, z0);
         fb_dump_clayout<H>(ws + (size_t)wo_.z0 * ld, ld, p, hi, z0);
         if (gx) {
             cn_f16v dx[TIN];
-            fb_zero(dx);
+            fld_zero(dx);
             fb_gemm_T<H, TIN, S64>(wl + lo.t0, w0, 64, dm.in_pad16, 0, dm.in_pad16, S64, z0, lane, dx);
             if (valid) {
                 elem_t *gxr = reinterpret_cast<elem_t *>(gx) + (size_t)p * ldgx;

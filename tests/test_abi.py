@@ -127,6 +127,45 @@ def test_argument_validation_without_launch():
     assert lib.cnerf_grid_encode_backward_needs_plan(big.ctypes.data, 2097152, 3, 2, 16, 16, S, 16, 0, 0, ctypes.addressof(needs)) == 0 and needs.value == 1   # float32 records: first form
 
 
+def _field_call(fn, **over):
+    """One fused-field entry point with dummy 16-byte-aligned non-NULL addresses (never dereferenced: every case below returns
+    before a launch).  P = 64, enc_dim = 32, 2 hidden layers, 4 outputs, fp16 unless overridden."""
+    from customnerf_amd._lib import lib
+    a = dict(enc=16, xyz=16, dirs=16, dir_group=1, P=64, enc_dim=32, n_hidden_geo=2, n_rgb_out=4, pnet=16, pden=16, prgb=16,
+             sigma=16, rgbc=16, dtype=1, enc_level_stride=0, weight_image=None, stream=None,
+             grad_sigma=16, grad_rgbc=16, grad_enc=16, g_net=16, g_den=16, g_rgb=16, workspace=16, workspace_bytes=1 << 40, tile_live=None)
+    if over.pop("all_null", False):
+        a.update({k: None for k, v in a.items() if v == 16})
+    a.update(over)
+    head = [a[k] for k in ("enc", "xyz", "dirs", "dir_group", "P", "enc_dim", "n_hidden_geo", "n_rgb_out", "pnet", "pden", "prgb")]
+    if fn == "forward_img":
+        return lib.cnerf_field_forward_img(*head, a["sigma"], a["rgbc"], a["dtype"], a["enc_level_stride"], a["weight_image"], a["stream"])
+    if fn == "forward_strided":
+        return lib.cnerf_field_forward_strided(*head, a["sigma"], a["rgbc"], a["dtype"], a["enc_level_stride"], a["stream"])
+    assert fn == "backward_img"
+    return lib.cnerf_field_backward_img(*head, a["grad_sigma"], a["grad_rgbc"], a["grad_enc"], a["g_net"], a["g_den"], a["g_rgb"], a["workspace"],
+                                        a["workspace_bytes"], a["dtype"], a["tile_live"], a["weight_image"], a["stream"])
+
+
+@pytest.mark.parametrize("fn, over, code", [
+    ("forward_img", dict(enc_dim=31), -1),
+    ("forward_img", dict(dtype=7), -1),
+    ("forward_img", dict(dtype=7, weight_image=16), -1),
+    ("forward_img", dict(P=0, all_null=True), 0),
+    ("forward_img", dict(enc=None), -2),
+    ("forward_img", dict(weight_image=24), -1),                          # fp16: the image must be 16-byte aligned
+    ("forward_img", dict(dtype=0, weight_image=24, enc=None), -2),       # fp32 ignores the image: the NULL enc is what is reported
+    ("forward_strided", dict(enc_level_stride=32), -1),                  # level stride < P
+    ("forward_strided", dict(rgbc=24), -1),
+    ("forward_strided", dict(dirs=None), -2),                            # rgbc given: dirs required
+    ("backward_img", dict(workspace_bytes=16), -1),
+    ("backward_img", dict(enc=None), -2),
+])
+def test_field_argument_return_codes(fn, over, code):
+    """The fused field's argument checks (CNERF_OK 0, CNERF_EINVAL -1, CNERF_ENULL -2) return before any HIP call."""
+    assert _field_call(fn, **over) == code
+
+
 def test_host_side_modules_on_cpu():
     """Module construction (offset tables, parameter shapes/names, tcnn parameter counts) needs no GPU;
     evaluating on CPU tensors must fail loudly (no CPU path)."""
