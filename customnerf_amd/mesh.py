@@ -1,7 +1,8 @@
 """Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*), mesh cleanup on the GPU (csrc/mesh_clean.hip:
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
 face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU
-(csrc/mesh_texture.hip), a binary PLY writer and an OBJ + MTL + PNG writer.
+(csrc/mesh_texture.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
+shaded images), a binary PLY writer and an OBJ + MTL + PNG writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -367,6 +368,116 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
             rgb = rgb.to(dev).contiguous()
         check(lib.cnerf_mesh_atlas_store(F, R, t0, t1, ptr(rgb), rgb.stride(0), fill_c, ptr(flags), ptr(tex), stream()), "mesh_atlas_store")
     return uvs, tex
+
+
+_CONVENTIONS = {'nerfstudio': 0, 'ngp': 1}
+_CULL = {'none': 0, 'back': 1, 'front': 2}
+_SHADING = {'colors': 0, 'texture': 1, 'normals': 2, 'depth': 3}
+
+
+def raster_workspace_bytes(V, F, H, W):
+    return _bytes("mesh_raster", int(V), int(F), int(H), int(W))
+
+
+def _camera(c2w, intrinsics, H, W, what):
+    """(c2w as 12 host floats, fx, fy, cx, cy, H, W) of one pinhole camera"""
+    m = _host(c2w, np.float32)
+    if m.shape not in ((3, 4), (4, 4)):
+        raise ValueError(f"{what}: c2w must be [3, 4] or [4, 4], got {m.shape}")
+    k = tuple(float(x) for x in intrinsics)
+    if len(k) != 4:
+        raise ValueError(f"{what}: intrinsics must be (fx, fy, cx, cy), got {len(k)} values")
+    H, W = int(H), int(W)
+    if H < 0 or W < 0 or H * W >= 2 ** 31:
+        raise ValueError(f"{what}: need H, W >= 0 and H * W < 2^31, got H = {H}, W = {W}")
+    return (C.c_float * 12)(*m[:3].ravel().tolist()), k, H, W
+
+
+def rasterize(verts, faces, c2w, intrinsics, H, W, convention='nerfstudio', near=0.01, cull='none'):
+    """Visibility buffer of a triangle mesh seen through one pinhole camera, on the device (csrc/mesh_raster.hip; the rules are in
+    include/customnerf_hip.h, cnerf_mesh_raster_*).  The camera is generate_rays': c2w [3, 4] or [4, 4] (tensor or array), intrinsics
+    (fx, fy, cx, cy), convention 'nerfstudio' or 'ngp'; pixels are sampled at their centres.  cull: 'none', 'back' or 'front' (faces wound
+    outwards, as marching cubes emits them, are front-facing from outside).  A face with a vertex nearer than `near` along the camera axis,
+    or behind the camera, is dropped whole (no clipping).  CUDA tensors verts [V, 3], faces [F, 3] (int).
+    -> dict of device tensors face [H, W] int32 (-1: none), depth [H, W] float32 (camera-axis depth, +inf: none), bary [H, W, 3] float32
+    (perspective-correct, in the face's vertex order), and dropped: the number of dropped faces.  Bad input raises ValueError."""
+    v, f, _ = _mesh_args(verts, faces, None, "rasterize")
+    m, k, H, W = _camera(c2w, intrinsics, H, W, "rasterize")
+    if convention not in _CONVENTIONS:
+        raise ValueError(f"rasterize: convention must be 'nerfstudio' or 'ngp', got {convention!r}")
+    if cull not in _CULL:
+        raise ValueError(f"rasterize: cull must be 'none', 'back' or 'front', got {cull!r}")
+    near = float(near)
+    if not (math.isfinite(near) and all(math.isfinite(x) for x in k) and k[0] != 0.0 and k[1] != 0.0):
+        raise ValueError(f"rasterize: need finite intrinsics with fx, fy != 0 and a finite near, got {k}, near = {near}")
+    V, F = v.shape[0], f.shape[0]
+    dev = v.device
+    ws, nbytes = _workspace(dev, "mesh_raster", V, F, H, W)
+    face = torch.empty(H, W, dtype=torch.int32, device=dev)
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    bary = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_raster_visibility(_p(v), V, _p(f), F, m, *k, H, W, _CONVENTIONS[convention], near, _CULL[cull], ptr(ws), nbytes,
+                                           _p(face), _p(depth), _p(bary), ptr(counts), stream()), "mesh_raster_visibility")
+    dropped, _ = _read(counts, "rasterize", _BAD_INDEX)                        # the one host read
+    return {'face': face, 'depth': depth, 'bary': bary, 'dropped': dropped}
+
+
+def render_mesh(verts, faces, c2w, intrinsics, H, W, *, colors=None, uvs=None, texture=None, normals=None, shading=None, bg=(0, 0, 0),
+                depth_range=None, **raster_kw):
+    """Shaded preview of a triangle mesh from one camera, on the device: rasterize(verts, faces, c2w, intrinsics, H, W, **raster_kw), then
+    one shading pass.  shading: 'texture' (uvs [F, 3, 2] float32 and texture [R, R, 3] uint8 as bake_texture returns them: bilinear, v up,
+    clamped to the edge), 'colors' (colors [V, 3] uint8, interpolated), 'normals' (0.5 + 0.5 n of the interpolated unit normal; without
+    `normals` these are vertex_normals() of the mesh) or 'depth' (grey, (depth - d0) / (d1 - d0) for depth_range = (d0, d1), by default
+    the smallest and largest hit depth).  shading=None picks texture when uvs and texture are given, else colours, else normals.  Pixels no
+    face covers get `bg` (uint8 RGB).  -> (image [H, W, 3] uint8, mask [H, W] bool, the dict of rasterize), on the device.  Inconsistent
+    arguments raise ValueError."""
+    v, f, n = _mesh_args(verts, faces, normals, "render_mesh")
+    V, F = v.shape[0], f.shape[0]
+    if shading is None:
+        shading = 'texture' if uvs is not None and texture is not None else 'colors' if colors is not None else 'normals'
+    if shading not in _SHADING:
+        raise ValueError(f"render_mesh: shading must be one of {sorted(_SHADING)} or None, got {shading!r}")
+    b = tuple(int(c) for c in bg)
+    if len(b) != 3 or min(b) < 0 or max(b) > 255:
+        raise ValueError(f"render_mesh: bg must be 3 values in [0, 255], got {bg}")
+    dev = v.device
+    col = uv = tex = None
+    R, d0, d1 = 0, 0.0, 1.0
+    if shading == 'colors':
+        if colors is None or tuple(colors.shape) != (V, 3) or colors.dtype != torch.uint8:
+            raise ValueError(f"render_mesh: shading='colors' needs colors [V, 3] uint8 for V = {V}, got "
+                             f"{None if colors is None else (tuple(colors.shape), colors.dtype)}")
+        require_cuda(colors)
+        col = colors.detach().contiguous()
+    elif shading == 'texture':
+        if uvs is None or texture is None:
+            raise ValueError("render_mesh: shading='texture' needs uvs and texture")
+        require_cuda(uvs, texture)
+        if tuple(uvs.shape) != (F, 3, 2):
+            raise ValueError(f"render_mesh: uvs must be [F, 3, 2] for F = {F} faces, got {tuple(uvs.shape)}")
+        if texture.dim() != 3 or texture.shape[0] != texture.shape[1] or texture.shape[2] != 3 or texture.dtype != torch.uint8 or \
+                not 1 <= texture.shape[0] <= 16384:
+            raise ValueError(f"render_mesh: texture must be [R, R, 3] uint8 with 1 <= R <= 16384, got {tuple(texture.shape)} {texture.dtype}")
+        uv, tex, R = uvs.detach().contiguous().float(), texture.detach().contiguous(), texture.shape[0]
+    elif shading == 'depth' and depth_range is not None:
+        d0, d1 = (float(x) for x in depth_range)
+        if not (math.isfinite(d0) and math.isfinite(d1)):
+            raise ValueError(f"render_mesh: depth_range must be two finite values, got {depth_range}")
+    vis = rasterize(v, f, c2w, intrinsics, H, W, **raster_kw)
+    H, W = vis['face'].shape
+    if shading == 'normals' and n is None:
+        n = vertex_normals(v, f)
+    if shading == 'depth' and depth_range is None:
+        hit = vis['depth'][vis['face'] >= 0]
+        if hit.numel():
+            d0, d1 = (float(x) for x in torch.aminmax(hit))
+    image = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    mask = torch.empty(H, W, dtype=torch.uint8, device=dev)
+    check(lib.cnerf_mesh_raster_shade(_p(vis['face']), _p(vis['depth']), _p(vis['bary']), H, W, _p(f), V, F, _SHADING[shading], _p(col), _p(uv),
+                                      _p(tex), R, _p(v), _p(n), d0, d1, (C.c_uint8 * 3)(*b), _p(image), _p(mask), stream()),
+          "mesh_raster_shade")
+    return image, mask != 0, vis
 
 
 def write_png(path, image):

@@ -559,6 +559,18 @@ class NeRFRenderer(nn.Module):
             _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=m['colors'])
         return m
 
+    def render_mesh(self, mesh, c2w, intrinsics, H, W, path=None, **kw):
+        """Preview of an exported mesh from a camera pose, rasterised on the device (mesh.render_mesh, csrc/mesh_raster.hip).  `mesh` is the
+        dict extract_mesh / save_mesh return: its verts, faces, normals, colors, uvs and texture are forwarded (so the texture is shown
+        when the mesh has one, else the vertex colours, else the normals); the camera is generate_rays' (c2w [3, 4] or [4, 4], intrinsics
+        (fx, fy, cx, cy), convention= in **kw).  With `path` the image is also written as a PNG (mesh.write_png).
+        -> (image [H, W, 3] uint8, mask [H, W] bool, the visibility dict of mesh.rasterize)."""
+        image, mask, vis = _mesh.render_mesh(mesh['verts'], mesh['faces'], c2w, intrinsics, H, W, normals=mesh.get('normals'),
+                                             colors=mesh.get('colors'), uvs=mesh.get('uvs'), texture=mesh.get('texture'), **kw)
+        if path is not None:
+            _mesh.write_png(path, image)
+        return image, mask, vis
+
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=2048, **kwargs):
         """renderer.py:1719-1733."""
         _run = self.run_cuda if self.cuda_ray else self.run

@@ -39,7 +39,8 @@ extern "C" {
  *    needs them fails at load on the missing symbol) — cnerf_mesh_components_* and cnerf_mesh_cluster_* (workspace_bytes / _count / _emit);
  *    quadric decimation (additive, same version) — cnerf_mesh_decimate_workspace_bytes / _init / _round / _emit; texture baking (additive,
  *    same version) — cnerf_mesh_atlas_layout / _uvs / _points / _store / _fill; smoothing and normals (additive, same version) —
- *    cnerf_mesh_smooth_workspace_bytes / _init / _steps / _normals. */
+ *    cnerf_mesh_smooth_workspace_bytes / _init / _steps / _normals; mesh rasteriser (additive, same version) —
+ *    cnerf_mesh_raster_workspace_bytes / _visibility / _shade. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -665,6 +666,59 @@ int cnerf_mesh_smooth_steps(const float *verts_in, uint32_t V, uint32_t F, uint3
                             void *ws, uint64_t ws_bytes, float *verts_out, void *stream);
 int cnerf_mesh_smooth_normals(const float *verts, const float *normals_in, uint32_t V, const int32_t *faces, uint32_t F, void *ws,
                               uint64_t ws_bytes, float *normals_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh rasteriser: visibility buffer and shaded previews (customnerf_amd/mesh.py rasterize / render_mesh; csrc/mesh_raster.hip; the reference
+ * has no rasteriser).  One pinhole camera per call, the cameras of cnerf_generate_rays.  All float arithmetic is float32, one rounding per
+ * written operation, in the order written (the build has -ffp-contract=off); divisions and square roots are correctly rounded; rintf and
+ * int64 -> float round to nearest even.
+ *   Camera: c2w_host float32 [3][4] row-major ON THE HOST (m[r][k], t = column 3); fx, fy, cx, cy as in cnerf_generate_rays; convention 0 =
+ *   'nerfstudio' (the camera looks down -z, y up), 1 = 'ngp' (+z forward, y down).  Pixel (ix, iy) is sampled at its centre
+ *   (ix + 0.5, iy + 0.5), where both conventions of cnerf_generate_rays put the ray at level = 1.  Per vertex p: d = p - t,
+ *   c_k = (m[0][k] d0 + m[1][k] d1) + m[2][k] d2; convention 0: z = -c_2, Y = cy + (-1) (fy (c_1 / z)); convention 1: z = c_2,
+ *   Y = cy + fy (c_1 / z); both: X = cx + fx (c_0 / z).  Snapped to 1/256 pixel: xi = (int) rintf(X 256), yi = (int) rintf(Y 256); the centre
+ *   of pixel ix is the fixed-point value 256 ix + 128.  q = 1 / z.
+ *   Dropped faces: a face is dropped whole, never clipped, when one of its vertices has a non-finite z or z < near, a non-finite X or Y, or
+ *   |rintf(X 256)| or |rintf(Y 256)| >= 2^28 (below it every edge function stays inside int64).  counts[0] counts them.  A dropped face
+ *   leaves a hole, never a wrong pixel; near-plane clipping is not done.
+ *   Coverage, exact in int64: A = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) in pixel coordinates (x right, y down).  A == 0 covers nothing.
+ *   A < 0 is front-facing: a mesh wound outwards (marching cubes) appears counter-clockwise on the screen.  cull 0 none, 1 back (skips
+ *   A > 0), 2 front (skips A < 0).  For A < 0 vertices 1 and 2 are swapped, so that A > 0.  For vertex k, i = (k + 1) % 3, j = (k + 2) % 3:
+ *   E_k = (xj - xi)(py - yi) - (yj - yi)(px - xi).  A pixel centre (px, py) is covered when for every k E_k > 0, or E_k == 0 and the edge is
+ *   top-left: dy < 0, or dy == 0 and dx > 0, (dx, dy) = (xj - xi, yj - yi).  Candidate pixels per axis:
+ *   ceil((min - 128) / 256) ... floor((max - 128) / 256), clamped to the image.
+ *   Depth and winner: b_k = (float) E_k / (float) A, iz = (b0 q0 + b1 q1) + b2 q2 with each b_k q_k rounded, depth = 1 / iz (camera-axis
+ *   depth).  The winner of a pixel is the covering face with the smallest 64-bit key (bits(depth) << 32) | face: the nearest, the lower index
+ *   on a tie (depth is positive for near > 0, so the bit order is the numeric order).  Perspective-correct barycentrics of the winner:
+ *   beta_k = (b_k q_k) depth, reported in the INPUT face's vertex order (the swap is undone).
+ *   visibility : verts float32 [V][3], faces int32 [F][3]; per pixel in [H][W] row order: face_out int32 (-1: none), depth_out float32
+ *            (+inf: none), bary_out float32 [3] (0: none).  counts (device uint32 [2]): [0] dropped faces, [1] flags, bit 0 = a face index
+ *            lies outside [0, V) — the outputs are then all-empty; the one host read.  ws 16-byte aligned, >= workspace_bytes(V, F, H, W).
+ *            F = 0 or H W = 0 is accepted (F = 0: every pixel is empty).
+ *   shade  : from face / depth / bary of visibility (a face entry outside [0, F), or one whose indices lie outside [0, V), shades as a
+ *            miss): image RGB8 [H][W][3], mask uint8 [H][W] (255 hit, 0 miss); a miss gets bg_host[3] (uint8 on the host).  mode
+ *            0 vertex colours: colors uint8 [V][3], x = ((beta0 c0 + beta1 c1) + beta2 c2) / 255;
+ *            1 texture: uvs float32 [F][3][2] (corner k of face f, v up) and texture RGB8 [R][R][3] (row 0 at the top, 1 <= R <= 16384) as
+ *              cnerf_mesh_atlas_* make them: (u, v) = (beta0 uv0 + beta1 uv1) + beta2 uv2 per component, px = u R - 0.5,
+ *              py = (1 - v) R - 0.5, X = floor(px), Y = floor(py), wx = px - X, wy = py - Y, texels clamped to the edge,
+ *              x = (((1-wx)(1-wy) T[Y][X] + wx (1-wy) T[Y][X+1]) + (1-wx) wy T[Y+1][X]) + wx wy T[Y+1][X+1]) / 255;
+ *            2 normals: a = (beta0 n0 + beta1 n1) + beta2 n2 (normals float32 [V][3]), l2 = (ax ax + ay ay) + az az; 0 < l2 < inf:
+ *              n = a / sqrt(l2), else the same of (p1 - p0) x (p2 - p0) (verts), else n = 0; x = 0.5 + 0.5 n;
+ *            3 depth: x = (depth - d0) / (d1 - d0) on the three channels.
+ *            To uint8: round(clamp(x, 0, 1) 255), half to even, NaN -> 0, as cnerf_mesh_atlas_store does.  Buffers of other modes may be NULL.
+ *   CNERF_EINVAL: fx or fy zero or non-finite, cx / cy / near non-finite, V, F or H W >= 2^31, convention, cull or mode out of range, a short or
+ *   misaligned ws, R outside [1, 16384] in mode 1.  CNERF_ENULL: a required pointer is NULL.  Both return before any launch.
+ *   The caller's stream and workspace; no allocation, no host sync; the only atomics are 64-bit integer minima on the key buffer and integer
+ *   counters, so the output is bit-reproducible.  workspace_bytes: 8 bytes per pixel + 16 per vertex + 20 per face.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_raster_workspace_bytes(uint32_t V, uint32_t F, uint32_t H, uint32_t W, uint64_t *bytes_host);
+int cnerf_mesh_raster_visibility(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, const float *c2w_host, float fx, float fy,
+                                 float cx, float cy, uint32_t H, uint32_t W, int convention, float near, int cull, void *ws, uint64_t ws_bytes,
+                                 int32_t *face_out, float *depth_out, float *bary_out, uint32_t *counts, void *stream);
+int cnerf_mesh_raster_shade(const int32_t *face, const float *depth, const float *bary, uint32_t H, uint32_t W, const int32_t *faces, uint32_t V,
+                            uint32_t F, int mode, const uint8_t *colors, const float *uvs, const uint8_t *texture, uint32_t R,
+                            const float *verts, const float *normals, float d0, float d1, const uint8_t *bg_host, uint8_t *image, uint8_t *mask,
+                            void *stream);
 
 #ifdef __cplusplus
 }
