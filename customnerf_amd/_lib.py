@@ -112,6 +112,12 @@ SIGNATURES = {
     "cnerf_mesh_raster_workspace_bytes": [u32, u32, u32, u32, vp],
     "cnerf_mesh_raster_visibility": [vp, u32, vp, u32, vp, f32, f32, f32, f32, u32, u32, i32, f32, i32, vp, u64, vp, vp, vp, vp, vp],
     "cnerf_mesh_raster_shade": [vp, vp, vp, u32, u32, vp, u32, u32, i32, vp, vp, vp, u32, vp, vp, f32, f32, vp, vp, vp, vp],
+    "cnerf_mesh_bvh_workspace_bytes": [u32, u32, vp],
+    "cnerf_mesh_bvh_build": [vp, u32, vp, u32, vp, u64, vp, vp],
+    "cnerf_mesh_bvh_closest": [vp, u64, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp],
+    "cnerf_mesh_sample_workspace_bytes": [u32, vp],
+    "cnerf_mesh_sample_count": [vp, u32, vp, u32, f32, vp, u64, vp, vp],
+    "cnerf_mesh_sample_emit": [vp, u32, vp, u32, f32, vp, u64, vp, vp, vp, vp, u64, vp],
     # ---- include/customnerf_sd.h (score-distillation primitives)
     "cnerf_sd_gemm": [vp, vp, u64, vp],
     "cnerf_sd_gemm_workspace_bytes": [vp, vp],

@@ -1,0 +1,688 @@
+// Closest-point queries against a triangle mesh through a bounding-volume hierarchy, and a deterministic surface sampler (cnerf_mesh_bvh_*,
+// cnerf_mesh_sample_*): what mesh.distance() measures the deviation between two meshes with.  Same conventions as the other mesh passes: the
+// caller's stream, buffers and workspace, no allocation, no host synchronisation, no float atomics.  The rules (which faces take part, the
+// point-triangle rule, the sampler's enumeration) are in include/customnerf_hip.h; tests/bvh_restatement.py restates them bit for bit.
+//
+// Build
+//   k_bvh_bounds  : per face: index and finiteness check (flags), the number of faces that take part, the box of their centroids (integer
+//                   maxima of order-preserving codes: any order of arrival gives the same box)
+//   k_bvh_keys    : per face: key = (30-bit Morton code of the centroid in that box << 32) | face; a face left out gets Morton 0xffffffff
+//   k_bvh_hist / k_bvh_scan / k_bvh_scatter : LSD radix sort, 8 bits per pass, BV_TILE keys per workgroup.  hist: the tile's 256 digit counts;
+//                   scan: mc_scan_totals over the digit-major table (digits 0..127 in .x, 128..255 in .y, the .x total carried into .y);
+//                   scatter: the stable rank of a key = its digit's offset + the keys of that digit before it in the tile.  Counts and ranks
+//                   come from wave ballots (the lanes holding my digit), one writer per (round, wave, digit): no atomics, so every run moves
+//                   every key to the same slot.  The keys are made in face order, so they are already sorted by their low word: the four
+//                   passes over bits 32..63 complete the order of the whole 64-bit key.
+//   k_bvh_leaves  : per sorted slot: the triangle's record (nine coordinates, face index; 48 B), padded with NaN records to whole leaves;
+//                   counts out
+//   k_bvh_fit     : one launch per level, deepest first: the boxes.  The tree is implicit and balanced over the sorted order: leaves of
+//                   BV_LEAF records, NL of them, depth D = ceil(log2 NL); node (d, j) covers leaves [j NL >> d, (j + 1) NL >> d) and sits at
+//                   heap index 2^d + j (children 2 i and 2 i + 1).  No pointers, no atomics, no ordering between workgroups.
+// Query
+//   k_bvh_closest : one thread per query point, a stackless walk: the path is the heap index, a bit per level says whether the sibling is
+//                   still to be visited (nearer child first), so the traversal state is two registers — nothing in LDS or scratch.
+//                   Conservative under rounding: a leaf box is grown by 2^-18 of its largest |coordinate| and a subtree is skipped only when
+//                   its lower bound, shrunk by 2^-16, is strictly above the best d^2; ties are always visited.  Why that is enough: the
+//                   computed closest point x can leave the triangle, and for a far query by much more than ulps (the face region
+//                   divides by (va + vb) + vc, whose relative error grows like 2^-23 (|p| / edge)^2).  But an error in v or w moves x
+//                   inside the triangle's plane (on an edge: along the edge's line), and p - x of the exact answer is perpendicular
+//                   to that plane (line), so such an excursion can only lengthen the computed distance.  What can shorten it is the
+//                   rounding of x's coordinates — ulps of the coordinates, covered by the grown box — and of the d^2 arithmetic — ulps
+//                   of d^2, covered by the shrink; far away d^2 is dominated by |p|^2 and the shrink dwarfs both.  The tests demand
+//                   equality with brute force from the surface out to thousands of diagonals.
+// Sampler
+//   k_sample_count / k_sample_scan / k_sample_emit : k^2 per face -> workgroup totals -> offsets -> one thread per sample (a binary search in
+//                   the workgroup's 256 prefix sums finds its face), so the writes are coalesced whatever the mix of face sizes.
+#include "mesh_common.h"
+
+#define BV_BAD_INDEX 1u
+#define BV_NONFINITE 2u
+#define BV_CLAMPED 4u
+#define BV_LEAF 4u
+#define BV_KPT 4
+#define BV_TILE (MC_BLOCK * BV_KPT)
+#define BV_NOFACE 0xffffffffu
+#define BV_GROW 3.814697265625e-06f                              // 2^-18
+#define BV_SHRINK 0.9999847412109375f                            // 1 - 2^-16
+#define BV_MAX_K 256.0f
+
+namespace {
+
+enum { H_N = 0, H_FLAGS = 1, H_CARRY = 2, H_BOX = 4, H_TOTAL = 10 };   // uint32 slots of the header (H_BOX: 6, H_TOTAL: 2)
+
+typedef unsigned long long bv_key;
+
+struct BvPtr {
+    uint32_t *hdr;
+    float4 *tri;                                                 // [BV_LEAF NLmax][3]
+    float4 *box;                                                 // [2^(Dmax + 1)][2], heap index, [0] unused
+    bv_key *keys[2];                                             // [F] each
+    uint2 *sums;                                                 // [128 tiles]
+};
+
+inline uint32_t bv_max_leaves(uint64_t F) { return (uint32_t)(F ? cn_div_up64(F, BV_LEAF) : 1); }
+inline uint32_t bv_max_depth(uint64_t F) {
+    uint32_t d = 0;
+    while ((1ull << d) < bv_max_leaves(F)) ++d;
+    return d;
+}
+inline uint32_t bv_tiles(uint64_t F) { return (uint32_t)cn_div_up64(F ? F : 1, BV_TILE); }
+
+// header | records | boxes (what a query reads) | two key buffers | digit table
+uint64_t bv_carve(void *ws, uint64_t F, BvPtr &p) {
+    MeshCarve c(ws);
+    p.hdr = c.header();
+    p.tri = c.take<float4>(3ull * BV_LEAF * bv_max_leaves(F));
+    p.box = c.take<float4>(2ull << (bv_max_depth(F) + 1));
+    p.keys[0] = c.take<bv_key>(F);
+    p.keys[1] = c.take<bv_key>(F);
+    p.sums = c.take<uint2>(128ull * bv_tiles(F));
+    return c.total();
+}
+
+__device__ __forceinline__ bool bv_finite(float x) { return fabsf(x) < INFINITY; }
+
+// the nine coordinates of face f; false when it takes no part (flag tells why)
+__device__ __forceinline__ bool bv_face(const float *__restrict__ verts, const int32_t *__restrict__ faces, uint32_t f, uint32_t V, float x[9],
+                                        uint32_t &flag) {
+    uint32_t t[3];
+    if (!mesh_face(faces, f, V, t)) {
+        flag = BV_BAD_INDEX;
+        return false;
+    }
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            x[3 * k + a] = verts[3 * (uint64_t)t[k] + a];
+            fin &= bv_finite(x[3 * k + a]);
+        }
+    flag = fin ? 0u : BV_NONFINITE;
+    return fin;
+}
+
+__device__ __forceinline__ float bv_centroid(const float x[9], int a) { return ((x[a] + x[3 + a]) + x[6 + a]) / 3.0f; }
+
+// order-preserving code of a float, and back
+__device__ __forceinline__ uint32_t bv_ord(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float bv_unord(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o); }
+
+__device__ __forceinline__ void bv_shape(uint32_t n, uint32_t &NL, uint32_t &D) {
+    NL = (n + BV_LEAF - 1) / BV_LEAF;
+    D = NL <= 1 ? 0 : 32 - __clz(NL - 1);
+}
+
+// ------------------------------------------------------------------------------------------------ build: keys
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_bounds(const float *__restrict__ verts, const int32_t *__restrict__ faces, uint32_t V, uint32_t F,
+                                                         BvPtr p) {
+    __shared__ uint32_t red[MC_WAVES][6];
+    const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
+    float x[9];
+    uint32_t flag = 0, m[6] = {0, 0, 0, 0, 0, 0};
+    const bool ok = f < F && bv_face(verts, faces, f, V, x, flag);
+    if (ok) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t o = bv_ord(bv_centroid(x, a));
+            m[a] = ~o;                                           // the minimum as a maximum of the complement: a zeroed header is neutral
+            m[3 + a] = o;
+        }
+    }
+    const uint64_t bok = __ballot(ok);
+    const uint32_t bfl = (__ballot(flag & BV_BAD_INDEX) ? BV_BAD_INDEX : 0u) | (__ballot(flag & BV_NONFINITE) ? BV_NONFINITE : 0u);
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        for (int o = CN_WAVE / 2; o; o >>= 1) m[k] = max(m[k], (uint32_t)__shfl_xor((int)m[k], o));
+    const uint32_t w = threadIdx.x / CN_WAVE;
+    if (cn_lane() == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) red[w][k] = m[k];
+        if (bok) atomicAdd(p.hdr + H_N, (uint32_t)__popcll(bok));
+        if (bfl) atomicOr(p.hdr + H_FLAGS, bfl);
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        uint32_t r = 0;
+        for (int j = 0; j < MC_WAVES; ++j) r = max(r, red[j][threadIdx.x]);
+        if (r) atomicMax(p.hdr + H_BOX + threadIdx.x, r);
+    }
+}
+
+__device__ __forceinline__ uint32_t bv_spread(uint32_t v) {     // 10 bits -> every third bit
+    v = (v | (v << 16)) & 0x030000ffu;
+    v = (v | (v << 8)) & 0x0300f00fu;
+    v = (v | (v << 4)) & 0x030c30c3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_keys(const float *__restrict__ verts, const int32_t *__restrict__ faces, uint32_t V, uint32_t F,
+                                                       BvPtr p) {
+    const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    float x[9];
+    uint32_t flag, code = 0xffffffffu;
+    if (bv_face(verts, faces, f, V, x, flag)) {
+        code = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float lo = bv_unord(~p.hdr[H_BOX + a]), hi = bv_unord(p.hdr[H_BOX + 3 + a]);
+            const float t = ((bv_centroid(x, a) - lo) / (hi - lo)) * 1024.0f;
+            const uint32_t q = t >= 0.0f ? (uint32_t)fminf(t, 1023.0f) : 0u;      // NaN (a flat box) -> 0
+            code |= bv_spread(q) << a;
+        }
+    }
+    p.keys[0][f] = ((bv_key)code << 32) | f;
+}
+
+// ------------------------------------------------------------------------------------------------ build: radix sort
+// This workgroup's tile: key[k] = element tile + k MC_BLOCK + thread, rank[k] = the keys with its digit before it in its wave's round,
+// cnt[k][w][digit] = the keys with that digit in round k of wave w.  Every thread of the block must call it.
+__device__ __forceinline__ void bv_digits(const bv_key *__restrict__ keys, uint32_t N, uint32_t shift, bv_key key[BV_KPT], uint32_t digit[BV_KPT],
+                                          uint32_t rank[BV_KPT], uint32_t (*cnt)[MC_WAVES][256]) {
+    for (uint32_t i = threadIdx.x; i < BV_KPT * MC_WAVES * 256; i += MC_BLOCK) (&cnt[0][0][0])[i] = 0;
+    __syncthreads();
+    const uint32_t w = threadIdx.x / CN_WAVE;
+#pragma unroll
+    for (int k = 0; k < BV_KPT; ++k) {
+        const uint64_t i = (uint64_t)blockIdx.x * BV_TILE + (uint32_t)k * MC_BLOCK + threadIdx.x;
+        const bool valid = i < N;
+        key[k] = valid ? keys[i] : 0;
+        const uint32_t d = (uint32_t)(key[k] >> shift) & 255u;
+        uint64_t peers = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const uint64_t bal = __ballot((d >> b) & 1u);
+            peers &= ((d >> b) & 1u) ? bal : ~bal;
+        }
+        digit[k] = valid ? d : 256u;
+        rank[k] = mc_rank(peers);
+        if (valid && rank[k] == 0) cnt[k][w][d] = (uint32_t)__popcll(peers);
+    }
+    __syncthreads();
+}
+
+// digit t of tile b in the digit-major table: digits below 128 in .x, the others in .y
+__device__ __forceinline__ uint32_t &bv_slot(uint2 *sums, uint32_t tiles, uint32_t t, uint32_t b) {
+    uint2 &e = sums[(uint64_t)(t & 127u) * tiles + b];
+    return (t >> 7) ? e.y : e.x;
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_hist(const bv_key *__restrict__ keys, uint32_t N, uint32_t shift, BvPtr p) {
+    __shared__ uint32_t cnt[BV_KPT][MC_WAVES][256];
+    bv_key key[BV_KPT];
+    uint32_t digit[BV_KPT], rank[BV_KPT];
+    bv_digits(keys, N, shift, key, digit, rank, cnt);
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < BV_KPT; ++k)
+#pragma unroll
+        for (int w = 0; w < MC_WAVES; ++w) s += cnt[k][w][threadIdx.x];
+    bv_slot(p.sums, gridDim.x, threadIdx.x, blockIdx.x) = s;
+}
+
+__global__ __launch_bounds__(MC_SCAN_BLOCK) void k_bvh_scan(uint32_t entries, BvPtr p) {
+    uint64_t cx, cy;
+    mc_scan_totals(p.sums, entries, cx, cy);                     // cx + cy = N < 2^31
+    if (threadIdx.x == 0) p.hdr[H_CARRY] = (uint32_t)cx;
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_scatter(const bv_key *__restrict__ keys, bv_key *__restrict__ out, uint32_t N, uint32_t shift,
+                                                          BvPtr p) {
+    __shared__ uint32_t cnt[BV_KPT][MC_WAVES][256];
+    bv_key key[BV_KPT];
+    uint32_t digit[BV_KPT], rank[BV_KPT];
+    bv_digits(keys, N, shift, key, digit, rank, cnt);
+    uint32_t base = bv_slot(p.sums, gridDim.x, threadIdx.x, blockIdx.x) + ((threadIdx.x >> 7) ? p.hdr[H_CARRY] : 0u);
+#pragma unroll
+    for (int k = 0; k < BV_KPT; ++k)
+#pragma unroll
+        for (int w = 0; w < MC_WAVES; ++w) {
+            const uint32_t c = cnt[k][w][threadIdx.x];
+            cnt[k][w][threadIdx.x] = base;
+            base += c;
+        }
+    __syncthreads();
+    const uint32_t w = threadIdx.x / CN_WAVE;
+#pragma unroll
+    for (int k = 0; k < BV_KPT; ++k) {
+        if (digit[k] > 255u) continue;
+        const uint32_t dst = cnt[k][w][digit[k]] + rank[k];
+        if (dst < N) out[dst] = key[k];                          // always: the offsets of N keys end at N
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ build: records and boxes
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_leaves(const float *__restrict__ verts, const int32_t *__restrict__ faces, uint32_t V, uint32_t F,
+                                                         BvPtr p, uint32_t *__restrict__ counts) {
+    const uint32_t i = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = p.hdr[H_N];
+    if (i == 0) {
+        counts[0] = n;
+        counts[1] = p.hdr[H_FLAGS];
+    }
+    if (i >= BV_LEAF * ((n + BV_LEAF - 1) / BV_LEAF)) return;
+    float x[9];
+    uint32_t f = BV_NOFACE, flag;
+    if (i < n) {
+        f = (uint32_t)p.keys[0][i];
+        if (f >= F || !bv_face(verts, faces, f, V, x, flag)) f = BV_NOFACE;      // never: the first n keys are faces that take part
+    }
+    if (f == BV_NOFACE)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) x[k] = __uint_as_float(0x7fc00000u);
+    float4 *r = p.tri + 3 * (uint64_t)i;
+    r[0] = make_float4(x[0], x[1], x[2], x[3]);
+    r[1] = make_float4(x[4], x[5], x[6], x[7]);
+    r[2] = make_float4(x[8], __uint_as_float(f), 0.0f, 0.0f);
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_fit(uint32_t d, BvPtr p) {
+    const uint32_t j = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = p.hdr[H_N];
+    uint32_t NL, D;
+    bv_shape(n, NL, D);
+    if (!n || d > D || j >= (1u << d)) return;
+    const uint64_t idx = ((uint64_t)1 << d) + j;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (d == D) {
+        const uint32_t l0 = (uint32_t)(((uint64_t)j * NL) >> D), l1 = (uint32_t)((((uint64_t)j + 1) * NL) >> D);
+        for (uint32_t l = l0; l < l1; ++l)                       // none or one
+            for (uint32_t t = 0; t < BV_LEAF; ++t) {
+                const float4 *r = p.tri + 3 * ((uint64_t)l * BV_LEAF + t);
+                const float4 r0 = r[0], r1 = r[1], r2 = r[2];
+                if (__float_as_uint(r2.y) == BV_NOFACE) continue;
+                const float x[9] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x};
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    lo[k % 3] = fminf(lo[k % 3], x[k]);
+                    hi[k % 3] = fmaxf(hi[k % 3], x[k]);
+                }
+            }
+        if (lo[0] <= hi[0]) {
+            float s = 0.0f;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) s = fmaxf(s, fmaxf(fabsf(lo[a]), fabsf(hi[a])));
+            const float g = s * BV_GROW;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                lo[a] -= g;
+                hi[a] += g;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float4 a = p.box[2 * (2 * idx + c)], b = p.box[2 * (2 * idx + c) + 1];
+            lo[0] = fminf(lo[0], a.x);
+            lo[1] = fminf(lo[1], a.y);
+            lo[2] = fminf(lo[2], a.z);
+            hi[0] = fmaxf(hi[0], b.x);
+            hi[1] = fmaxf(hi[1], b.y);
+            hi[2] = fmaxf(hi[2], b.z);
+        }
+    }
+    p.box[2 * idx] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+    p.box[2 * idx + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+}
+
+// ------------------------------------------------------------------------------------------------ query
+__device__ __forceinline__ float bv_dot(const float u[3], const float v[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
+
+// Closest point of triangle (a, b, c) to p (Ericson, Real-Time Collision Detection, 5.1.5), the regions tested in the order A, B, edge AB, C,
+// edge AC, edge BC, face: cp, its barycentrics, and d^2 = (dx^2 + dy^2) + dz^2 from the rounded cp.  The order of operations is the header's.
+__device__ __forceinline__ float bv_closest(const float p[3], const float a[3], const float b[3], const float c[3], float cp[3], float bary[3]) {
+    float ab[3], ac[3], ap[3], bp[3], cq[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        ab[k] = b[k] - a[k];
+        ac[k] = c[k] - a[k];
+        ap[k] = p[k] - a[k];
+        bp[k] = p[k] - b[k];
+        cq[k] = p[k] - c[k];
+    }
+    const float d1 = bv_dot(ab, ap), d2 = bv_dot(ac, ap), d3 = bv_dot(ab, bp), d4 = bv_dot(ac, bp), d5 = bv_dot(ab, cq), d6 = bv_dot(ac, cq);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    if (d1 <= 0.0f && d2 <= 0.0f) {
+        bary[0] = 1.0f; bary[1] = 0.0f; bary[2] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cp[k] = a[k];
+    } else if (d3 >= 0.0f && d4 <= d3) {
+        bary[0] = 0.0f; bary[1] = 1.0f; bary[2] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cp[k] = b[k];
+    } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
+        const float v = d1 / (d1 - d3);
+        bary[0] = 1.0f - v; bary[1] = v; bary[2] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cp[k] = a[k] + v * ab[k];
+    } else if (d6 >= 0.0f && d5 <= d6) {
+        bary[0] = 0.0f; bary[1] = 0.0f; bary[2] = 1.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cp[k] = c[k];
+    } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
+        const float w = d2 / (d2 - d6);
+        bary[0] = 1.0f - w; bary[1] = 0.0f; bary[2] = w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cp[k] = a[k] + w * ac[k];
+    } else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {
+        const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+        bary[0] = 0.0f; bary[1] = 1.0f - w; bary[2] = w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cp[k] = b[k] + w * (c[k] - b[k]);
+    } else {
+        const float denom = 1.0f / ((va + vb) + vc), v = vb * denom, w = vc * denom;
+        bary[0] = (1.0f - v) - w; bary[1] = v; bary[2] = w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cp[k] = (a[k] + ab[k] * v) + ac[k] * w;
+    }
+    const float dx = p[0] - cp[0], dy = p[1] - cp[1], dz = p[2] - cp[2];
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// the shrunk lower bound of the squared distance from p to the box of node idx
+__device__ __forceinline__ float bv_bound(const float4 *__restrict__ box, uint32_t idx, const float p[3]) {
+    const float4 lo = box[2 * (uint64_t)idx], hi = box[2 * (uint64_t)idx + 1];
+    const float ex = fmaxf(fmaxf(lo.x - p[0], p[0] - hi.x), 0.0f), ey = fmaxf(fmaxf(lo.y - p[1], p[1] - hi.y), 0.0f);
+    const float ez = fmaxf(fmaxf(lo.z - p[2], p[2] - hi.z), 0.0f);
+    return ((ex * ex + ey * ey) + ez * ez) * BV_SHRINK;
+}
+
+__device__ __forceinline__ uint32_t bv_record(const float4 *__restrict__ tri, uint64_t slot, float a[3], float b[3], float c[3]) {
+    const float4 r0 = tri[3 * slot], r1 = tri[3 * slot + 1], r2 = tri[3 * slot + 2];
+    a[0] = r0.x; a[1] = r0.y; a[2] = r0.z;
+    b[0] = r0.w; b[1] = r1.x; b[2] = r1.y;
+    c[0] = r1.z; c[1] = r1.w; c[2] = r2.x;
+    return __float_as_uint(r2.y);
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_closest(BvPtr ws, uint32_t F, const float *__restrict__ points, uint32_t Q, float *__restrict__ dist2,
+                                                          int32_t *__restrict__ face, float *__restrict__ point, float *__restrict__ bary,
+                                                          unsigned long long *__restrict__ stats) {
+    const uint32_t q = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = min(ws.hdr[H_N], F);                      // a workspace that was never built must not send the walk out of it
+    uint32_t NL, D;
+    bv_shape(n, NL, D);
+    float p[3] = {0.0f, 0.0f, 0.0f};
+    bool live = q < Q && n;
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p[k] = points[3 * (uint64_t)q + k];
+            live &= bv_finite(p[k]);
+        }
+    }
+    float best = INFINITY;
+    uint32_t bestf = BV_NOFACE, bests = 0, visits = 0, tests = 0;
+    if (live) {
+        uint32_t node = 1, depth = 0, pending = 0;               // pending bit i: the sibling of the path's node i levels up is still to come
+        ++visits;
+        // until the first triangle is tested best is +inf, and the bound of an empty node (+inf) is not strictly above it: such a node is
+        // entered and counted in `visits`; its leaf range is empty, so nothing else changes
+        bool go = !(bv_bound(ws.box, 1, p) > best);
+        while (go) {
+            bool descend = false;
+            if (depth == D) {
+                const uint32_t j = node - (1u << D);
+                const uint32_t l0 = (uint32_t)(((uint64_t)j * NL) >> D), l1 = (uint32_t)((((uint64_t)j + 1) * NL) >> D);
+                if (l0 < l1) {
+#pragma unroll
+                    for (uint32_t t = 0; t < BV_LEAF; ++t) {
+                        float a[3], b[3], c[3], cp[3], br[3];
+                        const uint64_t slot = (uint64_t)l0 * BV_LEAF + t;
+                        const uint32_t f = bv_record(ws.tri, slot, a, b, c);
+                        if (f == BV_NOFACE) continue;
+                        ++tests;
+                        const float d2 = bv_closest(p, a, b, c, cp, br);
+                        if (d2 < best || (d2 == best && f < bestf)) {   // false for a NaN
+                            best = d2;
+                            bestf = f;
+                            bests = (uint32_t)slot;
+                        }
+                    }
+                }
+            } else {
+                visits += 2;
+                const float b0 = bv_bound(ws.box, 2 * node, p), b1 = bv_bound(ws.box, 2 * node + 1, p);
+                const bool ok0 = !(b0 > best), ok1 = !(b1 > best);
+                if (ok0 || ok1) {
+                    const uint32_t first = (ok0 && ok1) ? (b1 < b0 ? 1u : 0u) : (ok1 ? 1u : 0u);
+                    pending = (pending << 1) | ((ok0 && ok1) ? 1u : 0u);
+                    node = 2 * node + first;
+                    ++depth;
+                    descend = true;
+                }
+            }
+            while (!descend) {                                   // back up to the nearest sibling still to come; its box is tested again
+                if (!pending) {
+                    go = false;
+                    break;
+                }
+                const uint32_t k = (uint32_t)__ffs((int)pending) - 1;
+                node = (node >> k) ^ 1u;
+                depth -= k;
+                pending = (pending >> k) & ~1u;
+                ++visits;
+                descend = !(bv_bound(ws.box, node, p) > best);
+            }
+        }
+    }
+    if (q < Q) {
+        const bool hit = bestf != BV_NOFACE;
+        dist2[q] = best;
+        face[q] = hit ? (int32_t)bestf : -1;
+        if (point || bary) {
+            float cp[3] = {0.0f, 0.0f, 0.0f}, br[3] = {0.0f, 0.0f, 0.0f};
+            if (hit) {
+                float a[3], b[3], c[3];
+                bv_record(ws.tri, bests, a, b, c);
+                bv_closest(p, a, b, c, cp, br);
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (point) point[3 * (uint64_t)q + k] = cp[k];
+                if (bary) bary[3 * (uint64_t)q + k] = br[k];
+            }
+        }
+    }
+    if (stats) {                                                 // one pair of adds per wave
+        const uint32_t sv = cn_wave_sum(visits), st = cn_wave_sum(tests);
+        if (cn_lane() == 0 && (sv | st)) {
+            atomicAdd(stats, (unsigned long long)sv);
+            atomicAdd(stats + 1, (unsigned long long)st);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ sampler
+struct SmpPtr {
+    uint32_t *hdr;
+    uint2 *sums;                                                 // [F / 256]: x = the workgroup's samples
+};
+
+uint64_t smp_carve(void *ws, uint64_t F, SmpPtr &p) {
+    MeshCarve c(ws);
+    p.hdr = c.header();
+    p.sums = c.take<uint2>(cn_div_up64(F ? F : 1, MC_BLOCK));
+    return c.total();
+}
+
+// area and subdivision order of a face that takes part
+__device__ __forceinline__ uint32_t smp_order(const float x[9], float spacing, float &area, bool &clamped) {
+    const float e1x = x[3] - x[0], e1y = x[4] - x[1], e1z = x[5] - x[2], e2x = x[6] - x[0], e2y = x[7] - x[1], e2z = x[8] - x[2];
+    const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+    area = 0.5f * sqrtf((cx * cx + cy * cy) + cz * cz);
+    const float r = ceilf(sqrtf(2.0f * area) / spacing);
+    clamped = r > BV_MAX_K;
+    return clamped ? (uint32_t)BV_MAX_K : (r >= 1.0f ? (uint32_t)r : 1u);          // NaN -> 1
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_sample_count(const float *__restrict__ verts, const int32_t *__restrict__ faces, uint32_t V, uint32_t F,
+                                                           float spacing, SmpPtr p) {
+    __shared__ uint32_t red[MC_WAVES];
+    const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
+    float x[9], area;
+    uint32_t flag = 0, cnt = 0;
+    if (f < F && bv_face(verts, faces, f, V, x, flag)) {
+        bool clamped;
+        const uint32_t k = smp_order(x, spacing, area, clamped);
+        cnt = k * k;
+        if (clamped) flag = BV_CLAMPED;
+    }
+    const uint32_t bfl = (__ballot(flag & BV_BAD_INDEX) ? BV_BAD_INDEX : 0u) | (__ballot(flag & BV_NONFINITE) ? BV_NONFINITE : 0u) |
+                         (__ballot(flag & BV_CLAMPED) ? BV_CLAMPED : 0u);
+    if (bfl && cn_lane() == 0) atomicOr(p.hdr + H_FLAGS, bfl);
+    uint32_t tot;
+    mc_block_excl(cnt, red, tot);                                // <= 256 * 65536
+    if (threadIdx.x == 0) p.sums[blockIdx.x] = make_uint2(tot, 0u);
+}
+
+__global__ __launch_bounds__(MC_SCAN_BLOCK) void k_sample_scan(uint32_t nblk, SmpPtr p, unsigned long long *__restrict__ counts) {
+    uint64_t cx, cy;
+    mc_scan_totals(p.sums, nblk, cx, cy);
+    if (threadIdx.x == 0) {
+        p.hdr[H_TOTAL] = (uint32_t)cx;
+        p.hdr[H_TOTAL + 1] = (uint32_t)(cx >> 32);
+        counts[0] = cx;
+        counts[1] = p.hdr[H_FLAGS];
+    }
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_sample_emit(const float *__restrict__ verts, const int32_t *__restrict__ faces, uint32_t V, uint32_t F,
+                                                          float spacing, SmpPtr p, float *__restrict__ points, int32_t *__restrict__ face,
+                                                          float *__restrict__ bary, float *__restrict__ weight, uint64_t max_samples) {
+    __shared__ uint32_t red[MC_WAVES], start[MC_BLOCK], order[MC_BLOCK];
+    __shared__ float fx[9][MC_BLOCK], fw[MC_BLOCK];
+    if (p.hdr[H_TOTAL + 1]) return;                              // 2^32 samples or more: the 32-bit offsets do not hold them
+    const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
+    float x[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, area = 0.0f;
+    uint32_t flag, k = 0;
+    if (f < F && bv_face(verts, faces, f, V, x, flag)) {
+        bool clamped;
+        k = smp_order(x, spacing, area, clamped);
+    }
+    uint32_t tot;
+    start[threadIdx.x] = mc_block_excl(k * k, red, tot);
+    order[threadIdx.x] = k;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) fx[i][threadIdx.x] = x[i];
+    fw[threadIdx.x] = k ? area / (float)(k * k) : 0.0f;
+    __syncthreads();
+    const uint64_t base = p.sums[blockIdx.x].x;
+    for (uint32_t s = threadIdx.x; s < tot; s += MC_BLOCK) {
+        const uint64_t g = base + s;
+        if (g >= max_samples) break;
+        uint32_t j = 0;                                          // the last face whose start is <= s: the one that holds sample s
+#pragma unroll
+        for (uint32_t h = MC_BLOCK / 2; h; h >>= 1)
+            if (start[j + h] <= s) j += h;
+        const uint32_t kk = order[j], m = s - start[j];
+        // row i holds 2 (kk - i) - 1 sub-triangles and starts at i (2 kk - i): i = kk - ceil(sqrt(kk^2 - m))
+        const uint32_t t = kk * kk - m;
+        uint32_t r = (uint32_t)sqrtf((float)t);
+        r += r * r < t ? 1u : 0u;
+        const uint32_t i = kk - r, rem = m - i * (2 * kk - i), up = rem & 1u, jj = rem >> 1;
+        const float den = (float)(3 * kk);
+        const float u = (float)(3 * i + 1 + up) / den, v = (float)(3 * jj + 1 + up) / den, b0 = (1.0f - u) - v;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) points[3 * g + a] = (fx[a][j] + u * (fx[3 + a][j] - fx[a][j])) + v * (fx[6 + a][j] - fx[a][j]);
+        bary[3 * g] = b0;
+        bary[3 * g + 1] = u;
+        bary[3 * g + 2] = v;
+        face[g] = (int32_t)(blockIdx.x * MC_BLOCK + j);
+        weight[g] = fw[j];
+    }
+}
+
+bool bv_sizes_ok(uint32_t V, uint32_t F) { return V < (1u << 31) && F < (1u << 31); }
+
+}  // namespace
+
+extern "C" {
+
+int cnerf_mesh_bvh_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host) {
+    if (!bytes_host) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F)) return CNERF_EINVAL;
+    BvPtr p;
+    *bytes_host = bv_carve(nullptr, F, p);
+    return CNERF_OK;
+}
+
+int cnerf_mesh_bvh_build(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, void *ws, uint64_t ws_bytes, uint32_t *counts,
+                         void *stream) {
+    if (!ws || !counts || (F && (!faces || (V && !verts)))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F)) return CNERF_EINVAL;
+    BvPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, bv_carve(ws, F, p))) return rc;
+    hipStream_t st = CN_STREAM(stream);
+    if (const int rc = (int)hipMemsetAsync(p.hdr, 0, 64 * sizeof(uint32_t), st)) return rc;
+    if (const int rc = (int)hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), st)) return rc;
+    if (!F) return CNERF_OK;
+    hipLaunchKernelGGL(k_bvh_bounds, mesh_grid(F), dim3(MC_BLOCK), 0, st, verts, faces, V, F, p);
+    hipLaunchKernelGGL(k_bvh_keys, mesh_grid(F), dim3(MC_BLOCK), 0, st, verts, faces, V, F, p);
+    const uint32_t tiles = bv_tiles(F);
+    for (uint32_t pass = 0; pass < 4; ++pass) {                  // keys[0] -> [1] -> [0] -> [1] -> [0]
+        const bv_key *src = p.keys[pass & 1];
+        const uint32_t shift = 32 + 8 * pass;
+        hipLaunchKernelGGL(k_bvh_hist, dim3(tiles), dim3(MC_BLOCK), 0, st, src, F, shift, p);
+        hipLaunchKernelGGL(k_bvh_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, 128u * tiles, p);
+        hipLaunchKernelGGL(k_bvh_scatter, dim3(tiles), dim3(MC_BLOCK), 0, st, src, p.keys[(pass + 1) & 1], F, shift, p);
+    }
+    hipLaunchKernelGGL(k_bvh_leaves, mesh_grid((uint64_t)BV_LEAF * bv_max_leaves(F)), dim3(MC_BLOCK), 0, st, verts, faces, V, F, p, counts);
+    for (int d = (int)bv_max_depth(F); d >= 0; --d)
+        hipLaunchKernelGGL(k_bvh_fit, mesh_grid(1ull << d), dim3(MC_BLOCK), 0, st, (uint32_t)d, p);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_bvh_closest(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const float *points, uint32_t Q, float *dist2,
+                           int32_t *face, float *point, float *bary, uint64_t *stats, void *stream) {
+    if (!ws || (Q && (!points || !dist2 || !face))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F) || Q >= (1u << 31)) return CNERF_EINVAL;
+    BvPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, bv_carve((void *)ws, F, p))) return rc;
+    if (!Q) return CNERF_OK;
+    hipLaunchKernelGGL(k_bvh_closest, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, F, points, Q, dist2, face, point, bary,
+                       (unsigned long long *)stats);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_sample_workspace_bytes(uint32_t F, uint64_t *bytes_host) {
+    if (!bytes_host) return CNERF_ENULL;
+    if (F >= (1u << 31)) return CNERF_EINVAL;
+    SmpPtr p;
+    *bytes_host = smp_carve(nullptr, F, p);
+    return CNERF_OK;
+}
+
+int cnerf_mesh_sample_count(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, float spacing, void *ws, uint64_t ws_bytes,
+                            uint64_t *counts, void *stream) {
+    if (!ws || !counts || (F && (!faces || (V && !verts)))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F) || !(spacing > 0.0f) || !(spacing < INFINITY)) return CNERF_EINVAL;
+    SmpPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, smp_carve(ws, F, p))) return rc;
+    hipStream_t st = CN_STREAM(stream);
+    if (const int rc = (int)hipMemsetAsync(p.hdr, 0, 64 * sizeof(uint32_t), st)) return rc;
+    if (const int rc = (int)hipMemsetAsync(counts, 0, 2 * sizeof(uint64_t), st)) return rc;
+    if (!F) return CNERF_OK;
+    hipLaunchKernelGGL(k_sample_count, mesh_grid(F), dim3(MC_BLOCK), 0, st, verts, faces, V, F, spacing, p);
+    hipLaunchKernelGGL(k_sample_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, (uint32_t)cn_div_up64(F, MC_BLOCK), p, (unsigned long long *)counts);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_sample_emit(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, float spacing, void *ws, uint64_t ws_bytes,
+                           float *points, int32_t *face, float *bary, float *weight, uint64_t max_samples, void *stream) {
+    if (!ws || (F && (!faces || (V && !verts))) || (F && max_samples && (!points || !face || !bary || !weight))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F) || !(spacing > 0.0f) || !(spacing < INFINITY)) return CNERF_EINVAL;
+    SmpPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, smp_carve(ws, F, p))) return rc;
+    if (!F || !max_samples) return CNERF_OK;
+    hipLaunchKernelGGL(k_sample_emit, mesh_grid(F), dim3(MC_BLOCK), 0, CN_STREAM(stream), verts, faces, V, F, spacing, p, points, face, bary, weight,
+                       max_samples);
+    return cn_launch_status();
+}
+
+}  // extern "C"

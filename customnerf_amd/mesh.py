@@ -2,7 +2,8 @@
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
 face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU
 (csrc/mesh_texture.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
-shaded images), a binary PLY writer and an OBJ + MTL + PNG writer.
+shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them
+(csrc/mesh_bvh.hip), a binary PLY writer and an OBJ + MTL + PNG writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -478,6 +479,161 @@ def render_mesh(verts, faces, c2w, intrinsics, H, W, *, colors=None, uvs=None, t
                                       _p(tex), R, _p(v), _p(n), d0, d1, (C.c_uint8 * 3)(*b), _p(image), _p(mask), stream()),
           "mesh_raster_shade")
     return image, mask != 0, vis
+
+
+def bvh_workspace_bytes(V, F):
+    return _bytes("mesh_bvh", int(V), int(F))
+
+
+_BVH_FLAGS = ((1, "a face index lies outside [0, V)"), (2, "a face has a non-finite coordinate"), (4, "a face needs more than 256^2 samples"))
+
+
+class MeshBVH:
+    """A triangle mesh indexed for closest-point queries (build_bvh): the workspace of cnerf_mesh_bvh_* (self-contained: it holds the
+    triangles), V and F of the mesh it was built from, n_faces = the faces in the tree, and which faces were left out: bad_index (some
+    index outside [0, V)), non_finite (some coordinate not finite)."""
+
+    def __init__(self, ws, nbytes, V, F, n_faces, flags):
+        self.ws, self.nbytes, self.V, self.F, self.n_faces = ws, nbytes, V, F, n_faces
+        self.bad_index, self.non_finite = bool(flags & 1), bool(flags & 2)
+
+
+def build_bvh(verts, faces):
+    """Index a triangle mesh for closest_point() on the device (csrc/mesh_bvh.hip; the rules are in include/customnerf_hip.h,
+    cnerf_mesh_bvh_*): the faces ordered along a Morton curve by a device radix sort, a balanced tree of boxes over leaves of four
+    triangles.  CUDA tensors verts [V, 3], faces [F, 3] (int); any triangle mesh.  A face with an index outside [0, V) or a non-finite
+    coordinate is left out and reported on the returned MeshBVH, not raised."""
+    v, f, _ = _mesh_args(verts, faces, None, "build_bvh")
+    V, F = v.shape[0], f.shape[0]
+    ws, nbytes = _workspace(v.device, "mesh_bvh", V, F)
+    counts = torch.empty(2, dtype=torch.int32, device=v.device)
+    check(lib.cnerf_mesh_bvh_build(_p(v), V, _p(f), F, ptr(ws), nbytes, ptr(counts), stream()), "mesh_bvh_build")
+    n, flags = _read(counts, "build_bvh", ())                                   # the one host read
+    return MeshBVH(ws, nbytes, V, F, n, flags)
+
+
+def closest_point(bvh, points, want_point=False, want_bary=False, want_stats=False):
+    """The closest point of the mesh of `bvh` (build_bvh) to each of points [Q, 3] (CUDA float tensor), on the device.
+    -> dict: dist2 [Q] float32 (squared distance), face [Q] int32 (the smallest face index at that distance; -1 with dist2 = +inf for a
+    non-finite point or a mesh without valid faces), and on request point [Q, 3] (the closest point), bary [Q, 3] (its barycentrics in the
+    face) and stats = (node boxes tested, triangles tested) summed over the call.  The result is the brute-force minimum over the faces
+    under the float32 rule of include/customnerf_hip.h, bit for bit: the tree only prunes."""
+    if not isinstance(bvh, MeshBVH):
+        raise ValueError("closest_point: bvh must come from build_bvh")
+    require_cuda(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"closest_point: points must be [Q, 3], got {tuple(points.shape)}")
+    x = points.detach().contiguous().float()
+    Q, dev = x.shape[0], x.device
+    if Q >= 2 ** 31:
+        raise ValueError(f"closest_point: at most 2^31 - 1 points per call, got {Q}")
+    out = {'dist2': torch.empty(Q, dtype=torch.float32, device=dev), 'face': torch.empty(Q, dtype=torch.int32, device=dev)}
+    if want_point:
+        out['point'] = torch.empty(Q, 3, dtype=torch.float32, device=dev)
+    if want_bary:
+        out['bary'] = torch.empty(Q, 3, dtype=torch.float32, device=dev)
+    stats = torch.zeros(2, dtype=torch.int64, device=dev) if want_stats else None
+    check(lib.cnerf_mesh_bvh_closest(ptr(bvh.ws), bvh.nbytes, bvh.V, bvh.F, _p(x), Q, _p(out['dist2']), _p(out['face']), _p(out.get('point')),
+                                     _p(out.get('bary')), _p(stats), stream()), "mesh_bvh_closest")
+    if want_stats:
+        out['stats'] = tuple(int(s) for s in stats.cpu())
+    return out
+
+
+def _sample(verts, faces, spacing, max_samples, what):
+    """the sampler behind sample_surface and distance -> ((points, face, bary, weight), flags); a face that needs k > 256 is sampled at
+    k = 256 and sets flags bit 2: the caller decides"""
+    v, f, _ = _mesh_args(verts, faces, None, what)
+    sp = float(np.float32(spacing))
+    if not (math.isfinite(sp) and sp > 0.0):
+        raise ValueError(f"{what}: spacing must be finite and > 0, got {spacing}")
+    V, F, dev = v.shape[0], f.shape[0], v.device
+    ws, nbytes = _workspace(dev, "mesh_sample", F)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    check(lib.cnerf_mesh_sample_count(_p(v), V, _p(f), F, sp, ptr(ws), nbytes, ptr(counts), stream()), "mesh_sample_count")
+    n, flags = (int(c) for c in counts.cpu())                                   # the one host read
+    if n > int(max_samples):
+        raise ValueError(f"{what}: {n} samples at spacing {sp} exceed max_samples = {max_samples}")
+    pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    bary = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    weight = torch.empty(n, dtype=torch.float32, device=dev)
+    check(lib.cnerf_mesh_sample_emit(_p(v), V, _p(f), F, sp, ptr(ws), nbytes, _p(pts), _p(face), _p(bary), _p(weight), n, stream()),
+          "mesh_sample_emit")
+    return (pts, face, bary, weight), flags
+
+
+def sample_surface(verts, faces, spacing, max_samples=1 << 26):
+    """Deterministic samples of a mesh's surface about `spacing` apart, on the device (csrc/mesh_bvh.hip, cnerf_mesh_sample_*): a face of
+    area A is cut into k^2 congruent triangles, k = ceil(sqrt(2 A) / spacing) in [1, 256], with one sample at the centroid of each,
+    weighted A / k^2; faces with a bad index or a non-finite coordinate give none.  -> (points [n, 3] float32, face [n] int32,
+    bary [n, 3] float32, weight [n] float32) in face order.  More than max_samples samples, or a face that needs k > 256, raises ValueError."""
+    out, flags = _sample(verts, faces, spacing, max_samples, "sample_surface")
+    if flags & 4:
+        raise ValueError(f"sample_surface: {_BVH_FLAGS[2][1]} at spacing {spacing} (a larger spacing)")
+    return out
+
+
+def _used_vertices(v, f):
+    """the vertices of the faces that take part (valid indices, finite coordinates), in index order"""
+    V = v.shape[0]
+    fl = f.long()
+    ok = ((fl >= 0) & (fl < V)).all(1)
+    fl = fl[ok]
+    fl = fl[torch.isfinite(v[fl.reshape(-1)]).reshape(-1, 9).all(1)]
+    used = torch.zeros(V, dtype=torch.bool, device=v.device)
+    used[fl.reshape(-1)] = True
+    return v[used]
+
+
+def _one_way(v, f, bvh, spacing, include_vertices, max_samples):
+    (pts, _, _, w), _ = _sample(v, f, spacing, max_samples, "distance")          # a face that needs k > 256 gets k = 256: its weights still sum to its area
+    n = pts.shape[0]
+    if include_vertices:
+        extra = _used_vertices(v, f)
+        pts = torch.cat([pts, extra])
+        w = torch.cat([w, torch.zeros(extra.shape[0], dtype=torch.float32, device=v.device)])
+    if pts.shape[0] == 0:
+        raise ValueError("distance: a mesh has no face to sample")
+    r = closest_point(bvh, pts)
+    d2, w = r['dist2'].double(), w.double()
+    i = int(torch.nonzero(r['dist2'] == r['dist2'].max())[0])                    # the first sample at the maximum
+    area = float(w.sum())
+    mean = float((w * d2.sqrt()).sum()) / area if area > 0.0 else 0.0
+    rms = math.sqrt(float((w * d2).sum()) / area) if area > 0.0 else 0.0
+    return {'max': math.sqrt(float(d2[i])), 'mean': mean, 'rms': rms, 'n_samples': n, 'max_point': tuple(float(c) for c in pts[i]),
+            'max_face': int(r['face'][i])}
+
+
+def distance(verts_a, faces_a, verts_b, faces_b, spacing=None, symmetric=True, include_vertices=True, max_samples=1 << 26):
+    """Geometric deviation between two triangle meshes, as Metro and MeshLab report it, on the device: A's surface is sampled about
+    `spacing` apart (sample_surface; default 0.002 x the diagonal of the box around both meshes) and each sample's distance to B comes
+    from closest_point on B's tree; with symmetric=True also B to A.  A face so large that it would need more than 256^2 samples gets
+    256^2.  include_vertices adds the sampled mesh's vertices with weight 0: they count for the maximum only (extremes sit at vertices).
+    CUDA tensors verts [V, 3], faces [F, 3] (int) per mesh; at most max_samples samples per direction (ValueError beyond).
+    -> dict: 'a_to_b' (and 'b_to_a'): max, mean and rms (area-weighted, summed in float64) in the meshes' units, n_samples, max_point (the
+    sample where the maximum is attained) and max_face (the face of the other mesh closest to it); 'hausdorff' = the largest max;
+    'spacing'.  A mesh without a valid face raises ValueError."""
+    va, fa, _ = _mesh_args(verts_a, faces_a, None, "distance")
+    vb, fb, _ = _mesh_args(verts_b, faces_b, None, "distance")
+    if spacing is None:
+        both = torch.cat([va, vb])
+        both = both[torch.isfinite(both).all(1)]
+        if both.shape[0] == 0:
+            raise ValueError("distance: no finite vertex")
+        lo, hi = torch.aminmax(both, dim=0)
+        spacing = 0.002 * float((hi - lo).double().norm())
+    spacing = float(spacing)
+    if not (math.isfinite(spacing) and spacing > 0.0):
+        raise ValueError(f"distance: spacing must be finite and > 0, got {spacing}")
+    out = {'spacing': spacing}
+    for key, (v, f), (tv, tf) in (('a_to_b', (va, fa), (vb, fb)), ('b_to_a', (vb, fb), (va, fa)))[:2 if symmetric else 1]:
+        bvh = build_bvh(tv, tf)
+        if bvh.n_faces == 0:
+            raise ValueError("distance: a mesh has no valid face to measure against")
+        out[key] = _one_way(v, f, bvh, spacing, include_vertices, max_samples)
+    out['hausdorff'] = max(out[k]['max'] for k in ('a_to_b', 'b_to_a') if k in out)
+    return out
 
 
 def write_png(path, image):

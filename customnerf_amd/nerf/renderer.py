@@ -487,7 +487,7 @@ class NeRFRenderer(nn.Module):
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
-                     smooth_mu=-0.53):
+                     smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -501,7 +501,12 @@ class NeRFRenderer(nn.Module):
         simplify and decimate carry the normals along, and color / texture look along them.  The defaults return the marching-cubes mesh
         as it is.
         texture=R > 0 bakes the field's colour, looking at the surface, into an R x R texture atlas of the final mesh (mesh.bake_texture,
-        csrc/mesh_texture.hip): 'uvs' [F, 3, 2] float32 and 'texture' [R, R, 3] uint8 join the dict (both None with texture=0)."""
+        csrc/mesh_texture.hip): 'uvs' [F, 3, 2] float32 and 'texture' [R, R, 3] uint8 join the dict (both None with texture=0).
+        deviation=True reports what the lossy passes cost in geometry: 'deviation' joins the dict — mesh.distance(final mesh, the mesh as it
+        stood after marching cubes and component removal), both directions (max, mean, rms per direction and 'hausdorff', in world units),
+        sampled deviation_spacing apart (default: half the smallest lattice step; at most deviation_max_samples samples per direction,
+        ValueError beyond), plus 'step', the lattice step, so that the error reads in voxels; None when neither smooth, simplify nor
+        target_faces ran.  Without deviation=True the key is absent."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -524,6 +529,7 @@ class NeRFRenderer(nn.Module):
         if int(min_component_faces) > 0 or keep_largest:
             verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
                                                                      largest=bool(keep_largest))
+        kept = (verts, faces) if deviation else None                             # held only for the report
         if n_smooth:
             verts, normals = _mesh.smooth(verts, faces, n_smooth, smooth_lambda, smooth_mu, normals=normals)
         if k >= 2:
@@ -541,14 +547,22 @@ class NeRFRenderer(nn.Module):
         uvs = tex = None
         if tex_r:
             uvs, tex = _mesh.bake_texture(verts, faces, tex_r, lambda x, d: self(x, d)[1][:, :3], normals=normals, chunk=chunk)
-        return {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
-                'uvs': uvs, 'texture': tex}
+        m = {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
+             'uvs': uvs, 'texture': tex}
+        if deviation:
+            m['deviation'] = None
+            if n_smooth or k >= 2 or tf:
+                sp = 0.5 * float(step.min()) if deviation_spacing is None else float(deviation_spacing)
+                m['deviation'] = dict(_mesh.distance(verts, faces, kept[0], kept[1], spacing=sp, max_samples=deviation_max_samples),
+                                      step=tuple(step.tolist()))
+        return m
 
     def save_mesh(self, path, **kw):
         """extract_mesh(**kw) written to `path` -> the mesh dict.  A path ending in .obj writes a Wavefront OBJ (mesh.write_obj: positions,
         normals, and with texture=R the UVs, <stem>.mtl and the R x R <stem>.png beside it; vertex colours are not written to OBJ); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
-        extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces) pass through."""
+        extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces) and deviation / deviation_spacing
+        pass through."""
         obj = str(path).lower().endswith(".obj")
         if int(kw.get('texture', 0) or 0) and not obj:
             raise ValueError(f"save_mesh: texture= needs an .obj path (PLY carries no texture), got {path!r}")

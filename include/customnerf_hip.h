@@ -40,7 +40,8 @@ extern "C" {
  *    quadric decimation (additive, same version) — cnerf_mesh_decimate_workspace_bytes / _init / _round / _emit; texture baking (additive,
  *    same version) — cnerf_mesh_atlas_layout / _uvs / _points / _store / _fill; smoothing and normals (additive, same version) —
  *    cnerf_mesh_smooth_workspace_bytes / _init / _steps / _normals; mesh rasteriser (additive, same version) —
- *    cnerf_mesh_raster_workspace_bytes / _visibility / _shade. */
+ *    cnerf_mesh_raster_workspace_bytes / _visibility / _shade; closest-point queries and surface samples (additive, same version) —
+ *    cnerf_mesh_bvh_workspace_bytes / _build / _closest and cnerf_mesh_sample_workspace_bytes / _count / _emit. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -719,6 +720,65 @@ int cnerf_mesh_raster_shade(const int32_t *face, const float *depth, const float
                             uint32_t F, int mode, const uint8_t *colors, const float *uvs, const uint8_t *texture, uint32_t R,
                             const float *verts, const float *normals, float d0, float d1, const uint8_t *bg_host, uint8_t *image, uint8_t *mask,
                             void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Closest-point queries against a triangle mesh and a deterministic surface sampler: what the deviation report is made of
+ * (customnerf_amd/mesh.py build_bvh / closest_point / sample_surface / distance; csrc/mesh_bvh.hip; the reference has none).  verts float32
+ * [V][3], faces int32 [F][3].  All arithmetic is float32, one rounding per written operation in the order written (the build has
+ * -ffp-contract=off); divisions and square roots are correctly rounded; dot(u, v) = (ux vx + uy vy) + uz vz.
+ *   Taking part: a face takes part when its three indices lie in [0, V) and its nine coordinates are finite.  Every other face is left out
+ *   of the tree and of the sampler; flags bit 0 = some index lies outside [0, V), bit 1 = some face with valid indices has a non-finite
+ *   coordinate.  Neither is an error here: the caller decides.
+ *   build   : counts (device uint32 [2]): [0] the faces in the tree, [1] the flags; the one host read.  The faces are ordered along a Morton
+ *             curve of their centroids by a radix sort without atomics, so ws is bit-identical from run to run.  ws: 256-byte header |
+ *             triangle records (48 B each, in sorted order) | node boxes (32 B each) | sort scratch; a query reads the first three only, needs
+ *             neither verts nor faces, and may run any number of times.  The tree's shape is not part of the contract: no output depends on it.
+ *   closest : after build with the same ws, V and F.  points float32 [Q][3].  Per query p, over the faces that take part:
+ *             dist2 [Q] = the smallest d2(p, face), face [Q] = the smallest face index attaining it, point [Q][3] and bary [Q][3] (either
+ *             may be NULL) that face's closest point and its barycentrics (point = b0 v0 + b1 v1 + b2 v2 up to rounding).  A face whose d2
+ *             is NaN never wins (every comparison with it is false); +inf may win.  A non-finite p, a tree without faces, or no winner:
+ *             face = -1, dist2 = +inf, point = bary = 0.  stats (NULL or device uint64 [2], ADDED to, so zero it first): node boxes tested
+ *             and triangles tested, summed over the call.
+ *             d2(p, (a, b, c)) — Ericson, Real-Time Collision Detection, 5.1.5; the first region that holds, in this order:
+ *               ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c; d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp),
+ *               d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp); vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4
+ *               1 vertex a : d1 <= 0 and d2 <= 0                          x = a, bary (1, 0, 0)
+ *               2 vertex b : d3 >= 0 and d4 <= d3                         x = b, bary (0, 1, 0)
+ *               3 edge ab  : vc <= 0 and d1 >= 0 and d3 <= 0              v = d1 / (d1 - d3), x = a + v ab, bary (1 - v, v, 0)
+ *               4 vertex c : d6 >= 0 and d5 <= d6                         x = c, bary (0, 0, 1)
+ *               5 edge ac  : vb <= 0 and d2 >= 0 and d6 <= 0              w = d2 / (d2 - d6), x = a + w ac, bary (1 - w, 0, w)
+ *               6 edge bc  : va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0    w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), x = b + w (c - b),
+ *                                                                         bary (0, 1 - w, w)
+ *               7 inside   : otherwise                                    e = 1 / ((va + vb) + vc), v = vb e, w = vc e,
+ *                                                                         x = (a + ab v) + ac w, bary ((1 - v) - w, v, w)
+ *               then r = p - x and d2 = (rx rx + ry ry) + rz rz from the rounded x.  (A face with a == b can give 0 / 0 in region 3: NaN.)
+ *   sample  : face f that takes part has e1 = v1 - v0, e2 = v2 - v0, c = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x),
+ *             area A = 0.5 sqrt((cx cx + cy cy) + cz cz) and order k = ceil(sqrt(2 A) / spacing) clamped to [1, 256] (k = 1 when that is
+ *             NaN or below 1; a value above 256 sets flags bit 2).  Its k^2 samples are the centroids of the k^2 congruent sub-triangles, in
+ *             the order m = 0 .. k^2 - 1: row i = k - ceil(sqrt(k^2 - m)) starts at m = i (2 k - i); rem = m - i (2 k - i), j = rem / 2,
+ *             up = rem % 2 (0: the sub-triangle with corners (i, j), (i + 1, j), (i, j + 1) of the k-fold lattice, 1: the inverted one
+ *             beside it); u = (float) (3 i + 1 + up) / (float) (3 k), v = (float) (3 j + 1 + up) / (float) (3 k), bary = ((1 - u) - v, u, v),
+ *             point = (v0 + u e1) + v e2 per component (exact in a coordinate the three vertices share), weight = A / (float) (k k).  A
+ *             zero-area face gives one sample of weight 0.
+ *             Samples come in face order; outputs points [n][3], face int32 [n], bary [n][3], weight [n].
+ *             count : counts (device uint64 [2]): [0] the number of samples n, exact, [1] the flags; the one host read.
+ *             emit  : after count on the same stream with the same ws and arguments; writes the samples with index < max_samples.  When
+ *                     n >= 2^32 it writes nothing.
+ *   CNERF_ENULL: a required pointer is NULL.  CNERF_EINVAL: V, F or Q >= 2^31, a short or misaligned (16 bytes) ws, spacing not finite or
+ *   <= 0.  Both return before any launch; F = 0 and Q = 0 are accepted.  The caller's stream and workspace; no allocation, no host sync,
+ *   no float atomics; the integer atomics (flags, the count, the centroid box as integer maxima, stats) do not depend on their order, so
+ *   every output is bit-reproducible.  bvh workspace_bytes: 48 (records) + 16 (sort keys) + 16 .. 32 (boxes) bytes per face; sample workspace_bytes: 256 + F / 32.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_bvh_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_bvh_build(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, void *ws, uint64_t ws_bytes, uint32_t *counts,
+                         void *stream);
+int cnerf_mesh_bvh_closest(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const float *points, uint32_t Q, float *dist2,
+                           int32_t *face, float *point, float *bary, uint64_t *stats, void *stream);
+int cnerf_mesh_sample_workspace_bytes(uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_sample_count(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, float spacing, void *ws, uint64_t ws_bytes,
+                            uint64_t *counts, void *stream);
+int cnerf_mesh_sample_emit(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, float spacing, void *ws, uint64_t ws_bytes,
+                           float *points, int32_t *face, float *bary, float *weight, uint64_t max_samples, void *stream);
 
 #ifdef __cplusplus
 }
