@@ -57,11 +57,15 @@ __device__ __forceinline__ float cn_clamp(float x, float lo, float hi) { return 
 __device__ __forceinline__ uint32_t cn_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // wave scans / sums on the DPP data path (row_shr inside the 16-lane rows, row_bcast:15 / :31 across them) — no ds_bpermute round trips
-template <int CTRL, int ROW_MASK, typename T>
-__device__ __forceinline__ T cn_dpp_zero(T src) {      // lanes without a source lane (or masked rows) get 0
+// in the per-ray dependency chains.  `old` is what a lane keeps when its DPP source lane does not exist or its row is masked (the identity).
+#define CN_DPP_WAVE_SHR1 0x138                          // wave_shr:1: lane l reads lane l - 1
+template <int CTRL, int ROW_MASK = 0xF, typename T>
+__device__ __forceinline__ T cn_dpp(T old, T src) {
     static_assert(sizeof(T) == 4, "32-bit types only");
-    return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, src), CTRL, ROW_MASK, 0xF, false));
+    return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src), CTRL, ROW_MASK, 0xF, false));
 }
+template <int CTRL, int ROW_MASK, typename T>
+__device__ __forceinline__ T cn_dpp_zero(T src) { return cn_dpp<CTRL, ROW_MASK>(T(0), src); }
 
 template <typename T>
 __device__ __forceinline__ T cn_wave_incl_scan(T v) {   // inclusive prefix sum across the 64 lanes
@@ -73,11 +77,29 @@ __device__ __forceinline__ T cn_wave_incl_scan(T v) {   // inclusive prefix sum 
     v += cn_dpp_zero<0x143, 0xC>(v);                     // row_bcast:31 into rows 2 and 3
     return v;
 }
+__device__ __forceinline__ float cn_wave_incl_prod(float x) {   // inclusive prefix product across the 64 lanes
+    x *= cn_dpp<0x111>(1.0f, x);
+    x *= cn_dpp<0x112>(1.0f, x);
+    x *= cn_dpp<0x114>(1.0f, x);
+    x *= cn_dpp<0x118>(1.0f, x);
+    x *= cn_dpp<0x142, 0xA>(1.0f, x);
+    x *= cn_dpp<0x143, 0xC>(1.0f, x);
+    return x;
+}
 
 template <typename T>
-__device__ __forceinline__ T cn_wave_sum(T v) {
-    v = cn_wave_incl_scan(v);
+__device__ __forceinline__ T cn_lane63(T v) {           // the last lane's value, wave-uniform
     return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+template <typename T>
+__device__ __forceinline__ T cn_wave_sum(T v) { return cn_lane63(cn_wave_incl_scan(v)); }
+
+// four floats -> four halves (round to nearest even) in one 8-byte value: the fp16 shadow of a parameter, the data-parallel payload
+__device__ __forceinline__ uint2 cn_pack_half4(float4 f) {
+    union { __half2 h[2]; uint2 u; } o;
+    o.h[0] = __floats2half2_rn(f.x, f.y);
+    o.h[1] = __floats2half2_rn(f.z, f.w);
+    return o.u;
 }
 
 // near / far of a ray against an axis-aligned box (raymarching.cu:91-145): shared by k_near_far_from_aabb and the fused coarse sampler

@@ -91,6 +91,63 @@ __device__ __forceinline__ uint32_t ge_index(uint32_t gridtype, bool align_corne
     return index % hashmap_size;
 }
 
+// is the coordinate / the sample inside the unit cube?  (the reference's `inputs[d] < 0 || inputs[d] > 1` test: NaN counts as inside)
+__device__ __forceinline__ bool ge_in_range(float x) { return !(x < 0 || x > 1); }
+template <int D>
+__device__ __forceinline__ bool ge_in_range(const float (&in)[D]) {
+    bool ok = true;
+#pragma unroll
+    for (int d = 0; d < D; d++) ok = ok && ge_in_range(in[d]);
+    return ok;
+}
+
+// the grid cell of a sample on a level of scale `scale`: lower corner and the fraction inside the cell (interp 1: its smoothstep)
+template <int D>
+__device__ __forceinline__ void ge_cell(const float (&in)[D], float scale, bool align_corners, uint32_t (&pos_grid)[D], float (&frac)[D],
+                                        uint32_t interp = 0) {
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        frac[d] = cn_fma(in[d], scale, align_corners ? 0.0f : 0.5f);
+        pos_grid[d] = (uint32_t)floorf(frac[d]);
+        frac[d] -= (float)pos_grid[d];
+        if (interp == 1) frac[d] = ge_smoothstep(frac[d]);
+    }
+}
+
+// corner `idx` (= x + 2 y + 4 z ...) of a cell: its table entry and its weight, multiplied up in the reference's order (x factor first,
+// gridencoder.cu:171-178)
+template <int D>
+__device__ __forceinline__ void ge_corner(int idx, const uint32_t (&pos_grid)[D], const float (&frac)[D], uint32_t gridtype, bool align_corners,
+                                          uint32_t hashmap_size, uint32_t resolution, uint32_t &entry, float &w) {
+    uint32_t pgl[D];
+    w = 1;
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        if ((idx & (1 << d)) == 0) { w *= 1 - frac[d]; pgl[d] = pos_grid[d]; }
+        else { w *= frac[d]; pgl[d] = pos_grid[d] + 1; }
+    }
+    entry = ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pgl);
+}
+
+// f(corner, entry, weight) for the 1 << D corners of a sample's cell
+template <int D, typename F>
+__device__ __forceinline__ void ge_corners(const float (&in)[D], float scale, bool align_corners, uint32_t interp, uint32_t gridtype,
+                                           uint32_t hashmap_size, uint32_t resolution, F &&f) {
+    float pos[D];
+    uint32_t pos_grid[D];
+    ge_cell<D>(in, scale, align_corners, pos_grid, pos);
+#pragma unroll
+    for (int d = 0; d < D; d++)                      // (after the cell, not inside it: k_bin_emit<float> is allocated two registers fewer otherwise)
+        if (interp == 1) pos[d] = ge_smoothstep(pos[d]);
+#pragma unroll
+    for (int idx = 0; idx < (1 << D); idx++) {
+        float w;
+        uint32_t entry;
+        ge_corner<D>(idx, pos_grid, pos, gridtype, align_corners, hashmap_size, resolution, entry, w);
+        f(idx, entry, w);
+    }
+}
+
 // Level-uniform shortcuts of ge_index (same results, bit for bit).  The generic form costs a 32-bit remainder per corner (~30 VALU
 // instructions, eight times per sample and level); which branch it takes depends on the level only:
 //   GE_MODE_DENSE   every dimension enters the stride product and the product fits the table: index = sum p[d] * step^d < size, no wrap

@@ -1,5 +1,5 @@
 // The specialised forward gather of one (sample, level): fp16 table, D = 3, C = 2, linear interpolation, align_corners = false — the
-// configuration CustomNeRF runs.  Shared by k_grid_fwd_fast (gridencoder.hip) and the fused gather + field kernel (field_fused_fwd.hip);
+// configuration CustomNeRF runs.  Used by k_grid_fwd_fast and k_grid_fwd_fast_sm (gridencoder.hip);
 // bit-identical to the generic k_grid_fwd and to oracle/gridencoder_ref.c (same operations on the same values in the same order).
 #pragma once
 #include "grid_common.h"
@@ -31,7 +31,7 @@ __device__ __forceinline__ uint32_t gf_eval_level(const float (&in)[3], const un
     float fr[3], om[3];
     uint32_t pg[3];
 #pragma unroll
-    for (int d = 0; d < 3; d++) {
+    for (int d = 0; d < 3; d++) {                              // (restates ge_cell<3>, grid_common.h, in its own text: calling it changes the timed kernels' listings)
         const float pos = cn_fma(in[d], scale, 0.5f);
         pg[d] = (uint32_t)floorf(pos);
         fr[d] = pos - (float)pg[d];

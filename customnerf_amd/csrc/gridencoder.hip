@@ -27,6 +27,8 @@ __global__ void __launch_bounds__(GE_BLOCK) k_grid_fwd(const float *__restrict__
     const Vec *__restrict__ table = reinterpret_cast<const Vec *>(grid) + lv.offset[level];
     Vec *out = reinterpret_cast<Vec *>(outputs) + ((size_t)level * ostride + b);      // ostride = rows per level of the output buffer (>= B)
 
+    // (the in-range test and the cell below restate ge_in_range<D> and ge_cell<D>, grid_common.h, in their own text: through the helpers every
+    // instantiation of this kernel is allocated other scalar registers, some other vector registers: profiles/shared_rules_isa.txt)
     float in[D];
     bool oob = false;
     ge_load_coords<D>(inputs, b, in);
@@ -204,7 +206,7 @@ __global__ void __launch_bounds__(GE_BLOCK) k_grid_fwd_fast(const float *__restr
     uint32_t *out = reinterpret_cast<uint32_t *>(outputs) + ((size_t)level * ostride + b);
     float in[3];
     ge_load_coords<3>(inputs, b, in);
-    if (in[0] < 0 || in[0] > 1 || in[1] < 0 || in[1] > 1 || in[2] < 0 || in[2] > 1) { *out = 0u; return; }
+    if (in[0] < 0 || in[0] > 1 || in[1] < 0 || in[1] > 1 || in[2] < 0 || in[2] > 1) { *out = 0u; return; }     // (restates ge_in_range<3>: the timed kernels keep their own text)
 
     const unsigned char *__restrict__ table = reinterpret_cast<const unsigned char *>(grid) + (size_t)lv.offset[level] * 4;   // 4 bytes per entry
     *out = gf_eval_level(in, table, lv.size[level], lv.resolution[level], lv.scale[level], gridtype);
@@ -257,7 +259,7 @@ __global__ void __launch_bounds__(GE_BLOCK) k_grid_bwd(const T *__restrict__ gra
 #pragma unroll
     for (int d = 0; d < D; d++) {
         in[d] = inputs[(size_t)b * D + d];
-        if (in[d] < 0 || in[d] > 1) return;
+        if (!ge_in_range(in[d])) return;
     }
     using Vec = FeatVec<T, C>;
     const Vec g = reinterpret_cast<const Vec *>(grad)[(size_t)level * B + b];
@@ -268,13 +270,7 @@ __global__ void __launch_bounds__(GE_BLOCK) k_grid_bwd(const T *__restrict__ gra
 
     float pos[D];
     uint32_t pos_grid[D];
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-        pos[d] = cn_fma(in[d], scale, align_corners ? 0.0f : 0.5f);
-        pos_grid[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pos_grid[d];
-        if (interp == 1) pos[d] = ge_smoothstep(pos[d]);
-    }
+    ge_cell<D>(in, scale, align_corners, pos_grid, pos, interp);
     float gf[C];
 #pragma unroll
     for (int c = 0; c < C; c++) {
@@ -283,14 +279,10 @@ __global__ void __launch_bounds__(GE_BLOCK) k_grid_bwd(const T *__restrict__ gra
     }
 #pragma unroll
     for (int idx = 0; idx < (1 << D); idx++) {
-        float w = 1;
-        uint32_t pgl[D];
-#pragma unroll
-        for (int d = 0; d < D; d++) {
-            if ((idx & (1 << d)) == 0) { w *= 1 - pos[d]; pgl[d] = pos_grid[d]; }
-            else { w *= pos[d]; pgl[d] = pos_grid[d] + 1; }
-        }
-        const uint32_t index = ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pgl) * C;
+        float w;
+        uint32_t entry;
+        ge_corner<D>(idx, pos_grid, pos, gridtype, align_corners, hashmap_size, resolution, entry, w);
+        const uint32_t index = entry * C;
 #pragma unroll
         for (int c = 0; c < C; c++) unsafeAtomicAdd(&gtable[index + c], w * gf[c]);
     }
@@ -324,15 +316,15 @@ __global__ void __launch_bounds__(GE_BLOCK) k_grad_tv(const float *__restrict__ 
 #pragma unroll
     for (int d = 0; d < D; d++) {
         in[d] = inputs[(size_t)b * D + d];
-        if (in[d] < 0 || in[d] > 1) return;
+        if (!ge_in_range(in[d])) return;
     }
     const float *__restrict__ table = grid + (size_t)lv.offset[level] * C;
     float *__restrict__ gtable = grad + (size_t)lv.offset[level] * C;
     const uint32_t hashmap_size = lv.size[level], resolution = lv.resolution[level];
     const float scale = lv.scale[level];
     uint32_t pos_grid[D];
-#pragma unroll
-    for (int d = 0; d < D; d++) pos_grid[d] = (uint32_t)floorf(cn_fma(in[d], scale, align_corners ? 0.0f : 0.5f));
+    float frac[D];                                                              // (unused: the total variation is taken at the cell's lower corner)
+    ge_cell<D>(in, scale, align_corners, pos_grid, frac);
     float results[C], idelta[C];
 #pragma unroll
     for (int c = 0; c < C; c++) { results[c] = 0; idelta[c] = 0; }

@@ -29,6 +29,7 @@
 // table CustomNeRF runs — the benchmark table and the reference field's own 2^21-entry table.  Its records are 8-byte fp16 PAIR records (one per
 // x-pair of corners, see "fp16 pair records" below).  The form numbering follows docs/HISTORY.md.
 #include "grid_common.h"
+#include "optim_common.h"
 #include <vector>
 #include <algorithm>
 #include <cstdio>
@@ -59,41 +60,17 @@ template <typename T> struct BinRec;
 template <> struct alignas(8) BinRec<__half> { uint32_t idx; __half2 v; };
 template <> struct BinRec<float> { uint32_t idx; float v0, v1; };
 
+// the eight corner entries and weights of a sample on one level
 __device__ __forceinline__ void bn_corners(const float (&in)[3], const GridLevels &lv, uint32_t level, uint32_t gridtype, bool align_corners,
                                            uint32_t interp, uint32_t (&index)[8], float (&wgt)[8]) {
-    const uint32_t hashmap_size = lv.size[level];
-    const float scale = lv.scale[level];
-    const uint32_t resolution = lv.resolution[level];
-    float pos[3];
-    uint32_t pos_grid[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        pos[d] = cn_fma(in[d], scale, align_corners ? 0.0f : 0.5f);
-        pos_grid[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pos_grid[d];
-        if (interp == 1) pos[d] = ge_smoothstep(pos[d]);
-    }
-#pragma unroll
-    for (int idx = 0; idx < 8; idx++) {
-        float w = 1;
-        uint32_t pgl[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            if ((idx & (1 << d)) == 0) { w *= 1 - pos[d]; pgl[d] = pos_grid[d]; }
-            else { w *= pos[d]; pgl[d] = pos_grid[d] + 1; }
-        }
-        wgt[idx] = w;
-        index[idx] = ge_index<3>(gridtype, align_corners, hashmap_size, resolution, pgl);
-    }
+    ge_corners<3>(in, lv.scale[level], align_corners, interp, gridtype, lv.size[level], lv.resolution[level],
+                  [&](int c, uint32_t entry, float w) { index[c] = entry; wgt[c] = w; });
 }
 
 __device__ __forceinline__ bool bn_load_point(const float *__restrict__ inputs, uint32_t b, uint32_t B, float (&in)[3]) {
     if (b >= B) return false;
-    bool ok = true;
     ge_load_coords<3>(inputs, b, in);
-#pragma unroll
-    for (int d = 0; d < 3; d++) ok = ok && !(in[d] < 0 || in[d] > 1);
-    return ok;
+    return ge_in_range<3>(in);
 }
 
 // ---- sweep 1a: histogram of corner updates per chunk, one block = BN_PTS points of one level
@@ -181,12 +158,12 @@ __global__ void __launch_bounds__(1024) k_bin_scan_bins(const uint32_t *bin_tota
     if (adam_const && tid == 1023) {
         // the optimiser step carried by the accumulate (B3Adam): k_adam_scaled's prologue, evaluated ONCE per backward pass here (two double-precision
         // powers) — the scaler's found_inf is final: field backward and emit, its only producers on this path, precede this launch
-        const double step = (double)adam_state[3] + 1.0;
-        const double bc1 = 1.0 - pow((double)adam_beta1, step), bc2 = 1.0 - pow((double)adam_beta2, step);
-        adam_const[0] = adam_extra_inv / adam_state[0];
-        adam_const[1] = (float)((double)adam_lr / bc1);
-        adam_const[2] = (float)(1.0 / sqrt(bc2));
-        adam_const[3] = adam_state[2] != 0.0f ? 1.0f : 0.0f;
+        double bc1, bc2;
+        cn_adam_bias(cn_scaler_step(adam_state), adam_beta1, adam_beta2, bc1, bc2);
+        adam_const[0] = cn_scaler_gscale(adam_state, adam_extra_inv);
+        adam_const[1] = cn_adam_step_size(adam_lr, bc1);
+        adam_const[2] = cn_adam_rsqrt_bc2(bc2);
+        adam_const[3] = cn_scaler_skip(adam_state) ? 1.0f : 0.0f;
     }
     if (tid == 0) { carry_r = 0; carry_s = 0; n_split = 0; }
     __syncthreads();
@@ -393,6 +370,7 @@ __global__ void __launch_bounds__(1024) k_bin_accum(const BinRec<T> *__restrict_
 
 
 // the four (y, z) corner pairs of a sample on one level: entries of the x and x+1 corner, the weight of the pair, the x fraction
+// (restates ge_cell<3>, grid_common.h, in its own text: calling it changes k_bin3_emit's listing)
 __device__ __forceinline__ void b3_pairs(const float (&in)[3], const GridLevels &lv, uint32_t level, uint32_t gridtype, bool align_corners,
                                          uint32_t interp, uint32_t (&i0)[4], uint32_t (&i1)[4], float (&wyz)[4], float &fx) {
     const uint32_t hashmap_size = lv.size[level];
@@ -942,7 +920,7 @@ __global__ void __launch_bounds__(BN_SCAN_THREADS) k_bin3_totals(const uint32_t 
 // ---- the table's optimiser step inside the scatter (round 6, cnerf_grid_backward_adam): the flush below is where a table entry's gradient of this
 // backward pass becomes final — one owner per bin, or k_bin3_reduce_split for a split one — and k_adam_scaled would read it back 0.4 ms later, together
 // with p / m / v, at the HBM roofline (62 us for the benchmark table).  Applied here the update rides on kernels that are bound by LDS atomics, and the
-// gradient never makes the round trip.  Same arithmetic as k_adam_scaled (misc.hip), value for value: the parameters after a step are bit-identical.
+// gradient never makes the round trip.  k_adam_scaled's arithmetic (optim_common.h), value for value: the parameters after a step are bit-identical.
 struct B3Adam {
     float *p, *m, *v;
     __half *ph;
@@ -960,24 +938,15 @@ __device__ __forceinline__ B3AdamConst b3_adam_const(const B3Adam &ad) {        
 // gg = the final gradient of four consecutive floats at float index `idx` (a multiple of 4), pp / mm / vv = parameter and moments there;
 // d4 = their slot in the gradient table
 __device__ __forceinline__ void b3_adam_update(const B3Adam &ad, const B3AdamConst &c, size_t idx, float4 gg, float4 pp, float4 mm, float4 vv, float4 *d4) {
+    const CnAdamK ak = {c.gscale, c.step_size, c.rsqrt_bc2, ad.beta1, ad.beta2, ad.eps};
     float *pa = &pp.x, *ga = &gg.x, *ma = &mm.x, *va = &vv.x;
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float gk = ga[k] * c.gscale;
-        ma[k] = ad.beta1 * ma[k] + (1.0f - ad.beta1) * gk;
-        va[k] = ad.beta2 * va[k] + (1.0f - ad.beta2) * gk * gk;
-        pa[k] -= c.step_size * ma[k] / (sqrtf(va[k]) * c.rsqrt_bc2 + ad.eps);
-    }
+    for (int k = 0; k < 4; k++) cn_adam_elem(pa[k], ma[k], va[k], ga[k], ak);
     *reinterpret_cast<float4 *>(ad.p + idx) = pp;
     *reinterpret_cast<float4 *>(ad.m + idx) = mm;
     *reinterpret_cast<float4 *>(ad.v + idx) = vv;
     *d4 = ad.zero_grad ? make_float4(0, 0, 0, 0) : gg;
-    if (ad.ph) {
-        union { __half2 h[2]; uint2 u; } o;
-        o.h[0] = __floats2half2_rn(pp.x, pp.y);
-        o.h[1] = __floats2half2_rn(pp.z, pp.w);
-        *reinterpret_cast<uint2 *>(ad.ph + idx) = o.u;
-    }
+    if (ad.ph) *reinterpret_cast<uint2 *>(ad.ph + idx) = cn_pack_half4(pp);
 }
 __device__ __forceinline__ void b3_adam_apply(const B3Adam &ad, const B3AdamConst &c, size_t idx, float4 gg, float4 *d4) {
     if (c.skip) {                                    // non-finite gradients somewhere in this step: no update, the gradients are still cleared

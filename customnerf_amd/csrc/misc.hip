@@ -1,5 +1,5 @@
 // Ray generation, fused Adam step and library identification for gfx950.
-#include "common.h"
+#include "optim_common.h"
 
 // ------------------------------------------------------------------------------------------------ ray generation
 // One thread per pixel of one view.  convention 0: nerfstudio / OpenGL pinhole (reference nerf/provider.py:402-464,
@@ -75,12 +75,12 @@ __global__ void __launch_bounds__(256) k_generate_rays(const float *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ Adam
-// torch.optim.Adam semantics (no weight decay, no amsgrad):  m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
-// p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).  One pass: 16 B/lane vector loads, optional fp16 shadow store,
+// torch.optim.Adam (cn_adam_elem, optim_common.h) in one pass: 16 B/lane vector loads, optional fp16 shadow store,
 // optional gradient zeroing (saves the separate 4 B/param memset pass of zero_grad).
 __global__ void __launch_bounds__(256) k_adam(float *__restrict__ p, float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
                                               __half *__restrict__ ph, uint64_t n, float step_size, float beta1, float beta2, float eps,
                                               float rsqrt_bc2, float gscale, int zero_grad) {
+    const CnAdamK ak = {gscale, step_size, rsqrt_bc2, beta1, beta2, eps};
     const uint64_t n4 = n / 4;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -88,28 +88,16 @@ __global__ void __launch_bounds__(256) k_adam(float *__restrict__ p, float *__re
         float4 mm = reinterpret_cast<float4 *>(m)[i], vv = reinterpret_cast<float4 *>(v)[i];
         float *pa = &pp.x, *ga = &gg.x, *ma = &mm.x, *va = &vv.x;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float gk = ga[k] * gscale;
-            ma[k] = beta1 * ma[k] + (1.0f - beta1) * gk;
-            va[k] = beta2 * va[k] + (1.0f - beta2) * gk * gk;
-            pa[k] -= step_size * ma[k] / (sqrtf(va[k]) * rsqrt_bc2 + eps);
-        }
+        for (int k = 0; k < 4; k++) cn_adam_elem(pa[k], ma[k], va[k], ga[k], ak);
         reinterpret_cast<float4 *>(p)[i] = pp;
         reinterpret_cast<float4 *>(m)[i] = mm;
         reinterpret_cast<float4 *>(v)[i] = vv;
         if (zero_grad) reinterpret_cast<float4 *>(g)[i] = make_float4(0, 0, 0, 0);
-        if (ph) {
-            union { __half2 h[2]; uint2 u; } o;
-            o.h[0] = __floats2half2_rn(pp.x, pp.y);
-            o.h[1] = __floats2half2_rn(pp.z, pp.w);
-            reinterpret_cast<uint2 *>(ph)[i] = o.u;
-        }
+        if (ph) reinterpret_cast<uint2 *>(ph)[i] = cn_pack_half4(pp);
     }
     for (uint64_t i = n4 * 4 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float gk = g[i] * gscale;
-        const float mk = beta1 * m[i] + (1.0f - beta1) * gk;
-        const float vk = beta2 * v[i] + (1.0f - beta2) * gk * gk;
-        const float pk = p[i] - step_size * mk / (sqrtf(vk) * rsqrt_bc2 + eps);
+        float pk = p[i], mk = m[i], vk = v[i];
+        cn_adam_elem(pk, mk, vk, g[i], ak);
         m[i] = mk; v[i] = vk; p[i] = pk;
         if (zero_grad) g[i] = 0;
         if (ph) ph[i] = __float2half_rn(pk);
@@ -132,13 +120,7 @@ __global__ void __launch_bounds__(256) k_scaler_check(const float *__restrict__ 
 }
 
 __global__ void k_scaler_update(float *state, float growth, float backoff, float interval) {
-    if (state[2] != 0.0f) { state[0] *= backoff; state[1] = 0.0f; }
-    else {
-        state[3] += 1.0f;
-        const float t = state[1] + 1.0f;
-        if (t >= interval) { state[0] *= growth; state[1] = 0.0f; } else state[1] = t;
-    }
-    state[2] = 0.0f;
+    cn_scaler_update(state, cn_scaler_skip(state), growth, backoff, interval);
 }
 
 // ---- data-parallel exchange (customnerf_amd/dp.py).  pack: float32 gradient * scale -> float16 payload, the float32 source zeroed in the same pass
@@ -147,10 +129,7 @@ __global__ void __launch_bounds__(256) k_dp_pack(float *__restrict__ g, __half *
     const uint64_t n4 = n / 4, stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 v = reinterpret_cast<const float4 *>(g)[i];
-        union { __half2 h[2]; uint2 u; } o;
-        o.h[0] = __floats2half2_rn(v.x * scale, v.y * scale);
-        o.h[1] = __floats2half2_rn(v.z * scale, v.w * scale);
-        reinterpret_cast<uint2 *>(out)[i] = o.u;
+        reinterpret_cast<uint2 *>(out)[i] = cn_pack_half4(make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale));
         reinterpret_cast<float4 *>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (uint64_t i = n4 * 4 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) { out[i] = __float2half_rn(g[i] * scale); g[i] = 0.f; }
@@ -182,11 +161,11 @@ __global__ void __launch_bounds__(256) k_dp_reduce(const __half *__restrict__ re
 __global__ void __launch_bounds__(256) k_adam_scaled(float *__restrict__ p, float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
                                                      __half *__restrict__ ph, uint64_t n, float lr, float beta1, float beta2, float eps,
                                                      const float *__restrict__ state, float extra_inv, int zero_grad) {
-    const bool skip = state[2] != 0.0f;
-    const float gscale = extra_inv / state[0];
-    const double step = (double)state[3] + 1.0;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const float step_size = (float)((double)lr / bc1), rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    const bool skip = cn_scaler_skip(state);
+    const float gscale = cn_scaler_gscale(state, extra_inv);
+    double bc1, bc2;
+    cn_adam_bias(cn_scaler_step(state), beta1, beta2, bc1, bc2);
+    const CnAdamK ak = {gscale, cn_adam_step_size(lr, bc1), cn_adam_rsqrt_bc2(bc2), beta1, beta2, eps};
     const uint64_t n4 = n / 4;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     if (skip) {                                                           // non-finite gradients: optimizer.step() is skipped, gradients are still cleared
@@ -201,28 +180,16 @@ __global__ void __launch_bounds__(256) k_adam_scaled(float *__restrict__ p, floa
         float4 mm = reinterpret_cast<float4 *>(m)[i], vv = reinterpret_cast<float4 *>(v)[i];
         float *pa = &pp.x, *ga = &gg.x, *ma = &mm.x, *va = &vv.x;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float gk = ga[k] * gscale;
-            ma[k] = beta1 * ma[k] + (1.0f - beta1) * gk;
-            va[k] = beta2 * va[k] + (1.0f - beta2) * gk * gk;
-            pa[k] -= step_size * ma[k] / (sqrtf(va[k]) * rsqrt_bc2 + eps);
-        }
+        for (int k = 0; k < 4; k++) cn_adam_elem(pa[k], ma[k], va[k], ga[k], ak);
         reinterpret_cast<float4 *>(p)[i] = pp;
         reinterpret_cast<float4 *>(m)[i] = mm;
         reinterpret_cast<float4 *>(v)[i] = vv;
         if (zero_grad) reinterpret_cast<float4 *>(g)[i] = make_float4(0, 0, 0, 0);
-        if (ph) {
-            union { __half2 h[2]; uint2 u; } o;
-            o.h[0] = __floats2half2_rn(pp.x, pp.y);
-            o.h[1] = __floats2half2_rn(pp.z, pp.w);
-            reinterpret_cast<uint2 *>(ph)[i] = o.u;
-        }
+        if (ph) reinterpret_cast<uint2 *>(ph)[i] = cn_pack_half4(pp);
     }
     for (uint64_t i = n4 * 4 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float gk = g[i] * gscale;
-        const float mk = beta1 * m[i] + (1.0f - beta1) * gk;
-        const float vk = beta2 * v[i] + (1.0f - beta2) * gk * gk;
-        const float pk = p[i] - step_size * mk / (sqrtf(vk) * rsqrt_bc2 + eps);
+        float pk = p[i], mk = m[i], vk = v[i];
+        cn_adam_elem(pk, mk, vk, g[i], ak);
         m[i] = mk; v[i] = vk; p[i] = pk;
         if (zero_grad) g[i] = 0;
         if (ph) ph[i] = __float2half_rn(pk);
@@ -233,34 +200,33 @@ __global__ void __launch_bounds__(256) k_adam_scaled(float *__restrict__ p, floa
 // being the last Adam launch of the step, also applies GradScaler.update() (one more launch saved).  Round 6: several workgroups (one element
 // per thread and job; a single workgroup walked 22 trips of dependent loads: 21 us for 90 KB), the scaler update by whichever workgroup
 // finishes LAST (a device-global ticket: every workgroup has read the state — scale, found_inf, step count — before it takes its ticket).
-// Same arithmetic as k_adam_scaled, element by element.
+// The element update and the bias correction are k_adam_scaled's (optim_common.h): bit-identical updates.
 __device__ unsigned int g_adam_multi_ticket = 0;
 __global__ void __launch_bounds__(1024) k_adam_scaled_multi(CnerfAdamJobs jobs, float beta1, float beta2, float eps, float *__restrict__ state,
                                                             float extra_inv, int zero_grad, int update_scaler, float growth, float backoff, float interval) {
     __shared__ double s_bc1;
     __shared__ float s_r2;
     __shared__ unsigned int s_last;
-    const bool skip = state[2] != 0.0f;
-    const float gscale = extra_inv / state[0];
+    const bool skip = cn_scaler_skip(state);
+    CnAdamK ak = {cn_scaler_gscale(state, extra_inv), 0.0f, 0.0f, beta1, beta2, eps};
     if (threadIdx.x == 0) {                                               // the double-precision pow()s once per workgroup, not once per thread
-        const double step = (double)state[3] + 1.0;
-        s_bc1 = 1.0 - pow((double)beta1, step);
-        s_r2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, step)));
+        double bc1, bc2;
+        cn_adam_bias(cn_scaler_step(state), beta1, beta2, bc1, bc2);
+        s_bc1 = bc1;
+        s_r2 = cn_adam_rsqrt_bc2(bc2);
     }
     __syncthreads();
     const double bc1 = s_bc1;
-    const float rsqrt_bc2 = s_r2;
+    ak.rsqrt_bc2 = s_r2;
     for (uint32_t j = 0; j < jobs.n_jobs; j++) {
         float *__restrict__ p = jobs.p[j], *__restrict__ g = jobs.g[j], *__restrict__ m = jobs.m[j], *__restrict__ v = jobs.v[j];
         __half *__restrict__ ph = reinterpret_cast<__half *>(jobs.p_half[j]);
-        const float step_size = (float)((double)jobs.lr[j] / bc1);             // (the same expression as k_adam_scaled: bit-identical updates)
+        ak.step_size = cn_adam_step_size(jobs.lr[j], bc1);
         const uint64_t n = jobs.n[j];
         for (uint64_t i = (uint64_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 1024) {
             if (!skip) {
-                const float gs = g[i] * gscale;
-                const float mn = beta1 * m[i] + (1.0f - beta1) * gs;
-                const float vn = beta2 * v[i] + (1.0f - beta2) * gs * gs;
-                const float pn = p[i] - step_size * mn / (sqrtf(vn) * rsqrt_bc2 + eps);
+                float pn = p[i], mn = m[i], vn = v[i];
+                cn_adam_elem(pn, mn, vn, g[i], ak);
                 m[i] = mn; v[i] = vn; p[i] = pn;
                 if (ph) ph[i] = __float2half_rn(pn);
             }
@@ -276,13 +242,7 @@ __global__ void __launch_bounds__(1024) k_adam_scaled_multi(CnerfAdamJobs jobs, 
         __syncthreads();
         if (s_last && threadIdx.x == 0) {                                     // ... and so has every other workgroup: they took their tickets before
             g_adam_multi_ticket = 0;
-            if (skip) { state[0] *= backoff; state[1] = 0.0f; }
-            else {
-                state[3] += 1.0f;
-                const float t = state[1] + 1.0f;
-                if (t >= interval) { state[0] *= growth; state[1] = 0.0f; } else state[1] = t;
-            }
-            state[2] = 0.0f;
+            cn_scaler_update(state, skip, growth, backoff, interval);
         }
     }
 }
@@ -329,9 +289,9 @@ int cnerf_adam_step(float *p, float *g, float *m, float *v, void *p_half, uint64
     if (n == 0) return CNERF_OK;
     if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return CNERF_EINVAL;
     if (p_half && (((uintptr_t)p_half) & 7)) return CNERF_EINVAL;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    double bc1, bc2;
+    cn_adam_bias((double)step, beta1, beta2, bc1, bc2);
+    const float step_size = cn_adam_step_size(lr, bc1), rsqrt_bc2 = cn_adam_rsqrt_bc2(bc2);
     const uint64_t want = cn_div_up64(cn_div_up64(n, 4), 256);
     const uint32_t blocks = (uint32_t)(want < 4096 ? (want ? want : 1) : 4096);
     hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, CN_STREAM(stream), p, g, m, v, (__half *)p_half, n, step_size, beta1, beta2, eps,

@@ -109,11 +109,6 @@ __global__ void __launch_bounds__(RM_BLOCK) k_packbits(const float *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ marching core
-// DPP lane exchange: `old` is what a lane keeps when its source lane does not exist
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float rm_dpp(float old, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src), CTRL, ROW_MASK, 0xF, false));
-}
 struct RayState {
     float ox, oy, oz, dx, dy, dz, rdx, rdy, rdz;
 };
@@ -219,7 +214,7 @@ __global__ void __launch_bounds__(256) k_march_train_count_wave(const float *__r
         // the chunk's 64 points: lane l = t_base advanced l times
         float t = t_base;
         for (int i = 0; i < 63; i++) {
-            const float prev = rm_dpp<0x138>(t, t);                     // lane l-1's value (lane 0 keeps its own)
+            const float prev = cn_dpp<CN_DPP_WAVE_SHR1>(t, t);                     // lane l-1's value (lane 0 keeps its own)
             const float step = lane == 0 ? 0.0f : cn_clamp(prev * k.dt_gamma, k.dt_min, k.dt_max);
             t = prev + step;                                             // lanes <= i are final and recompute themselves
         }
@@ -392,12 +387,6 @@ __global__ void __launch_bounds__(256) k_march_train_write_hits(const float *__r
 // every sample once, coalesced.  Association of the sums / products differs from the serial loop (rounding level); a sample is kept iff
 // it is the first or the transmittance before it is >= T_thresh — the serial loop's `if (T < T_thresh) break` after the update,
 // restated per sample.
-__device__ __forceinline__ float rm_incl_prod(float x) {
-    x *= rm_dpp<0x111>(1.0f, x); x *= rm_dpp<0x112>(1.0f, x); x *= rm_dpp<0x114>(1.0f, x); x *= rm_dpp<0x118>(1.0f, x);
-    x *= rm_dpp<0x142, 0xA>(1.0f, x); x *= rm_dpp<0x143, 0xC>(1.0f, x);
-    return x;
-}
-__device__ __forceinline__ float rm_lane63(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63)); }
 
 #define RMW_WAVES 4
 template <int RS>
@@ -423,16 +412,16 @@ __global__ void __launch_bounds__(RMW_WAVES * 64) k_composite_train_fwd_wave(con
                 c0 = pc[(size_t)i * RS]; c1 = pc[(size_t)i * RS + 1]; c2 = pc[(size_t)i * RS + 2];
             }
             const float alpha = ok ? 1.0f - __expf(-sigma * dl.x) : 0.0f;
-            const float incl = rm_incl_prod(1.0f - alpha);
-            const float T_before = rm_dpp<0x138>(1.0f, incl) * T_carry;  // exclusive product, times the chunks before
+            const float incl = cn_wave_incl_prod(1.0f - alpha);
+            const float T_before = cn_dpp<CN_DPP_WAVE_SHR1>(1.0f, incl) * T_carry;  // exclusive product, times the chunks before
             const float t = cn_wave_incl_scan(dl.y) + t_carry;          // path length up to and including this sample
             const bool keep = ok && (i == 0 || T_before >= T_thresh);
             const float w = keep ? alpha * T_before : 0.0f;
             r = cn_fma(w, c0, r); g = cn_fma(w, c1, g); b = cn_fma(w, c2, b);
             d = cn_fma(w, t, d);
             ws += w;
-            T_carry *= rm_lane63(incl);
-            t_carry = rm_lane63(t);
+            T_carry *= cn_lane63(incl);
+            t_carry = cn_lane63(t);
             if (T_carry < T_thresh) break;                               // wave-uniform: nothing after this chunk is kept
         }
         r = cn_wave_sum(r); g = cn_wave_sum(g); b = cn_wave_sum(b); d = cn_wave_sum(d); ws = cn_wave_sum(ws);
@@ -472,8 +461,8 @@ __global__ void __launch_bounds__(RMW_WAVES * 64) k_composite_train_bwd_wave(con
             c0 = pc[(size_t)i * RS]; c1 = pc[(size_t)i * RS + 1]; c2 = pc[(size_t)i * RS + 2];
         }
         const float alpha = ok ? 1.0f - __expf(-sigma * dl) : 0.0f;
-        const float incl = rm_incl_prod(1.0f - alpha);
-        const float T_before = rm_dpp<0x138>(1.0f, incl) * T_carry;
+        const float incl = cn_wave_incl_prod(1.0f - alpha);
+        const float T_before = cn_dpp<CN_DPP_WAVE_SHR1>(1.0f, incl) * T_carry;
         const float T_after = incl * T_carry;
         const bool keep = ok && (i == 0 || T_before >= T_thresh);
         const float w = keep ? alpha * T_before : 0.0f;
@@ -483,8 +472,8 @@ __global__ void __launch_bounds__(RMW_WAVES * 64) k_composite_train_bwd_wave(con
             gs[i] = dl * (gi0 * cn_fma(T_after, c0, -(r_final - r)) + gi1 * cn_fma(T_after, c1, -(g_final - g)) +
                           gi2 * cn_fma(T_after, c2, -(b_final - b)) + gws * (1 - ws_final));
         }
-        T_carry *= rm_lane63(incl);
-        r_carry = rm_lane63(r); g_carry = rm_lane63(g); b_carry = rm_lane63(b);
+        T_carry *= cn_lane63(incl);
+        r_carry = cn_lane63(r); g_carry = cn_lane63(g); b_carry = cn_lane63(b);
         if (T_carry < T_thresh) break;
     }
 }

@@ -57,58 +57,22 @@ __global__ void __launch_bounds__(256) k_sample_coarse(const float *__restrict__
     }
 }
 
-// Wave scans on the DPP data path (row_shr inside the 16-lane rows, row_bcast:15 / :31 across them): no LDS-crossbar round trips
-// (ds_bpermute) in the per-ray dependency chains.  `old` is what a lane keeps when its DPP source lane does not exist (the identity).
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float rn_dpp(float old, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src), CTRL, ROW_MASK, 0xF, false));
-}
-#define RN_ROW_SHR(n) (0x110 + (n))
-#define RN_ROW_BCAST15 0x142
-#define RN_ROW_BCAST31 0x143
-#define RN_WAVE_SHR1 0x138
-
-__device__ __forceinline__ float rn_wave_incl_prod(float x) {
-    x *= rn_dpp<RN_ROW_SHR(1)>(1.0f, x);
-    x *= rn_dpp<RN_ROW_SHR(2)>(1.0f, x);
-    x *= rn_dpp<RN_ROW_SHR(4)>(1.0f, x);
-    x *= rn_dpp<RN_ROW_SHR(8)>(1.0f, x);
-    x *= rn_dpp<RN_ROW_BCAST15, 0xA>(1.0f, x);
-    x *= rn_dpp<RN_ROW_BCAST31, 0xC>(1.0f, x);
-    return x;
-}
-__device__ __forceinline__ float rn_wave_incl_sum(float x) {
-    x += rn_dpp<RN_ROW_SHR(1)>(0.0f, x);
-    x += rn_dpp<RN_ROW_SHR(2)>(0.0f, x);
-    x += rn_dpp<RN_ROW_SHR(4)>(0.0f, x);
-    x += rn_dpp<RN_ROW_SHR(8)>(0.0f, x);
-    x += rn_dpp<RN_ROW_BCAST15, 0xA>(0.0f, x);
-    x += rn_dpp<RN_ROW_BCAST31, 0xC>(0.0f, x);
-    return x;
-}
-__device__ __forceinline__ float rn_lane63(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
-}
-
+// Per-ray scans on the wave (cn_wave_incl_prod / cn_wave_incl_scan, common.h), carried across chunks of 64 samples.
 // exclusive multiplicative scan of v over the 64 lanes, times carry; returns the wave total (times carry) in `carry`
-__device__ __forceinline__ float rn_excl_prod_scan(float v, float &carry, uint32_t lane) {
-    (void)lane;
-    const float incl = rn_wave_incl_prod(v);
-    const float excl = rn_dpp<RN_WAVE_SHR1>(1.0f, incl);
+__device__ __forceinline__ float rn_excl_prod_scan(float v, float &carry) {
+    const float incl = cn_wave_incl_prod(v);
+    const float excl = cn_dpp<CN_DPP_WAVE_SHR1>(1.0f, incl);
     const float res = excl * carry;
-    carry = carry * rn_lane63(incl);
+    carry = carry * cn_lane63(incl);
     return res;
 }
 
-__device__ __forceinline__ float rn_incl_sum_scan(float v, float &carry, uint32_t lane) {
-    (void)lane;
-    const float incl = rn_wave_incl_sum(v);
+__device__ __forceinline__ float rn_incl_sum_scan(float v, float &carry) {
+    const float incl = cn_wave_incl_scan(v);
     const float res = incl + carry;
-    carry = carry + rn_lane63(incl);
+    carry = carry + cn_lane63(incl);
     return res;
 }
-
-__device__ __forceinline__ float rn_wave_sum(float v) { return rn_lane63(rn_wave_incl_sum(v)); }
 
 __global__ void __launch_bounds__(RN_THREADS) k_sample_fine_merge(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                                   const float *__restrict__ nears, const float *__restrict__ fars,
@@ -139,7 +103,7 @@ __global__ void __launch_bounds__(RN_THREADS) k_sample_fine_merge(const float *_
             delta = (i + 1 < T) ? zz[i + 1] - zz[i] : sd;
             alpha = 1.0f - expf(-delta * sr[i]);
         }
-        const float tr = rn_excl_prod_scan((i < T) ? (1.0f - alpha + 1e-15f) : 1.0f, carry, lane);
+        const float tr = rn_excl_prod_scan((i < T) ? (1.0f - alpha + 1e-15f) : 1.0f, carry);
         if (i < T) {
             ww[i] = alpha * tr;
             bins[i] = zz[i] + 0.5f * delta;               // z_vals_mid (only i < T-1 is used)
@@ -150,12 +114,12 @@ __global__ void __launch_bounds__(RN_THREADS) k_sample_fine_merge(const float *_
     const uint32_t nb = T - 2;                            // number of pdf bins; cdf has nb + 1 = T - 1 entries
     float tot = 0.0f;
     for (uint32_t k = lane; k < nb; k += 64) tot += ww[k + 1] + 1e-5f;
-    tot = rn_wave_sum(tot);
+    tot = cn_wave_sum(tot);
     float csum = 0.0f;
     for (uint32_t base = 0; base < nb; base += 64) {
         const uint32_t k = base + lane;
         const float pdf = (k < nb) ? (ww[k + 1] + 1e-5f) / tot : 0.0f;
-        const float c = rn_incl_sum_scan(pdf, csum, lane);
+        const float c = rn_incl_sum_scan(pdf, csum);
         if (k < nb) cdf[k + 1] = c;
     }
     if (lane == 0) cdf[0] = 0.0f;
@@ -263,12 +227,12 @@ __global__ void __launch_bounds__(RN_THREADS) k_sample_pdf(const float *__restri
     for (uint32_t i = lane; i < n_bins; i += 64) bn[i] = br[i];
     float tot = 0.0f;
     for (uint32_t k = lane; k < nw; k += 64) tot += wr[k] + 1e-5f;
-    tot = rn_wave_sum(tot);
+    tot = cn_wave_sum(tot);
     float csum = 0.0f;
     for (uint32_t base = 0; base < nw; base += 64) {
         const uint32_t k = base + lane;
         const float pdf = (k < nw) ? (wr[k] + 1e-5f) / tot : 0.0f;
-        const float c = rn_incl_sum_scan(pdf, csum, lane);
+        const float c = rn_incl_sum_scan(pdf, csum);
         if (k < nw) cdf[k + 1] = c;
     }
     if (lane == 0) cdf[0] = 0.0f;
@@ -349,7 +313,7 @@ __global__ void __launch_bounds__(RN_THREADS) k_composite_run_fwd(const float *_
                 continue;
             }
             const float alpha = ok ? 1.0f - expf(-delta * (sigma * rn_variant_scale(v, e))) : 0.0f;
-            const float tr = rn_excl_prod_scan(ok ? (1.0f - alpha + 1e-15f) : 1.0f, carry[v], lane);
+            const float tr = rn_excl_prod_scan(ok ? (1.0f - alpha + 1e-15f) : 1.0f, carry[v]);
             const float w = alpha * tr;
             if (ok) {
                 acc[v][0] += w * c.x; acc[v][1] += w * c.y; acc[v][2] += w * c.z;
@@ -366,7 +330,7 @@ __global__ void __launch_bounds__(RN_THREADS) k_composite_run_fwd(const float *_
         }
 #pragma unroll
         for (int k = 0; k < 6; k++) {
-            const float s = rn_wave_sum(acc[v][k]);
+            const float s = cn_wave_sum(acc[v][k]);
             if (lane == 0) out_ray[((size_t)v * N + n) * 6 + k] = s;
         }
     }
@@ -441,7 +405,7 @@ __global__ void __launch_bounds__(RN_THREADS) k_composite_run_bwd(const float *_
             for (int v = 0; v < 3; v++) {
                 if (!use[v]) continue;
                 const float alpha = ok ? 1.0f - expf(-delta * (sigma * rn_variant_scale(v, e))) : 0.0f;
-                const float tr = rn_excl_prod_scan(ok ? (1.0f - alpha + 1e-15f) : 1.0f, carry[v], lane);
+                const float tr = rn_excl_prod_scan(ok ? (1.0f - alpha + 1e-15f) : 1.0f, carry[v]);
                 alpha_[v][ch] = alpha; tr_[v][ch] = tr;
                 const float G = go[v][0] * c.x + go[v][1] * c.y + go[v][2] * c.z + go[v][3] * zn + go[v][4] + (detach_mask ? 0.0f : go[v][5] * c.w);
                 if (ok) tot[v] += G * alpha * tr;
@@ -449,7 +413,7 @@ __global__ void __launch_bounds__(RN_THREADS) k_composite_run_bwd(const float *_
         }
 #pragma unroll
         for (int v = 0; v < 3; v++)
-            if (use[v]) tot[v] = rn_wave_sum(tot[v]);
+            if (use[v]) tot[v] = cn_wave_sum(tot[v]);
     }
     // pass 2: gradients
     float pref[3] = {0, 0, 0};
@@ -473,7 +437,7 @@ __global__ void __launch_bounds__(RN_THREADS) k_composite_run_bwd(const float *_
             const float tr = tr_[v][ch];
             const float w = alpha * tr;
             const float G = go[v][0] * c.x + go[v][1] * c.y + go[v][2] * c.z + go[v][3] * zn + go[v][4] + (detach_mask ? 0.0f : go[v][5] * c.w);
-            const float incl = rn_incl_sum_scan(ok ? G * w : 0.0f, pref[v], lane);      // sum_{k<=i} G_k w_k
+            const float incl = rn_incl_sum_scan(ok ? G * w : 0.0f, pref[v]);      // sum_{k<=i} G_k w_k
             const float suffix = tot[v] - incl;
             const float dalpha = G * tr - suffix / q;
             const float dsv = dalpha * delta * (1.0f - alpha);
@@ -550,8 +514,8 @@ __global__ void __launch_bounds__(256) k_recon_loss(const float *__restrict__ ou
             g_out[((size_t)2 * N + n) * 6 + c] = 0.0f;
         }
     }
-    s_rgb = rn_wave_sum(s_rgb);
-    s_m = rn_wave_sum(s_m);
+    s_rgb = cn_wave_sum(s_rgb);
+    s_m = cn_wave_sum(s_m);
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { red[0][wave] = s_rgb; red[1][wave] = s_m; }
     __syncthreads();
@@ -565,7 +529,7 @@ __global__ void __launch_bounds__(256) k_recon_loss(const float *__restrict__ ou
     __syncthreads();
     if (s_last && threadIdx.x < 64) {
         __threadfence();
-        const float v = rn_wave_sum(threadIdx.x < gridDim.x ? __builtin_nontemporal_load(partial + threadIdx.x) : 0.0f);
+        const float v = cn_wave_sum(threadIdx.x < gridDim.x ? __builtin_nontemporal_load(partial + threadIdx.x) : 0.0f);
         if (threadIdx.x == 0) { loss[0] = v; g_recon_loss_ticket = 0; }
     }
 }
