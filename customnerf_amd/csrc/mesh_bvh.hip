@@ -1,7 +1,9 @@
-// Closest-point queries against a triangle mesh through a bounding-volume hierarchy, and a deterministic surface sampler (cnerf_mesh_bvh_*,
-// cnerf_mesh_sample_*): what mesh.distance() measures the deviation between two meshes with.  Same conventions as the other mesh passes: the
+// Closest-point and ray queries against a triangle mesh through a bounding-volume hierarchy, and a deterministic surface sampler
+// (cnerf_mesh_bvh_*, cnerf_mesh_sample_*): what mesh.distance() measures the deviation between two meshes with, and what mesh.ray_cast(),
+// mesh.occluded() and mesh.ambient_occlusion() ask.  Same conventions as the other mesh passes: the
 // caller's stream, buffers and workspace, no allocation, no host synchronisation, no float atomics.  The rules (which faces take part, the
-// point-triangle rule, the sampler's enumeration) are in include/customnerf_hip.h; tests/bvh_restatement.py restates them bit for bit.
+// point-triangle rule, the ray-triangle rule, the sampler's enumeration) are in include/customnerf_hip.h; tests/bvh_restatement.py and
+// tests/ray_restatement.py restate them bit for bit.
 //
 // Build
 //   k_bvh_bounds  : per face: index and finiteness check (flags), the number of faces that take part, the box of their centroids (integer
@@ -30,6 +32,32 @@
 //                   rounding of x's coordinates — ulps of the coordinates, covered by the grown box — and of the d^2 arithmetic — ulps
 //                   of d^2, covered by the shrink; far away d^2 is dominated by |p|^2 and the shrink dwarfs both.  The tests demand
 //                   equality with brute force from the surface out to thousands of diagonals.
+//   k_bvh_raycast / k_bvh_occluded : one thread per ray, the same stackless walk (nearer box entry first), for the closest hit (t_max shrinks
+//                   to the best hit; a subtree is skipped only when it lies strictly beyond it, so ties reach the smallest-face rule) and for
+//                   the any-hit bit (the walk ends at the first face accepted).  The ray/triangle rule is the watertight one of Woop,
+//                   Benthin and Wald in the header; bv_ray_box must never skip a face that rule accepts.  With u = 2^-24 and, for a node
+//                   box [lo, hi] and a ray origin o, M = the largest |lo[a] - o[a]|, |hi[a] - o[a]| (so |p - o| <= M per axis for every
+//                   vertex p under the node, whatever the leaf growth):
+//                   (1) sideways.  The rule accepts a face only when 0 lies in the triangle of its three sheared points, whose edge
+//                   functions have the right sign (a float32 difference of two rounded products cannot take the wrong sign, and a zero is
+//                   redone exactly).  A sheared coordinate is (p - o)[kx] - (d[kx] / d[kz]) (p - o)[kz] up to four roundings (the
+//                   difference p - o twice, Sx, the product, the difference) of quantities bounded by 2 M: less than 7 u M.  So some point
+//                   P of the real triangle lies within 7 u M, along kx and along ky, of the exact line's point with P's kz coordinate:
+//                   the exact line meets the node's box grown by 7 u M.  bv_ray_box grows the box by g = 2^-19 M = 32 u M in
+//                   origin-relative coordinates (lo - o is a float32 difference of float32 values: its error is u M, not an ulp of the
+//                   coordinates) and intersects the three slabs in the forward parameter w = |d[kz]| t, where the slopes are +-Sx, +-Sy
+//                   and +-1: one more product and the rounding of 1 / Sx and of Sx against d[kx] / d[kz] move a slab's end by 3 u of
+//                   itself, i.e. the box's side by less than 3 u (M + g).  7 + 2 + 3 < 32.  A direction component so small that 1 / Sx
+//                   overflows moves the ray sideways by less than 2^-126 M over the box: the axis is treated as having no motion (the
+//                   origin's coordinate must lie in the grown slab), and never meets 0 * inf.
+//                   (2) along the ray.  The accepted t is (U Az + V Bz + W Cz) / (U + V + W) with U, V, W of one sign: a weighted mean of
+//                   the three Az = Sz (p - o)[kz] with non-negative weights, up to 9 u of the largest |Az|.  So t lies in the node's kz
+//                   slab widened by 10 u M / |d[kz]|; the slab bv_ray_box compares with [t_min, t_max] is the one grown by g and costs 2 u
+//                   more for |Sz| and the product.  Only the kz slab is compared with the range: for a sliver the float32 weights can be
+//                   far from the exact barycentrics, so t need not lie where the exact line crosses the other two slabs.
+//                   Both hold while no intermediate overflows or underflows; an empty node is skipped by its inverted box, the NaN
+//                   records that pad the last leaf by their face index.  tests/test_gpu_mesh_ray.py demands equality with brute force for
+//                   origins on box planes, on faces and thousands of diagonals away.
 // Sampler
 //   k_sample_count / k_sample_scan / k_sample_emit : k^2 per face -> workgroup totals -> offsets -> one thread per sample (a binary search in
 //                   the workgroup's 256 prefix sums finds its face), so the writes are coalesced whatever the mix of face sizes.
@@ -45,6 +73,7 @@
 #define BV_GROW 3.814697265625e-06f                              // 2^-18
 #define BV_SHRINK 0.9999847412109375f                            // 1 - 2^-16
 #define BV_MAX_K 256.0f
+#define BV_RAY_GROW 1.9073486328125e-06f                         // 2^-19
 
 namespace {
 
@@ -400,6 +429,14 @@ __device__ __forceinline__ uint32_t bv_record(const float4 *__restrict__ tri, ui
     return __float_as_uint(r2.y);
 }
 
+__device__ __forceinline__ void bv_add_stats(unsigned long long *__restrict__ stats, uint32_t visits, uint32_t tests) {
+    const uint32_t sv = cn_wave_sum(visits), st = cn_wave_sum(tests);                     // one pair of adds per wave
+    if (cn_lane() == 0 && (sv | st)) {
+        atomicAdd(stats, (unsigned long long)sv);
+        atomicAdd(stats + 1, (unsigned long long)st);
+    }
+}
+
 __global__ __launch_bounds__(MC_BLOCK) void k_bvh_closest(BvPtr ws, uint32_t F, const float *__restrict__ points, uint32_t Q, float *__restrict__ dist2,
                                                           int32_t *__restrict__ face, float *__restrict__ point, float *__restrict__ bary,
                                                           unsigned long long *__restrict__ stats) {
@@ -489,13 +526,246 @@ __global__ __launch_bounds__(MC_BLOCK) void k_bvh_closest(BvPtr ws, uint32_t F, 
             }
         }
     }
-    if (stats) {                                                 // one pair of adds per wave
-        const uint32_t sv = cn_wave_sum(visits), st = cn_wave_sum(tests);
-        if (cn_lane() == 0 && (sv | st)) {
-            atomicAdd(stats, (unsigned long long)sv);
-            atomicAdd(stats + 1, (unsigned long long)st);
+    if (stats) bv_add_stats(stats, visits, tests);
+}
+
+// ------------------------------------------------------------------------------------------------ rays
+__device__ __forceinline__ float bv_pick(const float v[3], int k) { return k == 0 ? v[0] : (k == 1 ? v[1] : v[2]); }
+
+// A ray as the rule of the header sees it (the shear) and as the boxes see it: the forward parameter w = |d[kz]| t, the point at w being
+// o + w (+-Sx, +-Sy, +-1) on the axes (kx, ky, kz); rw[a] = w per unit of offset along world axis a (+-1 on kz, +-1 / Sx, +-1 / Sy; not
+// finite where the ray does not move along a).  Selects, not indexed arrays: nothing here may land in scratch.
+struct BvRay {
+    float o[3];
+    float sx, sy, sz, asz;                                       // asz = |Sz|: t = w asz
+    float rw[3];
+    int kx, ky, kz;
+};
+
+// false: a degenerate ray (it misses everything)
+__device__ __forceinline__ bool bv_ray_setup(const float o[3], const float d[3], BvRay &r) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        r.o[k] = o[k];
+        ok &= bv_finite(o[k]) && bv_finite(d[k]);
+    }
+    int kz = 0;
+    float m = fabsf(d[0]);
+    if (fabsf(d[1]) > m) {
+        kz = 1;
+        m = fabsf(d[1]);
+    }
+    if (fabsf(d[2]) > m) {
+        kz = 2;
+        m = fabsf(d[2]);
+    }
+    int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+    const float dz = bv_pick(d, kz);
+    if (dz < 0.0f) {
+        const int s = kx;
+        kx = ky;
+        ky = s;
+    }
+    r.kx = kx;
+    r.ky = ky;
+    r.kz = kz;
+    r.sx = bv_pick(d, kx) / dz;
+    r.sy = bv_pick(d, ky) / dz;
+    r.sz = 1.0f / dz;
+    r.asz = fabsf(r.sz);
+    const float sg = dz < 0.0f ? -1.0f : 1.0f, rx = sg * (1.0f / r.sx), ry = sg * (1.0f / r.sy);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) r.rw[a] = a == kz ? sg : (a == kx ? rx : ry);
+    return ok && m > 0.0f && bv_finite(r.sx) && bv_finite(r.sy) && bv_finite(r.sz);
+}
+
+// The rule of the header for one face: false = a miss whatever the range; true: t and the barycentrics (t may be NaN or infinite; the
+// caller's range test decides).
+__device__ __forceinline__ bool bv_ray_tri(const BvRay &r, const float a[3], const float b[3], const float c[3], int cull, float &t,
+                                           float bary[3]) {
+    float A[3], B[3], C[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        A[k] = a[k] - r.o[k];
+        B[k] = b[k] - r.o[k];
+        C[k] = c[k] - r.o[k];
+    }
+    const float Akz = bv_pick(A, r.kz), Bkz = bv_pick(B, r.kz), Ckz = bv_pick(C, r.kz);
+    const float Ax = bv_pick(A, r.kx) - r.sx * Akz, Ay = bv_pick(A, r.ky) - r.sy * Akz;
+    const float Bx = bv_pick(B, r.kx) - r.sx * Bkz, By = bv_pick(B, r.ky) - r.sy * Bkz;
+    const float Cx = bv_pick(C, r.kx) - r.sx * Ckz, Cy = bv_pick(C, r.ky) - r.sy * Ckz;
+    float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    bool neg, pos;
+    if (U == 0.0f || V == 0.0f || W == 0.0f) {                   // on an edge as far as float32 can tell: the products are exact in float64
+        const double Ud = (double)Cx * (double)By - (double)Cy * (double)Bx, Vd = (double)Ax * (double)Cy - (double)Ay * (double)Cx;
+        const double Wd = (double)Bx * (double)Ay - (double)By * (double)Ax;
+        neg = Ud < 0.0 || Vd < 0.0 || Wd < 0.0;
+        pos = Ud > 0.0 || Vd > 0.0 || Wd > 0.0;
+        U = (float)Ud;
+        V = (float)Vd;
+        W = (float)Wd;
+    } else {
+        neg = U < 0.0f || V < 0.0f || W < 0.0f;
+        pos = U > 0.0f || V > 0.0f || W > 0.0f;
+    }
+    if (neg && pos) return false;
+    const float det = (U + V) + W;
+    if (det == 0.0f || (cull == 1 && det < 0.0f) || (cull == 2 && det > 0.0f)) return false;
+    const float Az = r.sz * Akz, Bz = r.sz * Bkz, Cz = r.sz * Ckz;
+    t = ((U * Az + V * Bz) + W * Cz) / det;
+    bary[0] = U / det;
+    bary[1] = V / det;
+    bary[2] = W / det;
+    return true;
+}
+
+// Can the subtree of node idx hold a face that the rule accepts with t in [tmin, tcur]?  false only when it cannot (the argument is in the
+// file header); `enter` = where the ray enters the grown box, in w, for the order of the visit only.
+__device__ __forceinline__ bool bv_ray_box(const float4 *__restrict__ box, uint32_t idx, const BvRay &r, float tmin, float tcur, float &enter) {
+    const float4 lo = box[2 * (uint64_t)idx], hi = box[2 * (uint64_t)idx + 1];
+    enter = INFINITY;
+    if (!(lo.x <= hi.x)) return false;                           // a node without leaves
+    const float l[3] = {lo.x - r.o[0], lo.y - r.o[1], lo.z - r.o[2]}, h[3] = {hi.x - r.o[0], hi.y - r.o[1], hi.z - r.o[2]};
+    float M = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) M = fmaxf(M, fmaxf(fabsf(l[a]), fabsf(h[a])));
+    const float g = M * BV_RAY_GROW;
+    float en = -INFINITY, ex = INFINITY, zn = 0.0f, zf = 0.0f;
+    bool off = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float el = l[a] - g, eh = h[a] + g, rw = r.rw[a];
+        if (fabsf(rw) < INFINITY) {
+            const float p = el * rw, q = eh * rw, n = fminf(p, q), f = fmaxf(p, q);
+            en = fmaxf(en, n);
+            ex = fminf(ex, f);
+            if (a == r.kz) {
+                zn = n;
+                zf = f;
+            }
+        } else {
+            off |= el > 0.0f || eh < 0.0f;                       // no motion along a: the origin's coordinate must lie in the slab
         }
     }
+    enter = en;
+    return !(off || en > ex || zn * r.asz > tcur || zf * r.asz < tmin);
+}
+
+// The walk of k_bvh_closest for a ray.  ANY: leave at the first accepted hit (bestf says whether there was one).
+template <bool ANY>
+__device__ __forceinline__ void bv_trace(const BvPtr &ws, uint32_t n, const BvRay &ray, float tmin, float tmax, int cull, float &best,
+                                         uint32_t &bestf, float bb[3], uint32_t &visits, uint32_t &tests) {
+    uint32_t NL, D;
+    bv_shape(n, NL, D);
+    uint32_t node = 1, depth = 0, pending = 0;
+    float tcur = tmax, e0, e1;
+    ++visits;
+    bool go = bv_ray_box(ws.box, 1, ray, tmin, tcur, e0);
+    while (go) {
+        bool descend = false;
+        if (depth == D) {
+            const uint32_t j = node - (1u << D);
+            const uint32_t l0 = (uint32_t)(((uint64_t)j * NL) >> D), l1 = (uint32_t)((((uint64_t)j + 1) * NL) >> D);
+            if (l0 < l1) {
+#pragma unroll
+                for (uint32_t i = 0; i < BV_LEAF; ++i) {
+                    float a[3], b[3], c[3], br[3], t;
+                    const uint32_t f = bv_record(ws.tri, (uint64_t)l0 * BV_LEAF + i, a, b, c);
+                    if (f == BV_NOFACE || (ANY && bestf != BV_NOFACE)) continue;
+                    ++tests;
+                    if (bv_ray_tri(ray, a, b, c, cull, t, br) && tmin <= t && t <= tmax && (t < best || (t == best && f < bestf))) {
+                        best = t;
+                        bestf = f;
+                        bb[0] = br[0];
+                        bb[1] = br[1];
+                        bb[2] = br[2];
+                    }
+                }
+                if (ANY && bestf != BV_NOFACE) break;
+                tcur = fminf(tmax, best);
+            }
+        } else {
+            visits += 2;
+            const bool ok0 = bv_ray_box(ws.box, 2 * node, ray, tmin, tcur, e0), ok1 = bv_ray_box(ws.box, 2 * node + 1, ray, tmin, tcur, e1);
+            if (ok0 || ok1) {
+                const uint32_t first = (ok0 && ok1) ? (e1 < e0 ? 1u : 0u) : (ok1 ? 1u : 0u);
+                pending = (pending << 1) | ((ok0 && ok1) ? 1u : 0u);
+                node = 2 * node + first;
+                ++depth;
+                descend = true;
+            }
+        }
+        while (!descend) {                                       // back up to the nearest sibling still to come; its box is tested again
+            if (!pending) {
+                go = false;
+                break;
+            }
+            const uint32_t k = (uint32_t)__ffs((int)pending) - 1;
+            node = (node >> k) ^ 1u;
+            depth -= k;
+            pending = (pending >> k) & ~1u;
+            ++visits;
+            descend = bv_ray_box(ws.box, node, ray, tmin, tcur, e0);
+        }
+    }
+}
+
+// the ray of thread q and its range; false: no walk (q >= Q, no face in the tree, a degenerate ray, an empty range)
+__device__ __forceinline__ bool bv_ray_load(const float *__restrict__ origins, const float *__restrict__ dirs, uint32_t q, uint32_t Q, uint32_t n,
+                                            float tmin_s, float tmax_s, const float *__restrict__ tmin_a, const float *__restrict__ tmax_a,
+                                            BvRay &ray, float &tmin, float &tmax) {
+    float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f};
+    tmin = tmin_s;
+    tmax = tmax_s;
+    if (q < Q) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            o[k] = origins[3 * (uint64_t)q + k];
+            d[k] = dirs[3 * (uint64_t)q + k];
+        }
+        if (tmin_a) tmin = tmin_a[q];
+        if (tmax_a) tmax = tmax_a[q];
+    }
+    const bool ok = bv_ray_setup(o, d, ray);
+    return ok && q < Q && n && !(tmin > tmax);
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_raycast(BvPtr ws, uint32_t F, const float *__restrict__ origins, const float *__restrict__ dirs,
+                                                          uint32_t Q, float tmin_s, float tmax_s, const float *__restrict__ tmin_a,
+                                                          const float *__restrict__ tmax_a, int cull, float *__restrict__ t_out,
+                                                          int32_t *__restrict__ face_out, float *__restrict__ bary_out,
+                                                          unsigned long long *__restrict__ stats) {
+    const uint32_t q = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = min(ws.hdr[H_N], F);
+    BvRay ray;
+    float tmin, tmax, best = INFINITY, bb[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t bestf = BV_NOFACE, visits = 0, tests = 0;
+    if (bv_ray_load(origins, dirs, q, Q, n, tmin_s, tmax_s, tmin_a, tmax_a, ray, tmin, tmax))
+        bv_trace<false>(ws, n, ray, tmin, tmax, cull, best, bestf, bb, visits, tests);
+    if (q < Q) {
+        if (t_out) t_out[q] = best;
+        if (face_out) face_out[q] = bestf != BV_NOFACE ? (int32_t)bestf : -1;
+        if (bary_out)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) bary_out[3 * (uint64_t)q + k] = bb[k];
+    }
+    if (stats) bv_add_stats(stats, visits, tests);
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_occluded(BvPtr ws, uint32_t F, const float *__restrict__ origins, const float *__restrict__ dirs,
+                                                           uint32_t Q, float tmin_s, float tmax_s, const float *__restrict__ tmin_a,
+                                                           const float *__restrict__ tmax_a, int cull, uint8_t *__restrict__ occluded,
+                                                           unsigned long long *__restrict__ stats) {
+    const uint32_t q = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = min(ws.hdr[H_N], F);
+    BvRay ray;
+    float tmin, tmax, best = INFINITY, bb[3];
+    uint32_t bestf = BV_NOFACE, visits = 0, tests = 0;
+    if (bv_ray_load(origins, dirs, q, Q, n, tmin_s, tmax_s, tmin_a, tmax_a, ray, tmin, tmax))
+        bv_trace<true>(ws, n, ray, tmin, tmax, cull, best, bestf, bb, visits, tests);
+    if (q < Q) occluded[q] = bestf != BV_NOFACE ? 1 : 0;
+    if (stats) bv_add_stats(stats, visits, tests);
 }
 
 // ------------------------------------------------------------------------------------------------ sampler
@@ -647,6 +917,32 @@ int cnerf_mesh_bvh_closest(const void *ws, uint64_t ws_bytes, uint32_t V, uint32
     if (!Q) return CNERF_OK;
     hipLaunchKernelGGL(k_bvh_closest, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, F, points, Q, dist2, face, point, bary,
                        (unsigned long long *)stats);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_bvh_raycast(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const float *origins, const float *dirs, uint32_t Q,
+                           float t_min, float t_max, const float *t_min_per_ray, const float *t_max_per_ray, int cull, float *t_out,
+                           int32_t *face_out, float *bary_out, uint64_t *stats, void *stream) {
+    if (!ws || (Q && (!origins || !dirs))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F) || Q >= (1u << 31) || cull < 0 || cull > 2) return CNERF_EINVAL;
+    BvPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, bv_carve((void *)ws, F, p))) return rc;
+    if (!Q) return CNERF_OK;
+    hipLaunchKernelGGL(k_bvh_raycast, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, F, origins, dirs, Q, t_min, t_max, t_min_per_ray,
+                       t_max_per_ray, cull, t_out, face_out, bary_out, (unsigned long long *)stats);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_bvh_occluded(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const float *origins, const float *dirs, uint32_t Q,
+                            float t_min, float t_max, const float *t_min_per_ray, const float *t_max_per_ray, int cull, uint8_t *occluded,
+                            uint64_t *stats, void *stream) {
+    if (!ws || (Q && (!origins || !dirs || !occluded))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F) || Q >= (1u << 31) || cull < 0 || cull > 2) return CNERF_EINVAL;
+    BvPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, bv_carve((void *)ws, F, p))) return rc;
+    if (!Q) return CNERF_OK;
+    hipLaunchKernelGGL(k_bvh_occluded, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, F, origins, dirs, Q, t_min, t_max, t_min_per_ray,
+                       t_max_per_ray, cull, occluded, (unsigned long long *)stats);
     return cn_launch_status();
 }
 

@@ -2,8 +2,9 @@
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
 face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU
 (csrc/mesh_texture.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
-shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them
-(csrc/mesh_bvh.hip), a binary PLY writer and an OBJ + MTL + PNG writer.
+shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them,
+watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them (csrc/mesh_bvh.hip), a binary PLY writer
+and an OBJ + MTL + PNG writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -540,6 +541,148 @@ def closest_point(bvh, points, want_point=False, want_bary=False, want_stats=Fal
     return out
 
 
+def _ray_args(bvh, origins, dirs, t_min, t_max, cull, what):
+    """validated arguments of the ray queries -> (o, d, Q, t_min, t_max as floats, their [Q] tensors or None, the cull code)"""
+    if not isinstance(bvh, MeshBVH):
+        raise ValueError(f"{what}: bvh must come from build_bvh")
+    if cull not in _CULL:
+        raise ValueError(f"{what}: cull must be 'none', 'back' or 'front', got {cull!r}")
+    for name, t in (("origins", origins), ("dirs", dirs)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a tensor on the GPU")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{what}: {name} must be [Q, 3], got {tuple(t.shape)}")
+    if origins.shape[0] != dirs.shape[0]:
+        raise ValueError(f"{what}: origins and dirs must have one row per ray, got {origins.shape[0]} and {dirs.shape[0]}")
+    o, d = origins.detach().contiguous().float(), dirs.detach().contiguous().float()
+    Q = o.shape[0]
+    if Q >= 2 ** 31:
+        raise ValueError(f"{what}: at most 2^31 - 1 rays per call, got {Q}")
+    lim, per = [], []
+    for name, t in (("t_min", t_min), ("t_max", t_max)):
+        if torch.is_tensor(t):
+            if not t.is_cuda or tuple(t.shape) != (Q,):
+                raise ValueError(f"{what}: {name} must be a number or a [Q] tensor on the GPU, got {tuple(t.shape)} on {t.device}")
+            lim.append(0.0)
+            per.append(t.detach().contiguous().float())
+        else:
+            lim.append(float(t))
+            per.append(None)
+    return o, d, Q, lim[0], lim[1], per[0], per[1], _CULL[cull]
+
+
+def ray_cast(bvh, origins, dirs, t_min=0.0, t_max=math.inf, cull='none', want_bary=False, want_stats=False):
+    """The first face of the mesh of `bvh` (build_bvh) that each ray origins[q] + t dirs[q] meets with t_min <= t <= t_max, on the device
+    (csrc/mesh_bvh.hip, k_bvh_raycast).  origins, dirs [Q, 3] CUDA float tensors; dirs are not normalised and t is in units of |dirs[q]|;
+    t_min / t_max are numbers or [Q] CUDA tensors; cull 'none', 'back' or 'front' as in rasterize (faces wound outwards are front-facing
+    from outside).  -> dict: t [Q] float32 (+inf: a miss), face [Q] int32 (the smallest face index at that t; -1: a miss), and on request
+    bary [Q, 3] (the hit's barycentrics in the face; 0 for a miss) and stats = (node boxes tested, triangles tested) summed over the call.
+    The ray/triangle test is the watertight one of Woop, Benthin and Wald (the rule is in include/customnerf_hip.h, cnerf_mesh_bvh_raycast):
+    a ray through a shared edge or vertex hits one of the faces around it.  The result is the brute-force answer under that float32 rule,
+    bit for bit: the tree only prunes.  A ray with a non-finite origin, a zero or non-finite direction or t_min > t_max misses.  Rays next
+    to each other in the batch should be next to each other in space: they walk the tree together.  Bad arguments raise ValueError."""
+    o, d, Q, t0, t1, p0, p1, c = _ray_args(bvh, origins, dirs, t_min, t_max, cull, "ray_cast")
+    dev = o.device
+    out = {'t': torch.empty(Q, dtype=torch.float32, device=dev), 'face': torch.empty(Q, dtype=torch.int32, device=dev)}
+    if want_bary:
+        out['bary'] = torch.empty(Q, 3, dtype=torch.float32, device=dev)
+    stats = torch.zeros(2, dtype=torch.int64, device=dev) if want_stats else None
+    check(lib.cnerf_mesh_bvh_raycast(ptr(bvh.ws), bvh.nbytes, bvh.V, bvh.F, _p(o), _p(d), Q, t0, t1, _p(p0), _p(p1), c, _p(out['t']),
+                                     _p(out['face']), _p(out.get('bary')), _p(stats), stream()), "mesh_bvh_raycast")
+    if want_stats:
+        out['stats'] = tuple(int(s) for s in stats.cpu())
+    return out
+
+
+def occluded(bvh, origins, dirs, t_min=0.0, t_max=math.inf, cull='none'):
+    """Whether some face of the mesh of `bvh` stops each ray within [t_min, t_max]: ray_cast(...)['face'] >= 0 without the search for the
+    first hit (csrc/mesh_bvh.hip, k_bvh_occluded, which leaves the tree at the first face it accepts).  Arguments as ray_cast.
+    -> [Q] bool on the device."""
+    o, d, Q, t0, t1, p0, p1, c = _ray_args(bvh, origins, dirs, t_min, t_max, cull, "occluded")
+    occ = torch.empty(Q, dtype=torch.uint8, device=o.device)
+    check(lib.cnerf_mesh_bvh_occluded(ptr(bvh.ws), bvh.nbytes, bvh.V, bvh.F, _p(o), _p(d), Q, t0, t1, _p(p0), _p(p1), c, _p(occ), None,
+                                      stream()), "mesh_bvh_occluded")
+    return occ != 0
+
+
+def ao_directions(K):
+    """K fixed directions on the hemisphere about +z, cosine-weighted (their density is proportional to z), as [K, 3] float32 on the host:
+    spherical-Fibonacci points, for i = 0 .. K - 1: u = (i + 0.5) / K, z = sqrt(1 - u), r = sqrt(u), phi = 2 pi frac(i (sqrt(5) - 1) / 2),
+    direction (r cos phi, r sin phi, z), computed in float64 and rounded once."""
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"ao_directions: need K >= 1, got {K}")
+    i = np.arange(K, dtype=np.float64)
+    u = (i + 0.5) / float(K)
+    phi = 2.0 * math.pi * np.mod(i * ((math.sqrt(5.0) - 1.0) / 2.0), 1.0)
+    r = np.sqrt(u)
+    return torch.from_numpy(np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - u)], 1).astype(np.float32))
+
+
+def ao_rays(verts, normals, dirs, bias):
+    """The ambient-occlusion rays of vertices verts [N, 3] with normals [N, 3] for hemisphere directions dirs [K, 3] (ao_directions), in
+    torch float32 on the device -> (origins [N, K, 3], directions [N, K, 3]).  n = normals / sqrt((nx nx + ny ny) + nz nz); the frame is
+    the branch-free orthonormal basis of Duff et al. (JCGT 6(1), 2017): s = copysign(1, nz), a = -1 / (s + nz), b = (nx ny) a,
+    b1 = (1 + (s (nx nx)) a, s b, -s nx), b2 = (b, s + (ny ny) a, -ny); direction = (dx b1 + dy b2) + dz n, origin = x + bias n."""
+    n = normals / ((normals[:, 0:1] * normals[:, 0:1] + normals[:, 1:2] * normals[:, 1:2]) + normals[:, 2:3] * normals[:, 2:3]).sqrt()
+    nx, ny, nz = n[:, 0], n[:, 1], n[:, 2]
+    s = torch.copysign(torch.ones_like(nz), nz)
+    a = -1.0 / (s + nz)
+    b = (nx * ny) * a
+    b1 = torch.stack([1.0 + (s * (nx * nx)) * a, s * b, (-s) * nx], 1)
+    b2 = torch.stack([b, s + (ny * ny) * a, -ny], 1)
+    d = dirs.to(n.device)
+    out = (d[None, :, 0:1] * b1[:, None] + d[None, :, 1:2] * b2[:, None]) + d[None, :, 2:3] * n[:, None]
+    org = verts + bias * n
+    return org[:, None].expand_as(out), out
+
+
+def ambient_occlusion(verts, faces, normals=None, samples=64, radius=None, bias=None, chunk=2 ** 22):
+    """Per-vertex ambient occlusion of a triangle mesh, as mesh viewers compute it, on the device: the share of `samples` rays from each
+    vertex that no face of the mesh stops.  The rays start at x + bias n (bias: by default 1e-4 of the diagonal of the mesh's box) and
+    follow ao_directions(samples) turned into the vertex's frame (ao_rays); a face stops a ray when it is hit at 0 <= t <= radius (by
+    default: anywhere).  Without `normals`, vertex_normals(verts, faces).  -> [V] float32 in [0, 1]; 1 for a vertex no valid face uses.
+    A composition over occluded() on build_bvh(verts, faces), at most `chunk` rays at a time.  CUDA tensors verts [V, 3], faces [F, 3]
+    (int), normals [V, 3] or None.  samples < 1, a non-finite bias, a radius that is not > 0 or chunk < 1 raise ValueError."""
+    for name, t in (("verts", verts), ("faces", faces), ("normals", normals)):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+            raise ValueError(f"ambient_occlusion: {name} must be a tensor on the GPU")
+    v, f, n = _mesh_args(verts, faces, normals, "ambient_occlusion")
+    K, chunk = int(samples), int(chunk)
+    if K < 1:
+        raise ValueError(f"ambient_occlusion: samples must be >= 1, got {samples}")
+    if chunk < 1:
+        raise ValueError(f"ambient_occlusion: chunk must be >= 1, got {chunk}")
+    radius = math.inf if radius is None else float(radius)
+    if not radius > 0.0:
+        raise ValueError(f"ambient_occlusion: radius must be > 0, got {radius}")
+    if bias is not None and not math.isfinite(float(bias)):
+        raise ValueError(f"ambient_occlusion: bias must be finite, got {bias}")
+    V, dev = v.shape[0], v.device
+    ao = torch.ones(V, dtype=torch.float32, device=dev)
+    bvh = build_bvh(v, f)
+    if V == 0 or bvh.n_faces == 0:
+        return ao
+    mask = _used_mask(v, f)
+    if bias is None:
+        lo, hi = torch.aminmax(v[mask], dim=0)
+        bias = 1e-4 * float((hi - lo).double().norm())
+    bias = float(bias)
+    if n is None:
+        n = vertex_normals(v, f)
+    dirs = ao_directions(K).to(dev)
+    kb = min(K, chunk)
+    vb = max(1, chunk // kb)
+    free = torch.zeros(V, dtype=torch.int64, device=dev)
+    for v0 in range(0, V, vb):
+        for k0 in range(0, K, kb):
+            org, d = ao_rays(v[v0:v0 + vb], n[v0:v0 + vb], dirs[k0:k0 + kb], bias)
+            occ = occluded(bvh, org.reshape(-1, 3), d.reshape(-1, 3), 0.0, radius)
+            free[v0:v0 + vb] += (~occ).reshape(org.shape[0], -1).sum(1)
+    ao[mask] = free[mask].float() / float(K)
+    return ao
+
+
 def _sample(verts, faces, spacing, max_samples, what):
     """the sampler behind sample_surface and distance -> ((points, face, bary, weight), flags); a face that needs k > 256 is sampled at
     k = 256 and sets flags bit 2: the caller decides"""
@@ -574,8 +717,8 @@ def sample_surface(verts, faces, spacing, max_samples=1 << 26):
     return out
 
 
-def _used_vertices(v, f):
-    """the vertices of the faces that take part (valid indices, finite coordinates), in index order"""
+def _used_mask(v, f):
+    """[V] bool: the vertices of the faces that take part (valid indices, finite coordinates)"""
     V = v.shape[0]
     fl = f.long()
     ok = ((fl >= 0) & (fl < V)).all(1)
@@ -583,7 +726,12 @@ def _used_vertices(v, f):
     fl = fl[torch.isfinite(v[fl.reshape(-1)]).reshape(-1, 9).all(1)]
     used = torch.zeros(V, dtype=torch.bool, device=v.device)
     used[fl.reshape(-1)] = True
-    return v[used]
+    return used
+
+
+def _used_vertices(v, f):
+    """the vertices of the faces that take part, in index order"""
+    return v[_used_mask(v, f)]
 
 
 def _one_way(v, f, bvh, spacing, include_vertices, max_samples):

@@ -487,7 +487,7 @@ class NeRFRenderer(nn.Module):
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
-                     smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26):
+                     smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -506,7 +506,11 @@ class NeRFRenderer(nn.Module):
         stood after marching cubes and component removal), both directions (max, mean, rms per direction and 'hausdorff', in world units),
         sampled deviation_spacing apart (default: half the smallest lattice step; at most deviation_max_samples samples per direction,
         ValueError beyond), plus 'step', the lattice step, so that the error reads in voxels; None when neither smooth, simplify nor
-        target_faces ran.  Without deviation=True the key is absent."""
+        target_faces ran.  Without deviation=True the key is absent.
+        ao=K > 0 adds 'ao' [V] float32 in [0, 1]: the per-vertex ambient occlusion of the final mesh from K rays per vertex
+        (mesh.ambient_occlusion: the share of the rays that escape), a shading cue for geometry-only previews — render_mesh(colors=) shows
+        it as grey.  It is never multiplied into colors or texture: the field's radiance already contains the scene's shading.  With ao=0
+        the key is absent."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -524,6 +528,9 @@ class NeRFRenderer(nn.Module):
         n_smooth = int(smooth)
         if n_smooth < 0:
             raise ValueError(f"extract_mesh: smooth must be 0 (off) or a number of iterations, got {smooth}")
+        n_ao = int(ao)
+        if n_ao < 0:
+            raise ValueError(f"extract_mesh: ao must be 0 (off) or a number of rays per vertex, got {ao}")
         vol = self.density_volume(R, aabb, chunk, part, view_dir)
         verts, faces, normals = _mesh.marching_cubes(vol, threshold, spacing=step.tolist(), origin=lo.tolist())
         if int(min_component_faces) > 0 or keep_largest:
@@ -555,14 +562,18 @@ class NeRFRenderer(nn.Module):
                 sp = 0.5 * float(step.min()) if deviation_spacing is None else float(deviation_spacing)
                 m['deviation'] = dict(_mesh.distance(verts, faces, kept[0], kept[1], spacing=sp, max_samples=deviation_max_samples),
                                       step=tuple(step.tolist()))
+        if n_ao:
+            m['ao'] = _mesh.ambient_occlusion(verts, faces, normals=normals, samples=n_ao)
         return m
 
     def save_mesh(self, path, **kw):
         """extract_mesh(**kw) written to `path` -> the mesh dict.  A path ending in .obj writes a Wavefront OBJ (mesh.write_obj: positions,
         normals, and with texture=R the UVs, <stem>.mtl and the R x R <stem>.png beside it; vertex colours are not written to OBJ); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
-        extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces) and deviation / deviation_spacing
-        pass through."""
+        extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), deviation / deviation_spacing
+        and ao pass through.  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
+        round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written
+        unchanged (a NeRF's radiance already contains its shading, so AO is never multiplied into baked colour or texture)."""
         obj = str(path).lower().endswith(".obj")
         if int(kw.get('texture', 0) or 0) and not obj:
             raise ValueError(f"save_mesh: texture= needs an .obj path (PLY carries no texture), got {path!r}")
@@ -570,7 +581,10 @@ class NeRFRenderer(nn.Module):
         if obj:
             _mesh.write_obj(path, m['verts'], m['faces'], uvs=m['uvs'], normals=m['normals'], texture=m['texture'])
         else:
-            _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=m['colors'])
+            colors = m['colors']
+            if colors is None and 'ao' in m:
+                colors = (m['ao'] * 255).round().to(torch.uint8)[:, None].expand(-1, 3)
+            _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=colors)
         return m
 
     def render_mesh(self, mesh, c2w, intrinsics, H, W, path=None, **kw):

@@ -41,7 +41,8 @@ extern "C" {
  *    same version) — cnerf_mesh_atlas_layout / _uvs / _points / _store / _fill; smoothing and normals (additive, same version) —
  *    cnerf_mesh_smooth_workspace_bytes / _init / _steps / _normals; mesh rasteriser (additive, same version) —
  *    cnerf_mesh_raster_workspace_bytes / _visibility / _shade; closest-point queries and surface samples (additive, same version) —
- *    cnerf_mesh_bvh_workspace_bytes / _build / _closest and cnerf_mesh_sample_workspace_bytes / _count / _emit. */
+ *    cnerf_mesh_bvh_workspace_bytes / _build / _closest and cnerf_mesh_sample_workspace_bytes / _count / _emit; ray queries on the same tree
+ *    (additive, same version) — cnerf_mesh_bvh_raycast / _occluded. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -779,6 +780,41 @@ int cnerf_mesh_sample_count(const float *verts, uint32_t V, const int32_t *faces
                             uint64_t *counts, void *stream);
 int cnerf_mesh_sample_emit(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, float spacing, void *ws, uint64_t ws_bytes,
                            float *points, int32_t *face, float *bary, float *weight, uint64_t max_samples, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Ray queries against the tree of cnerf_mesh_bvh_build: the closest hit and the any-hit bit (customnerf_amd/mesh.py ray_cast / occluded /
+ * ambient_occlusion; csrc/mesh_bvh.hip; the reference has none).  After build with the same ws, V and F; the faces that take part are
+ * those of the build.  origins, dirs float32 [Q][3]; the direction is not normalised and t is in units of |d|.  float32, one rounding per
+ * written operation in the order written, divisions correctly rounded, exactly as above; tests/ray_restatement.py restates the rule.
+ *   The ray/triangle rule is the watertight test of Woop, Benthin and Wald (JCGT 2(1), 2013): a ray through an edge or a vertex that two
+ *   faces share hits at least one of them, because both evaluate the shared edge's function from the same two sheared points, with the
+ *   opposite sign and the same magnitude, and a zero is settled exactly.
+ *   Per ray (o, d): kz = the axis of the largest |d| (the lowest axis on a tie); kx = (kz + 1) mod 3, ky = (kx + 1) mod 3, the two swapped
+ *     when d[kz] < 0; Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].
+ *   Per face (a, b, c): A = a - o per component (B, C alike); Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz] (B, C alike);
+ *     U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax.  When U, V or W is exactly 0, all three are computed again in float64 from the
+ *     float32 Ax .. Cy (the products are then exact), the signs are taken from the float64 values, and U, V, W become their float32
+ *     roundings.  A miss when some of the three is < 0 and some is > 0.  det = (U + V) + W; a miss when det == 0; cull 1 (back) misses
+ *     when det < 0, cull 2 (front) when det > 0 (det > 0: the ray meets the side (b - a) x (c - a) points to, the front of a face wound
+ *     outwards — the convention of cnerf_mesh_raster_visibility).  Az = Sz A[kz] (Bz, Cz alike), t = ((U Az + V Bz) + W Cz) / det,
+ *     bary = (U / det, V / det, W / det).  The face is hit when t_min <= t <= t_max (false for a NaN).
+ *   raycast : t_out [Q] = the smallest t over the faces hit, face_out [Q] = the smallest face index attaining it, bary_out [Q][3] that face's
+ *     barycentrics (a miss: t = +inf, face = -1, bary = 0).  Any of the three may be NULL.
+ *   occluded : occluded [Q] uint8 = 1 when some face is hit, else 0.
+ *   The range is t_min / t_max for every ray, or t_min_per_ray[q] / t_max_per_ray[q] where that pointer is not NULL.
+ *   A ray misses everything when a component of o or d is not finite, d = 0, Sx, Sy or Sz is not finite, or t_min > t_max.
+ *   stats (NULL or device uint64 [2], ADDED to, so zero it first): node boxes tested and triangles tested, summed over the call.  The tree
+ *   only prunes: every output is the brute-force result over the faces, bit for bit (csrc/mesh_bvh.hip says why, for coordinates whose
+ *   products do not overflow).
+ *   CNERF_ENULL: a required pointer is NULL.  CNERF_EINVAL: V, F or Q >= 2^31, a short or misaligned ws, cull outside 0 .. 2.  Both return
+ *   before any launch; Q = 0 is accepted.  The caller's stream; no allocation, no host sync; the only atomics are the integer stats.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_bvh_raycast(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const float *origins, const float *dirs, uint32_t Q,
+                           float t_min, float t_max, const float *t_min_per_ray, const float *t_max_per_ray, int cull, float *t_out,
+                           int32_t *face_out, float *bary_out, uint64_t *stats, void *stream);
+int cnerf_mesh_bvh_occluded(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const float *origins, const float *dirs, uint32_t Q,
+                            float t_min, float t_max, const float *t_min_per_ray, const float *t_max_per_ray, int cull, uint8_t *occluded,
+                            uint64_t *stats, void *stream);
 
 #ifdef __cplusplus
 }
