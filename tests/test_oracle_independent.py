@@ -9,6 +9,8 @@ from oracle import c_oracle as co
 from oracle import np_restatement as nr
 from oracle import torch_oracle as to
 
+import march_testlib as ML
+
 
 def test_fma32_is_single_rounding():
     rng = np.random.default_rng(0)
@@ -89,11 +91,86 @@ def test_march_rays_train_two_restatements_agree(dt_gamma, seed):
     xyzs, dirs, deltas, rays = co.march_rays_train(o, d, bound, bitfield, C, H, nears, fars, counter, -1, noises, -1, True, dt_gamma, max_steps)
     counts, pts, dls = nr.march_rays_train(o, d, bitfield, bound, dt_gamma, max_steps, C, H, nears, fars, noises)
     assert counts.sum() > 200 and (counts == 0).any()
+    _same_march(xyzs, deltas, rays, counts, pts, dls)
+
+
+def _same_march(xyzs, deltas, rays, counts, pts, dls):
     order = np.argsort(rays[:, 0])
     np.testing.assert_array_equal(rays[order, 2], counts)
-    for n in range(o.shape[0]):
+    for n in range(rays.shape[0]):
         r = rays[order[n]]
         if r[2] == 0:
             continue
         np.testing.assert_array_equal(xyzs[r[1]:r[1] + r[2]], pts[n], err_msg=f"ray {n} positions")
         np.testing.assert_array_equal(deltas[r[1]:r[1] + r[2]], dls[n], err_msg=f"ray {n} deltas")
+
+
+@pytest.mark.parametrize("dt_gamma,max_steps", [(1.0 / 32, 256), (0.0, 70), (1.0 / 32, 16)])      # 16 steps: dt_min > dt_max on the fine grids
+@pytest.mark.parametrize("bound,H", ML.CONFIGS)
+def test_march_rays_train_two_restatements_agree_across_cascades(bound, H, dt_gamma, max_steps):
+    """the same pair away from cascade 2 and bound 2: one, two, three and five cascades, a bound that is no power of two (an inexact
+    1 / mip_bound in front of the double-promoted voxel index), rays with +0 / -0 direction components and rays that start inside the box"""
+    c = ML.march_case(bound, H, N=61)
+    xyzs, dirs, deltas, rays = co.march_rays_train(c["o"], c["d"], bound, c["bitfield"], c["C"], H, c["nears"], c["fars"], None, -1, c["noises"], -1,
+                                                   True, dt_gamma, max_steps)
+    counts, pts, dls = nr.march_rays_train(c["o"], c["d"], c["bitfield"], bound, dt_gamma, max_steps, c["C"], H, c["nears"], c["fars"], c["noises"])
+    assert counts.sum() > 200 and (counts == 0).any()
+    _same_march(xyzs, deltas, rays, counts, pts, dls)
+
+
+def test_march_cases_hold_what_the_gpu_tests_rely_on():
+    """tests/march_testlib.py feeds the GPU shape tests; what they assert about their inputs is asserted here on the oracle alone, so a
+    change to the helpers cannot quietly empty a case: rays without a step, samples at every cascade level, rays longer than one 64-sample
+    chunk, the step cap reached where the tests say so, ragged ray counts, degenerate directions that still produce samples."""
+    assert ML.N_RAYS % 4 and ML.N_RAYS % 64 and ML.N_RAYS % 256
+    assert [ML.cascades(b) for b, _ in ML.CONFIGS] == [1, 2, 3, 5]
+    for bound, H in ML.CONFIGS:
+        c = ML.march_case(bound, H)
+        d = c["d"]
+        assert (c["nears"] >= c["fars"]).sum() >= 10                                        # rays that miss the box
+        assert np.all(np.abs(np.linalg.norm(d.astype(np.float64), axis=1) - 1) < 1e-6)
+        inside = np.all(np.abs(c["o"]) < bound, axis=1)
+        assert inside.sum() >= ML.N_RAYS // 5
+        frac = np.unpackbits(c["bitfield"]).mean()
+        assert c["bitfield"].shape[0] == c["C"] * H ** 3 // 8 and 0.29 < frac < 0.31
+        pz = (d[:, 0] == 0) & ~np.signbit(d[:, 0]) & (d[:, 1] != 0)
+        nz = (d[:, 1] == 0) & np.signbit(d[:, 1]) & (d[:, 0] != 0)
+        ax = (d[:, 0] == 0) & (d[:, 1] == 0)
+        for dt_gamma, max_steps in ML.SETTINGS:
+            xyzs, dirs, deltas, rays = ML.march_oracle(bound, H, dt_gamma, max_steps)
+            steps = rays[:, 2]
+            total = int(steps.sum())
+            assert total > 10 * ML.N_RAYS and (steps == 0).sum() >= 10
+            assert set(ML.sample_levels(xyzs[:total], c["C"]).tolist()) == set(range(c["C"]))
+            assert (int(steps.max()) == max_steps) == (((bound, H), (dt_gamma, max_steps)) in ML.CAPPED)
+            assert steps.max() > 128 or max_steps < 1024                                    # rays of several 64-sample chunks
+            for mask in (pz, nz, ax):
+                assert steps[mask].sum() > 0                                                # the degenerate rays march through occupied cells
+
+
+def test_composite_table_holds_what_the_gpu_test_relies_on():
+    """the compositing table of tests/march_testlib.py: the float64 loop stops rays 10-12 just before, at and just after sample 64; no keep
+    decision is within a factor e of T_thresh (so rounding cannot flip one); and the float32 C oracle meets, against float64, the very
+    tolerances the kernel is held to on this table."""
+    t = ML.composite_table()
+    rays, T = t["rays"], ML.TABLE_T_THRESH
+    assert sorted(rays[:, 0].tolist()) == list(range(14)) and not np.array_equal(rays[:, 0], np.arange(14))
+    assert rays[:, 2].tolist() == list(ML.TABLE_LENGTHS) and rays[-1, 1] + rays[-1, 2] == t["sigmas"].shape[0]
+    f = ML.composite_train_f64(t["sigmas"], t["rgbs"], t["deltas"], rays, T, t["grad_ws"], t["grad_image"])
+    assert f["margin"] > 1
+    for n, pos in ML.TABLE_OPAQUE.items():
+        off, ln = rays[n, 1], rays[n, 2]
+        assert f["kept"][off:off + ln].tolist() == [True] * (pos + 1) + [False] * (ln - pos - 1)
+        assert ln - pos - 1 >= 1
+    off = rays[13, 1]
+    assert f["kept"][off:off + 200].tolist() == [True] * 101 + [False] * 99 and f["ws"][rays[13, 0]] == 1.0
+    assert f["kept"][rays[9, 1]:rays[9, 1] + 300].all()                                      # the 300-sample ray runs through all five chunks
+    rgb = np.ascontiguousarray(t["rgbs"][:, :3])
+    ws, dep, img = co.composite_rays_train_forward(t["sigmas"], rgb, t["deltas"], rays, T)
+    gs, gc = co.composite_rays_train_backward(t["grad_ws"], t["grad_image"], t["sigmas"], rgb, t["deltas"], rays, ws, img, T)
+    np.testing.assert_allclose(ws, f["ws"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(img, f["image"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(dep, f["depth"], rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(gs, f["grad_sigmas"], rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(gc, f["grad_rgbs"], rtol=1e-4, atol=1e-6)
+    assert np.all(gs[~f["kept"]] == 0) and np.all(gc[~f["kept"]] == 0)
