@@ -161,13 +161,7 @@ __global__ void __launch_bounds__(RN_THREADS) k_sample_fine_merge(const float *_
     // and src_index[n][pos] = row of the sorted sample `pos` in that [coarse | fine] sample list — the compositing kernels read through it.
     float *za = z_all + (size_t)n * (T + t), *xa = xyz_all ? xyz_all + (size_t)n * (T + t) * 3 : nullptr;
     uint32_t *si = src_index ? src_index + (size_t)n * (T + t) : nullptr;
-    for (uint32_t i = lane; i < T; i += 64) {
-        const float v = zz[i];
-        uint32_t pos = i;
-        for (uint32_t m = 0; m < t4; m++) {
-            const float4 w = nz4[m];
-            pos += ((w.x < v) ? 1u : 0u) + ((w.y < v) ? 1u : 0u) + ((w.z < v) ? 1u : 0u) + ((w.w < v) ? 1u : 0u);
-        }
+    auto put_coarse = [&](uint32_t i, uint32_t pos, float v) {
         za[pos] = v;
         if (xa) {
             float p[3];
@@ -175,6 +169,56 @@ __global__ void __launch_bounds__(RN_THREADS) k_sample_fine_merge(const float *_
             xa[pos * 3] = p[0]; xa[pos * 3 + 1] = p[1]; xa[pos * 3 + 2] = p[2];
         }
         if (si) si[pos] = n * T + i;
+    };
+    auto put_fine = [&](uint32_t m, uint32_t pos, float v) {
+        float p[3];
+        rn_point(o, d, v, aabb, p);
+        za[pos] = v;
+        if (xa) { xa[pos * 3] = p[0]; xa[pos * 3 + 1] = p[1]; xa[pos * 3 + 2] = p[2]; }
+        if (xyz_fine) {
+            // draw order, NOT sorted along the ray: measured 1 % faster end to end (sorted neighbours collide in the scatter's LDS atomics)
+            float *xf = xyz_fine + ((size_t)n * t + m) * 3;
+            xf[0] = p[0]; xf[1] = p[1]; xf[2] = p[2];
+            if (unit_fine) {                                  // grid coordinates of the new samples, as k_sample_coarse writes them
+                float *uf = unit_fine + ((size_t)n * t + m) * 3;
+                const float inv = 1.0f / (2.0f * bound);
+                uf[0] = (p[0] + bound) * inv; uf[1] = (p[1] + bound) * inv; uf[2] = (p[2] + bound) * inv;
+            }
+        }
+        if (si) si[pos] = N * T + n * t + m;
+    };
+    // The rank rules above hold when the coarse samples ascend and every value can be compared.  A ray whose box lies behind it has far < near
+    // (descending samples) and one that starts on a slab plane with a zero direction component has a NaN near (near_far_from_aabb, 0 * inf):
+    // such a ray takes the general ranks below, so that src_index stays a permutation of the ray's rows whatever the values are.
+    bool unordered = false;
+    for (uint32_t i = lane; i + 1 < T; i += 64) unordered |= !(zz[i] <= zz[i + 1]);
+    for (uint32_t m = lane; m < t; m += 64) unordered |= nz[m] != nz[m];
+    if (__builtin_amdgcn_ballot_w64(unordered) != 0ull) {    // wave-uniform: one ray per wave
+        // full rank counts over [coarse | fine] under a total order: by value, NaN greatest, ties by position in that list (torch.sort's
+        // output: ascending, NaN last).  (T + t)^2 / 64 comparisons per lane, for such rays only.
+        const uint32_t S = T + t;
+        for (uint32_t j = lane; j < S; j += 64) {
+            const float v = j < T ? zz[j] : nz[j - T];
+            const bool vnan = v != v;
+            uint32_t pos = 0;
+            for (uint32_t k = 0; k < S; k++) {
+                const float w = k < T ? zz[k] : nz[k - T];
+                const bool wnan = w != w;
+                const bool before = vnan ? (!wnan || k < j) : (!wnan && (w < v || (w == v && k < j)));
+                pos += before ? 1u : 0u;
+            }
+            if (j < T) put_coarse(j, pos, v); else put_fine(j - T, pos, v);
+        }
+        return;
+    }
+    for (uint32_t i = lane; i < T; i += 64) {
+        const float v = zz[i];
+        uint32_t pos = i;
+        for (uint32_t m = 0; m < t4; m++) {
+            const float4 w = nz4[m];
+            pos += ((w.x < v) ? 1u : 0u) + ((w.y < v) ? 1u : 0u) + ((w.z < v) ? 1u : 0u) + ((w.w < v) ? 1u : 0u);
+        }
+        put_coarse(i, pos, v);
     }
     for (uint32_t m = lane; m < t; m += 64) {
         const float v = nz[m];
@@ -192,21 +236,7 @@ __global__ void __launch_bounds__(RN_THREADS) k_sample_fine_merge(const float *_
             }
             pos += lo;
         }
-        float p[3];
-        rn_point(o, d, v, aabb, p);
-        za[pos] = v;
-        if (xa) { xa[pos * 3] = p[0]; xa[pos * 3 + 1] = p[1]; xa[pos * 3 + 2] = p[2]; }
-        if (xyz_fine) {
-            // draw order, NOT sorted along the ray: measured 1 % faster end to end (sorted neighbours collide in the scatter's LDS atomics)
-            float *xf = xyz_fine + ((size_t)n * t + m) * 3;
-            xf[0] = p[0]; xf[1] = p[1]; xf[2] = p[2];
-            if (unit_fine) {                                  // grid coordinates of the new samples, as k_sample_coarse writes them
-                float *uf = unit_fine + ((size_t)n * t + m) * 3;
-                const float inv = 1.0f / (2.0f * bound);
-                uf[0] = (p[0] + bound) * inv; uf[1] = (p[1] + bound) * inv; uf[2] = (p[2] + bound) * inv;
-            }
-        }
-        if (si) si[pos] = N * T + n * t + m;
+        put_fine(m, pos, v);
     }
 }
 

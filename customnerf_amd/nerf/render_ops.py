@@ -99,7 +99,9 @@ class _CompositeRunIndexed(Function):
         num_steps, soft, thr, dbg, dmask = ctx.cfg
         N, S = z_vals.shape
         g_ray = g_ray.contiguous().float()
-        g_sigma = torch.empty_like(sigmas)                      # src_index is a permutation of the rows: every element is written
+        # every element is written: src_index is a permutation of the rows, which k_sample_fine_merge guarantees ray by ray for every float
+        # input (descending or NaN samples take its general rank path) and tests/test_gpu_run_shapes.py pins
+        g_sigma = torch.empty_like(sigmas)
         g_rgbc = torch.empty_like(rgbc)
         if ctx.flush:
             # early termination for the half-precision fused field: rows whose gradients round to zero in the form its backward consumes them are

@@ -370,7 +370,10 @@ int cnerf_sample_fine_merge(const float *rays_o, const float *rays_d, const floa
  * above; xyz_fine [N,t,3] receives the new samples in their own block; src_index [N,T+t] (uint32) maps every sorted position to its
  * row in the sample list [coarse block N*T rows | fine block N*t rows]: coarse i of ray n -> n*T + i, fine m (draw order) -> N*T + n*t + m.
  * The field is then evaluated on that list (the coarse block's grid features are already there from the density pass) and the
- * compositing entries below read through src_index.  xyz_all may be NULL here (or non-NULL to get both forms). */
+ * compositing entries below read through src_index.  xyz_all may be NULL here (or non-NULL to get both forms).
+ * For every float input — a ray looking away from the box (far < near: descending z_vals), a NaN near, NaN or infinite sigmas — row n of
+ * src_index is a permutation of ray n's rows, every output element is written and z_all is in sort order, ascending with NaN last: the
+ * compositing backward stores through src_index and relies on it. */
 int cnerf_sample_fine_merge_split(const float *rays_o, const float *rays_d, const float *nears, const float *fars,
                                   const float *aabb, const float *z_vals, const float *sigmas, const float *u, uint32_t N,
                                   uint32_t T, uint32_t t, float *z_all, float *xyz_all, float *xyz_fine, uint32_t *src_index,

@@ -223,7 +223,7 @@ def sample_pdf(bins, weights, n_samples, det=False, u=None):
     cdf = torch.cumsum(pdf, -1)
     cdf = torch.cat([torch.zeros_like(cdf[..., :1]), cdf], -1)
     if det:
-        u = torch.linspace(0. + 0.5 / n_samples, 1. - 0.5 / n_samples, steps=n_samples)
+        u = torch.linspace(0. + 0.5 / n_samples, 1. - 0.5 / n_samples, steps=n_samples, dtype=cdf.dtype)
         u = u.expand(list(cdf.shape[:-1]) + [n_samples])
     elif u is None:
         u = torch.rand(list(cdf.shape[:-1]) + [n_samples])
