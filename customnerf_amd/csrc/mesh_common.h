@@ -3,8 +3,9 @@
 // prefix sums and the one-workgroup scan of workgroup totals, the range-checked face load, the vertex -> list offset steps, the per-vertex
 // insertion sort and the compacted vertex store.
 // Every grid these kernels scan is one thread per item, MC_BLOCK threads per workgroup;
-// a count pass stores each workgroup's two totals (uint2), mc_scan_totals turns them into exclusive offsets in place, and an emit pass adds
-// the in-workgroup prefix (ballot + mbcnt, LDS wave totals) to its workgroup's offset.  Order follows the thread index: no atomics.
+// a count pass stores each workgroup's totals (two as uint2, or N as uint32 [N]), mc_scan_totals / mc_scan_totals_n turn them into exclusive
+// offsets in place, and an emit pass adds the in-workgroup prefix (ballot + mbcnt, LDS wave totals) to its workgroup's offset.  Order follows
+// the thread index: no atomics.
 #pragma once
 #include "common.h"
 
@@ -84,43 +85,80 @@ __device__ __forceinline__ uint32_t mc_block_total(uint32_t v, uint32_t *red) {
     return s;
 }
 
-// Body of a one-workgroup (MC_SCAN_BLOCK threads) scan: sums[0..nblk) -> exclusive offsets in place, component-wise; cv / ct = the two
-// totals (exact in 64 bits; every thread gets them).  Every thread of the block must call it.
-__device__ __forceinline__ void mc_scan_totals(uint2 *__restrict__ sums, uint32_t nblk, uint64_t &cv, uint64_t &ct) {
-    __shared__ uint32_t wv[MC_SCAN_BLOCK / CN_WAVE], wt[MC_SCAN_BLOCK / CN_WAVE];
+// Rank of this thread among the threads before it in its workgroup (thread order) that have the same class c < NC (c >= NC: no class, the
+// rank is 0), and every class's workgroup total in tot[]; every thread of the block must call it.  `red` = LDS [NC][MC_WAVES]
+template <int NC>
+__device__ __forceinline__ uint32_t mc_block_class_rank(uint32_t c, uint32_t (*red)[MC_WAVES], uint32_t tot[NC]) {
+    const uint32_t w = threadIdx.x / CN_WAVE, lane = cn_lane();
+    uint32_t pre = 0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        const uint64_t b = __ballot(c == (uint32_t)k);
+        if (c == (uint32_t)k) pre = mc_rank(b);
+        if (lane == 0) red[k][w] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        uint32_t before = 0, t = 0;
+        for (uint32_t j = 0; j < MC_WAVES; ++j) {
+            if (j < w) before += red[k][j];
+            t += red[k][j];
+        }
+        tot[k] = t;
+        if (c == (uint32_t)k) pre += before;
+    }
+    return pre;
+}
+
+// Body of a one-workgroup (MC_SCAN_BLOCK threads) scan of N counters per workgroup: sums[0..nblk)[N] -> exclusive offsets in place,
+// component-wise; tot[] = the N totals (exact in 64 bits; every thread gets them).  Every thread of the block must call it.
+template <int N>
+__device__ __forceinline__ void mc_scan_totals_n(uint32_t *__restrict__ sums, uint32_t nblk, uint64_t tot[N]) {
+    __shared__ uint32_t wsum[N][MC_SCAN_BLOCK / CN_WAVE];
     const uint32_t nw = MC_SCAN_BLOCK / CN_WAVE, w = threadIdx.x / CN_WAVE, lane = cn_lane();
-    cv = 0;                                          // carry: totals of the tiles before this one
-    ct = 0;
+#pragma unroll
+    for (int q = 0; q < N; ++q) tot[q] = 0;          // carry: totals of the tiles before this one
     for (uint32_t base = 0; base < nblk; base += MC_SCAN_BLOCK * MC_SCAN_PER_THREAD) {
         const uint32_t j0 = base + threadIdx.x * MC_SCAN_PER_THREAD;
-        uint2 e[MC_SCAN_PER_THREAD];
-        uint32_t sv = 0, st = 0;
+        uint32_t e[N][MC_SCAN_PER_THREAD], s[N], inc[N];
 #pragma unroll
-        for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
-            e[k] = j0 + k < nblk ? sums[j0 + k] : make_uint2(0, 0);
-            sv += e[k].x;
-            st += e[k].y;
+        for (int q = 0; q < N; ++q) {
+            s[q] = 0;
+#pragma unroll
+            for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
+                e[q][k] = j0 + k < nblk ? sums[(uint64_t)(j0 + k) * N + q] : 0u;
+                s[q] += e[q][k];
+            }
+            inc[q] = cn_wave_incl_scan(s[q]);
+            if (lane == CN_WAVE - 1) wsum[q][w] = inc[q];
         }
-        const uint32_t iv = cn_wave_incl_scan(sv), it = cn_wave_incl_scan(st);
-        if (lane == CN_WAVE - 1) { wv[w] = iv; wt[w] = it; }
         __syncthreads();
-        uint32_t ov = iv - sv, ot = it - st, tile_v = 0, tile_t = 0;
-        for (uint32_t j = 0; j < nw; ++j) {
-            if (j < w) { ov += wv[j]; ot += wt[j]; }
-            tile_v += wv[j];
-            tile_t += wt[j];
-        }
-        __syncthreads();                             // wv / wt are rewritten by the next tile
-        uint64_t pv = cv + ov, pt = ct + ot;
 #pragma unroll
-        for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
-            if (j0 + k < nblk) sums[j0 + k] = make_uint2((uint32_t)pv, (uint32_t)pt);
-            pv += e[k].x;
-            pt += e[k].y;
+        for (int q = 0; q < N; ++q) {
+            uint32_t o = inc[q] - s[q], tile = 0;
+            for (uint32_t j = 0; j < nw; ++j) {
+                if (j < w) o += wsum[q][j];
+                tile += wsum[q][j];
+            }
+            uint64_t p = tot[q] + o;
+#pragma unroll
+            for (int k = 0; k < MC_SCAN_PER_THREAD; ++k) {
+                if (j0 + k < nblk) sums[(uint64_t)(j0 + k) * N + q] = (uint32_t)p;
+                p += e[q][k];
+            }
+            tot[q] += tile;
         }
-        cv += tile_v;
-        ct += tile_t;
+        __syncthreads();                             // wsum is rewritten by the next tile
     }
+}
+
+// the two-counter form: sums as uint2, cv / ct = the two totals
+__device__ __forceinline__ void mc_scan_totals(uint2 *__restrict__ sums, uint32_t nblk, uint64_t &cv, uint64_t &ct) {
+    uint64_t tot[2];
+    mc_scan_totals_n<2>(&sums->x, nblk, tot);
+    cv = tot[0];
+    ct = tot[1];
 }
 
 __device__ __forceinline__ uint32_t mesh_fv(const int32_t *fa, uint32_t f, uint32_t q) { return (uint32_t)fa[3 * (uint64_t)f + q]; }

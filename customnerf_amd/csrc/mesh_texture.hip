@@ -10,7 +10,15 @@
 //   k_atlas_fill   : one thread per image texel: the fill colour on every texel outside the first P cells (the others are k_atlas_store's)
 //
 // Every texel is independent: the passes are bound by their stores (24 B of points and directions per texel, 3 B of image per texel).
-#include "common.h"
+//
+// The area-proportional layout (cnerf_mesh_atlas_sized_*; restatement: tests/atlas_sized_restatement.py) gives a face a cell of 4 * 2^k texels,
+// k from its longest edge, and lays the cells along a Z-order curve, largest first.  Inside a cell every rule above holds with the cell's s:
+//   k_sized_measure : one thread per face: its size key and the index check; the 2048-bin key histogram in LDS, flushed by integer atomics
+//   k_sized_count / k_sized_scan / k_sized_emit : class and in-class rank (face order: the scans of mesh_common.h) -> the face's cell record
+//                     (X0, Y0, s, b) and the cell -> (face A, face B) table
+//   k_sized_uvs / k_sized_points / k_sized_store / k_sized_fill : as the four above, reading the plan; a texel finds its class from the
+//                     at most eight class offsets
+#include "mesh_common.h"
 
 #define AT_BLOCK 256
 #define AT_BAD_INDEX 1u
@@ -97,6 +105,62 @@ __device__ __forceinline__ bool at_look(const float x[3], float d[3]) {
     return true;
 }
 
+// x and d of local texel (i, j) of face f (A: b = 0, B: b = 1) in a cell of edge s; false when an index of the face lies outside [0, V)
+__device__ __forceinline__ bool at_texel(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
+                                         const int32_t *__restrict__ faces, uint32_t f, uint32_t b, uint32_t i, uint32_t j, uint32_t s,
+                                         float x[3], float d[3]) {
+    const int32_t v0 = faces[3 * (uint64_t)f], v1 = faces[3 * (uint64_t)f + 1], v2 = faces[3 * (uint64_t)f + 2];
+    if (v0 < 0 || (uint32_t)v0 >= V || v1 < 0 || (uint32_t)v1 >= V || v2 < 0 || (uint32_t)v2 >= V) return false;
+    float w1, w2;
+    int corner;
+    if (!b) {
+        const float den = (float)(s - 2);
+        w1 = (float)j / den;
+        w2 = (float)i / den;
+        corner = (i == 0 && j == 0) ? 0 : (i == 0 && j == s - 2) ? 1 : (i == s - 2 && j == 0) ? 2 : -1;
+    } else {
+        const float den = (float)(s - 3);
+        w1 = (float)(s - 1 - j) / den;
+        w2 = (float)(s - 1 - i) / den;
+        corner = (i == s - 1 && j == s - 1) ? 0 : (i == s - 1 && j == 2) ? 1 : (i == 2 && j == s - 1) ? 2 : -1;
+    }
+    float p0[3], p1[3], p2[3];
+    at_load3(verts, (uint32_t)v0, p0);
+    at_load3(verts, (uint32_t)v1, p1);
+    at_load3(verts, (uint32_t)v2, p2);
+    at_interp(p0, p1, p2, w1, w2, corner, x);
+    bool ok = false;
+    if (normals) {
+        float n0[3], n1[3], n2[3], nn[3];
+        at_load3(normals, (uint32_t)v0, n0);
+        at_load3(normals, (uint32_t)v1, n1);
+        at_load3(normals, (uint32_t)v2, n2);
+        at_interp(n0, n1, n2, w1, w2, corner, nn);
+        ok = at_look(nn, d);
+    }
+    if (!ok) {                                               // the face's geometric normal, (p1 - p0) x (p2 - p0)
+        const float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+        const float e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+        const float gn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        if (!at_look(gn, d)) {
+            d[0] = 0.0f;
+            d[1] = 0.0f;
+            d[2] = -1.0f;
+        }
+    }
+    return true;
+}
+
+__device__ __forceinline__ void at_put(float *__restrict__ xo, float *__restrict__ dout, uint32_t q, const float x[3], const float d[3]) {
+    const uint64_t o = 3 * (uint64_t)q;
+    xo[o] = x[0];
+    xo[o + 1] = x[1];
+    xo[o + 2] = x[2];
+    dout[o] = d[0];
+    dout[o + 1] = d[1];
+    dout[o + 2] = d[2];
+}
+
 __global__ __launch_bounds__(AT_BLOCK) void k_atlas_points(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
                                                            const int32_t *__restrict__ faces, AtlasGeom g, uint32_t t0, uint32_t count,
                                                            const uint32_t *__restrict__ flags, float *__restrict__ xo, float *__restrict__ dout) {
@@ -106,54 +170,8 @@ __global__ __launch_bounds__(AT_BLOCK) void k_atlas_points(const float *__restri
     const uint32_t p = t / s2, r = t - p * s2, j = r / s, i = r - j * s;
     const uint32_t b = i + j > s - 1 ? 1u : 0u, f = 2 * p + b;
     float x[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, -1.0f};
-    if (f < g.F) {
-        const int32_t v0 = faces[3 * (uint64_t)f], v1 = faces[3 * (uint64_t)f + 1], v2 = faces[3 * (uint64_t)f + 2];
-        if (v0 < 0 || (uint32_t)v0 >= V || v1 < 0 || (uint32_t)v1 >= V || v2 < 0 || (uint32_t)v2 >= V) return;
-        float w1, w2;
-        int corner;
-        if (!b) {
-            const float den = (float)(s - 2);
-            w1 = (float)j / den;
-            w2 = (float)i / den;
-            corner = (i == 0 && j == 0) ? 0 : (i == 0 && j == s - 2) ? 1 : (i == s - 2 && j == 0) ? 2 : -1;
-        } else {
-            const float den = (float)(s - 3);
-            w1 = (float)(s - 1 - j) / den;
-            w2 = (float)(s - 1 - i) / den;
-            corner = (i == s - 1 && j == s - 1) ? 0 : (i == s - 1 && j == 2) ? 1 : (i == 2 && j == s - 1) ? 2 : -1;
-        }
-        float p0[3], p1[3], p2[3];
-        at_load3(verts, (uint32_t)v0, p0);
-        at_load3(verts, (uint32_t)v1, p1);
-        at_load3(verts, (uint32_t)v2, p2);
-        at_interp(p0, p1, p2, w1, w2, corner, x);
-        bool ok = false;
-        if (normals) {
-            float n0[3], n1[3], n2[3], nn[3];
-            at_load3(normals, (uint32_t)v0, n0);
-            at_load3(normals, (uint32_t)v1, n1);
-            at_load3(normals, (uint32_t)v2, n2);
-            at_interp(n0, n1, n2, w1, w2, corner, nn);
-            ok = at_look(nn, d);
-        }
-        if (!ok) {                                           // the face's geometric normal, (p1 - p0) x (p2 - p0)
-            const float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-            const float e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-            const float gn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-            if (!at_look(gn, d)) {
-                d[0] = 0.0f;
-                d[1] = 0.0f;
-                d[2] = -1.0f;
-            }
-        }
-    }
-    const uint64_t o = 3 * (uint64_t)q;
-    xo[o] = x[0];
-    xo[o + 1] = x[1];
-    xo[o + 2] = x[2];
-    dout[o] = d[0];
-    dout[o + 1] = d[1];
-    dout[o + 2] = d[2];
+    if (f < g.F && !at_texel(verts, normals, V, faces, f, b, i, j, s, x, d)) return;
+    at_put(xo, dout, q, x, d);
 }
 
 __device__ __forceinline__ uint8_t at_u8(float v) { return (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }   // NaN -> 0
@@ -186,6 +204,260 @@ __global__ __launch_bounds__(AT_BLOCK) void k_atlas_fill(AtlasGeom g, uchar3 fil
     image[3 * (uint64_t)e] = fill.x;
     image[3 * (uint64_t)e + 1] = fill.y;
     image[3 * (uint64_t)e + 2] = fill.z;
+}
+
+// ------------------------------------------------------------------------------------------------ the area-proportional layout
+#define SZ_BINS 2048
+#define SZ_CLASSES 8
+#define SZ_MAX_F (1u << 25)                                  // 2 (16384 / 4)^2: more faces fit no resolution
+
+// What every pass after the host read is given by value.  Classes lie along the Z-order curve from K down to 0: class k starts at tile
+// O[k] (cell texel 16 O[k]) and at cell B[k] of the cell -> faces table; both are 0 for the (empty) classes above K.
+struct SizedPlan {
+    uint32_t F, R, K, tiles;
+    uint32_t n[SZ_CLASSES], O[SZ_CLASSES], B[SZ_CLASSES];
+};
+
+struct SizedPtr {
+    uint32_t *hdr, *key, *sums;
+    int32_t *owner;                                          // [cells][2]: face A, face B or -1
+};
+
+uint64_t sz_carve(void *ws, uint64_t F, SizedPtr &p) {
+    MeshCarve c(ws);
+    p.hdr = c.header();
+    p.key = c.take<uint32_t>(F);
+    p.sums = c.take<uint32_t>(cn_div_up64(F, MC_BLOCK) * SZ_CLASSES);
+    p.owner = c.take<int32_t>(2 * F);                        // ceil(n_k / 2) <= n_k cells per class
+    return c.total();
+}
+
+int sz_log2(uint32_t R) {                                    // log2 of a power of two in [16, 16384], else -1
+    for (int l = 4; l <= 14; ++l)
+        if (R == (1u << l)) return l;
+    return -1;
+}
+
+// host: tiles of the classes with n[] faces each
+uint64_t sz_tiles(const uint32_t n[SZ_CLASSES]) {
+    uint64_t t = 0;
+    for (int k = 0; k < SZ_CLASSES; ++k) t += (((uint64_t)n[k] + 1) / 2) << (2 * k);
+    return t;
+}
+
+// host: the plan of counts n[] on an R x R image, or CNERF_EINVAL (R, a class above K, a sum that is not F, more tiles than the image has)
+int sz_plan(uint32_t F, uint32_t R, const uint32_t *n, SizedPlan *p) {
+    const int l = sz_log2(R);
+    if (l < 0 || F > SZ_MAX_F) return CNERF_EINVAL;
+    p->F = F;
+    p->R = R;
+    p->K = (uint32_t)(l - 2 < 7 ? l - 2 : 7);
+    uint64_t sum = 0;
+    for (int k = 0; k < SZ_CLASSES; ++k) {
+        if (n[k] > F || ((uint32_t)k > p->K && n[k])) return CNERF_EINVAL;
+        p->n[k] = n[k];
+        sum += n[k];
+    }
+    const uint64_t tiles = sz_tiles(n), cap = (uint64_t)(R / 4) * (R / 4);
+    if (sum != F || tiles > cap) return CNERF_EINVAL;
+    uint32_t o = 0, b = 0;
+    for (int k = SZ_CLASSES - 1; k >= 0; --k) {
+        p->O[k] = o;
+        p->B[k] = b;
+        const uint32_t c = (n[k] + 1) / 2;
+        o += c << (2 * k);
+        b += c;
+    }
+    p->tiles = o;
+    return CNERF_OK;
+}
+
+// the even bits of o, packed: the x of Z-order index o (its y: the even bits of o >> 1)
+__device__ __forceinline__ uint32_t sz_even_bits(uint32_t o) {
+    o &= 0x55555555u;
+    o = (o | (o >> 1)) & 0x33333333u;
+    o = (o | (o >> 2)) & 0x0f0f0f0fu;
+    o = (o | (o >> 4)) & 0x00ff00ffu;
+    o = (o | (o >> 8)) & 0x0000ffffu;
+    return o;
+}
+
+// the bits of x < 2^16 spread to the even positions
+__device__ __forceinline__ uint32_t sz_spread_bits(uint32_t x) {
+    x = (x | (x << 8)) & 0x00ff00ffu;
+    x = (x | (x << 4)) & 0x0f0f0f0fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;
+    return x;
+}
+
+__device__ __forceinline__ uint32_t sz_class(uint32_t key, uint32_t e, uint32_t K) {
+    if (key < e) return 0;
+    const uint32_t k = (key - e) >> 4;
+    return k < K ? k : K;
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_sized_measure(const float *__restrict__ verts, uint32_t V, const int32_t *__restrict__ faces,
+                                                            uint32_t F, uint32_t *__restrict__ key, uint32_t *__restrict__ hist) {
+    __shared__ uint32_t h[SZ_BINS];
+    for (uint32_t i = threadIdx.x; i < SZ_BINS; i += MC_BLOCK) h[i] = 0;
+    __syncthreads();
+    const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
+    if (f < F) {
+        uint32_t t[3];
+        if (!mesh_face(faces, f, V, t)) {
+            atomicOr(hist + SZ_BINS, AT_BAD_INDEX);
+            key[f] = 0;
+        } else {
+            float p[3][3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) at_load3(verts, t[q], p[q]);
+            float L2 = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {                    // edges (0,1), (1,2), (2,0)
+                const float *a = p[q], *b = p[(q + 1) % 3];
+                const float dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
+                const float l = (dx * dx + dy * dy) + dz * dz;
+                L2 = q ? fmaxf(L2, l) : l;                   // a NaN is ignored beside a number
+            }
+            const uint32_t kf = (L2 > 0.0f && L2 < INFINITY) ? __float_as_uint(L2) >> 20 : 0u;
+            key[f] = kf;
+            atomicAdd(&h[kf], 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < SZ_BINS; i += MC_BLOCK)
+        if (h[i]) atomicAdd(hist + i, h[i]);
+}
+
+// workgroup totals of the eight classes
+__global__ __launch_bounds__(MC_BLOCK) void k_sized_count(SizedPlan pl, uint32_t e, SizedPtr p) {
+    __shared__ uint32_t red[SZ_CLASSES][MC_WAVES];
+    const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
+    uint32_t tot[SZ_CLASSES];
+    mc_block_class_rank<SZ_CLASSES>(f < pl.F ? sz_class(p.key[f], e, pl.K) : SZ_CLASSES, red, tot);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < SZ_CLASSES; ++k) p.sums[(uint64_t)blockIdx.x * SZ_CLASSES + k] = tot[k];
+    }
+}
+
+__global__ __launch_bounds__(MC_SCAN_BLOCK) void k_sized_scan(uint32_t nblk, SizedPtr p) {
+    uint64_t tot[SZ_CLASSES];
+    mc_scan_totals_n<SZ_CLASSES>(p.sums, nblk, tot);         // each at most F < 2^32
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_sized_emit(SizedPlan pl, uint32_t e, SizedPtr p, const uint32_t *__restrict__ flags,
+                                                         int32_t *__restrict__ cells, uint32_t max_faces) {
+    __shared__ uint32_t red[SZ_CLASSES][MC_WAVES];
+    const uint32_t f = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t k = f < pl.F ? sz_class(p.key[f], e, pl.K) : SZ_CLASSES;
+    uint32_t tot[SZ_CLASSES];
+    uint32_t r = mc_block_class_rank<SZ_CLASSES>(k, red, tot);
+    if (f >= pl.F || flags[0]) return;                       // after a bad index nothing is written
+    r += p.sums[(uint64_t)blockIdx.x * SZ_CLASSES + k];
+    uint32_t nk = 0, Ok = 0, Bk = 0;
+#pragma unroll
+    for (int q = 0; q < SZ_CLASSES; ++q)
+        if (k == (uint32_t)q) {
+            nk = pl.n[q];
+            Ok = pl.O[q];
+            Bk = pl.B[q];
+        }
+    if (r >= nk) return;                                     // counts that are not this mesh's: no cell to give
+    const uint32_t c = r >> 1, b = r & 1u, o = Ok + (c << (2 * k));
+    p.owner[2 * (uint64_t)(Bk + c) + b] = (int32_t)f;
+    if (f >= max_faces) return;
+    int32_t *rec = cells + 4 * (uint64_t)f;
+    rec[0] = (int32_t)(4 * sz_even_bits(o));
+    rec[1] = (int32_t)(4 * sz_even_bits(o >> 1));
+    rec[2] = (int32_t)(4u << k);
+    rec[3] = (int32_t)b;
+}
+
+__global__ __launch_bounds__(AT_BLOCK) void k_sized_uvs(uint32_t F, uint32_t R, const int32_t *__restrict__ cells,
+                                                        const uint32_t *__restrict__ flags, float *__restrict__ uvs) {
+    const uint32_t c = blockIdx.x * AT_BLOCK + threadIdx.x;
+    if (c >= 3 * F || flags[0]) return;
+    const uint32_t f = c / 3, k = c - 3 * f;
+    const int32_t *rec = cells + 4 * (uint64_t)f;
+    uint32_t i, j;
+    at_corner((uint32_t)rec[3], k, (uint32_t)rec[2], i, j);
+    const float X = (float)((uint32_t)rec[0] + i), Y = (float)((uint32_t)rec[1] + j), Rf = (float)R;
+    uvs[2 * (uint64_t)c] = (X + 0.5f) / Rf;
+    uvs[2 * (uint64_t)c + 1] = 1.0f - (Y + 0.5f) / Rf;
+}
+
+// cell texel t < 16 tiles -> its cell (index into the cell -> faces table, tile offset o), the cell's edge s and the local texel (i, j)
+__device__ __forceinline__ void sz_texel(const SizedPlan &pl, uint32_t t, uint32_t &cell, uint32_t &o, uint32_t &s, uint32_t &i, uint32_t &j) {
+    const uint32_t tile = t >> 4;
+    uint32_t k = 0, Ok = pl.O[0], Bk = pl.B[0];
+#pragma unroll
+    for (int q = 1; q < SZ_CLASSES; ++q)                     // O[] descends with k: the class is the first whose offset is not above the tile
+        if (tile < pl.O[q - 1]) {
+            k = (uint32_t)q;
+            Ok = pl.O[q];
+            Bk = pl.B[q];
+        }
+    const uint32_t rel = t - (Ok << 4), c = rel >> (4 + 2 * k), r = rel & ((16u << (2 * k)) - 1);
+    s = 4u << k;
+    j = r >> (2 + k);
+    i = r & (s - 1);
+    cell = Bk + c;
+    o = Ok + (c << (2 * k));
+}
+
+__global__ __launch_bounds__(AT_BLOCK) void k_sized_points(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
+                                                           const int32_t *__restrict__ faces, SizedPlan pl, const int32_t *__restrict__ owner,
+                                                           uint32_t t0, uint32_t count, const uint32_t *__restrict__ flags,
+                                                           float *__restrict__ xo, float *__restrict__ dout) {
+    const uint32_t q = blockIdx.x * AT_BLOCK + threadIdx.x;
+    if (q >= count || flags[0]) return;
+    uint32_t cell, o, s, i, j;
+    sz_texel(pl, t0 + q, cell, o, s, i, j);
+    const uint32_t b = i + j > s - 1 ? 1u : 0u;
+    const int32_t f = owner[2 * (uint64_t)cell + b];
+    float x[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, -1.0f};
+    if (f >= 0 && ((uint32_t)f >= pl.F || !at_texel(verts, normals, V, faces, (uint32_t)f, b, i, j, s, x, d))) return;
+    at_put(xo, dout, q, x, d);
+}
+
+__global__ __launch_bounds__(AT_BLOCK) void k_sized_store(SizedPlan pl, const int32_t *__restrict__ owner, uint32_t t0, uint32_t count,
+                                                          const float *__restrict__ rgb, uint32_t stride, uchar3 fill,
+                                                          const uint32_t *__restrict__ flags, uint8_t *__restrict__ image) {
+    const uint32_t q = blockIdx.x * AT_BLOCK + threadIdx.x;
+    if (q >= count || flags[0]) return;
+    uint32_t cell, o, s, i, j;
+    sz_texel(pl, t0 + q, cell, o, s, i, j);
+    const int32_t f = owner[2 * (uint64_t)cell + (i + j > s - 1 ? 1u : 0u)];
+    const uint32_t X = 4 * sz_even_bits(o) + i, Y = 4 * sz_even_bits(o >> 1) + j;   // o < tiles <= (R / 4)^2: inside the image
+    const uint64_t at = 3 * ((uint64_t)Y * pl.R + X);
+    uchar3 c = fill;
+    if (f >= 0) {
+        const uint64_t a = (uint64_t)q * stride;
+        c = make_uchar3(at_u8(rgb[a]), at_u8(rgb[a + 1]), at_u8(rgb[a + 2]));
+    }
+    image[at] = c.x;
+    image[at + 1] = c.y;
+    image[at + 2] = c.z;
+}
+
+__global__ __launch_bounds__(AT_BLOCK) void k_sized_fill(uint32_t R, uint32_t tiles, uchar3 fill, uint8_t *__restrict__ image) {
+    const uint32_t e = blockIdx.x * AT_BLOCK + threadIdx.x;
+    if (e >= R * R) return;
+    const uint32_t Y = e / R, X = e - Y * R;
+    if ((sz_spread_bits(X >> 2) | (sz_spread_bits(Y >> 2) << 1)) < tiles) return;   // inside a cell: k_sized_store writes it
+    image[3 * (uint64_t)e] = fill.x;
+    image[3 * (uint64_t)e + 1] = fill.y;
+    image[3 * (uint64_t)e + 2] = fill.z;
+}
+
+// the checks the passes after the host read share: the plan of counts_host and the carved workspace
+int sz_check(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint64_t ws_bytes, SizedPlan &pl, SizedPtr &p) {
+    if (!counts_host) return CNERF_ENULL;
+    if (const int rc = sz_plan(F, R, counts_host, &pl)) return rc;
+    if (!ws) return CNERF_ENULL;
+    return mesh_check_ws(ws, ws_bytes, sz_carve(ws, F, p));
 }
 
 }  // namespace
@@ -247,6 +519,119 @@ int cnerf_mesh_atlas_fill(uint32_t F, uint32_t R, const uint8_t *fill_host, uint
     if (!fill_host || !image) return CNERF_ENULL;
     const uchar3 fill = make_uchar3(fill_host[0], fill_host[1], fill_host[2]);
     hipLaunchKernelGGL(k_atlas_fill, dim3(cn_div_up(R * R, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), g, fill, image);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_atlas_sized_workspace_bytes(uint32_t F, uint64_t *bytes_host) {
+    if (!bytes_host) return CNERF_ENULL;
+    if (F > SZ_MAX_F) return CNERF_EINVAL;
+    SizedPtr p;
+    *bytes_host = sz_carve(nullptr, F, p);
+    return CNERF_OK;
+}
+
+int cnerf_mesh_atlas_sized_measure(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, void *ws, uint64_t ws_bytes,
+                                   uint32_t *hist, void *stream) {
+    if (F > SZ_MAX_F || V >= (1u << 31)) return CNERF_EINVAL;
+    if (!ws || !hist || (F && (!faces || !verts))) return CNERF_ENULL;
+    SizedPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, sz_carve(ws, F, p))) return rc;
+    if (const int rc = (int)hipMemsetAsync(hist, 0, (SZ_BINS + 1) * sizeof(uint32_t), CN_STREAM(stream))) return rc;
+    if (F) hipLaunchKernelGGL(k_sized_measure, mesh_grid(F), dim3(MC_BLOCK), 0, CN_STREAM(stream), verts, V, faces, F, p.key, hist);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_atlas_sized_layout(const uint32_t *hist_host, uint32_t R, uint32_t *e_host, uint32_t *counts_host, uint32_t *tiles_host) {
+    if (!hist_host || !e_host || !counts_host || !tiles_host) return CNERF_ENULL;
+    const int l = sz_log2(R);
+    if (l < 0) return CNERF_EINVAL;
+    const uint32_t K = (uint32_t)(l - 2 < 7 ? l - 2 : 7);
+    uint64_t below[SZ_BINS + 1];                             // below[i] = faces with key < i
+    below[0] = 0;
+    for (uint32_t i = 0; i < SZ_BINS; ++i) below[i + 1] = below[i] + hist_host[i];
+    const uint64_t F = below[SZ_BINS], cap = (uint64_t)(R / 4) * (R / 4);
+    if (F > SZ_MAX_F) return CNERF_EINVAL;
+    for (uint32_t e = 0; e <= SZ_BINS; ++e) {                // tiles(e) can rise by a cell when a face moves down a class: no bisection
+        uint32_t n[SZ_CLASSES] = {0};
+        uint32_t lo = 0;                                     // class k holds the keys in [lo, hi): class 0 from 0, class K up to the last bin
+        for (uint32_t k = 0; k <= K; ++k) {
+            const uint32_t end = e + 16 * (k + 1), hi = (k == K || end > SZ_BINS) ? SZ_BINS : end;
+            n[k] = (uint32_t)(below[hi] - below[lo]);
+            lo = hi;
+        }
+        const uint64_t t = sz_tiles(n);
+        if (t <= cap) {
+            *e_host = e;
+            *tiles_host = (uint32_t)t;
+            for (int k = 0; k < SZ_CLASSES; ++k) counts_host[k] = n[k];
+            return CNERF_OK;
+        }
+    }
+    return CNERF_EINVAL;                                     // even one 4 x 4 cell per face pair does not fit: decimate or raise R
+}
+
+int cnerf_mesh_atlas_sized_plan(uint32_t F, uint32_t R, uint32_t e, const uint32_t *counts_host, void *ws, uint64_t ws_bytes,
+                                const uint32_t *flags, int32_t *cells, uint32_t max_faces, void *stream) {
+    SizedPlan pl;
+    SizedPtr p;
+    if (e > SZ_BINS) return CNERF_EINVAL;
+    if (const int rc = sz_check(F, R, counts_host, ws, ws_bytes, pl, p)) return rc;
+    if (!F) return CNERF_OK;
+    if (!flags || (max_faces && !cells)) return CNERF_ENULL;
+    const dim3 grid = mesh_grid(F);
+    if (const int rc = (int)hipMemsetAsync(p.owner, 0xff, 2 * (uint64_t)F * sizeof(int32_t), CN_STREAM(stream))) return rc;
+    hipLaunchKernelGGL(k_sized_count, grid, dim3(MC_BLOCK), 0, CN_STREAM(stream), pl, e, p);
+    hipLaunchKernelGGL(k_sized_scan, dim3(1), dim3(MC_SCAN_BLOCK), 0, CN_STREAM(stream), grid.x, p);
+    hipLaunchKernelGGL(k_sized_emit, grid, dim3(MC_BLOCK), 0, CN_STREAM(stream), pl, e, p, flags, cells, max_faces);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_atlas_sized_uvs(uint32_t F, uint32_t R, const int32_t *cells, const uint32_t *flags, float *uvs, uint32_t max_faces,
+                               void *stream) {
+    if (sz_log2(R) < 0 || F > SZ_MAX_F) return CNERF_EINVAL;
+    const uint32_t n = F < max_faces ? F : max_faces;
+    if (!n) return CNERF_OK;
+    if (!cells || !flags || !uvs) return CNERF_ENULL;
+    hipLaunchKernelGGL(k_sized_uvs, dim3(cn_div_up(3 * n, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), n, R, cells, flags, uvs);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_atlas_sized_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R,
+                                  const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0, uint32_t t1,
+                                  const uint32_t *flags, float *x, float *d, uint32_t max_points, void *stream) {
+    SizedPlan pl;
+    SizedPtr p;
+    if (const int rc = sz_check(F, R, counts_host, ws, ws_bytes, pl, p)) return rc;
+    if (V >= (1u << 31) || t0 > t1 || (uint64_t)t1 > 16 * (uint64_t)pl.tiles) return CNERF_EINVAL;
+    const uint32_t count = (t1 - t0) < max_points ? t1 - t0 : max_points;
+    if (!count) return CNERF_OK;
+    if (!flags || !faces || !verts || !x || !d) return CNERF_ENULL;
+    hipLaunchKernelGGL(k_sized_points, dim3(cn_div_up(count, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), verts, normals, V, faces, pl,
+                       p.owner, t0, count, flags, x, d);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_atlas_sized_store(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0,
+                                 uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host, const uint32_t *flags,
+                                 uint8_t *image, void *stream) {
+    SizedPlan pl;
+    SizedPtr p;
+    if (const int rc = sz_check(F, R, counts_host, ws, ws_bytes, pl, p)) return rc;
+    if (t0 > t1 || (uint64_t)t1 > 16 * (uint64_t)pl.tiles || rgb_stride < 3) return CNERF_EINVAL;
+    if (!fill_host) return CNERF_ENULL;
+    if (t1 == t0) return CNERF_OK;
+    if (!rgb || !flags || !image) return CNERF_ENULL;
+    const uchar3 fill = make_uchar3(fill_host[0], fill_host[1], fill_host[2]);
+    hipLaunchKernelGGL(k_sized_store, dim3(cn_div_up(t1 - t0, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), pl, p.owner, t0, t1 - t0, rgb,
+                       rgb_stride, fill, flags, image);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_atlas_sized_fill(uint32_t R, uint32_t tiles, const uint8_t *fill_host, uint8_t *image, void *stream) {
+    if (sz_log2(R) < 0 || (uint64_t)tiles > (uint64_t)(R / 4) * (R / 4)) return CNERF_EINVAL;
+    if (!fill_host || !image) return CNERF_ENULL;
+    const uchar3 fill = make_uchar3(fill_host[0], fill_host[1], fill_host[2]);
+    hipLaunchKernelGGL(k_sized_fill, dim3(cn_div_up(R * R, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), R, tiles, fill, image);
     return cn_launch_status();
 }
 

@@ -1,7 +1,7 @@
 """Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*), mesh cleanup on the GPU (csrc/mesh_clean.hip:
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
-face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU
-(csrc/mesh_texture.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
+face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU,
+uniform or with cells sized by the faces' edges (csrc/mesh_texture.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
 shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them,
 watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them (csrc/mesh_bvh.hip), a binary PLY writer
 and an OBJ + MTL + PNG writer.
@@ -327,17 +327,71 @@ def atlas_layout(F, resolution):
     return n.value, s.value
 
 
-def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21, fill=(0, 0, 0)):
-    """Bake color_fn into a resolution x resolution RGB8 texture atlas of the mesh (csrc/mesh_texture.hip).  Each face pair owns a square cell
-    of s x s texels (atlas_layout); every texel of a face is evaluated at the point of the face's plane under its centre, looking at the
-    surface: color_fn(x [N, 3] float32, d [N, 3] float32) -> RGB in [0, 1], [N, >= 3], any float dtype, called on chunks of at most `chunk`
-    texels.  d = -(interpolated vertex normal), or -(face normal) without normals.  Texels no face owns get `fill` (uint8 RGB).
+_NO_FIT = "decimate the mesh (target_faces=) or raise the resolution"
+
+
+class AtlasPlan:
+    """The area-proportional atlas of a mesh (atlas_plan): resolution; e, the size-key threshold, and threshold, the edge length it stands
+    for (faces whose longest edge is below it get the smallest cells, and every doubling above it doubles the cell edge); counts [K + 1],
+    the faces per class (class k: cells of 4 * 2^k texels); cells [F, 4] int32 on the device, (X0, Y0, s, b) per face: its cell's origin
+    texel and edge and whether it is the cell's face A (0) or B (1); texels, the number of cell texels, and tiles, the 4 x 4 tiles the
+    cells cover (texels = 16 tiles <= resolution^2)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _atlas_plan(v, f, R, what):
+    """-> (AtlasPlan, flags [1], counts (uint32 * 8), workspace, its size): what bake_texture needs beyond the plan itself"""
+    V, F = v.shape[0], f.shape[0]
+    if R < 16 or R > 16384 or R & (R - 1):
+        raise ValueError(f"{what}: the 'area' layout needs a resolution that is a power of two in [16, 16384], got {R}")
+    no_fit = f"{what}: {F} faces leave cells of fewer than 4 x 4 texels on a {R} x {R} texture; {_NO_FIT}"
+    if (F + 1) // 2 > (R // 4) ** 2:
+        raise ValueError(no_fit)
+    dev = v.device
+    ws, nbytes = _workspace(dev, "mesh_atlas_sized", F)
+    hist = torch.empty(2049, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_atlas_sized_measure(_p(v), V, _p(f), F, ptr(ws), nbytes, ptr(hist), stream()), "mesh_atlas_sized_measure")
+    h = (C.c_uint32 * 2048)(*_read(hist, what, _BAD_INDEX)[:2048])             # the one host read
+    e, tiles, counts = C.c_uint32(0), C.c_uint32(0), (C.c_uint32 * 8)()
+    if lib.cnerf_mesh_atlas_sized_layout(h, R, C.byref(e), counts, C.byref(tiles)) != 0:
+        raise ValueError(no_fit)
+    flags = hist[2048:]
+    cells = torch.empty(F, 4, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_atlas_sized_plan(F, R, e.value, counts, ptr(ws), nbytes, ptr(flags), _p(cells), F, stream()), "mesh_atlas_sized_plan")
+    K = min(7, R.bit_length() - 3)
+    thr = math.inf if e.value >= 2040 else math.sqrt(struct.unpack("<f", struct.pack("<I", e.value << 20))[0])
+    plan = AtlasPlan(resolution=R, e=e.value, threshold=thr, counts=list(counts)[:K + 1], cells=cells, texels=16 * tiles.value,
+                     tiles=tiles.value)
+    return plan, flags, counts, ws, nbytes
+
+
+def atlas_plan(verts, faces, resolution):
+    """The area-proportional texture atlas of a mesh on a resolution x resolution image (a power of two in [16, 16384]): every face gets a
+    square cell of 4 * 2^k texels, k growing with its longest edge, so that texels per unit length vary by about a factor of two instead of
+    with the face's size (the rules are in include/customnerf_hip.h, cnerf_mesh_atlas_sized_*).  CUDA tensors verts [V, 3], faces [F, 3]
+    -> AtlasPlan.  ValueError on a face index outside [0, V), a resolution that is no power of two, or more faces than fit."""
+    v, f, _ = _mesh_args(verts, faces, None, "atlas_plan")
+    return _atlas_plan(v, f, int(resolution), "atlas_plan")[0]
+
+
+def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21, fill=(0, 0, 0), layout='uniform'):
+    """Bake color_fn into a resolution x resolution RGB8 texture atlas of the mesh (csrc/mesh_texture.hip).  layout='uniform': each face pair
+    owns a square cell of s x s texels (atlas_layout), whatever the faces' sizes; layout='area': a face's cell has 4 * 2^k texels per edge,
+    k from its longest edge (atlas_plan; the resolution must be a power of two).  Every texel of a face is evaluated at the point of the
+    face's plane under its centre, looking at the surface: color_fn(x [N, 3] float32, d [N, 3] float32) -> RGB in [0, 1], [N, >= 3], any
+    float dtype, called on chunks of at most `chunk` texels.  d = -(interpolated vertex normal), or -(face normal) without normals.  Texels no face owns get `fill` (uint8 RGB).
     CUDA tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None.  -> (uvs [F, 3, 2] float32: the UV of corner k of face f,
     v pointing up; texture [R, R, 3] uint8, row 0 at the top), on the device.  A face index outside [0, V) raises ValueError."""
     v, f, n = _mesh_args(verts, faces, normals, "bake_texture")
     V, F = v.shape[0], f.shape[0]
     R = int(resolution)
-    _, s = atlas_layout(F, R)
+    if layout not in ('uniform', 'area'):
+        raise ValueError(f"bake_texture: layout must be 'uniform' or 'area', got {layout!r}")
+    area = layout == 'area'
+    if not area:
+        _, s = atlas_layout(F, R)
     fl = tuple(int(c) for c in fill)
     if len(fl) != 3 or min(fl) < 0 or max(fl) > 255:
         raise ValueError(f"bake_texture: fill must be 3 values in [0, 255], got {fill}")
@@ -347,20 +401,30 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
     fill_c = (C.c_uint8 * 3)(*fl)
     dev = v.device
     uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
-    flags = torch.empty(1, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_atlas_uvs(_p(f), V, F, R, _p(uvs), F, ptr(flags), stream()), "mesh_atlas_uvs")
-    _read(flags, "bake_texture", _BAD_INDEX)
     tex = torch.empty(R, R, 3, dtype=torch.uint8, device=dev)
-    check(lib.cnerf_mesh_atlas_fill(F, R, fill_c, ptr(tex), stream()), "mesh_atlas_fill")
-    total = (F + 1) // 2 * s * s
+    if area:
+        plan, flags, counts, ws, nbytes = _atlas_plan(v, f, R, "bake_texture")
+        check(lib.cnerf_mesh_atlas_sized_uvs(F, R, _p(plan.cells), ptr(flags), _p(uvs), F, stream()), "mesh_atlas_sized_uvs")
+        check(lib.cnerf_mesh_atlas_sized_fill(R, plan.tiles, fill_c, ptr(tex), stream()), "mesh_atlas_sized_fill")
+        total = plan.texels
+    else:
+        flags = torch.empty(1, dtype=torch.int32, device=dev)
+        check(lib.cnerf_mesh_atlas_uvs(_p(f), V, F, R, _p(uvs), F, ptr(flags), stream()), "mesh_atlas_uvs")
+        _read(flags, "bake_texture", _BAD_INDEX)
+        check(lib.cnerf_mesh_atlas_fill(F, R, fill_c, ptr(tex), stream()), "mesh_atlas_fill")
+        total = (F + 1) // 2 * s * s
     m = max(1, min(chunk, total))
     x = torch.empty(m, 3, dtype=torch.float32, device=dev)
     d = torch.empty(m, 3, dtype=torch.float32, device=dev)
     for t0 in range(0, total, m):
         t1 = min(t0 + m, total)
         k = t1 - t0
-        check(lib.cnerf_mesh_atlas_points(ptr(v), _p(n), V, ptr(f), F, R, t0, t1, ptr(flags), ptr(x), ptr(d), k,
-                                          stream()), "mesh_atlas_points")
+        if area:
+            check(lib.cnerf_mesh_atlas_sized_points(ptr(v), _p(n), V, ptr(f), F, R, counts, ptr(ws), nbytes, t0, t1, ptr(flags), ptr(x), ptr(d),
+                                                    k, stream()), "mesh_atlas_sized_points")
+        else:
+            check(lib.cnerf_mesh_atlas_points(ptr(v), _p(n), V, ptr(f), F, R, t0, t1, ptr(flags), ptr(x), ptr(d), k,
+                                              stream()), "mesh_atlas_points")
         rgb = color_fn(x[:k], d[:k])
         if not torch.is_tensor(rgb) or rgb.dim() != 2 or rgb.shape[0] != k or rgb.shape[1] < 3 or not rgb.is_floating_point():
             raise ValueError(f"bake_texture: color_fn must return a floating tensor [N, >= 3] for N = {k} points, got "
@@ -368,7 +432,12 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
         rgb = rgb.detach()[:, :3].float()
         if rgb.stride(1) != 1 or rgb.device != dev:
             rgb = rgb.to(dev).contiguous()
-        check(lib.cnerf_mesh_atlas_store(F, R, t0, t1, ptr(rgb), rgb.stride(0), fill_c, ptr(flags), ptr(tex), stream()), "mesh_atlas_store")
+        if area:
+            check(lib.cnerf_mesh_atlas_sized_store(F, R, counts, ptr(ws), nbytes, t0, t1, ptr(rgb), rgb.stride(0), fill_c, ptr(flags), ptr(tex),
+                                                   stream()), "mesh_atlas_sized_store")
+        else:
+            check(lib.cnerf_mesh_atlas_store(F, R, t0, t1, ptr(rgb), rgb.stride(0), fill_c, ptr(flags), ptr(tex), stream()),
+                  "mesh_atlas_store")
     return uvs, tex
 
 

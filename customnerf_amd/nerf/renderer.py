@@ -487,7 +487,8 @@ class NeRFRenderer(nn.Module):
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
-                     smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0):
+                     smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0,
+                     texture_layout='uniform'):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -502,6 +503,8 @@ class NeRFRenderer(nn.Module):
         as it is.
         texture=R > 0 bakes the field's colour, looking at the surface, into an R x R texture atlas of the final mesh (mesh.bake_texture,
         csrc/mesh_texture.hip): 'uvs' [F, 3, 2] float32 and 'texture' [R, R, 3] uint8 join the dict (both None with texture=0).
+        texture_layout='uniform' gives every face the same texels; 'area' (R a power of two) sizes a face's cell by its longest edge, which
+        is what a decimated mesh (target_faces), with its large faces on flat regions, wants.  'texture_layout' joins the dict.
         deviation=True reports what the lossy passes cost in geometry: 'deviation' joins the dict — mesh.distance(final mesh, the mesh as it
         stood after marching cubes and component removal), both directions (max, mean, rms per direction and 'hausdorff', in world units),
         sampled deviation_spacing apart (default: half the smallest lattice step; at most deviation_max_samples samples per direction,
@@ -525,6 +528,8 @@ class NeRFRenderer(nn.Module):
         tex_r = int(texture)
         if tex_r < 0:
             raise ValueError(f"extract_mesh: texture must be 0 (off) or a texture resolution, got {texture}")
+        if texture_layout not in ('uniform', 'area'):
+            raise ValueError(f"extract_mesh: texture_layout must be 'uniform' or 'area', got {texture_layout!r}")
         n_smooth = int(smooth)
         if n_smooth < 0:
             raise ValueError(f"extract_mesh: smooth must be 0 (off) or a number of iterations, got {smooth}")
@@ -553,9 +558,10 @@ class NeRFRenderer(nn.Module):
                 colors[s:s + chunk] = (rgb.clamp(0, 1) * 255).round().to(torch.uint8)
         uvs = tex = None
         if tex_r:
-            uvs, tex = _mesh.bake_texture(verts, faces, tex_r, lambda x, d: self(x, d)[1][:, :3], normals=normals, chunk=chunk)
+            uvs, tex = _mesh.bake_texture(verts, faces, tex_r, lambda x, d: self(x, d)[1][:, :3], normals=normals, chunk=chunk,
+                                          layout=texture_layout)
         m = {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
-             'uvs': uvs, 'texture': tex}
+             'uvs': uvs, 'texture': tex, 'texture_layout': texture_layout}
         if deviation:
             m['deviation'] = None
             if n_smooth or k >= 2 or tf:
@@ -570,8 +576,8 @@ class NeRFRenderer(nn.Module):
         """extract_mesh(**kw) written to `path` -> the mesh dict.  A path ending in .obj writes a Wavefront OBJ (mesh.write_obj: positions,
         normals, and with texture=R the UVs, <stem>.mtl and the R x R <stem>.png beside it; vertex colours are not written to OBJ); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
-        extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), deviation / deviation_spacing
-        and ao pass through.  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
+        extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), texture_layout, deviation /
+        deviation_spacing and ao pass through.  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written
         unchanged (a NeRF's radiance already contains its shading, so AO is never multiplied into baked colour or texture)."""
         obj = str(path).lower().endswith(".obj")

@@ -42,7 +42,8 @@ extern "C" {
  *    cnerf_mesh_smooth_workspace_bytes / _init / _steps / _normals; mesh rasteriser (additive, same version) —
  *    cnerf_mesh_raster_workspace_bytes / _visibility / _shade; closest-point queries and surface samples (additive, same version) —
  *    cnerf_mesh_bvh_workspace_bytes / _build / _closest and cnerf_mesh_sample_workspace_bytes / _count / _emit; ray queries on the same tree
- *    (additive, same version) — cnerf_mesh_bvh_raycast / _occluded. */
+ *    (additive, same version) — cnerf_mesh_bvh_raycast / _occluded; the area-proportional atlas (additive, same version) —
+ *    cnerf_mesh_atlas_sized_workspace_bytes / _measure / _layout / _plan / _uvs / _points / _store / _fill. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -608,7 +609,8 @@ int cnerf_mesh_decimate_emit(const float *normals, uint32_t V, uint32_t F, void 
 /* ------------------------------------------------------------------------------------------------
  * Texture atlas and baking (customnerf_amd/mesh.py atlas_layout / bake_texture; csrc/mesh_texture.hip; the reference writes positions only,
  * NeRF-to-mesh tools bake with xatlas + nvdiffrast on the host).  A trivial per-face-pair layout with no search, so every texel's owner
- * follows from its index; every face gets the same texels whatever its area (area-proportional or seam-minimising charts are not made).
+ * follows from its index; every face gets the same texels whatever its area (the area-proportional layout is the block after this one;
+ * seam-minimising charts are not made).
  *   Image: R x R texels, 16 <= R <= 16384, RGB8 [R][R][3], row Y = image row (top first).  Pair p holds faces 2p (A) and 2p + 1 (B),
  *   P = ceil(F / 2); n = max(1, ceil(sqrt(P))) cells per row, s = floor(R / n) texels per cell edge, s >= 4 (else CNERF_EINVAL: decimate or
  *   raise R); F = 0 gives n = 1, s = R and no cell.  Pair p owns cell (cx, cy) = (p mod n, p div n); its local texel (i, j) is global
@@ -644,6 +646,57 @@ int cnerf_mesh_atlas_points(const float *verts, const float *normals, uint32_t V
 int cnerf_mesh_atlas_store(uint32_t F, uint32_t R, uint32_t t0, uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host,
                            const uint32_t *flags, uint8_t *image, void *stream);
 int cnerf_mesh_atlas_fill(uint32_t F, uint32_t R, const uint8_t *fill_host, uint8_t *image, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Area-proportional texture atlas (customnerf_amd/mesh.py atlas_plan / bake_texture(layout='area'); csrc/mesh_texture.hip; restatement:
+ * tests/atlas_sized_restatement.py).  A face gets a square cell of 4 * 2^k texels, k from its longest edge; cells lie along a Z-order curve,
+ * largest first.  Still search-free: the owner of a texel follows from its index and a table of at most eight numbers, and inside a cell
+ * every rule of the block above holds with the cell's own s, the seam invariant included.
+ *   Size key of a face, float32 without sqrt (the build has -ffp-contract=off): for the edges (0,1), (1,2), (2,0), l = (dx dx + dy dy) + dz dz
+ *   of the float32 differences p_b - p_a; L2 = the maximum of the three (a NaN beside a number is ignored); key = float_bits(L2) >> 20 when
+ *   L2 is finite and > 0, else 0.  0 <= key <= 2047: 16 keys per octave of edge length.
+ *   Classes: R a power of two in [16, 16384] (else CNERF_EINVAL); K = min(7, log2(R) - 2); class k has cells of edge s_k = 4 * 2^k texels,
+ *   4^k tiles of 4 x 4 texels.  For a threshold e in [0, 2048]: k_f = 0 if key_f < e, else min((key_f - e) >> 4, K).  n_k faces in class k,
+ *   C_k = ceil(n_k / 2) cells, tiles(e) = sum_k C_k 4^k.  e = the smallest value with tiles(e) <= (R / 4)^2, found by going up from 0
+ *   (tiles(e) falls as e rises except that a face moving down a class can open one more cell there; it is not monotone); when even
+ *   tiles(2048) = ceil(F / 2) does not fit: CNERF_EINVAL (decimate or raise R).  F = 0 gives e = 0 and no cell.  F <= 2^25.
+ *   Cells: the rank r_f of face f = the number of faces g < f with k_g = k_f (face order); cell c = r_f >> 1 of its class, b = r_f & 1
+ *   (0: A, 1: B).  Classes are laid out from K down to 0: class tile offset O_k = sum_{k' > k} C_k' 4^k', the cell's tile offset
+ *   o = O_k + c 4^k, its tile (tx, ty) = (even bits of o, odd bits of o), its origin texel (X0, Y0) = (4 tx, 4 ty).  Sizes descend along
+ *   the curve, so every cell is aligned to its own size; cells are disjoint and inside the image.  Cell texel index (the order texels are
+ *   handed to the field in): t = T_k + c s_k^2 + j s_k + i with T_k = 16 O_k; t < 16 tiles(e) <= R^2.
+ *   Inside a cell, with s = s_k: corners of A and B, owner of (i, j), u = (X0 + i + 0.5) / R, v = 1 - (Y0 + j + 0.5) / R, texel -> point
+ *   and view direction with the corner-texel exception, all as above.  B of the last cell of a class with odd n_k is un-owned: x = 0,
+ *   d = (0, 0, -1), the fill colour.  Texel (X, Y) lies in a cell iff interleave(X >> 2, Y >> 2) < tiles(e) (X's bits at the even
+ *   positions); every other texel gets the fill colour.
+ * The caller's stream and workspace (ws_bytes >= workspace_bytes(F), 16-byte aligned; it carries the keys from measure to plan and the
+ * cell -> faces table from plan to points and store); no allocation, one host read (hist), integer atomics only, bit-reproducible.
+ *   measure : hist (device uint32 [2049]) = the histogram of the keys in [0, 2048) and the flags in [2048]: bit 0 when a face index lies
+ *             outside [0, V) (such a face is not counted).  The one host read; with a flag set plan, uvs, points and store write nothing.
+ *   layout  : host only: hist_host[2048] -> e_host, counts_host[8] (n_k; 0 above K), tiles_host = tiles(e); or CNERF_EINVAL.
+ *   plan    : for e and counts_host of layout: cells int32 [F][4] = (X0, Y0, s, b) per face (rows >= max_faces are not written) and the
+ *             workspace's cell -> (face A, face B or -1) table.  flags = hist + 2048.  counts_host that are no partition of F, use a class
+ *             above K or need more than (R / 4)^2 tiles are CNERF_EINVAL; a face whose rank is not below its class's count gets no cell.
+ *   uvs     : uvs [F][3][2] from cells; faces >= max_faces are neither read nor written.
+ *   points, store : as cnerf_mesh_atlas_points / _store for cell texels t in [t0, t1), t1 <= 16 tiles (else CNERF_EINVAL); a range may
+ *             cross class boundaries.
+ *   fill    : fill_host on every texel outside the cells (tiles = tiles_host of layout).
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_atlas_sized_workspace_bytes(uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_atlas_sized_measure(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, void *ws, uint64_t ws_bytes,
+                                   uint32_t *hist, void *stream);
+int cnerf_mesh_atlas_sized_layout(const uint32_t *hist_host, uint32_t R, uint32_t *e_host, uint32_t *counts_host, uint32_t *tiles_host);
+int cnerf_mesh_atlas_sized_plan(uint32_t F, uint32_t R, uint32_t e, const uint32_t *counts_host, void *ws, uint64_t ws_bytes,
+                                const uint32_t *flags, int32_t *cells, uint32_t max_faces, void *stream);
+int cnerf_mesh_atlas_sized_uvs(uint32_t F, uint32_t R, const int32_t *cells, const uint32_t *flags, float *uvs, uint32_t max_faces,
+                               void *stream);
+int cnerf_mesh_atlas_sized_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R,
+                                  const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0, uint32_t t1,
+                                  const uint32_t *flags, float *x, float *d, uint32_t max_points, void *stream);
+int cnerf_mesh_atlas_sized_store(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0,
+                                 uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host, const uint32_t *flags,
+                                 uint8_t *image, void *stream);
+int cnerf_mesh_atlas_sized_fill(uint32_t R, uint32_t tiles, const uint8_t *fill_host, uint8_t *image, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Taubin lambda|mu smoothing with uniform weights and area-weighted vertex normals (customnerf_amd/mesh.py smooth / vertex_normals;
