@@ -1,6 +1,7 @@
 // Closest-point and ray queries against a triangle mesh through a bounding-volume hierarchy, and a deterministic surface sampler
 // (cnerf_mesh_bvh_*, cnerf_mesh_sample_*): what mesh.distance() measures the deviation between two meshes with, and what mesh.ray_cast(),
-// mesh.occluded() and mesh.ambient_occlusion() ask.  Same conventions as the other mesh passes: the
+// mesh.occluded() and mesh.ambient_occlusion() ask, and what mesh.project_to_surface() moves the texels of a decimated mesh onto the
+// full-resolution surface with (cnerf_mesh_bvh_project).  Same conventions as the other mesh passes: the
 // caller's stream, buffers and workspace, no allocation, no host synchronisation, no float atomics.  The rules (which faces take part, the
 // point-triangle rule, the ray-triangle rule, the sampler's enumeration) are in include/customnerf_hip.h; tests/bvh_restatement.py and
 // tests/ray_restatement.py restate them bit for bit.
@@ -58,6 +59,17 @@
 //                   Both hold while no intermediate overflows or underflows; an empty node is skipped by its inverted box, the NaN
 //                   records that pad the last leaf by their face index.  tests/test_gpu_mesh_ray.py demands equality with brute force for
 //                   origins on box planes, on faces and thousands of diagonals away.
+//   k_bvh_project : one thread per query (x, n, reach) against the tree of the SOURCE mesh: the ray along +n that accepts only faces looking
+//                   the way n does (cull 2), the ray along -n that accepts only faces looking back at it (cull 1), the nearer of the two
+//                   hits, and where both miss the closest point within reach — what a baker projects a low-polygon mesh's texels with.  It
+//                   is the two walks above (bv_trace, bv_nearest), not a third: the two rays go through ONE copy of bv_trace in a loop of
+//                   two (the direction's sign and the cull are the loop's only variables), so the kernel's code and registers are those
+//                   of a ray cast plus a closest-point walk, and nothing lands in scratch.  The second ray's range ends at
+//                   min(reach, t of the first): only a strictly nearer backward hit can win, so the narrowing changes no result and only
+//                   prunes.  The closest-point walk is entered by the lanes both rays left without a face and by no others (the lanes of
+//                   a wave that hit idle meanwhile; on a baker's input, where the low mesh lies within reach of its source, those are the
+//                   texels past a rim).  The walks keep a face, its record's slot and its barycentrics; the point, the interpolated
+//                   normal (the one place the source's faces and normals are read) and the offset are made once, after the walks.
 // Sampler
 //   k_sample_count / k_sample_scan / k_sample_emit : k^2 per face -> workgroup totals -> offsets -> one thread per sample (a binary search in
 //                   the workgroup's 256 prefix sums finds its face), so the writes are coalesced whatever the mix of face sizes.
@@ -437,13 +449,70 @@ __device__ __forceinline__ void bv_add_stats(unsigned long long *__restrict__ st
     }
 }
 
+// The walk of k_bvh_closest for the point p (finite, of a tree with n > 0 faces): the smallest d2 (best), the smallest face attaining it
+// (bestf, BV_NOFACE: none) and its record (bests).
+__device__ __forceinline__ void bv_nearest(const BvPtr &ws, uint32_t n, const float p[3], float &best, uint32_t &bestf, uint32_t &bests,
+                                           uint32_t &visits, uint32_t &tests) {
+    uint32_t NL, D;
+    bv_shape(n, NL, D);
+    uint32_t node = 1, depth = 0, pending = 0;                   // pending bit i: the sibling of the path's node i levels up is still to come
+    ++visits;
+    // until the first triangle is tested best is +inf, and the bound of an empty node (+inf) is not strictly above it: such a node is
+    // entered and counted in `visits`; its leaf range is empty, so nothing else changes
+    bool go = !(bv_bound(ws.box, 1, p) > best);
+    while (go) {
+        bool descend = false;
+        if (depth == D) {
+            const uint32_t j = node - (1u << D);
+            const uint32_t l0 = (uint32_t)(((uint64_t)j * NL) >> D), l1 = (uint32_t)((((uint64_t)j + 1) * NL) >> D);
+            if (l0 < l1) {
+#pragma unroll
+                for (uint32_t t = 0; t < BV_LEAF; ++t) {
+                    float a[3], b[3], c[3], cp[3], br[3];
+                    const uint64_t slot = (uint64_t)l0 * BV_LEAF + t;
+                    const uint32_t f = bv_record(ws.tri, slot, a, b, c);
+                    if (f == BV_NOFACE) continue;
+                    ++tests;
+                    const float d2 = bv_closest(p, a, b, c, cp, br);
+                    if (d2 < best || (d2 == best && f < bestf)) {       // false for a NaN
+                        best = d2;
+                        bestf = f;
+                        bests = (uint32_t)slot;
+                    }
+                }
+            }
+        } else {
+            visits += 2;
+            const float b0 = bv_bound(ws.box, 2 * node, p), b1 = bv_bound(ws.box, 2 * node + 1, p);
+            const bool ok0 = !(b0 > best), ok1 = !(b1 > best);
+            if (ok0 || ok1) {
+                const uint32_t first = (ok0 && ok1) ? (b1 < b0 ? 1u : 0u) : (ok1 ? 1u : 0u);
+                pending = (pending << 1) | ((ok0 && ok1) ? 1u : 0u);
+                node = 2 * node + first;
+                ++depth;
+                descend = true;
+            }
+        }
+        while (!descend) {                                       // back up to the nearest sibling still to come; its box is tested again
+            if (!pending) {
+                go = false;
+                break;
+            }
+            const uint32_t k = (uint32_t)__ffs((int)pending) - 1;
+            node = (node >> k) ^ 1u;
+            depth -= k;
+            pending = (pending >> k) & ~1u;
+            ++visits;
+            descend = !(bv_bound(ws.box, node, p) > best);
+        }
+    }
+}
+
 __global__ __launch_bounds__(MC_BLOCK) void k_bvh_closest(BvPtr ws, uint32_t F, const float *__restrict__ points, uint32_t Q, float *__restrict__ dist2,
                                                           int32_t *__restrict__ face, float *__restrict__ point, float *__restrict__ bary,
                                                           unsigned long long *__restrict__ stats) {
     const uint32_t q = blockIdx.x * MC_BLOCK + threadIdx.x;
     const uint32_t n = min(ws.hdr[H_N], F);                      // a workspace that was never built must not send the walk out of it
-    uint32_t NL, D;
-    bv_shape(n, NL, D);
     float p[3] = {0.0f, 0.0f, 0.0f};
     bool live = q < Q && n;
     if (live) {
@@ -455,59 +524,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_bvh_closest(BvPtr ws, uint32_t F, 
     }
     float best = INFINITY;
     uint32_t bestf = BV_NOFACE, bests = 0, visits = 0, tests = 0;
-    if (live) {
-        uint32_t node = 1, depth = 0, pending = 0;               // pending bit i: the sibling of the path's node i levels up is still to come
-        ++visits;
-        // until the first triangle is tested best is +inf, and the bound of an empty node (+inf) is not strictly above it: such a node is
-        // entered and counted in `visits`; its leaf range is empty, so nothing else changes
-        bool go = !(bv_bound(ws.box, 1, p) > best);
-        while (go) {
-            bool descend = false;
-            if (depth == D) {
-                const uint32_t j = node - (1u << D);
-                const uint32_t l0 = (uint32_t)(((uint64_t)j * NL) >> D), l1 = (uint32_t)((((uint64_t)j + 1) * NL) >> D);
-                if (l0 < l1) {
-#pragma unroll
-                    for (uint32_t t = 0; t < BV_LEAF; ++t) {
-                        float a[3], b[3], c[3], cp[3], br[3];
-                        const uint64_t slot = (uint64_t)l0 * BV_LEAF + t;
-                        const uint32_t f = bv_record(ws.tri, slot, a, b, c);
-                        if (f == BV_NOFACE) continue;
-                        ++tests;
-                        const float d2 = bv_closest(p, a, b, c, cp, br);
-                        if (d2 < best || (d2 == best && f < bestf)) {   // false for a NaN
-                            best = d2;
-                            bestf = f;
-                            bests = (uint32_t)slot;
-                        }
-                    }
-                }
-            } else {
-                visits += 2;
-                const float b0 = bv_bound(ws.box, 2 * node, p), b1 = bv_bound(ws.box, 2 * node + 1, p);
-                const bool ok0 = !(b0 > best), ok1 = !(b1 > best);
-                if (ok0 || ok1) {
-                    const uint32_t first = (ok0 && ok1) ? (b1 < b0 ? 1u : 0u) : (ok1 ? 1u : 0u);
-                    pending = (pending << 1) | ((ok0 && ok1) ? 1u : 0u);
-                    node = 2 * node + first;
-                    ++depth;
-                    descend = true;
-                }
-            }
-            while (!descend) {                                   // back up to the nearest sibling still to come; its box is tested again
-                if (!pending) {
-                    go = false;
-                    break;
-                }
-                const uint32_t k = (uint32_t)__ffs((int)pending) - 1;
-                node = (node >> k) ^ 1u;
-                depth -= k;
-                pending = (pending >> k) & ~1u;
-                ++visits;
-                descend = !(bv_bound(ws.box, node, p) > best);
-            }
-        }
-    }
+    if (live) bv_nearest(ws, n, p, best, bestf, bests, visits, tests);
     if (q < Q) {
         const bool hit = bestf != BV_NOFACE;
         dist2[q] = best;
@@ -652,10 +669,11 @@ __device__ __forceinline__ bool bv_ray_box(const float4 *__restrict__ box, uint3
     return !(off || en > ex || zn * r.asz > tcur || zf * r.asz < tmin);
 }
 
-// The walk of k_bvh_closest for a ray.  ANY: leave at the first accepted hit (bestf says whether there was one).
+// The walk of k_bvh_closest for a ray.  ANY: leave at the first accepted hit (bestf says whether there was one).  bests: the record of
+// the face in bestf.
 template <bool ANY>
 __device__ __forceinline__ void bv_trace(const BvPtr &ws, uint32_t n, const BvRay &ray, float tmin, float tmax, int cull, float &best,
-                                         uint32_t &bestf, float bb[3], uint32_t &visits, uint32_t &tests) {
+                                         uint32_t &bestf, uint32_t &bests, float bb[3], uint32_t &visits, uint32_t &tests) {
     uint32_t NL, D;
     bv_shape(n, NL, D);
     uint32_t node = 1, depth = 0, pending = 0;
@@ -671,12 +689,14 @@ __device__ __forceinline__ void bv_trace(const BvPtr &ws, uint32_t n, const BvRa
 #pragma unroll
                 for (uint32_t i = 0; i < BV_LEAF; ++i) {
                     float a[3], b[3], c[3], br[3], t;
-                    const uint32_t f = bv_record(ws.tri, (uint64_t)l0 * BV_LEAF + i, a, b, c);
+                    const uint64_t slot = (uint64_t)l0 * BV_LEAF + i;
+                    const uint32_t f = bv_record(ws.tri, slot, a, b, c);
                     if (f == BV_NOFACE || (ANY && bestf != BV_NOFACE)) continue;
                     ++tests;
                     if (bv_ray_tri(ray, a, b, c, cull, t, br) && tmin <= t && t <= tmax && (t < best || (t == best && f < bestf))) {
                         best = t;
                         bestf = f;
+                        bests = (uint32_t)slot;
                         bb[0] = br[0];
                         bb[1] = br[1];
                         bb[2] = br[2];
@@ -740,9 +760,9 @@ __global__ __launch_bounds__(MC_BLOCK) void k_bvh_raycast(BvPtr ws, uint32_t F, 
     const uint32_t n = min(ws.hdr[H_N], F);
     BvRay ray;
     float tmin, tmax, best = INFINITY, bb[3] = {0.0f, 0.0f, 0.0f};
-    uint32_t bestf = BV_NOFACE, visits = 0, tests = 0;
+    uint32_t bestf = BV_NOFACE, bests = 0, visits = 0, tests = 0;
     if (bv_ray_load(origins, dirs, q, Q, n, tmin_s, tmax_s, tmin_a, tmax_a, ray, tmin, tmax))
-        bv_trace<false>(ws, n, ray, tmin, tmax, cull, best, bestf, bb, visits, tests);
+        bv_trace<false>(ws, n, ray, tmin, tmax, cull, best, bestf, bests, bb, visits, tests);
     if (q < Q) {
         if (t_out) t_out[q] = best;
         if (face_out) face_out[q] = bestf != BV_NOFACE ? (int32_t)bestf : -1;
@@ -761,10 +781,128 @@ __global__ __launch_bounds__(MC_BLOCK) void k_bvh_occluded(BvPtr ws, uint32_t F,
     const uint32_t n = min(ws.hdr[H_N], F);
     BvRay ray;
     float tmin, tmax, best = INFINITY, bb[3];
-    uint32_t bestf = BV_NOFACE, visits = 0, tests = 0;
+    uint32_t bestf = BV_NOFACE, bests = 0, visits = 0, tests = 0;
     if (bv_ray_load(origins, dirs, q, Q, n, tmin_s, tmax_s, tmin_a, tmax_a, ray, tmin, tmax))
-        bv_trace<true>(ws, n, ray, tmin, tmax, cull, best, bestf, bb, visits, tests);
+        bv_trace<true>(ws, n, ray, tmin, tmax, cull, best, bestf, bests, bb, visits, tests);
     if (q < Q) occluded[q] = bestf != BV_NOFACE ? 1 : 0;
+    if (stats) bv_add_stats(stats, visits, tests);
+}
+
+// ------------------------------------------------------------------------------------------------ projection
+// x / sqrt((x0 x0 + x1 x1) + x2 x2) when that sum is positive and finite: at_look of mesh_texture.hip without the sign flip
+__device__ __forceinline__ bool bv_unit(const float x[3], float u[3]) {
+    const float l2 = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2];
+    if (!(l2 > 0.0f && l2 < INFINITY)) return false;
+    const float l = sqrtf(l2);
+    u[0] = x[0] / l;
+    u[1] = x[1] / l;
+    u[2] = x[2] / l;
+    return true;
+}
+
+// One thread per query: the ray along +n (cull 2), the ray along -n (cull 1) over [0, min(reach, t of the first)] — one copy of the walk, run
+// twice — and, for the threads both rays left without a face, the closest-point walk.  What the walks keep is a face, its record and its
+// barycentrics; point and normal are made from the record afterwards.
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_project(BvPtr ws, uint32_t V, uint32_t F, const int32_t *__restrict__ faces,
+                                                          const float *__restrict__ normals, const float *__restrict__ xs,
+                                                          const float *__restrict__ ns, uint32_t Q, float reach_s, const float *__restrict__ reach_a,
+                                                          float *__restrict__ point, float *__restrict__ normal, float *__restrict__ offset,
+                                                          int32_t *__restrict__ face, uint8_t *__restrict__ kind,
+                                                          unsigned long long *__restrict__ stats) {
+    const uint32_t q = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = min(ws.hdr[H_N], F);
+    float x[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f}, reach = reach_s;
+    if (q < Q) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            x[k] = xs[3 * (uint64_t)q + k];
+            d[k] = ns[3 * (uint64_t)q + k];
+        }
+        if (reach_a) reach = reach_a[q];
+    }
+    bool live = q < Q && n && reach >= 0.0f && (d[0] != 0.0f || d[1] != 0.0f || d[2] != 0.0f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) live &= bv_finite(x[k]) && bv_finite(d[k]);
+    float t_hit = INFINITY, bh[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t f_hit = BV_NOFACE, s_hit = 0, kd = 0, visits = 0, tests = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        const float dir[3] = {pass ? -d[0] : d[0], pass ? -d[1] : d[1], pass ? -d[2] : d[2]};
+        BvRay ray;
+        float best = INFINITY, bb[3] = {0.0f, 0.0f, 0.0f};
+        uint32_t bestf = BV_NOFACE, bests = 0;
+        // t_hit is +inf until a ray has hit: the first walk's range ends at reach, the second's where only a strictly nearer face can be
+        if (bv_ray_setup(x, dir, ray) && live)
+            bv_trace<false>(ws, n, ray, 0.0f, fminf(reach, t_hit), pass ? 1 : 2, best, bestf, bests, bb, visits, tests);
+        if (bestf != BV_NOFACE && (f_hit == BV_NOFACE || best < t_hit)) {          // a tie goes forward
+            t_hit = best;
+            f_hit = bestf;
+            s_hit = bests;
+            bh[0] = bb[0];
+            bh[1] = bb[1];
+            bh[2] = bb[2];
+            kd = 1u + (uint32_t)pass;
+        }
+    }
+    const float nn = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+    if (live && kd == 0) {
+        float best = INFINITY;
+        uint32_t bestf = BV_NOFACE, bests = 0;
+        bv_nearest(ws, n, x, best, bestf, bests, visits, tests);
+        if (bestf != BV_NOFACE && best <= (reach * reach) * nn) {
+            kd = 3;
+            f_hit = bestf;
+            s_hit = bests;
+        }
+    }
+    if (q < Q) {
+        float a[3], b[3], c[3], pt[3] = {x[0], x[1], x[2]}, off = 0.0f;
+        if (kd) {
+            bv_record(ws.tri, s_hit, a, b, c);
+            if (kd == 3) {
+                bv_closest(x, a, b, c, pt, bh);
+                const float r[3] = {pt[0] - x[0], pt[1] - x[1], pt[2] - x[2]};
+                off = bv_dot(r, d) / nn;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) pt[k] = (bh[0] * a[k] + bh[1] * b[k]) + bh[2] * c[k];
+                off = kd == 2 ? -t_hit : t_hit;
+            }
+        }
+        if (point)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) point[3 * (uint64_t)q + k] = pt[k];
+        if (offset) offset[q] = off;
+        if (face) face[q] = kd ? (int32_t)f_hit : -1;
+        if (kind) kind[q] = (uint8_t)kd;
+        if (normal) {
+            float nm[3] = {0.0f, 0.0f, 1.0f};
+            bool ok = false;
+            if (kd) {
+                uint32_t t[3];
+                if (normals && f_hit < F && mesh_face(faces, f_hit, V, t)) {
+                    float m[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        m[k] = (bh[0] * normals[3 * (uint64_t)t[0] + k] + bh[1] * normals[3 * (uint64_t)t[1] + k]) +
+                               bh[2] * normals[3 * (uint64_t)t[2] + k];
+                    ok = bv_unit(m, nm);
+                }
+                if (!ok) {                                       // the face's geometric normal, (b - a) x (c - a)
+                    const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+                    const float gn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+                    ok = bv_unit(gn, nm);
+                }
+            }
+            if (!ok && !bv_unit(d, nm)) {
+                nm[0] = 0.0f;
+                nm[1] = 0.0f;
+                nm[2] = 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) normal[3 * (uint64_t)q + k] = nm[k];
+        }
+    }
     if (stats) bv_add_stats(stats, visits, tests);
 }
 
@@ -943,6 +1081,19 @@ int cnerf_mesh_bvh_occluded(const void *ws, uint64_t ws_bytes, uint32_t V, uint3
     if (!Q) return CNERF_OK;
     hipLaunchKernelGGL(k_bvh_occluded, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, F, origins, dirs, Q, t_min, t_max, t_min_per_ray,
                        t_max_per_ray, cull, occluded, (unsigned long long *)stats);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_bvh_project(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const int32_t *faces, const float *normals,
+                           const float *x, const float *n, uint32_t Q, float reach, const float *reach_per_query, float *point,
+                           float *normal, float *offset, int32_t *face, uint8_t *kind, uint64_t *stats, void *stream) {
+    if (!ws || (Q && (!x || !n || (F && !faces)))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F) || Q >= (1u << 31) || (!reach_per_query && !(reach >= 0.0f))) return CNERF_EINVAL;
+    BvPtr p;
+    if (const int rc = mesh_check_ws(ws, ws_bytes, bv_carve((void *)ws, F, p))) return rc;
+    if (!Q) return CNERF_OK;
+    hipLaunchKernelGGL(k_bvh_project, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, V, F, faces, normals, x, n, Q, reach,
+                       reach_per_query, point, normal, offset, face, kind, (unsigned long long *)stats);
     return cn_launch_status();
 }
 

@@ -3,8 +3,9 @@ removal of small connected components, simplification by vertex clustering; csrc
 face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU,
 uniform or with cells sized by the faces' edges (csrc/mesh_texture.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
 shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them,
-watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them (csrc/mesh_bvh.hip), a binary PLY writer
-and an OBJ + MTL + PNG writer.
+watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them, the projection of a low-polygon mesh's
+texels onto the full-resolution surface for baking colour and normal maps (csrc/mesh_bvh.hip), a binary PLY writer and an OBJ + MTL + PNG
+writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -376,15 +377,33 @@ def atlas_plan(verts, faces, resolution):
     return _atlas_plan(v, f, int(resolution), "atlas_plan")[0]
 
 
-def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21, fill=(0, 0, 0), layout='uniform'):
+def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21, fill=(0, 0, 0), layout='uniform', source=None, reach=None,
+                 normal_map=False):
     """Bake color_fn into a resolution x resolution RGB8 texture atlas of the mesh (csrc/mesh_texture.hip).  layout='uniform': each face pair
     owns a square cell of s x s texels (atlas_layout), whatever the faces' sizes; layout='area': a face's cell has 4 * 2^k texels per edge,
     k from its longest edge (atlas_plan; the resolution must be a power of two).  Every texel of a face is evaluated at the point of the
     face's plane under its centre, looking at the surface: color_fn(x [N, 3] float32, d [N, 3] float32) -> RGB in [0, 1], [N, >= 3], any
     float dtype, called on chunks of at most `chunk` texels.  d = -(interpolated vertex normal), or -(face normal) without normals.  Texels no face owns get `fill` (uint8 RGB).
     CUDA tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None.  -> (uvs [F, 3, 2] float32: the UV of corner k of face f,
-    v pointing up; texture [R, R, 3] uint8, row 0 at the top), on the device.  A face index outside [0, V) raises ValueError."""
+    v pointing up; texture [R, R, 3] uint8, row 0 at the top), on the device.  A face index outside [0, V) raises ValueError.
+    source=bake_source(...) bakes from another mesh's surface, as mesh bakers do for a decimated mesh: every texel's point is projected
+    onto the source along the mesh's normal within `reach` (project_to_surface(source, x, -d, reach); by default 2 % of the diagonal of
+    the source's box — a documented default, not a measured optimum) and color_fn is asked at the projected point, looking against the
+    source's normal there: color_fn(point, -normal).  A texel that finds no surface within reach keeps its own point and normal.
+    normal_map=True also writes an object-space normal map [R, R, 3] uint8 with the same layout and store: 0.5 + 0.5 n of the source's
+    normal at the projected point, or without a source of the mesh's own interpolated normal (-d); texels no face owns get
+    (128, 128, 128).  With source or normal_map the result is (uvs, texture, extra), extra = {'normal_map': the map or None, 'kinds':
+    [4] int64 on the device, the cell texels handed to color_fn by the kind of their projection (project_to_surface; zeros without a
+    source)}; with neither it is (uvs, texture) as above."""
     v, f, n = _mesh_args(verts, faces, normals, "bake_texture")
+    if source is not None and not isinstance(source, BakeSource):
+        raise ValueError("bake_texture: source must come from bake_source")
+    if source is None and reach is not None:
+        raise ValueError("bake_texture: reach needs a source")
+    if source is not None and reach is None:
+        reach = 0.02 * source.diagonal
+        if not reach > 0.0:
+            raise ValueError("bake_texture: the source has no valid face to take a default reach from")
     V, F = v.shape[0], f.shape[0]
     R = int(resolution)
     if layout not in ('uniform', 'area'):
@@ -402,16 +421,22 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
     dev = v.device
     uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
     tex = torch.empty(R, R, 3, dtype=torch.uint8, device=dev)
+    images = [(tex, fill_c)]                                                   # every image goes through the same fill and store
+    if normal_map:
+        images.append((torch.empty(R, R, 3, dtype=torch.uint8, device=dev), (C.c_uint8 * 3)(128, 128, 128)))
+    kinds = torch.zeros(4, dtype=torch.int64, device=dev)
     if area:
         plan, flags, counts, ws, nbytes = _atlas_plan(v, f, R, "bake_texture")
         check(lib.cnerf_mesh_atlas_sized_uvs(F, R, _p(plan.cells), ptr(flags), _p(uvs), F, stream()), "mesh_atlas_sized_uvs")
-        check(lib.cnerf_mesh_atlas_sized_fill(R, plan.tiles, fill_c, ptr(tex), stream()), "mesh_atlas_sized_fill")
+        for img, fc in images:
+            check(lib.cnerf_mesh_atlas_sized_fill(R, plan.tiles, fc, ptr(img), stream()), "mesh_atlas_sized_fill")
         total = plan.texels
     else:
         flags = torch.empty(1, dtype=torch.int32, device=dev)
         check(lib.cnerf_mesh_atlas_uvs(_p(f), V, F, R, _p(uvs), F, ptr(flags), stream()), "mesh_atlas_uvs")
         _read(flags, "bake_texture", _BAD_INDEX)
-        check(lib.cnerf_mesh_atlas_fill(F, R, fill_c, ptr(tex), stream()), "mesh_atlas_fill")
+        for img, fc in images:
+            check(lib.cnerf_mesh_atlas_fill(F, R, fc, ptr(img), stream()), "mesh_atlas_fill")
         total = (F + 1) // 2 * s * s
     m = max(1, min(chunk, total))
     x = torch.empty(m, 3, dtype=torch.float32, device=dev)
@@ -425,20 +450,30 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
         else:
             check(lib.cnerf_mesh_atlas_points(ptr(v), _p(n), V, ptr(f), F, R, t0, t1, ptr(flags), ptr(x), ptr(d), k,
                                               stream()), "mesh_atlas_points")
-        rgb = color_fn(x[:k], d[:k])
+        if source is not None:
+            pr = project_to_surface(source, x[:k], -d[:k], reach)
+            look = -pr['normal']
+            rgb = color_fn(pr['point'], look)
+            kinds += (pr['kind'][:, None] == torch.arange(4, dtype=torch.uint8, device=dev)).sum(0)       # no host read
+        else:
+            look = d[:k]
+            rgb = color_fn(x[:k], look)
         if not torch.is_tensor(rgb) or rgb.dim() != 2 or rgb.shape[0] != k or rgb.shape[1] < 3 or not rgb.is_floating_point():
             raise ValueError(f"bake_texture: color_fn must return a floating tensor [N, >= 3] for N = {k} points, got "
                              f"{tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__}")
         rgb = rgb.detach()[:, :3].float()
         if rgb.stride(1) != 1 or rgb.device != dev:
             rgb = rgb.to(dev).contiguous()
-        if area:
-            check(lib.cnerf_mesh_atlas_sized_store(F, R, counts, ptr(ws), nbytes, t0, t1, ptr(rgb), rgb.stride(0), fill_c, ptr(flags), ptr(tex),
-                                                   stream()), "mesh_atlas_sized_store")
-        else:
-            check(lib.cnerf_mesh_atlas_store(F, R, t0, t1, ptr(rgb), rgb.stride(0), fill_c, ptr(flags), ptr(tex), stream()),
-                  "mesh_atlas_store")
-    return uvs, tex
+        for (img, fc), val in zip(images, (rgb, look * -0.5 + 0.5 if normal_map else None)):
+            if area:
+                check(lib.cnerf_mesh_atlas_sized_store(F, R, counts, ptr(ws), nbytes, t0, t1, ptr(val), val.stride(0), fc, ptr(flags), ptr(img),
+                                                       stream()), "mesh_atlas_sized_store")
+            else:
+                check(lib.cnerf_mesh_atlas_store(F, R, t0, t1, ptr(val), val.stride(0), fc, ptr(flags), ptr(img), stream()),
+                      "mesh_atlas_store")
+    if source is None and not normal_map:
+        return uvs, tex
+    return uvs, tex, {'normal_map': images[1][0] if normal_map else None, 'kinds': kinds}
 
 
 _CONVENTIONS = {'nerfstudio': 0, 'ngp': 1}
@@ -674,6 +709,76 @@ def occluded(bvh, origins, dirs, t_min=0.0, t_max=math.inf, cull='none'):
     return occ != 0
 
 
+class BakeSource:
+    """A mesh to bake from (bake_source): bvh, the MeshBVH of its faces; faces [F, 3] int32 and normals [V, 3] float32 or None, contiguous,
+    on the device — what project_to_surface reads beyond the tree; diagonal, the diagonal of the box of the faces that take part (0.0
+    without any)."""
+
+    def __init__(self, bvh, faces, normals, diagonal):
+        self.bvh, self.faces, self.normals, self.diagonal = bvh, faces, normals, diagonal
+
+
+def bake_source(verts, faces, normals=None):
+    """Index a (full-resolution) mesh as the surface that project_to_surface and bake_texture(source=) project onto: build_bvh plus the
+    faces and the vertex normals, from which the projected points' normals are interpolated (without normals they are the faces' own).
+    CUDA tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None -> BakeSource.  Faces left out of the tree (build_bvh) are
+    never projected onto."""
+    v, f, n = _mesh_args(verts, faces, normals, "bake_source")
+    bvh = build_bvh(v, f)
+    diag = 0.0
+    if bvh.n_faces:
+        lo, hi = torch.aminmax(v[_used_mask(v, f)], dim=0)
+        diag = float((hi - lo).double().norm())
+    return BakeSource(bvh, f, n, diag)
+
+
+def project_to_surface(source, points, normals, reach, want_stats=False):
+    """Project points [Q, 3] onto the surface of `source` (bake_source) along their normals [Q, 3] (the outward normals of the mesh the
+    points lie on; not normalised), at most `reach` away (a number > 0, or a [Q] CUDA tensor), on the device (csrc/mesh_bvh.hip,
+    k_bvh_project; the rule is in include/customnerf_hip.h, cnerf_mesh_bvh_project).  Two rays leave each point: along the normal, accepting
+    only source faces that look the way the normal does (met from behind), and against it, accepting only faces that look back at it; the
+    nearer hit wins, so a point of a thin part never lands on the opposite wall.  Where both miss (past a rim), the closest point of the
+    source is taken when it lies within reach.  -> dict: point [Q, 3] (the projected point; the input point where nothing was found),
+    normal [Q, 3] (unit: the source's normal there, interpolated from its vertex normals, else its face's; the input normal normalised
+    where nothing was found), offset [Q] (the signed distance moved along the normal, in units of its length), face [Q] int32 (the source
+    face, -1: none), kind [Q] uint8 (0 nothing found, 1 along the normal, 2 against it, 3 closest point) and on request stats = (node
+    boxes tested, triangles tested) summed over the call.  The result is the brute-force answer under the float32 rule, bit for bit.
+    Points next to each other in the batch should be next to each other in space.  Bad arguments raise ValueError."""
+    what = "project_to_surface"
+    if not isinstance(source, BakeSource):
+        raise ValueError(f"{what}: source must come from bake_source")
+    for name, t in (("points", points), ("normals", normals)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a tensor on the GPU")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{what}: {name} must be [Q, 3], got {tuple(t.shape)}")
+    if points.shape[0] != normals.shape[0]:
+        raise ValueError(f"{what}: points and normals must have one row per query, got {points.shape[0]} and {normals.shape[0]}")
+    x, n = points.detach().contiguous().float(), normals.detach().contiguous().float()
+    Q, dev = x.shape[0], x.device
+    if Q >= 2 ** 31:
+        raise ValueError(f"{what}: at most 2^31 - 1 queries per call, got {Q}")
+    if torch.is_tensor(reach):
+        if not reach.is_cuda or tuple(reach.shape) != (Q,):
+            raise ValueError(f"{what}: reach must be a number or a [Q] tensor on the GPU, got {tuple(reach.shape)} on {reach.device}")
+        r0, per = 0.0, reach.detach().contiguous().float()
+    else:
+        r0, per = float(reach), None
+        if not r0 > 0.0:
+            raise ValueError(f"{what}: reach must be > 0, got {reach}")
+    out = {'point': torch.empty(Q, 3, dtype=torch.float32, device=dev), 'normal': torch.empty(Q, 3, dtype=torch.float32, device=dev),
+           'offset': torch.empty(Q, dtype=torch.float32, device=dev), 'face': torch.empty(Q, dtype=torch.int32, device=dev),
+           'kind': torch.empty(Q, dtype=torch.uint8, device=dev)}
+    stats = torch.zeros(2, dtype=torch.int64, device=dev) if want_stats else None
+    bvh = source.bvh
+    check(lib.cnerf_mesh_bvh_project(ptr(bvh.ws), bvh.nbytes, bvh.V, bvh.F, _p(source.faces), _p(source.normals), _p(x), _p(n), Q, r0, _p(per),
+                                     _p(out['point']), _p(out['normal']), _p(out['offset']), _p(out['face']), _p(out['kind']), _p(stats),
+                                     stream()), "mesh_bvh_project")
+    if want_stats:
+        out['stats'] = tuple(int(s) for s in stats.cpu())
+    return out
+
+
 def ao_directions(K):
     """K fixed directions on the hemisphere about +z, cosine-weighted (their density is proportional to z), as [K, 3] float32 on the host:
     spherical-Fibonacci points, for i = 0 .. K - 1: u = (i + 0.5) / K, z = sqrt(1 - u), r = sqrt(u), phi = 2 pi frac(i (sqrt(5) - 1) / 2),
@@ -877,11 +982,12 @@ def _lines(fmt, a):
     return (fmt * len(a)) % tuple(a.ravel().tolist()) if len(a) else ""
 
 
-def write_obj(path, verts, faces, uvs=None, normals=None, texture=None):
+def write_obj(path, verts, faces, uvs=None, normals=None, texture=None, normal_map=None):
     """Wavefront OBJ: `v x y z`, `vt u v` (three per face, in face order, when uvs [F, 3, 2] are given), `vn` (one per vertex, when normals
     [V, 3] are given) and `f v/vt/vn` lines, 1-based.  Floats are written with 9 significant digits, so float32 values read back exactly.
     With `texture` ([R, R, 3] uint8, needs uvs) the material goes to <stem>.mtl (map_Kd) and the image to <stem>.png beside the OBJ.
-    Accepts tensors (any device) or arrays."""
+    With `normal_map` ([R, R, 3] uint8, needs uvs; object space, as bake_texture(normal_map=True) makes it) the image goes to
+    <stem>_normal.png and a `norm <stem>_normal.png` line into the material.  Accepts tensors (any device) or arrays."""
     v = _host(verts, np.float32).reshape(-1, 3)
     f = _host(faces, np.int64).reshape(-1, 3)
     uv = _host(uvs, np.float32)
@@ -897,19 +1003,22 @@ def write_obj(path, verts, faces, uvs=None, normals=None, texture=None):
             raise ValueError(f"write_obj: normals must be [V, 3] like verts, got {len(n)} for V = {len(v)}")
     if texture is not None and uv is None:
         raise ValueError("write_obj: a texture needs uvs")
+    if normal_map is not None and uv is None:
+        raise ValueError("write_obj: a normal map needs uvs")
+    material = texture is not None or normal_map is not None
     if F and (f.min() < 0 or f.max() >= len(v)):
         raise ValueError("write_obj: a face index lies outside [0, V)")
     root, _ = os.path.splitext(path)
     stem = os.path.basename(root)
     head = ["# customnerf_amd mesh export", f"# {len(v)} vertices, {F} faces"]
-    if texture is not None:
+    if material:
         head += [f"mtllib {stem}.mtl"]
     out = ["\n".join(head) + "\n", _lines("v %.9g %.9g %.9g\n", v.astype(np.float64))]
     if uv is not None:
         out.append(_lines("vt %.9g %.9g\n", uv.astype(np.float64)))
     if n is not None:
         out.append(_lines("vn %.9g %.9g %.9g\n", n.astype(np.float64)))
-    if texture is not None:
+    if material:
         out.append("usemtl material0\n")
     vi = f + 1
     if uv is not None:
@@ -925,7 +1034,11 @@ def write_obj(path, verts, faces, uvs=None, normals=None, texture=None):
     out.append(_lines(f"f {fmt} {fmt} {fmt}\n", idx.reshape(F, 3 * idx.shape[2])))
     with open(path, "w") as fh:
         fh.write("".join(out))
-    if texture is not None:
+    if material:
         with open(root + ".mtl", "w") as fh:
-            fh.write(f"newmtl material0\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {stem}.png\n")
+            fh.write("newmtl material0\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\n" + (f"map_Kd {stem}.png\n" if texture is not None else "") +
+                     (f"norm {stem}_normal.png\n" if normal_map is not None else ""))
+    if texture is not None:
         write_png(root + ".png", texture)
+    if normal_map is not None:
+        write_png(root + "_normal.png", normal_map)

@@ -488,7 +488,7 @@ class NeRFRenderer(nn.Module):
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
                      smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0,
-                     texture_layout='uniform'):
+                     texture_layout='uniform', bake_from='mesh', bake_reach=None, normal_map=False):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -513,7 +513,17 @@ class NeRFRenderer(nn.Module):
         ao=K > 0 adds 'ao' [V] float32 in [0, 1]: the per-vertex ambient occlusion of the final mesh from K rays per vertex
         (mesh.ambient_occlusion: the share of the rays that escape), a shading cue for geometry-only previews — render_mesh(colors=) shows
         it as grey.  It is never multiplied into colors or texture: the field's radiance already contains the scene's shading.  With ao=0
-        the key is absent."""
+        the key is absent.
+        bake_from='source' samples colour where the field was trained instead of on the decimated or smoothed faces, which lie off the
+        isosurface by what 'deviation' reports: every texel of texture=R and every vertex of color=True is projected along the final mesh's
+        normal onto the mesh as it stood after marching cubes and component removal (mesh.project_to_surface), at most bake_reach away
+        (default: four times the largest lattice step; compare it with deviation['hausdorff'] — a reach below the deviation leaves texels
+        unprojected, kind 0 below), and the field is asked there, looking against that surface's normal.  It is accepted when no lossy pass
+        ran; the projections are then near zero.  'bake_kinds' joins the dict: [4] int64, the texels (with texture=0: the vertices) by the
+        kind of their projection (0 nothing within reach, 1 along the normal, 2 against it, 3 the closest point past a rim).
+        normal_map=True (needs texture=R) adds 'normal_map' [R, R, 3] uint8, an object-space normal map in the texture's layout: the
+        normals of the full-resolution surface under bake_from='source' — the detail decimation removed, in a form a viewer can use —
+        else the final mesh's own interpolated normals.  With the defaults neither key is present."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -536,12 +546,20 @@ class NeRFRenderer(nn.Module):
         n_ao = int(ao)
         if n_ao < 0:
             raise ValueError(f"extract_mesh: ao must be 0 (off) or a number of rays per vertex, got {ao}")
+        if bake_from not in ('mesh', 'source'):
+            raise ValueError(f"extract_mesh: bake_from must be 'mesh' or 'source', got {bake_from!r}")
+        from_source = bake_from == 'source'
+        if normal_map and not tex_r:
+            raise ValueError("extract_mesh: normal_map=True needs texture=R, the resolution of the atlas it shares")
+        reach = 4.0 * float(step.max()) if bake_reach is None else float(bake_reach)
+        if from_source and not reach > 0.0:
+            raise ValueError(f"extract_mesh: bake_reach must be > 0, got {bake_reach}")
         vol = self.density_volume(R, aabb, chunk, part, view_dir)
         verts, faces, normals = _mesh.marching_cubes(vol, threshold, spacing=step.tolist(), origin=lo.tolist())
         if int(min_component_faces) > 0 or keep_largest:
             verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
                                                                      largest=bool(keep_largest))
-        kept = (verts, faces) if deviation else None                             # held only for the report
+        kept = (verts, faces, normals) if deviation or from_source else None     # held only for the report and the projection
         if n_smooth:
             verts, normals = _mesh.smooth(verts, faces, n_smooth, smooth_lambda, smooth_mu, normals=normals)
         if k >= 2:
@@ -549,19 +567,34 @@ class NeRFRenderer(nn.Module):
             verts, faces, normals = _mesh.simplify(verts, faces, (step * k).tolist(), normals=normals, origin=lo.tolist(), grid=g)
         if tf:
             verts, faces, normals, _ = _mesh.decimate(verts, faces, tf, normals=normals)
+        source = _mesh.bake_source(*kept) if from_source and (color or tex_r) else None
+        kinds = torch.zeros(4, dtype=torch.int64, device=verts.device) if from_source else None
         colors = None
         if color:
             colors = torch.empty(verts.shape[0], 3, dtype=torch.uint8, device=verts.device)
             for s in range(0, verts.shape[0], chunk):
-                x = verts[s:s + chunk].contiguous()
-                rgb = self(x, (-normals[s:s + chunk]).contiguous())[1][:, :3].float()
+                x, look = verts[s:s + chunk].contiguous(), (-normals[s:s + chunk]).contiguous()
+                if source is not None:
+                    pr = _mesh.project_to_surface(source, x, normals[s:s + chunk], reach)
+                    x, look = pr['point'], -pr['normal']
+                    if not tex_r:
+                        kinds += (pr['kind'][:, None] == torch.arange(4, dtype=torch.uint8, device=x.device)).sum(0)
+                rgb = self(x, look)[1][:, :3].float()
                 colors[s:s + chunk] = (rgb.clamp(0, 1) * 255).round().to(torch.uint8)
-        uvs = tex = None
+        uvs = tex = nmap = None
         if tex_r:
-            uvs, tex = _mesh.bake_texture(verts, faces, tex_r, lambda x, d: self(x, d)[1][:, :3], normals=normals, chunk=chunk,
-                                          layout=texture_layout)
+            baked = _mesh.bake_texture(verts, faces, tex_r, lambda x, d: self(x, d)[1][:, :3], normals=normals, chunk=chunk,
+                                       layout=texture_layout, source=source, reach=reach if source is not None else None,
+                                       normal_map=bool(normal_map))
+            uvs, tex = baked[:2]
+            if len(baked) > 2:
+                nmap, kinds = baked[2]['normal_map'], baked[2]['kinds'] if source is not None else kinds
         m = {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
              'uvs': uvs, 'texture': tex, 'texture_layout': texture_layout}
+        if normal_map:
+            m['normal_map'] = nmap
+        if from_source:
+            m['bake_kinds'] = kinds
         if deviation:
             m['deviation'] = None
             if n_smooth or k >= 2 or tf:
@@ -577,15 +610,19 @@ class NeRFRenderer(nn.Module):
         normals, and with texture=R the UVs, <stem>.mtl and the R x R <stem>.png beside it; vertex colours are not written to OBJ); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
         extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), texture_layout, deviation /
-        deviation_spacing and ao pass through.  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
+        deviation_spacing, ao, bake_from and bake_reach pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
+        in the material) and, like texture=, needs an .obj path.  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written
         unchanged (a NeRF's radiance already contains its shading, so AO is never multiplied into baked colour or texture)."""
         obj = str(path).lower().endswith(".obj")
         if int(kw.get('texture', 0) or 0) and not obj:
             raise ValueError(f"save_mesh: texture= needs an .obj path (PLY carries no texture), got {path!r}")
+        if kw.get('normal_map') and not obj:
+            raise ValueError(f"save_mesh: normal_map=True needs an .obj path (PLY carries no normal map), got {path!r}")
         m = self.extract_mesh(**kw)
         if obj:
-            _mesh.write_obj(path, m['verts'], m['faces'], uvs=m['uvs'], normals=m['normals'], texture=m['texture'])
+            _mesh.write_obj(path, m['verts'], m['faces'], uvs=m['uvs'], normals=m['normals'], texture=m['texture'],
+                            normal_map=m.get('normal_map'))
         else:
             colors = m['colors']
             if colors is None and 'ao' in m:
@@ -593,14 +630,19 @@ class NeRFRenderer(nn.Module):
             _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=colors)
         return m
 
-    def render_mesh(self, mesh, c2w, intrinsics, H, W, path=None, **kw):
+    def render_mesh(self, mesh, c2w, intrinsics, H, W, path=None, map='texture', **kw):
         """Preview of an exported mesh from a camera pose, rasterised on the device (mesh.render_mesh, csrc/mesh_raster.hip).  `mesh` is the
         dict extract_mesh / save_mesh return: its verts, faces, normals, colors, uvs and texture are forwarded (so the texture is shown
         when the mesh has one, else the vertex colours, else the normals); the camera is generate_rays' (c2w [3, 4] or [4, 4], intrinsics
-        (fx, fy, cx, cy), convention= in **kw).  With `path` the image is also written as a PNG (mesh.write_png).
+        (fx, fy, cx, cy), convention= in **kw).  map='normal_map' shows the mesh's normal map (extract_mesh(normal_map=True)) in place of
+        its texture, through the same 'texture' shading.  With `path` the image is also written as a PNG (mesh.write_png).
         -> (image [H, W, 3] uint8, mask [H, W] bool, the visibility dict of mesh.rasterize)."""
+        if map not in ('texture', 'normal_map'):
+            raise ValueError(f"render_mesh: map must be 'texture' or 'normal_map', got {map!r}")
+        if map == 'normal_map' and mesh.get('normal_map') is None:
+            raise ValueError("render_mesh: map='normal_map' needs a mesh from extract_mesh(normal_map=True)")
         image, mask, vis = _mesh.render_mesh(mesh['verts'], mesh['faces'], c2w, intrinsics, H, W, normals=mesh.get('normals'),
-                                             colors=mesh.get('colors'), uvs=mesh.get('uvs'), texture=mesh.get('texture'), **kw)
+                                             colors=mesh.get('colors'), uvs=mesh.get('uvs'), texture=mesh.get(map), **kw)
         if path is not None:
             _mesh.write_png(path, image)
         return image, mask, vis

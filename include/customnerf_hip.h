@@ -43,7 +43,8 @@ extern "C" {
  *    cnerf_mesh_raster_workspace_bytes / _visibility / _shade; closest-point queries and surface samples (additive, same version) —
  *    cnerf_mesh_bvh_workspace_bytes / _build / _closest and cnerf_mesh_sample_workspace_bytes / _count / _emit; ray queries on the same tree
  *    (additive, same version) — cnerf_mesh_bvh_raycast / _occluded; the area-proportional atlas (additive, same version) —
- *    cnerf_mesh_atlas_sized_workspace_bytes / _measure / _layout / _plan / _uvs / _points / _store / _fill. */
+ *    cnerf_mesh_atlas_sized_workspace_bytes / _measure / _layout / _plan / _uvs / _points / _store / _fill; projection onto a source
+ *    mesh (additive, same version) — cnerf_mesh_bvh_project. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -871,6 +872,48 @@ int cnerf_mesh_bvh_raycast(const void *ws, uint64_t ws_bytes, uint32_t V, uint32
 int cnerf_mesh_bvh_occluded(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const float *origins, const float *dirs, uint32_t Q,
                             float t_min, float t_max, const float *t_min_per_ray, const float *t_max_per_ray, int cull, uint8_t *occluded,
                             uint64_t *stats, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Projection of points onto a source mesh along a direction, within a reach: what a texture baker moves the texels of a low-polygon mesh
+ * onto the high-resolution surface with (customnerf_amd/mesh.py project_to_surface / bake_texture(source=); csrc/mesh_bvh.hip,
+ * k_bvh_project; the reference has none).  After build over the SOURCE mesh with the same ws, V and F; faces int32 [F][3] are the source's
+ * (read for the normals' indices only: the positions are the tree's records), normals float32 [V][3] the source's vertex normals or NULL.
+ * x float32 [Q][3] the points, n float32 [Q][3] their directions (the low mesh's outward normal, not normalised: offsets are in units of
+ * |n|), reach for every query or reach_per_query[q] where that pointer is not NULL.  float32, one rounding per written operation in the
+ * order written, divisions and square roots correctly rounded, exactly as above; tests/project_restatement.py restates the rule.
+ *   Per query, the two rays and then the closest point:
+ *     forward  : the raycast rule for origin x, direction n, range [0, reach], cull 2 -> t_f, face, barycentrics.  Along +n only faces
+ *                whose front looks the way n does are accepted, and those are met from behind.
+ *     backward : the raycast rule for origin x, direction (-n0, -n1, -n2), range [0, reach], cull 1 -> t_b, face, barycentrics.
+ *                (The culls keep a point of a thin part from landing on the opposite wall, whose faces look the other way.)
+ *     kind 2 when the backward ray hit and either the forward ray missed or t_b < t_f: that hit, offset = -t_b.
+ *     kind 1 otherwise, when the forward ray hit (a tie goes forward): that hit, offset = t_f.
+ *     kind 3 when both missed and the closest rule of cnerf_mesh_bvh_closest for x finds a face with
+ *            dist2 <= (reach reach) ((n0 n0 + n1 n1) + n2 n2): that face, its closest point cp and barycentrics;
+ *            r = cp - x, offset = ((r0 n0 + r1 n1) + r2 n2) / ((n0 n0 + n1 n1) + n2 n2).
+ *     kind 0 otherwise, and for a degenerate query: a component of x or n not finite, n = 0, a reach that is negative or NaN, or a tree
+ *            without faces.  (A direction the raycast rule calls degenerate although it is finite and not 0 misses with both rays and
+ *            goes on to the closest rule.)
+ *   point [Q][3] : kinds 1, 2: (b0 a + b1 b) + b2 c per component, a, b, c the hit face's float32 vertices and b its barycentrics by the
+ *                  raycast rule; kind 3: cp; kind 0: x, bit for bit.
+ *   normal [Q][3]: unit(v) = v / sqrt((v0 v0 + v1 v1) + v2 v2), defined when that sum is positive and finite (the rule of the atlas's view
+ *                  direction without its sign).  Kinds 1 - 3, with normals: unit((b0 n_a + b1 n_b) + b2 n_c) of the face's three vertex
+ *                  normals; where that is not defined, or normals is NULL: unit(e1 x e2) with e1 = b - a, e2 = c - a,
+ *                  e1 x e2 = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x); where that is not defined, and for kind 0: unit(n);
+ *                  where that is not defined: (0, 0, 1).
+ *   offset [Q]   : as above, the signed distance from x to point along n in units of |n|; 0 for kind 0.
+ *   face [Q] int32 : the source face, -1 for kind 0.   kind [Q] uint8 : 0 .. 3.
+ *   Any of the five may be NULL.  stats (NULL or device uint64 [2], ADDED to, so zero it first): node boxes tested and triangles tested,
+ *   summed over the call.  The second ray is walked over [0, min(reach, t_f)] — by the strict t_b < t_f no result depends on that — and
+ *   the closest point is searched only by the queries both rays left without a face, so one call tests no more than the two raycast
+ *   calls (and, where needed, the closest call) it stands for.
+ *   CNERF_ENULL: ws, x, n or (with F > 0) faces is NULL.  CNERF_EINVAL: V, F or Q >= 2^31, a short or misaligned ws, a reach that is
+ *   negative or NaN where reach_per_query is NULL.  Both return before any launch; Q = 0 is accepted.  The caller's stream; no allocation,
+ *   no host sync; the only atomics are the integer stats; every output is the brute-force result over the faces, bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_bvh_project(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const int32_t *faces, const float *normals,
+                           const float *x, const float *n, uint32_t Q, float reach, const float *reach_per_query, float *point,
+                           float *normal, float *offset, int32_t *face, uint8_t *kind, uint64_t *stats, void *stream);
 
 #ifdef __cplusplus
 }
