@@ -13,6 +13,12 @@
 //     transposing read of CDNA4 (ds_read_b64_tr_b16) instead of identity MFMAs, the transposed weight copy is gone (W^T fragments are
 //     transposing reads of the forward fragment store), ReLU / masks are packed 16-bit integer operations, every prefetch is
 //     unconditional with statically named buffers (no exposed global latency), weights and images are separate LDS objects.  517 us.
+//   * shorter per-tile LDS chain (docs/HISTORY.md B.23, profiles/field_bwd_chain_*): the compiled backward read every W^T fragment of a
+//     data-gradient product right in front of its MFMA and waited for it (wave B: 16 exposed LDS round trips per tile), and every
+//     weight-gradient operand at its point of use.  Now a layer's W^T fragments and the operands of the previous layer's dW products are
+//     issued as one batch ahead of the mask / convert sequence that produces the layer's dz (x4_frags_T / x4_gemm_pre, order pinned by
+//     x4_pin), the dW MFMAs follow under that sequence, and wave A publishes a tile's activation images at the end of the step before the
+//     tile's backward instead of at its start.  Same MFMAs, same operands, same order: bit-identical results.
 #include "field_bwd_common.h"
 
 typedef short x4_s4 __attribute__((__vector_size__(4 * sizeof(short))));
@@ -94,6 +100,29 @@ __device__ __forceinline__ void x4_gemm_T(const unsigned char *layer, X4Img lane
         for (int t = 0; t < T; t++) acc[t] = Prec<true>::mfma(x4_frag_T<S>(layer, lane_off, t, s), b[s], acc[t]);
     }
 }
+
+// The same product with its W^T fragments issued as one batch ahead of the MFMAs (x4_frags_T, then x4_gemm_pre): x4_gemm_T reads every
+// fragment at its point of use, and with one wave per SIMD the compiler's schedule then pays one LDS round trip per MFMA.  The weights do
+// not change during the launch, so a layer's batch is issued before the mask / convert sequence that produces the layer's dz: the reads
+// land under that vector work.  Same MFMAs on the same operands in the same order as x4_gemm_T.
+template <int T, int NS, int S>
+__device__ __forceinline__ void x4_frags_T(const unsigned char *layer, X4Img lane_off, cn_h8 (&w)[NS][T]) {
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+#pragma unroll
+        for (int t = 0; t < T; t++) w[s][t] = x4_frag_T<S>(layer, lane_off, t, s);
+    }
+}
+template <int T, int NS>
+__device__ __forceinline__ void x4_gemm_pre(const cn_h8 (&w)[NS][T], const cn_h8 *b, cn_f16v (&acc)[T]) {
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+#pragma unroll
+        for (int t = 0; t < T; t++) acc[t] = Prec<true>::mfma(w[s][t], b[s], acc[t]);
+    }
+}
+// order pin for the batches: what was issued above stays above (the reads are in flight before the dependent sequence below starts)
+__device__ __forceinline__ void x4_pin() { __builtin_amdgcn_sched_barrier(0); }
 
 // C registers of two 32-row tiles -> B fragments of the next layer, rounded to half; ReLU as a signed 16-bit integer max on the packed
 // halves (positive halves order like their bit patterns; every non-positive value, -0 included, becomes +0).  The packed 16-bit integer
@@ -408,53 +437,58 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
 #pragma unroll
         for (int s = 0; s < SENC; s++) N1[s] = PR::zero();
         unsigned char *my = xch + X2_A;
-        auto phase = [&](uint32_t k, ASet &S, frag_t (&xcur)[SENC], frag_t (&xnext)[SENC]) __attribute__((always_inline)) {
+        auto phase = [&](uint32_t k, ASet &S, const ASet &Snext, frag_t (&xcur)[SENC], frag_t (&xnext)[SENC]) __attribute__((always_inline)) {
             X4_T0();
             asm volatile("" ::: "memory");
             const uint32_t pn = pk == END ? END : it_next(it, true);                // window of step k + 1
             if (pn == END && kend == END) kend = k + 1;
             x4_enc_request<SENC>(enc, P_, dm.L, (pn == END ? 0u : tile_at(pn)) * FLD_TILE + li, hi, xnext);   // (beyond the last: some tile, never used)
-            // ---- backward of the tile of step k-2 (dz_3 was published by wave B in step k-1); S still holds that tile
+            // ---- backward of the tile of step k-2 (dz_3 was published by wave B in step k-1); S still holds that tile, and its activation
+            // images (x0, h1, h2) were published at the end of step k-1 (below): the first product finds them in place
             if (!(ablate & 1) && S.live) {
                 const unsigned char *z3i = xch + X2_Z3 + (k & 1) * 4 * X4_K;
+                const unsigned char *hl = my + ((NGEO == 2) ? X2_A_H2 : X2_A_H1);
                 frag_t z3[4];
+                cn_h8 w2[S64][2];
+                x4_frags_T<2, S64, S64>(wb + off_n2, lw, w2);
                 x4_fetch<4>(z3i, lane, z3);
-                x4_publish<SENC>(my + X2_A_X0, lane, S.x0);
-                x4_publish<4>(my + X2_A_H1, lane, S.h1);
-                if (NGEO == 2) x4_publish<4>(my + X2_A_H2, lane, S.h2);
+                cn_h8 z[2][2], a[2][2];                                             // operands of dW_n2 = dz3 . hlast^T: issued ahead of the chain's MFMAs
+                x4_load_block(z3i, lc, 0, z[0]); x4_load_block(z3i, lc, 1, z[1]);
+                x4_load_block(hl, lc, 0, a[0]); x4_load_block(hl, lc, 1, a[1]);
+                x4_pin();
                 cn_f16v acc[2];
                 fld_zero(acc);
-                x4_gemm_T<2, S64, S64>(wb + off_n2, lw, z3, acc);
-                {   // dW_n2 = dz3 . hlast^T
-                    const unsigned char *hl = my + ((NGEO == 2) ? X2_A_H2 : X2_A_H1);
-                    cn_h8 z[2][2], a[2][2];
-                    x4_load_block(z3i, lc, 0, z[0]); x4_load_block(z3i, lc, 1, z[1]);
-                    x4_load_block(hl, lc, 0, a[0]); x4_load_block(hl, lc, 1, a[1]);
-                    x4_dw(wn2[0][0], z[0], a[0]); x4_dw(wn2[0][1], z[0], a[1]); x4_dw(wn2[1][0], z[1], a[0]); x4_dw(wn2[1][1], z[1], a[1]);
-                }
+                x4_gemm_pre<2, S64>(w2, z3, acc);
                 frag_t z1[4];
+                cn_h8 w0[S64][1];
                 if (NGEO == 2) {
+                    cn_h8 w1[S64][2];
+                    x4_frags_T<2, S64, S64>(wb + off_n1, lw, w1);
+                    x4_pin();
+                    x4_dw(wn2[0][0], z[0], a[0]); x4_dw(wn2[0][1], z[0], a[1]); x4_dw(wn2[1][0], z[1], a[0]); x4_dw(wn2[1][1], z[1], a[1]);
                     frag_t z2[4];
                     x4_c_to_b_masked(acc, S.h2, z2);
                     x4_publish<4>(my + X2_A_Z2, lane, z2);
-                    fld_zero(acc);
-                    x4_gemm_T<2, S64, S64>(wb + off_n1, lw, z2, acc);
-                    cn_h8 z[2][2], a[2][2];
                     x4_load_block(my + X2_A_Z2, lc, 0, z[0]); x4_load_block(my + X2_A_Z2, lc, 1, z[1]);
                     x4_load_block(my + X2_A_H1, lc, 0, a[0]); x4_load_block(my + X2_A_H1, lc, 1, a[1]);
+                    fld_zero(acc);
+                    x4_gemm_pre<2, S64>(w1, z2, acc);
+                    x4_frags_T<1, S64, SENC>(wb + off_n0, lwn, w0);
+                    x4_pin();
                     x4_dw(wn1[0][0], z[0], a[0]); x4_dw(wn1[0][1], z[0], a[1]); x4_dw(wn1[1][0], z[1], a[0]); x4_dw(wn1[1][1], z[1], a[1]);
+                } else {
+                    x4_frags_T<1, S64, SENC>(wb + off_n0, lwn, w0);
+                    x4_pin();
+                    x4_dw(wn2[0][0], z[0], a[0]); x4_dw(wn2[0][1], z[0], a[1]); x4_dw(wn2[1][0], z[1], a[0]); x4_dw(wn2[1][1], z[1], a[1]);
                 }
                 x4_c_to_b_masked(acc, S.h1, z1);
                 x4_publish<4>(my + X2_A_Z1, lane, z1);
+                x4_load_block(my + X2_A_Z1, lc, 0, z[0]); x4_load_block(my + X2_A_Z1, lc, 1, z[1]);
+                x4_load_block(my + X2_A_X0, ln, 0, a[0]);
                 cn_f16v denc[1];
                 fld_zero(denc);
-                x4_gemm_T<1, S64, SENC>(wb + off_n0, lwn, z1, denc);
-                {
-                    cn_h8 z[2][2], a[2];
-                    x4_load_block(my + X2_A_Z1, lc, 0, z[0]); x4_load_block(my + X2_A_Z1, lc, 1, z[1]);
-                    x4_load_block(my + X2_A_X0, ln, 0, a);
-                    x4_dw(wn0[0], z[0], a); x4_dw(wn0[1], z[1], a);
-                }
+                x4_gemm_pre<1, S64>(w0, z1, denc);
+                x4_dw(wn0[0], z[0], a[0]); x4_dw(wn0[1], z[1], a[0]);
                 if (S.v) {
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
@@ -493,12 +527,20 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
                 x4_c_to_b<false>(acc, fea);
                 x4_publish<4>(xch + X2_FEA + (k & 1) * 4 * X4_K, lane, fea);
             }
+            // ---- the activation images of the tile whose backward is the next step (the other set, held since its forward one step ago): this
+            // step's backward has issued its last read of the images (DS operations of one wave execute in order), and the stores leave the
+            // backward's critical path for the end of the short forward step
+            if (!(ablate & 1) && Snext.live) {
+                x4_publish<SENC>(my + X2_A_X0, lane, Snext.x0);
+                x4_publish<4>(my + X2_A_H1, lane, Snext.h1);
+                if (NGEO == 2) x4_publish<4>(my + X2_A_H2, lane, Snext.h2);
+            }
             pk = pn;
             X4_T1();
         };
         for (uint32_t k = 0; kend == END || k < kend + 2; k += 2) {                 // kend live windows + 2 steps to drain, in pairs
-            phase(k, S0, N0, N1);
-            phase(k + 1, S1, N1, N0);
+            phase(k, S0, S1, N0, N1);
+            phase(k + 1, S1, S0, N1, N0);
         }
 #pragma unroll
         for (int a = 0; a < 2; a++) {
@@ -596,44 +638,47 @@ __global__ void __launch_bounds__(FLD_THREADS) k_field_bwd_x2(const void *__rest
                 x4_publish<1>(my + X2_B_BDO, lane, bdo);
                 cn_f16v dfea[2];
                 fld_zero(dfea);
-                // ---- colour head
+                // ---- colour head: the W^T fragments of the hidden layer and the operands of dW_rO (all published by the forward above) are
+                // issued before the mask / convert sequence of dz_r
+                cn_h8 fa[2][2];                                                    // fea^T: second operand of dW_r0 (fea part) and dW_d0
+                cn_h8 wh[S64][2];
+                cn_h8 zo[2], z[2][2], a[2][2], d[2];
+                fld_zero(acc);
+                x4_gemm_T<2, 1, S64>(wb + off_rO, lw, bro, acc);
+                x4_frags_T<2, S64, SR0>(wb + off_r0, lw, wh);
+                x4_load_block(my + X2_B_BRO, lc, 0, zo);
+                x4_load_block(my + X2_B_HR, lc, 0, a[0]); x4_load_block(my + X2_B_HR, lc, 1, a[1]);
+                x4_pin();
                 {
                     frag_t zr[4];
-                    fld_zero(acc);
-                    x4_gemm_T<2, 1, S64>(wb + off_rO, lw, bro, acc);
                     x4_c_to_b_masked(acc, hr, zr);
                     x4_publish<4>(my + X2_B_ZR, lane, zr);
-                    x4_gemm_T<2, S64, SR0>(wb + off_r0, lw, zr, dfea);
-                }
-                cn_h8 fa[2][2];                                                    // fea^T: second operand of dW_r0 (fea part) and dW_d0
-                x4_load_block(fe, lc, 0, fa[0]); x4_load_block(fe, lc, 1, fa[1]);
-                {   // dW_rO = d(out) . hr^T, dW_r0 = dz_r . [dir | fea]^T
-                    cn_h8 zo[2], z[2][2], a[2][2], d[2];
-                    x4_load_block(my + X2_B_BRO, lc, 0, zo);
-                    x4_load_block(my + X2_B_HR, lc, 0, a[0]); x4_load_block(my + X2_B_HR, lc, 1, a[1]);
-                    x4_dw(wro[0], zo, a[0]); x4_dw(wro[1], zo, a[1]);
                     x4_load_block(my + X2_B_ZR, lc, 0, z[0]); x4_load_block(my + X2_B_ZR, lc, 1, z[1]);
                     x4_load_block(my + X2_B_DIR, ln, 0, d);
-                    x4_dw(wrd[0], z[0], d); x4_dw(wrd[1], z[1], d);
-                    x4_dw(wrf[0][0], z[0], fa[0]); x4_dw(wrf[0][1], z[0], fa[1]); x4_dw(wrf[1][0], z[1], fa[0]); x4_dw(wrf[1][1], z[1], fa[1]);
+                    x4_load_block(fe, lc, 0, fa[0]); x4_load_block(fe, lc, 1, fa[1]);
+                    x4_gemm_pre<2, S64>(wh, zr, dfea);
                 }
-                // ---- density head
+                // ---- density head, its batch ahead of the colour head's weight-gradient products: those fill the slots under the next mask sequence
+                fld_zero(acc);
+                x4_gemm_T<2, 1, S64>(wb + off_dO, lw, bdo, acc);
+                x4_frags_T<2, S64, S64>(wb + off_d0, lw, wh);
+                x4_pin();
+                // dW_rO = d(out) . hr^T, dW_r0 = dz_r . [dir | fea]^T
+                x4_dw(wro[0], zo, a[0]); x4_dw(wro[1], zo, a[1]);
+                x4_dw(wrd[0], z[0], d); x4_dw(wrd[1], z[1], d);
+                x4_dw(wrf[0][0], z[0], fa[0]); x4_dw(wrf[0][1], z[0], fa[1]); x4_dw(wrf[1][0], z[1], fa[0]); x4_dw(wrf[1][1], z[1], fa[1]);
+                x4_load_block(my + X2_B_BDO, lc, 0, zo);
+                x4_load_block(my + X2_B_HD, lc, 0, a[0]); x4_load_block(my + X2_B_HD, lc, 1, a[1]);
                 {
                     frag_t zd[4];
-                    fld_zero(acc);
-                    x4_gemm_T<2, 1, S64>(wb + off_dO, lw, bdo, acc);
                     x4_c_to_b_masked(acc, hd, zd);
                     x4_publish<4>(my + X2_B_ZD, lane, zd);
-                    x4_gemm_T<2, S64, S64>(wb + off_d0, lw, zd, dfea);
-                }
-                {   // dW_dO = d(raw) . hd^T, dW_d0 = dz_d . fea^T
-                    cn_h8 zo[2], z[2][2], a[2][2];
-                    x4_load_block(my + X2_B_BDO, lc, 0, zo);
-                    x4_load_block(my + X2_B_HD, lc, 0, a[0]); x4_load_block(my + X2_B_HD, lc, 1, a[1]);
-                    x4_dw(wdo[0], zo, a[0]); x4_dw(wdo[1], zo, a[1]);
                     x4_load_block(my + X2_B_ZD, lc, 0, z[0]); x4_load_block(my + X2_B_ZD, lc, 1, z[1]);
-                    x4_dw(wd0[0][0], z[0], fa[0]); x4_dw(wd0[0][1], z[0], fa[1]); x4_dw(wd0[1][0], z[1], fa[0]); x4_dw(wd0[1][1], z[1], fa[1]);
+                    x4_gemm_pre<2, S64>(wh, zd, dfea);
                 }
+                // dW_dO = d(raw) . hd^T, dW_d0 = dz_d . fea^T
+                x4_dw(wdo[0], zo, a[0]); x4_dw(wdo[1], zo, a[1]);
+                x4_dw(wd0[0][0], z[0], fa[0]); x4_dw(wd0[0][1], z[0], fa[1]); x4_dw(wd0[1][0], z[1], fa[0]); x4_dw(wd0[1][1], z[1], fa[1]);
                 frag_t z3[4];
                 x4_c_to_b<false>(dfea, z3);
                 x4_publish<4>(xch + X2_Z3 + (i & 1) * 4 * X4_K, lane, z3);
