@@ -117,6 +117,13 @@ SIGNATURES = {
     "cnerf_mesh_atlas_sized_points": [vp, vp, u32, vp, u32, u32, vp, vp, u64, u32, u32, vp, vp, vp, u32, vp],
     "cnerf_mesh_atlas_sized_store": [u32, u32, vp, vp, u64, u32, u32, vp, u32, vp, vp, vp, vp],
     "cnerf_mesh_atlas_sized_fill": [u32, u32, vp, vp, vp],
+    "cnerf_mesh_atlas_proj_workspace_bytes": [u32, u32, u32, vp],
+    "cnerf_mesh_atlas_proj_charts": [vp, vp, u32, vp, u32, u32, vp, u64, vp, vp, vp, u32, vp, u32, vp],
+    "cnerf_mesh_atlas_proj_pack": [vp, u32, u32, u32, vp, vp],
+    "cnerf_mesh_atlas_proj_raster": [vp, u32, vp, u32, u32, u32, C.c_double, vp, u32, vp, u64, vp, vp, u32, vp, vp, vp, vp],
+    "cnerf_mesh_atlas_proj_points": [vp, vp, u32, vp, u32, u32, vp, u64, u32, u32, vp, vp, vp, u32, vp],
+    "cnerf_mesh_atlas_proj_store": [u32, u32, u32, vp, u64, u32, u32, vp, u32, vp, vp, vp],
+    "cnerf_mesh_atlas_proj_fill": [u32, u32, u32, vp, u64, vp, vp, vp, vp],
     "cnerf_mesh_raster_workspace_bytes": [u32, u32, u32, u32, vp],
     "cnerf_mesh_raster_visibility": [vp, u32, vp, u32, vp, f32, f32, f32, f32, u32, u32, i32, f32, i32, vp, u64, vp, vp, vp, vp, vp],
     "cnerf_mesh_raster_shade": [vp, vp, vp, u32, u32, vp, u32, u32, i32, vp, vp, vp, u32, vp, vp, f32, f32, vp, vp, vp, vp],

@@ -48,8 +48,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t ld_rlx(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_rlx(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void add_i64(int64_t *p, int64_t v) {
     if (v) __hip_atomic_fetch_add((unsigned long long *)p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -83,34 +81,6 @@ __global__ __launch_bounds__(MC_BLOCK) void k_cc_init(uint32_t V, uint32_t *__re
         fcount[i] = 0;
     }
     if (i < 3) hdr[i] = 0;
-}
-
-// root of x; shortens the walked path (each visited node gets its grandparent: still an ancestor, so any interleaving is safe)
-__device__ __forceinline__ uint32_t cc_find(uint32_t *parent, uint32_t x) {
-    uint32_t cur = ld_rlx(parent + x);
-    if (cur == x) return x;
-    uint32_t prev = x, next;
-    while (cur > (next = ld_rlx(parent + cur))) {
-        st_rlx(parent + prev, next);
-        prev = cur;
-        cur = next;
-    }
-    return cur;
-}
-
-__device__ __forceinline__ void cc_union(uint32_t *parent, uint32_t a, uint32_t b) {
-    uint32_t ra = cc_find(parent, a), rb = cc_find(parent, b);
-    while (ra != rb) {
-        if (ra < rb) {                               // hook rb under ra; a failed CAS returns rb's current parent: climb from there
-            const uint32_t old = atomicCAS(parent + rb, rb, ra);
-            if (old == rb) break;
-            rb = old;
-        } else {
-            const uint32_t old = atomicCAS(parent + ra, ra, rb);
-            if (old == ra) break;
-            ra = old;
-        }
-    }
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void k_cc_hook(const int32_t *__restrict__ faces, uint32_t V, uint32_t F, uint32_t *parent,

@@ -1,7 +1,8 @@
-// What the mesh passes share (mesh.hip: marching cubes, mesh_clean.hip: component removal and clustering, mesh_decimate.hip, mesh_smooth.hip).
+// What the mesh passes share (mesh.hip: marching cubes, mesh_clean.hip: component removal and clustering, mesh_decimate.hip, mesh_smooth.hip,
+// mesh_texture.hip and mesh_charts.hip: the texture atlases).
 // Host: the 256-byte alignment, the launch grid and the bump carver every pass describes its workspace with, once.  Device: workgroup
 // prefix sums and the one-workgroup scan of workgroup totals, the range-checked face load, the vertex -> list offset steps, the per-vertex
-// insertion sort and the compacted vertex store.
+// insertion sort and the compacted vertex store, the lock-free union-find, and the texel -> point helpers of the texture passes.
 // Every grid these kernels scan is one thread per item, MC_BLOCK threads per workgroup;
 // a count pass stores each workgroup's totals (two as uint2, or N as uint32 [N]), mc_scan_totals / mc_scan_totals_n turn them into exclusive
 // offsets in place, and an emit pass adds the in-workgroup prefix (ballot + mbcnt, LDS wave totals) to its workgroup's offset.  Order follows
@@ -214,5 +215,80 @@ __device__ __forceinline__ void mesh_emit_vertex(const float *__restrict__ pos, 
     }
     if (old_index) old_index[k] = (int32_t)i;
 }
+
+// relaxed agent-scope loads and stores of words other workgroups write in the same pass
+__device__ __forceinline__ uint32_t ld_rlx(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_rlx(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Lock-free union-find over uint32 nodes, parent[i] = i at first: the smaller root always wins, so every component's root is its
+// smallest node whatever the order of the unions (mesh_clean.hip: vertex components; mesh_charts.hip: charts).
+// root of x; shortens the walked path (each visited node gets its grandparent: still an ancestor, so any interleaving is safe)
+__device__ __forceinline__ uint32_t cc_find(uint32_t *parent, uint32_t x) {
+    uint32_t cur = ld_rlx(parent + x);
+    if (cur == x) return x;
+    uint32_t prev = x, next;
+    while (cur > (next = ld_rlx(parent + cur))) {
+        st_rlx(parent + prev, next);
+        prev = cur;
+        cur = next;
+    }
+    return cur;
+}
+
+__device__ __forceinline__ void cc_union(uint32_t *parent, uint32_t a, uint32_t b) {
+    uint32_t ra = cc_find(parent, a), rb = cc_find(parent, b);
+    while (ra != rb) {
+        if (ra < rb) {                               // hook rb under ra; a failed CAS returns rb's current parent: climb from there
+            const uint32_t old = atomicCAS(parent + rb, rb, ra);
+            if (old == rb) break;
+            rb = old;
+        } else {
+            const uint32_t old = atomicCAS(parent + ra, ra, rb);
+            if (old == ra) break;
+            ra = old;
+        }
+    }
+}
+
+// What the texture passes share (mesh_texture.hip, mesh_charts.hip): a vertex row, the affine interpolation, the view direction, the
+// point / direction store and the uint8 rounding.
+__device__ __forceinline__ void at_load3(const float *__restrict__ a, uint32_t v, float o[3]) {
+    const uint64_t b = 3 * (uint64_t)v;
+    o[0] = a[b];
+    o[1] = a[b + 1];
+    o[2] = a[b + 2];
+}
+
+// a0 + w1 (a1 - a0) + w2 (a2 - a0), in this order (the build has -ffp-contract=off); at a corner texel (corner >= 0) the vertex's own value
+__device__ __forceinline__ void at_interp(const float a0[3], const float a1[3], const float a2[3], float w1, float w2, int corner, float o[3]) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const float v = (a0[q] + w1 * (a1[q] - a0[q])) + w2 * (a2[q] - a0[q]);
+        o[q] = corner == 0 ? a0[q] : corner == 1 ? a1[q] : corner == 2 ? a2[q] : v;
+    }
+}
+
+// -x / |x| when |x|^2 is positive and finite
+__device__ __forceinline__ bool at_look(const float x[3], float d[3]) {
+    const float l2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
+    if (!(l2 > 0.0f && l2 < INFINITY)) return false;
+    const float l = sqrtf(l2);
+    d[0] = -(x[0] / l);
+    d[1] = -(x[1] / l);
+    d[2] = -(x[2] / l);
+    return true;
+}
+
+__device__ __forceinline__ void at_put(float *__restrict__ xo, float *__restrict__ dout, uint32_t q, const float x[3], const float d[3]) {
+    const uint64_t o = 3 * (uint64_t)q;
+    xo[o] = x[0];
+    xo[o + 1] = x[1];
+    xo[o + 2] = x[2];
+    dout[o] = d[0];
+    dout[o + 1] = d[1];
+    dout[o + 2] = d[2];
+}
+
+__device__ __forceinline__ uint8_t at_u8(float v) { return (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }   // NaN -> 0
 
 }  // namespace

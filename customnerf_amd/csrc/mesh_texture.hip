@@ -78,33 +78,6 @@ __global__ __launch_bounds__(AT_BLOCK) void k_atlas_uvs(const int32_t *__restric
     uvs[2 * (uint64_t)c + 1] = 1.0f - (Y + 0.5f) / Rf;
 }
 
-__device__ __forceinline__ void at_load3(const float *__restrict__ a, uint32_t v, float o[3]) {
-    const uint64_t b = 3 * (uint64_t)v;
-    o[0] = a[b];
-    o[1] = a[b + 1];
-    o[2] = a[b + 2];
-}
-
-// a0 + w1 (a1 - a0) + w2 (a2 - a0), in this order (the build has -ffp-contract=off); at a corner texel (corner >= 0) the vertex's own value
-__device__ __forceinline__ void at_interp(const float a0[3], const float a1[3], const float a2[3], float w1, float w2, int corner, float o[3]) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const float v = (a0[q] + w1 * (a1[q] - a0[q])) + w2 * (a2[q] - a0[q]);
-        o[q] = corner == 0 ? a0[q] : corner == 1 ? a1[q] : corner == 2 ? a2[q] : v;
-    }
-}
-
-// -x / |x| when |x|^2 is positive and finite
-__device__ __forceinline__ bool at_look(const float x[3], float d[3]) {
-    const float l2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-    if (!(l2 > 0.0f && l2 < INFINITY)) return false;
-    const float l = sqrtf(l2);
-    d[0] = -(x[0] / l);
-    d[1] = -(x[1] / l);
-    d[2] = -(x[2] / l);
-    return true;
-}
-
 // x and d of local texel (i, j) of face f (A: b = 0, B: b = 1) in a cell of edge s; false when an index of the face lies outside [0, V)
 __device__ __forceinline__ bool at_texel(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
                                          const int32_t *__restrict__ faces, uint32_t f, uint32_t b, uint32_t i, uint32_t j, uint32_t s,
@@ -151,16 +124,6 @@ __device__ __forceinline__ bool at_texel(const float *__restrict__ verts, const 
     return true;
 }
 
-__device__ __forceinline__ void at_put(float *__restrict__ xo, float *__restrict__ dout, uint32_t q, const float x[3], const float d[3]) {
-    const uint64_t o = 3 * (uint64_t)q;
-    xo[o] = x[0];
-    xo[o + 1] = x[1];
-    xo[o + 2] = x[2];
-    dout[o] = d[0];
-    dout[o + 1] = d[1];
-    dout[o + 2] = d[2];
-}
-
 __global__ __launch_bounds__(AT_BLOCK) void k_atlas_points(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
                                                            const int32_t *__restrict__ faces, AtlasGeom g, uint32_t t0, uint32_t count,
                                                            const uint32_t *__restrict__ flags, float *__restrict__ xo, float *__restrict__ dout) {
@@ -173,8 +136,6 @@ __global__ __launch_bounds__(AT_BLOCK) void k_atlas_points(const float *__restri
     if (f < g.F && !at_texel(verts, normals, V, faces, f, b, i, j, s, x, d)) return;
     at_put(xo, dout, q, x, d);
 }
-
-__device__ __forceinline__ uint8_t at_u8(float v) { return (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }   // NaN -> 0
 
 __global__ __launch_bounds__(AT_BLOCK) void k_atlas_store(AtlasGeom g, uint32_t t0, uint32_t count, const float *__restrict__ rgb,
                                                           uint32_t stride, uchar3 fill, const uint32_t *__restrict__ flags,

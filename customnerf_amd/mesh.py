@@ -1,7 +1,7 @@
 """Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*), mesh cleanup on the GPU (csrc/mesh_clean.hip:
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
 face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU,
-uniform or with cells sized by the faces' edges (csrc/mesh_texture.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
+uniform or with cells sized by the faces' edges (csrc/mesh_texture.hip), or into an atlas of axis-projected charts (csrc/mesh_charts.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
 shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them,
 watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them, the projection of a low-polygon mesh's
 texels onto the full-resolution surface for baking colour and normal maps (csrc/mesh_bvh.hip), a binary PLY writer and an OBJ + MTL + PNG
@@ -377,11 +377,71 @@ def atlas_plan(verts, faces, resolution):
     return _atlas_plan(v, f, int(resolution), "atlas_plan")[0]
 
 
+class ChartPlan:
+    """The chart-based atlas of a mesh (chart_plan): resolution, gutter; charts, their number; density, texels per unit length; rects
+    [C, 4] int32 on the device, (X0, Y0, w, h) of every chart's rectangle, gutter included; face_chart [F] int32 (-1: a face without area,
+    which gets no texel) and face_class [F] int32 (2 axis + (the normal points down the axis), 6: none); owner [R, R] int32, the face
+    every texel is baked from (-1: none); texels, the owned texels; overlap_texels, the (face, texel) pairs where a face covers a texel
+    centre that another face owns (charts that fold over themselves in projection; 0 on a convex blob); coverage = texels / R^2."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _chart_plan(v, f, n, R, gutter, what):
+    """-> (ChartPlan, uvs [F, 3, 2], flags [1], workspace, its size): what bake_texture needs beyond the plan itself"""
+    V, F = v.shape[0], f.shape[0]
+    g = int(gutter)
+    if R < 16 or R > 16384:
+        raise ValueError(f"{what}: the 'projected' layout needs a resolution in [16, 16384], got {R}")
+    if g < 0 or g > 8:
+        raise ValueError(f"{what}: gutter must be in [0, 8], got {gutter}")
+    dev = v.device
+    ws, nbytes = _workspace(dev, "mesh_atlas_proj", V, F, R)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    ext = torch.empty(F, 4, dtype=torch.float32, device=dev)
+    fclass = torch.empty(F, dtype=torch.int32, device=dev)
+    fchart = torch.empty(F, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_atlas_proj_charts(_p(v), _p(n), V, _p(f), F, R, ptr(ws), nbytes, ptr(counts), _p(fclass), _p(fchart), F, _p(ext), F,
+                                           stream()), "mesh_atlas_proj_charts")
+    nc = _read(counts, what, _BAD_INDEX)[0]                                    # host read: C and the flags
+    e = np.ascontiguousarray(ext[:nc].cpu().numpy())                           # host read: exactly the C extents
+    rho = C.c_double(0.0)
+    rects_h = np.zeros((nc, 4), np.int32)
+    rc = lib.cnerf_mesh_atlas_proj_pack(e.ctypes.data_as(C.c_void_p), nc, R, g, C.byref(rho), rects_h.ctypes.data_as(C.c_void_p))
+    if rc == -1:                                                               # CNERF_EINVAL with arguments in range: not even rho = 0 fits
+        raise ValueError(f"{what}: {nc} charts with a gutter of {g} do not fit a {R} x {R} texture; {_NO_FIT}")
+    check(rc, "mesh_atlas_proj_pack")
+    rects = torch.from_numpy(rects_h).to(dev)
+    uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
+    owner = torch.empty(R, R, dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    flags = counts[1:]
+    check(lib.cnerf_mesh_atlas_proj_raster(_p(v), V, _p(f), F, R, g, rho.value, _p(rects), nc, ptr(ws), nbytes, ptr(flags), _p(uvs), F,
+                                           None, ptr(owner), ptr(totals), stream()), "mesh_atlas_proj_raster")
+    total, overlap = (int(t) for t in totals.cpu())                            # host read: the totals
+    plan = ChartPlan(resolution=R, gutter=g, charts=nc, density=rho.value, rects=rects, face_chart=fchart, face_class=fclass, owner=owner,
+                     texels=total, overlap_texels=overlap, coverage=total / float(R * R))
+    return plan, uvs, flags, ws, nbytes
+
+
+def chart_plan(verts, faces, resolution, normals=None, gutter=2):
+    """The chart-based texture atlas of a mesh on a resolution x resolution image (16 to 16384, any value): faces are grouped into charts
+    by the dominant axis of their normal (of the vertex normals' sum when `normals` is given and the face stays within 60 degrees of that
+    axis), each chart is projected along its axis, the charts are packed at one texel density with `gutter` (0 to 8) texels grown round
+    each (the rules are in include/customnerf_hip.h, cnerf_mesh_atlas_proj_*).  CUDA tensors verts [V, 3], faces [F, 3] -> ChartPlan.
+    ValueError on a face index outside [0, V), a resolution or gutter out of range, or more charts than fit."""
+    v, f, n = _mesh_args(verts, faces, normals, "chart_plan")
+    return _chart_plan(v, f, n, int(resolution), gutter, "chart_plan")[0]
+
+
 def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21, fill=(0, 0, 0), layout='uniform', source=None, reach=None,
-                 normal_map=False):
+                 normal_map=False, gutter=None):
     """Bake color_fn into a resolution x resolution RGB8 texture atlas of the mesh (csrc/mesh_texture.hip).  layout='uniform': each face pair
     owns a square cell of s x s texels (atlas_layout), whatever the faces' sizes; layout='area': a face's cell has 4 * 2^k texels per edge,
-    k from its longest edge (atlas_plan; the resolution must be a power of two).  Every texel of a face is evaluated at the point of the
+    k from its longest edge (atlas_plan; the resolution must be a power of two); layout='projected': the faces are grouped into charts by the
+    axis of their normal, projected and packed at one density, with `gutter` texels (default 2) grown round every chart (chart_plan,
+    csrc/mesh_charts.hip) — seams only between charts, a texture that reads as an image.  Every texel of a face is evaluated at the point of the
     face's plane under its centre, looking at the surface: color_fn(x [N, 3] float32, d [N, 3] float32) -> RGB in [0, 1], [N, >= 3], any
     float dtype, called on chunks of at most `chunk` texels.  d = -(interpolated vertex normal), or -(face normal) without normals.  Texels no face owns get `fill` (uint8 RGB).
     CUDA tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None.  -> (uvs [F, 3, 2] float32: the UV of corner k of face f,
@@ -406,10 +466,12 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
             raise ValueError("bake_texture: the source has no valid face to take a default reach from")
     V, F = v.shape[0], f.shape[0]
     R = int(resolution)
-    if layout not in ('uniform', 'area'):
-        raise ValueError(f"bake_texture: layout must be 'uniform' or 'area', got {layout!r}")
-    area = layout == 'area'
-    if not area:
+    if layout not in ('uniform', 'area', 'projected'):
+        raise ValueError(f"bake_texture: layout must be 'uniform', 'area' or 'projected', got {layout!r}")
+    area, proj = layout == 'area', layout == 'projected'
+    if gutter is not None and not proj:
+        raise ValueError(f"bake_texture: gutter belongs to layout='projected', got layout={layout!r}")
+    if not area and not proj:
         _, s = atlas_layout(F, R)
     fl = tuple(int(c) for c in fill)
     if len(fl) != 3 or min(fl) < 0 or max(fl) > 255:
@@ -419,13 +481,20 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
         raise ValueError(f"bake_texture: chunk must be >= 1, got {chunk}")
     fill_c = (C.c_uint8 * 3)(*fl)
     dev = v.device
-    uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
+    if proj:
+        plan, uvs, flags, ws, nbytes = _chart_plan(v, f, n, R, 2 if gutter is None else gutter, "bake_texture")
+    else:
+        uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
     tex = torch.empty(R, R, 3, dtype=torch.uint8, device=dev)
     images = [(tex, fill_c)]                                                   # every image goes through the same fill and store
     if normal_map:
         images.append((torch.empty(R, R, 3, dtype=torch.uint8, device=dev), (C.c_uint8 * 3)(128, 128, 128)))
     kinds = torch.zeros(4, dtype=torch.int64, device=dev)
-    if area:
+    if proj:
+        for img, fc in images:
+            check(lib.cnerf_mesh_atlas_proj_fill(V, F, R, ptr(ws), nbytes, fc, ptr(flags), ptr(img), stream()), "mesh_atlas_proj_fill")
+        total = plan.texels
+    elif area:
         plan, flags, counts, ws, nbytes = _atlas_plan(v, f, R, "bake_texture")
         check(lib.cnerf_mesh_atlas_sized_uvs(F, R, _p(plan.cells), ptr(flags), _p(uvs), F, stream()), "mesh_atlas_sized_uvs")
         for img, fc in images:
@@ -444,7 +513,10 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
     for t0 in range(0, total, m):
         t1 = min(t0 + m, total)
         k = t1 - t0
-        if area:
+        if proj:
+            check(lib.cnerf_mesh_atlas_proj_points(ptr(v), _p(n), V, ptr(f), F, R, ptr(ws), nbytes, t0, t1, ptr(flags), ptr(x), ptr(d), k,
+                                                   stream()), "mesh_atlas_proj_points")
+        elif area:
             check(lib.cnerf_mesh_atlas_sized_points(ptr(v), _p(n), V, ptr(f), F, R, counts, ptr(ws), nbytes, t0, t1, ptr(flags), ptr(x), ptr(d),
                                                     k, stream()), "mesh_atlas_sized_points")
         else:
@@ -465,7 +537,10 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
         if rgb.stride(1) != 1 or rgb.device != dev:
             rgb = rgb.to(dev).contiguous()
         for (img, fc), val in zip(images, (rgb, look * -0.5 + 0.5 if normal_map else None)):
-            if area:
+            if proj:
+                check(lib.cnerf_mesh_atlas_proj_store(V, F, R, ptr(ws), nbytes, t0, t1, ptr(val), val.stride(0), ptr(flags), ptr(img),
+                                                      stream()), "mesh_atlas_proj_store")
+            elif area:
                 check(lib.cnerf_mesh_atlas_sized_store(F, R, counts, ptr(ws), nbytes, t0, t1, ptr(val), val.stride(0), fc, ptr(flags), ptr(img),
                                                        stream()), "mesh_atlas_sized_store")
             else:

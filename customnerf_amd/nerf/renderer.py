@@ -504,7 +504,9 @@ class NeRFRenderer(nn.Module):
         texture=R > 0 bakes the field's colour, looking at the surface, into an R x R texture atlas of the final mesh (mesh.bake_texture,
         csrc/mesh_texture.hip): 'uvs' [F, 3, 2] float32 and 'texture' [R, R, 3] uint8 join the dict (both None with texture=0).
         texture_layout='uniform' gives every face the same texels; 'area' (R a power of two) sizes a face's cell by its longest edge, which
-        is what a decimated mesh (target_faces), with its large faces on flat regions, wants.  'texture_layout' joins the dict.
+        is what a decimated mesh (target_faces), with its large faces on flat regions, wants; 'projected' groups the faces into charts by
+        the axis of their normal and packs the projected charts (mesh.chart_plan, csrc/mesh_charts.hip): a texture that reads as an image
+        and has seams only between charts.  'texture_layout' joins the dict.
         deviation=True reports what the lossy passes cost in geometry: 'deviation' joins the dict — mesh.distance(final mesh, the mesh as it
         stood after marching cubes and component removal), both directions (max, mean, rms per direction and 'hausdorff', in world units),
         sampled deviation_spacing apart (default: half the smallest lattice step; at most deviation_max_samples samples per direction,
@@ -538,8 +540,8 @@ class NeRFRenderer(nn.Module):
         tex_r = int(texture)
         if tex_r < 0:
             raise ValueError(f"extract_mesh: texture must be 0 (off) or a texture resolution, got {texture}")
-        if texture_layout not in ('uniform', 'area'):
-            raise ValueError(f"extract_mesh: texture_layout must be 'uniform' or 'area', got {texture_layout!r}")
+        if texture_layout not in ('uniform', 'area', 'projected'):
+            raise ValueError(f"extract_mesh: texture_layout must be 'uniform', 'area' or 'projected', got {texture_layout!r}")
         n_smooth = int(smooth)
         if n_smooth < 0:
             raise ValueError(f"extract_mesh: smooth must be 0 (off) or a number of iterations, got {smooth}")

@@ -44,7 +44,8 @@ extern "C" {
  *    cnerf_mesh_bvh_workspace_bytes / _build / _closest and cnerf_mesh_sample_workspace_bytes / _count / _emit; ray queries on the same tree
  *    (additive, same version) — cnerf_mesh_bvh_raycast / _occluded; the area-proportional atlas (additive, same version) —
  *    cnerf_mesh_atlas_sized_workspace_bytes / _measure / _layout / _plan / _uvs / _points / _store / _fill; projection onto a source
- *    mesh (additive, same version) — cnerf_mesh_bvh_project. */
+ *    mesh (additive, same version) — cnerf_mesh_bvh_project; the chart-based atlas (additive, same version) —
+ *    cnerf_mesh_atlas_proj_workspace_bytes / _charts / _pack / _raster / _points / _store / _fill. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -610,8 +611,8 @@ int cnerf_mesh_decimate_emit(const float *normals, uint32_t V, uint32_t F, void 
 /* ------------------------------------------------------------------------------------------------
  * Texture atlas and baking (customnerf_amd/mesh.py atlas_layout / bake_texture; csrc/mesh_texture.hip; the reference writes positions only,
  * NeRF-to-mesh tools bake with xatlas + nvdiffrast on the host).  A trivial per-face-pair layout with no search, so every texel's owner
- * follows from its index; every face gets the same texels whatever its area (the area-proportional layout is the block after this one;
- * seam-minimising charts are not made).
+ * follows from its index; every face gets the same texels whatever its area (the area-proportional layout is the block after this one, the
+ * chart-based layout the block after that; least-squares or angle-based unwrapping is not done).
  *   Image: R x R texels, 16 <= R <= 16384, RGB8 [R][R][3], row Y = image row (top first).  Pair p holds faces 2p (A) and 2p + 1 (B),
  *   P = ceil(F / 2); n = max(1, ceil(sqrt(P))) cells per row, s = floor(R / n) texels per cell edge, s >= 4 (else CNERF_EINVAL: decimate or
  *   raise R); F = 0 gives n = 1, s = R and no cell.  Pair p owns cell (cx, cy) = (p mod n, p div n); its local texel (i, j) is global
@@ -698,6 +699,88 @@ int cnerf_mesh_atlas_sized_store(uint32_t F, uint32_t R, const uint32_t *counts_
                                  uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host, const uint32_t *flags,
                                  uint8_t *image, void *stream);
 int cnerf_mesh_atlas_sized_fill(uint32_t R, uint32_t tiles, const uint8_t *fill_host, uint8_t *image, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Chart-based texture atlas (customnerf_amd/mesh.py chart_plan / bake_texture(layout='projected'); csrc/mesh_charts.hip; restatement:
+ * tests/atlas_proj_restatement.py).  Faces are grouped into charts by the dominant axis of their normal, every chart is projected along
+ * its axis (box projection: six large charts on a blob, stretch bounded by 2, no flipped face), the charts are shelf-packed at one texel
+ * density, texels find their face by an exact rasterisation in UV space, and a gutter is grown round every chart.  Charts are not merged
+ * across axes, the parameterisation is not relaxed, and charts that fold over themselves in projection are counted, not repaired.
+ * verts / normals float32 [V][3], faces int32 [F][3], V <= 2^28, F <= 2^26, 16 <= R <= 16384 (any value), gutter g in [0, 8]; else CNERF_EINVAL.
+ *   1. Class of a face, float32, one rounding per written operation: e1 = p1 - p0, e2 = p2 - p0, c = (e1y e2z - e1z e2y, e1z e2x - e1x e2z,
+ *      e1x e2y - e1y e2x) (as cnerf_mesh_smooth_normals), q = (cx cx + cy cy) + cz cz.  q not in (0, inf): class 6, no chart: UVs 0, no
+ *      texel.  Axis of a vector: k = argmax |c_k|, ties to the lowest k (k = 0; k = 1 if |c1| > |c0|; k = 2 if |c2| > |c_k|); class
+ *      2 k + (c_k < 0).  With normals: g = (n0 + n1) + n2 per component; when every component is finite and one is nonzero, (k', s') = the
+ *      axis and sign of g; the face takes class 2 k' + s' iff (c_k' < 0) == s' and 4 (c_k' c_k') >= q (|n . axis| >= 0.5); otherwise, and
+ *      without normals, it keeps its own class.  A face index outside [0, V) sets flag bit 0; after that no pass writes anything.
+ *   2. Charts: faces of one class that share a vertex are one chart: union-find over the nodes 6 v + class, uniting the three nodes of every
+ *      classed face; a component's root is its smallest node.  Chart index = rank of the root among the roots of the nodes that a face
+ *      uses, in increasing order; C charts, C <= F.  face_chart = -1 for class 6.
+ *   3. Projection: class (k, +): (a, b) = (x[(k+1)%3], x[(k+2)%3]); class (k, -): (a, b) = (x[(k+2)%3], x[(k+1)%3]): a classed face is
+ *      counter-clockwise in (a, b) with b up.  Extents of a chart: a0 / a1 = min / max of a over the corners of its faces, b0 / b1 alike, by
+ *      integer atomics on the order-preserving image of the float (bits with the sign bit set, or all bits inverted for a negative: -0 < +0).
+ *   4. Density and packing (host, fp64, cnerf_mesh_atlas_proj_pack).  At density rho chart c needs w = ceil(rho (a1 - a0)) + 1 + 2 g by
+ *      h = ceil(rho (b1 - b0)) + 1 + 2 g texels (the differences of the float32 extents in fp64).  fits(rho): every w, h <= R; the charts in
+ *      the order h descending, then w descending, then index ascending; x = y = 0, the shelf's height H = the first chart's h; per chart: if
+ *      x + w > R then y += H, x = 0, H = h; if y + H > R it does not fit; the chart's rectangle is (X0, Y0, w, h) = (x, y, w, h); x += w.
+ *      rho = 0 must fit, else CNERF_EINVAL (more than floor(R / (1 + 2 g))^2 charts: decimate or raise R).  D = the largest a1 - a0 or
+ *      b1 - b0 of any chart; D = 0 gives rho = 0.  rho_hi = (R - 1 - 2 g) / D; if fits(rho_hi), rho = rho_hi; else lo = 0, hi = rho_hi and
+ *      24 times: m = 0.5 (lo + hi), lo = m if fits(m) else hi = m; rho = lo.  fits is not monotone in rho under shelf packing; the rule is
+ *      still well defined and returns a fitting rho.  An extent with a1 < a0, b1 < b0 or a non-finite difference is CNERF_EINVAL.
+ *   5. UVs, fp64 in the order written, rounded to float32 once: tx = ((X0 + g) + 0.5) + rho (a - a0), ty = ((Y0 + h - 1 - g) + 0.5) -
+ *      rho (b - b0) (texel space, rows from the top; texel (X, Y) has its centre at (X + 0.5, Y + 0.5)); u = tx / R, v = 1 - ty / R.
+ *   6. Ownership, exact in int64.  Corners snapped to 1 / 256 texel: xi = rint(256 tx), yi = rint(256 ty) of the fp64 values (half to even);
+ *      the centre of texel (X, Y) is (256 X + 128, 256 Y + 128).  As in the rasteriser's block below with the sign turned, because rows count
+ *      from the top while the faces are counter-clockwise with v up: A = (y1 - y0)(x2 - x0) - (x1 - x0)(y2 - y0), and for corner k,
+ *      i = (k + 1) % 3, j = (k + 2) % 3: E_k(px, py) = (yj - yi)(px - xi) - (xj - xi)(py - yi); E_0 + E_1 + E_2 = A.
+ *      Pass A: a face with A > 0 covers the texels whose centre has every E_k >= 0 (edges inclusive; shared edges snap identically: no
+ *      holes); candidates per axis ceil((min - 128) / 256) .. floor((max - 128) / 256), clamped to the image.  The owner is the smallest
+ *      covering face index.  Pass B, only on texels un-owned after A: a face with A > 0 claims the texels X in ceil((min - 256) / 256) ..
+ *      floor(max / 256) (Y alike, clamped to the image: the closed squares [256 X, 256 X + 256] that meet its box) with
+ *      E_k(centre) + 128 (|xj - xi| + |yj - yi|) >= 0 for every k; a charted face with A <= 0 claims every texel of that range.  The
+ *      smallest claiming index wins.  overlap_texels = the number of (face, texel) pairs with A > 0, every E_k > 0 at the centre and another
+ *      face the owner after A.  The result does not depend on how the work is spread over threads (a face whose
+ *      range has more than 1024 texels is covered by a workgroup).
+ *   7. Gutter: g Jacobi rounds.  An un-owned texel takes the owner of its first owned neighbour inside the image in the order W, E, N, S, NW,
+ *      NE, SW, SE (N = row Y - 1), read from the previous round's map.  Owned texels of a chart stay inside its rectangle, so growth never
+ *      meets another chart.  Seam invariant for g >= 1: every texel with a nonzero bilinear weight at a point of a charted face's UV triangle
+ *      is owned by a face of the same chart.
+ *   8. Texel list: the owned texels after the gutter, numbered in row-major order, t in [0, total).  Point of texel t with owner f:
+ *      w_k = (float) ((double) E_k / (double) A) at the texel's centre, unclamped; p = (p0 + w1 (p1 - p0)) + w2 (p2 - p0) in float32 (no
+ *      corner exception); for an owner with A <= 0, p = p0 and w1 = w2 = 0.  d as cnerf_mesh_atlas_points with these weights: the
+ *      interpolated normal, then the face normal, then (0, 0, -1).  Store: round(clamp(rgb, 0, 1) 255) as cnerf_mesh_atlas_store.
+ * The caller's stream and workspace (16-byte aligned, >= workspace_bytes(V, F, R); it carries classes, charts, snapped corners, the owner map
+ * and the texel list from pass to pass); no allocation, three host reads (counts; the C extents; totals), integer atomics only,
+ * bit-reproducible.
+ *   charts : counts (device uint32 [2]) is zeroed first; [1] = the flags, bit 0: an index outside [0, V); without a flag [0] = C,
+ *            face_class / face_chart int32 [F] (rows >= max_faces are not written) and extents float32 [C][4] = (a0, a1, b0, b1) (rows >=
+ *            max_charts are not written).  The host reads counts, then the C extents.  normals may be NULL.
+ *   pack   : host only, no GPU needed: extents_host [C][4], R, g -> rho_host, rects_host int32 [C][4] = (X0, Y0, w, h), disjoint and inside
+ *            the image; or CNERF_EINVAL.  A failed host allocation returns hipErrorOutOfMemory (2), never CNERF_EINVAL.
+ *   raster : after charts on the same stream with the same ws, V, F, R; flags = counts + 1; rho and rects (device int32 [C][4]) of pack.
+ *            uvs [F][3][2] (rows >= max_faces are not written), owner_ab int32 [R][R] (the map after A and B; may be NULL), owner int32
+ *            [R][R] (after the gutter; -1: none), totals (device uint64 [2], zeroed first): [0] = total, [1] = overlap_texels — the last
+ *            host read.  A face whose chart is not below C is treated as class 6.
+ *   points : texels t in [t0, t1), t1 <= R^2 (else CNERF_EINVAL; t >= total writes nothing): x, d at row t - t0; rows >= max_points are not
+ *            written.
+ *   store  : rgb rows for t in [t0, t1) -> the texel's position in image [R][R][3].
+ *   fill   : fill_host on every un-owned texel.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_atlas_proj_workspace_bytes(uint32_t V, uint32_t F, uint32_t R, uint64_t *bytes_host);
+int cnerf_mesh_atlas_proj_charts(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, void *ws,
+                                 uint64_t ws_bytes, uint32_t *counts, int32_t *face_class, int32_t *face_chart, uint32_t max_faces,
+                                 float *extents, uint32_t max_charts, void *stream);
+int cnerf_mesh_atlas_proj_pack(const float *extents_host, uint32_t C, uint32_t R, uint32_t gutter, double *rho_host, int32_t *rects_host);
+int cnerf_mesh_atlas_proj_raster(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, uint32_t gutter, double rho,
+                                 const int32_t *rects, uint32_t C, void *ws, uint64_t ws_bytes, const uint32_t *flags, float *uvs,
+                                 uint32_t max_faces, int32_t *owner_ab, int32_t *owner, uint64_t *totals, void *stream);
+int cnerf_mesh_atlas_proj_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, void *ws,
+                                 uint64_t ws_bytes, uint32_t t0, uint32_t t1, const uint32_t *flags, float *x, float *d, uint32_t max_points,
+                                 void *stream);
+int cnerf_mesh_atlas_proj_store(uint32_t V, uint32_t F, uint32_t R, void *ws, uint64_t ws_bytes, uint32_t t0, uint32_t t1, const float *rgb,
+                                uint32_t rgb_stride, const uint32_t *flags, uint8_t *image, void *stream);
+int cnerf_mesh_atlas_proj_fill(uint32_t V, uint32_t F, uint32_t R, void *ws, uint64_t ws_bytes, const uint8_t *fill_host,
+                               const uint32_t *flags, uint8_t *image, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Taubin lambda|mu smoothing with uniform weights and area-weighted vertex normals (customnerf_amd/mesh.py smooth / vertex_normals;
