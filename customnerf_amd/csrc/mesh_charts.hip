@@ -18,10 +18,10 @@
 //                   pass B also counts the strictly covered texels another face owns
 //   k_pj_merge / k_pj_grow : A's owner, else B's; then one Jacobi round per gutter texel
 //   k_pj_list_count / _scan / _emit : owned texels in row-major order -> the texel list; the last host read (total, overlap_texels)
-//   k_pj_points / k_pj_store / k_pj_fill : as the passes of mesh_texture.hip, for listed texels
-#include "mesh_common.h"
+//   k_bake_points / _store / _fill<PjTexels> : the bake of mesh_bake.h (once k_pj_points / k_pj_store / k_pj_fill), for listed texels
+#include "mesh_bake.h"
 
-#define PJ_BLOCK 256
+#define PJ_BLOCK BK_BLOCK
 #define PJ_BAD_INDEX 1u
 #define PJ_MAX_V (1u << 28)                                  // 6 V nodes fit 32 bits
 #define PJ_MAX_F (1u << 26)
@@ -409,74 +409,48 @@ __global__ __launch_bounds__(MC_BLOCK) void k_pj_list_emit(uint32_t R, PjPtr p, 
     if (o >= 0) p.list[r] = e;
 }
 
-__global__ __launch_bounds__(PJ_BLOCK) void k_pj_points(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
-                                                        const int32_t *__restrict__ faces, uint32_t F, uint32_t R, PjPtr p, uint32_t t0,
-                                                        uint32_t count, const uint32_t *__restrict__ flags, float *__restrict__ xo,
-                                                        float *__restrict__ dout) {
-    const uint32_t q = blockIdx.x * PJ_BLOCK + threadIdx.x;
-    if (q >= count || flags[0] || t0 + q >= p.hdr[1]) return;
-    const uint32_t e = p.list[t0 + q];
-    if (e >= R * R) return;
-    const int32_t f = p.map_a[e];
-    uint32_t t[3];
-    PjTri tri;
-    if (f < 0 || (uint32_t)f >= F || !mesh_face(faces, (uint32_t)f, V, t) || !tri.load(p.snap, (uint32_t)f)) return;
-    float p0[3], p1[3], p2[3], x[3], d[3];
-    at_load3(verts, t[0], p0);
-    at_load3(verts, t[1], p1);
-    at_load3(verts, t[2], p2);
-    float w1 = 0.0f, w2 = 0.0f;
-    if (tri.A > 0) {
-        const uint32_t Y = e / R, X = e - Y * R;
+// The locator of the bake (mesh_bake.h): cell texel t is entry t of the texel list, owned by the face map_a names.  A face whose snapped
+// triangle has no area is baked at its vertex 0.
+struct PjTexels {
+    uint32_t F, R;
+    const uint32_t *hdr, *list;
+    const int32_t *map_a, *snap;
+    struct Texel {
+        uint32_t e;
+        int32_t f;
+    };
+    static constexpr bool FILL_FLAGS = true;
+
+    // the store pass reads neither the owner map nor the snapped corners: every listed texel is owned
+    template <bool FACE>
+    __device__ __forceinline__ bool find(uint32_t t, Texel &tx) const {
+        if (t >= hdr[1]) return false;
+        tx.e = list[t];
+        if (tx.e >= R * R) return false;
+        tx.f = FACE ? map_a[tx.e] : 0;
+        return !FACE || (tx.f >= 0 && (uint32_t)tx.f < F && snap[6 * (uint64_t)tx.f] != PJ_UNCHARTED);
+    }
+    __device__ __forceinline__ bool bary(const Texel &tx, float &w1, float &w2, int &corner) const {
+        PjTri tri;
+        tri.load(snap, (uint32_t)tx.f);                      // charted: find looked
+        w1 = w2 = 0.0f;
+        corner = -1;
+        if (tri.A <= 0) return false;
+        const uint32_t Y = tx.e / R, X = tx.e - Y * R;
         const int64_t px = 256 * (int64_t)X + 128, py = 256 * (int64_t)Y + 128;
         w1 = (float)((double)tri.edge(1, px, py) / (double)tri.A);
         w2 = (float)((double)tri.edge(2, px, py) / (double)tri.A);
-        at_interp(p0, p1, p2, w1, w2, -1, x);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x[k] = p0[k];
+        return true;
     }
-    bool ok = false;
-    if (normals) {
-        float n0[3], n1[3], n2[3], nn[3];
-        at_load3(normals, t[0], n0);
-        at_load3(normals, t[1], n1);
-        at_load3(normals, t[2], n2);
-        at_interp(n0, n1, n2, w1, w2, -1, nn);
-        ok = at_look(nn, d);
-    }
-    if (!ok) {                                               // the face's geometric normal, (p1 - p0) x (p2 - p0)
-        const float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-        const float e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-        const float gn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-        if (!at_look(gn, d)) {
-            d[0] = 0.0f;
-            d[1] = 0.0f;
-            d[2] = -1.0f;
-        }
-    }
-    at_put(xo, dout, q, x, d);
-}
+    __device__ __forceinline__ bool stored(uint32_t e) const { return map_a[e] >= 0; }
+};
 
-__global__ __launch_bounds__(PJ_BLOCK) void k_pj_store(uint32_t R, PjPtr p, uint32_t t0, uint32_t count, const float *__restrict__ rgb,
-                                                       uint32_t stride, const uint32_t *__restrict__ flags, uint8_t *__restrict__ image) {
-    const uint32_t q = blockIdx.x * PJ_BLOCK + threadIdx.x;
-    if (q >= count || flags[0] || t0 + q >= p.hdr[1]) return;
-    const uint32_t e = p.list[t0 + q];
-    if (e >= R * R) return;
-    const uint64_t a = (uint64_t)q * stride;
-    image[3 * (uint64_t)e] = at_u8(rgb[a]);
-    image[3 * (uint64_t)e + 1] = at_u8(rgb[a + 1]);
-    image[3 * (uint64_t)e + 2] = at_u8(rgb[a + 2]);
-}
-
-__global__ __launch_bounds__(PJ_BLOCK) void k_pj_fill(uint32_t R, PjPtr p, uchar3 fill, const uint32_t *__restrict__ flags,
-                                                      uint8_t *__restrict__ image) {
-    const uint32_t e = blockIdx.x * PJ_BLOCK + threadIdx.x;
-    if (e >= R * R || flags[0] || p.map_a[e] >= 0) return;   // an owned texel is k_pj_store's
-    image[3 * (uint64_t)e] = fill.x;
-    image[3 * (uint64_t)e + 1] = fill.y;
-    image[3 * (uint64_t)e + 2] = fill.z;
+// the checks the bake passes share, and their locator
+int pj_locate(uint32_t V, uint32_t F, uint32_t R, void *ws, uint64_t ws_bytes, PjTexels &loc) {
+    PjPtr p;
+    if (const int rc = pj_check(V, F, R, ws, ws_bytes, p)) return rc;
+    loc = {F, R, p.hdr, p.list, p.map_a, p.snap};
+    return CNERF_OK;
 }
 
 // host: the shelf packing of C charts at density rho; false when it does not fit.  ord = the charts by h, then w, descending, then index
@@ -670,37 +644,25 @@ int cnerf_mesh_atlas_proj_raster(const float *verts, uint32_t V, const int32_t *
 int cnerf_mesh_atlas_proj_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, void *ws,
                                  uint64_t ws_bytes, uint32_t t0, uint32_t t1, const uint32_t *flags, float *x, float *d, uint32_t max_points,
                                  void *stream) {
-    PjPtr p;
-    if (const int rc = pj_check(V, F, R, ws, ws_bytes, p)) return rc;
-    if (t0 > t1 || t1 > R * R) return CNERF_EINVAL;
-    const uint32_t count = (t1 - t0) < max_points ? t1 - t0 : max_points;
-    if (!count) return CNERF_OK;
-    if (!flags || !faces || !verts || !x || !d) return CNERF_ENULL;
-    hipLaunchKernelGGL(k_pj_points, dim3(cn_div_up(count, PJ_BLOCK)), dim3(PJ_BLOCK), 0, CN_STREAM(stream), verts, normals, V, faces, F, R, p, t0,
-                       count, flags, x, d);
-    return cn_launch_status();
+    PjTexels loc;
+    if (const int rc = pj_locate(V, F, R, ws, ws_bytes, loc)) return rc;
+    return bake_launch_points(loc, (uint64_t)R * R, verts, normals, V, faces, t0, t1, flags, x, d, max_points, stream);
 }
 
 int cnerf_mesh_atlas_proj_store(uint32_t V, uint32_t F, uint32_t R, void *ws, uint64_t ws_bytes, uint32_t t0, uint32_t t1, const float *rgb,
                                 uint32_t rgb_stride, const uint32_t *flags, uint8_t *image, void *stream) {
-    PjPtr p;
-    if (const int rc = pj_check(V, F, R, ws, ws_bytes, p)) return rc;
-    if (t0 > t1 || t1 > R * R || rgb_stride < 3) return CNERF_EINVAL;
-    if (t1 == t0) return CNERF_OK;
-    if (!rgb || !flags || !image) return CNERF_ENULL;
-    hipLaunchKernelGGL(k_pj_store, dim3(cn_div_up(t1 - t0, PJ_BLOCK)), dim3(PJ_BLOCK), 0, CN_STREAM(stream), R, p, t0, t1 - t0, rgb, rgb_stride,
-                       flags, image);
-    return cn_launch_status();
+    PjTexels loc;
+    if (const int rc = pj_locate(V, F, R, ws, ws_bytes, loc)) return rc;
+    static const uint8_t no_fill[3] = {0, 0, 0};             // never written: a listed texel has an owner
+    return bake_launch_store(loc, (uint64_t)R * R, t0, t1, rgb, rgb_stride, no_fill, flags, image, stream);
 }
 
 int cnerf_mesh_atlas_proj_fill(uint32_t V, uint32_t F, uint32_t R, void *ws, uint64_t ws_bytes, const uint8_t *fill_host,
                                const uint32_t *flags, uint8_t *image, void *stream) {
-    PjPtr p;
-    if (const int rc = pj_check(V, F, R, ws, ws_bytes, p)) return rc;
-    if (!fill_host || !flags || !image) return CNERF_ENULL;
-    const uchar3 fill = make_uchar3(fill_host[0], fill_host[1], fill_host[2]);
-    hipLaunchKernelGGL(k_pj_fill, dim3(cn_div_up(R * R, PJ_BLOCK)), dim3(PJ_BLOCK), 0, CN_STREAM(stream), R, p, fill, flags, image);
-    return cn_launch_status();
+    PjTexels loc;
+    if (const int rc = pj_locate(V, F, R, ws, ws_bytes, loc)) return rc;
+    if (!flags) return CNERF_ENULL;
+    return bake_launch_fill(loc, fill_host, flags, image, stream);
 }
 
 }  // extern "C"

@@ -3,11 +3,16 @@
 // no allocation, no host synchronisation, no float atomics (the output is bit-reproducible).  The rules are in include/customnerf_hip.h;
 // the NumPy restatement the tests pin them to: tests/atlas_restatement.py.
 //
-//   k_atlas_uvs    : one thread per face corner: its UV (the centre of a corner texel) and the index check into flags bit 0
-//   k_atlas_points : one thread per cell texel t in [t0, t1): its face, the surface point at its (unclamped) barycentrics and the view
-//                    direction looking at the surface; the field is evaluated on these between this pass and the next
-//   k_atlas_store  : one thread per cell texel: round(clamp(rgb, 0, 1) * 255) at its global position, the fill colour on an un-owned texel
-//   k_atlas_fill   : one thread per image texel: the fill colour on every texel outside the first P cells (the others are k_atlas_store's)
+//   k_atlas_uvs             : one thread per face corner: its UV (the centre of a corner texel) and the index check into flags bit 0
+//   k_bake_points<AtlasGeom> : one thread per cell texel t in [t0, t1): its face, the surface point at its (unclamped) barycentrics and the
+//                    view direction looking at the surface; the field is evaluated on these between this pass and the next
+//   k_bake_store<AtlasGeom>  : one thread per cell texel: round(clamp(rgb, 0, 1) * 255) at its global position, the fill colour on an
+//                    un-owned texel
+//   k_bake_fill<AtlasGeom>   : one thread per image texel: the fill colour on every texel outside the first P cells (the others are the
+//                    store pass's)
+// The three k_bake_* kernels are mesh_bake.h's, shared by every layout; a layout says where a cell texel lies (AtlasGeom; SizedTexels,
+// SizedCells).
+// (They were k_atlas_points / _store / _fill, k_sized_points / _store / _fill and k_pj_points / _store / _fill, one copy per layout.)
 //
 // Every texel is independent: the passes are bound by their stores (24 B of points and directions per texel, 3 B of image per texel).
 //
@@ -16,17 +21,62 @@
 //   k_sized_measure : one thread per face: its size key and the index check; the 2048-bin key histogram in LDS, flushed by integer atomics
 //   k_sized_count / k_sized_scan / k_sized_emit : class and in-class rank (face order: the scans of mesh_common.h) -> the face's cell record
 //                     (X0, Y0, s, b) and the cell -> (face A, face B) table
-//   k_sized_uvs / k_sized_points / k_sized_store / k_sized_fill : as the four above, reading the plan; a texel finds its class from the
+//   k_sized_uvs, k_bake_points / _store<SizedTexels>, k_bake_fill<SizedCells> : as the four above, reading the plan; a texel finds its class from the
 //                     at most eight class offsets
-#include "mesh_common.h"
+#include "mesh_bake.h"
 
-#define AT_BLOCK 256
+#define AT_BLOCK BK_BLOCK
 #define AT_BAD_INDEX 1u
 
 namespace {
 
+// A cell texel of either layout: image texel e, owning face f (-1: none), local texel (i, j) in a cell of edge s.  Face A of the cell owns
+// the texels up to the anti-diagonal, face B the ones beyond it.
+struct CellTexel {
+    uint32_t e;
+    int32_t f;
+    uint32_t i, j, s;
+};
+
+__device__ __forceinline__ uint32_t at_side(uint32_t i, uint32_t j, uint32_t s) { return i + j > s - 1 ? 1u : 0u; }
+
+// the weights of a cell texel in its face, and the corner whose texel it is
+__device__ __forceinline__ bool at_cell_bary(const CellTexel &tx, float &w1, float &w2, int &corner) {
+    const uint32_t i = tx.i, j = tx.j, s = tx.s;
+    if (!at_side(i, j, s)) {
+        const float den = (float)(s - 2);
+        w1 = (float)j / den;
+        w2 = (float)i / den;
+        corner = (i == 0 && j == 0) ? 0 : (i == 0 && j == s - 2) ? 1 : (i == s - 2 && j == 0) ? 2 : -1;
+    } else {
+        const float den = (float)(s - 3);
+        w1 = (float)(s - 1 - j) / den;
+        w2 = (float)(s - 1 - i) / den;
+        corner = (i == s - 1 && j == s - 1) ? 0 : (i == s - 1 && j == 2) ? 1 : (i == 2 && j == s - 1) ? 2 : -1;
+    }
+    return true;
+}
+
+// The uniform layout, and its locator (mesh_bake.h): cell p = t / s^2 holds the faces 2 p and 2 p + 1
 struct AtlasGeom {
     uint32_t F, R, n, s, P;
+    typedef CellTexel Texel;
+    static constexpr bool FILL_FLAGS = false;
+
+    template <bool FACE>
+    __device__ __forceinline__ bool find(uint32_t t, CellTexel &tx) const {
+        const uint32_t s2 = s * s, p = t / s2, r = t - p * s2, j = r / s, i = r - j * s;
+        const uint32_t f = 2 * p + at_side(i, j, s), cy = p / n, cx = p - cy * n;
+        tx = {(cy * s + j) * R + cx * s + i, f < F ? (int32_t)f : -1, i, j, s};
+        return true;
+    }
+    __device__ __forceinline__ bool bary(const CellTexel &tx, float &w1, float &w2, int &corner) const {
+        return at_cell_bary(tx, w1, w2, corner);
+    }
+    __device__ __forceinline__ bool stored(uint32_t e) const {  // a used cell
+        const uint32_t Y = e / R, X = e - Y * R, cx = X / s, cy = Y / s;
+        return cx < n && cy < n && cy * n + cx < P;
+    }
 };
 
 // host: the layout of F faces on an R x R image, or CNERF_EINVAL
@@ -62,6 +112,12 @@ __device__ __forceinline__ void at_corner(uint32_t b, uint32_t k, uint32_t s, ui
     }
 }
 
+// the UV of the centre of image texel (X, Y): v points up
+__device__ __forceinline__ void at_uv(uint32_t X, uint32_t Y, uint32_t R, float *__restrict__ uv) {
+    uv[0] = ((float)X + 0.5f) / (float)R;
+    uv[1] = 1.0f - ((float)Y + 0.5f) / (float)R;
+}
+
 __global__ __launch_bounds__(AT_BLOCK) void k_atlas_uvs(const int32_t *__restrict__ faces, uint32_t V, AtlasGeom g, float *__restrict__ uvs,
                                                         uint32_t max_faces, uint32_t *__restrict__ flags) {
     const uint32_t c = blockIdx.x * AT_BLOCK + threadIdx.x;
@@ -73,98 +129,7 @@ __global__ __launch_bounds__(AT_BLOCK) void k_atlas_uvs(const int32_t *__restric
     const uint32_t p = f >> 1, cy = p / g.n, cx = p - cy * g.n;
     uint32_t i, j;
     at_corner(f & 1u, k, g.s, i, j);
-    const float X = (float)(cx * g.s + i), Y = (float)(cy * g.s + j), Rf = (float)g.R;
-    uvs[2 * (uint64_t)c] = (X + 0.5f) / Rf;
-    uvs[2 * (uint64_t)c + 1] = 1.0f - (Y + 0.5f) / Rf;
-}
-
-// x and d of local texel (i, j) of face f (A: b = 0, B: b = 1) in a cell of edge s; false when an index of the face lies outside [0, V)
-__device__ __forceinline__ bool at_texel(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
-                                         const int32_t *__restrict__ faces, uint32_t f, uint32_t b, uint32_t i, uint32_t j, uint32_t s,
-                                         float x[3], float d[3]) {
-    const int32_t v0 = faces[3 * (uint64_t)f], v1 = faces[3 * (uint64_t)f + 1], v2 = faces[3 * (uint64_t)f + 2];
-    if (v0 < 0 || (uint32_t)v0 >= V || v1 < 0 || (uint32_t)v1 >= V || v2 < 0 || (uint32_t)v2 >= V) return false;
-    float w1, w2;
-    int corner;
-    if (!b) {
-        const float den = (float)(s - 2);
-        w1 = (float)j / den;
-        w2 = (float)i / den;
-        corner = (i == 0 && j == 0) ? 0 : (i == 0 && j == s - 2) ? 1 : (i == s - 2 && j == 0) ? 2 : -1;
-    } else {
-        const float den = (float)(s - 3);
-        w1 = (float)(s - 1 - j) / den;
-        w2 = (float)(s - 1 - i) / den;
-        corner = (i == s - 1 && j == s - 1) ? 0 : (i == s - 1 && j == 2) ? 1 : (i == 2 && j == s - 1) ? 2 : -1;
-    }
-    float p0[3], p1[3], p2[3];
-    at_load3(verts, (uint32_t)v0, p0);
-    at_load3(verts, (uint32_t)v1, p1);
-    at_load3(verts, (uint32_t)v2, p2);
-    at_interp(p0, p1, p2, w1, w2, corner, x);
-    bool ok = false;
-    if (normals) {
-        float n0[3], n1[3], n2[3], nn[3];
-        at_load3(normals, (uint32_t)v0, n0);
-        at_load3(normals, (uint32_t)v1, n1);
-        at_load3(normals, (uint32_t)v2, n2);
-        at_interp(n0, n1, n2, w1, w2, corner, nn);
-        ok = at_look(nn, d);
-    }
-    if (!ok) {                                               // the face's geometric normal, (p1 - p0) x (p2 - p0)
-        const float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-        const float e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-        const float gn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-        if (!at_look(gn, d)) {
-            d[0] = 0.0f;
-            d[1] = 0.0f;
-            d[2] = -1.0f;
-        }
-    }
-    return true;
-}
-
-__global__ __launch_bounds__(AT_BLOCK) void k_atlas_points(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
-                                                           const int32_t *__restrict__ faces, AtlasGeom g, uint32_t t0, uint32_t count,
-                                                           const uint32_t *__restrict__ flags, float *__restrict__ xo, float *__restrict__ dout) {
-    const uint32_t q = blockIdx.x * AT_BLOCK + threadIdx.x;
-    if (q >= count || flags[0]) return;                      // after a bad index nothing is written
-    const uint32_t s = g.s, s2 = s * s, t = t0 + q;
-    const uint32_t p = t / s2, r = t - p * s2, j = r / s, i = r - j * s;
-    const uint32_t b = i + j > s - 1 ? 1u : 0u, f = 2 * p + b;
-    float x[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, -1.0f};
-    if (f < g.F && !at_texel(verts, normals, V, faces, f, b, i, j, s, x, d)) return;
-    at_put(xo, dout, q, x, d);
-}
-
-__global__ __launch_bounds__(AT_BLOCK) void k_atlas_store(AtlasGeom g, uint32_t t0, uint32_t count, const float *__restrict__ rgb,
-                                                          uint32_t stride, uchar3 fill, const uint32_t *__restrict__ flags,
-                                                          uint8_t *__restrict__ image) {
-    const uint32_t q = blockIdx.x * AT_BLOCK + threadIdx.x;
-    if (q >= count || flags[0]) return;
-    const uint32_t s = g.s, s2 = s * s, t = t0 + q;
-    const uint32_t p = t / s2, r = t - p * s2, j = r / s, i = r - j * s;
-    const uint32_t f = 2 * p + (i + j > s - 1 ? 1u : 0u);
-    const uint32_t cy = p / g.n, cx = p - cy * g.n;
-    const uint64_t o = 3 * ((uint64_t)(cy * s + j) * g.R + cx * s + i);
-    uchar3 c = fill;
-    if (f < g.F) {
-        const uint64_t a = (uint64_t)q * stride;
-        c = make_uchar3(at_u8(rgb[a]), at_u8(rgb[a + 1]), at_u8(rgb[a + 2]));
-    }
-    image[o] = c.x;
-    image[o + 1] = c.y;
-    image[o + 2] = c.z;
-}
-
-__global__ __launch_bounds__(AT_BLOCK) void k_atlas_fill(AtlasGeom g, uchar3 fill, uint8_t *__restrict__ image) {
-    const uint32_t e = blockIdx.x * AT_BLOCK + threadIdx.x;
-    if (e >= g.R * g.R) return;
-    const uint32_t Y = e / g.R, X = e - Y * g.R, cx = X / g.s, cy = Y / g.s;
-    if (cx < g.n && cy < g.n && cy * g.n + cx < g.P) return;    // a used cell: k_atlas_store writes it
-    image[3 * (uint64_t)e] = fill.x;
-    image[3 * (uint64_t)e + 1] = fill.y;
-    image[3 * (uint64_t)e + 2] = fill.z;
+    at_uv(cx * g.s + i, cy * g.s + j, g.R, uvs + 2 * (uint64_t)c);
 }
 
 // ------------------------------------------------------------------------------------------------ the area-proportional layout
@@ -344,9 +309,7 @@ __global__ __launch_bounds__(AT_BLOCK) void k_sized_uvs(uint32_t F, uint32_t R, 
     const int32_t *rec = cells + 4 * (uint64_t)f;
     uint32_t i, j;
     at_corner((uint32_t)rec[3], k, (uint32_t)rec[2], i, j);
-    const float X = (float)((uint32_t)rec[0] + i), Y = (float)((uint32_t)rec[1] + j), Rf = (float)R;
-    uvs[2 * (uint64_t)c] = (X + 0.5f) / Rf;
-    uvs[2 * (uint64_t)c + 1] = 1.0f - (Y + 0.5f) / Rf;
+    at_uv((uint32_t)rec[0] + i, (uint32_t)rec[1] + j, R, uvs + 2 * (uint64_t)c);
 }
 
 // cell texel t < 16 tiles -> its cell (index into the cell -> faces table, tile offset o), the cell's edge s and the local texel (i, j)
@@ -368,50 +331,34 @@ __device__ __forceinline__ void sz_texel(const SizedPlan &pl, uint32_t t, uint32
     o = Ok + (c << (2 * k));
 }
 
-__global__ __launch_bounds__(AT_BLOCK) void k_sized_points(const float *__restrict__ verts, const float *__restrict__ normals, uint32_t V,
-                                                           const int32_t *__restrict__ faces, SizedPlan pl, const int32_t *__restrict__ owner,
-                                                           uint32_t t0, uint32_t count, const uint32_t *__restrict__ flags,
-                                                           float *__restrict__ xo, float *__restrict__ dout) {
-    const uint32_t q = blockIdx.x * AT_BLOCK + threadIdx.x;
-    if (q >= count || flags[0]) return;
-    uint32_t cell, o, s, i, j;
-    sz_texel(pl, t0 + q, cell, o, s, i, j);
-    const uint32_t b = i + j > s - 1 ? 1u : 0u;
-    const int32_t f = owner[2 * (uint64_t)cell + b];
-    float x[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, -1.0f};
-    if (f >= 0 && ((uint32_t)f >= pl.F || !at_texel(verts, normals, V, faces, (uint32_t)f, b, i, j, s, x, d))) return;
-    at_put(xo, dout, q, x, d);
-}
-
-__global__ __launch_bounds__(AT_BLOCK) void k_sized_store(SizedPlan pl, const int32_t *__restrict__ owner, uint32_t t0, uint32_t count,
-                                                          const float *__restrict__ rgb, uint32_t stride, uchar3 fill,
-                                                          const uint32_t *__restrict__ flags, uint8_t *__restrict__ image) {
-    const uint32_t q = blockIdx.x * AT_BLOCK + threadIdx.x;
-    if (q >= count || flags[0]) return;
-    uint32_t cell, o, s, i, j;
-    sz_texel(pl, t0 + q, cell, o, s, i, j);
-    const int32_t f = owner[2 * (uint64_t)cell + (i + j > s - 1 ? 1u : 0u)];
-    const uint32_t X = 4 * sz_even_bits(o) + i, Y = 4 * sz_even_bits(o >> 1) + j;   // o < tiles <= (R / 4)^2: inside the image
-    const uint64_t at = 3 * ((uint64_t)Y * pl.R + X);
-    uchar3 c = fill;
-    if (f >= 0) {
-        const uint64_t a = (uint64_t)q * stride;
-        c = make_uchar3(at_u8(rgb[a]), at_u8(rgb[a + 1]), at_u8(rgb[a + 2]));
+// The area-proportional layout's locators (mesh_bake.h).  The fill pass is given R and tiles alone: the cells cover the first `tiles` tiles
+// of the Z-order curve
+struct SizedCells {
+    uint32_t R, tiles;
+    static constexpr bool FILL_FLAGS = false;
+    __device__ __forceinline__ bool stored(uint32_t e) const {
+        const uint32_t Y = e / R, X = e - Y * R;
+        return (sz_spread_bits(X >> 2) | (sz_spread_bits(Y >> 2) << 1)) < tiles;
     }
-    image[at] = c.x;
-    image[at + 1] = c.y;
-    image[at + 2] = c.z;
-}
+};
 
-__global__ __launch_bounds__(AT_BLOCK) void k_sized_fill(uint32_t R, uint32_t tiles, uchar3 fill, uint8_t *__restrict__ image) {
-    const uint32_t e = blockIdx.x * AT_BLOCK + threadIdx.x;
-    if (e >= R * R) return;
-    const uint32_t Y = e / R, X = e - Y * R;
-    if ((sz_spread_bits(X >> 2) | (sz_spread_bits(Y >> 2) << 1)) < tiles) return;   // inside a cell: k_sized_store writes it
-    image[3 * (uint64_t)e] = fill.x;
-    image[3 * (uint64_t)e + 1] = fill.y;
-    image[3 * (uint64_t)e + 2] = fill.z;
-}
+// the points and the store pass: the plan and the cell -> faces table
+struct SizedTexels : SizedPlan {
+    const int32_t *owner;
+    typedef CellTexel Texel;
+
+    template <bool FACE>
+    __device__ __forceinline__ bool find(uint32_t t, CellTexel &tx) const {
+        uint32_t cell, o;
+        sz_texel(*this, t, cell, o, tx.s, tx.i, tx.j);
+        tx.f = owner[2 * (uint64_t)cell + at_side(tx.i, tx.j, tx.s)];
+        tx.e = (4 * sz_even_bits(o >> 1) + tx.j) * R + 4 * sz_even_bits(o) + tx.i;   // o < tiles <= (R / 4)^2: inside the image
+        return true;
+    }
+    __device__ __forceinline__ bool bary(const CellTexel &tx, float &w1, float &w2, int &corner) const {
+        return at_cell_bary(tx, w1, w2, corner);
+    }
+};
 
 // the checks the passes after the host read share: the plan of counts_host and the carved workspace
 int sz_check(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint64_t ws_bytes, SizedPlan &pl, SizedPtr &p) {
@@ -419,6 +366,15 @@ int sz_check(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint
     if (const int rc = sz_plan(F, R, counts_host, &pl)) return rc;
     if (!ws) return CNERF_ENULL;
     return mesh_check_ws(ws, ws_bytes, sz_carve(ws, F, p));
+}
+
+// the same for a bake pass: the locator and the cell texels it covers
+int sz_locate(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint64_t ws_bytes, SizedTexels &loc, uint64_t &total) {
+    SizedPtr p;
+    if (const int rc = sz_check(F, R, counts_host, ws, ws_bytes, loc, p)) return rc;
+    loc.owner = p.owner;
+    total = 16 * (uint64_t)loc.tiles;
+    return CNERF_OK;
 }
 
 }  // namespace
@@ -451,36 +407,21 @@ int cnerf_mesh_atlas_points(const float *verts, const float *normals, uint32_t V
                             uint32_t t1, const uint32_t *flags, float *x, float *d, uint32_t max_points, void *stream) {
     AtlasGeom g;
     if (const int rc = at_layout(F, R, &g)) return rc;
-    if (V >= (1u << 31) || t0 > t1 || (uint64_t)t1 > (uint64_t)g.P * g.s * g.s) return CNERF_EINVAL;
-    const uint32_t count = (t1 - t0) < max_points ? t1 - t0 : max_points;
-    if (!count) return CNERF_OK;
-    if (!flags || !faces || !verts || !x || !d) return CNERF_ENULL;
-    hipLaunchKernelGGL(k_atlas_points, dim3(cn_div_up(count, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), verts, normals, V, faces, g, t0,
-                       count, flags, x, d);
-    return cn_launch_status();
+    if (V >= (1u << 31)) return CNERF_EINVAL;
+    return bake_launch_points(g, (uint64_t)g.P * g.s * g.s, verts, normals, V, faces, t0, t1, flags, x, d, max_points, stream);
 }
 
 int cnerf_mesh_atlas_store(uint32_t F, uint32_t R, uint32_t t0, uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host,
                            const uint32_t *flags, uint8_t *image, void *stream) {
     AtlasGeom g;
     if (const int rc = at_layout(F, R, &g)) return rc;
-    if (t0 > t1 || (uint64_t)t1 > (uint64_t)g.P * g.s * g.s || rgb_stride < 3) return CNERF_EINVAL;
-    if (!fill_host) return CNERF_ENULL;
-    if (t1 == t0) return CNERF_OK;
-    if (!rgb || !flags || !image) return CNERF_ENULL;
-    const uchar3 fill = make_uchar3(fill_host[0], fill_host[1], fill_host[2]);
-    hipLaunchKernelGGL(k_atlas_store, dim3(cn_div_up(t1 - t0, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), g, t0, t1 - t0, rgb, rgb_stride,
-                       fill, flags, image);
-    return cn_launch_status();
+    return bake_launch_store(g, (uint64_t)g.P * g.s * g.s, t0, t1, rgb, rgb_stride, fill_host, flags, image, stream);
 }
 
 int cnerf_mesh_atlas_fill(uint32_t F, uint32_t R, const uint8_t *fill_host, uint8_t *image, void *stream) {
     AtlasGeom g;
     if (const int rc = at_layout(F, R, &g)) return rc;
-    if (!fill_host || !image) return CNERF_ENULL;
-    const uchar3 fill = make_uchar3(fill_host[0], fill_host[1], fill_host[2]);
-    hipLaunchKernelGGL(k_atlas_fill, dim3(cn_div_up(R * R, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), g, fill, image);
-    return cn_launch_status();
+    return bake_launch_fill(g, fill_host, nullptr, image, stream);
 }
 
 int cnerf_mesh_atlas_sized_workspace_bytes(uint32_t F, uint64_t *bytes_host) {
@@ -560,40 +501,25 @@ int cnerf_mesh_atlas_sized_uvs(uint32_t F, uint32_t R, const int32_t *cells, con
 int cnerf_mesh_atlas_sized_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R,
                                   const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0, uint32_t t1,
                                   const uint32_t *flags, float *x, float *d, uint32_t max_points, void *stream) {
-    SizedPlan pl;
-    SizedPtr p;
-    if (const int rc = sz_check(F, R, counts_host, ws, ws_bytes, pl, p)) return rc;
-    if (V >= (1u << 31) || t0 > t1 || (uint64_t)t1 > 16 * (uint64_t)pl.tiles) return CNERF_EINVAL;
-    const uint32_t count = (t1 - t0) < max_points ? t1 - t0 : max_points;
-    if (!count) return CNERF_OK;
-    if (!flags || !faces || !verts || !x || !d) return CNERF_ENULL;
-    hipLaunchKernelGGL(k_sized_points, dim3(cn_div_up(count, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), verts, normals, V, faces, pl,
-                       p.owner, t0, count, flags, x, d);
-    return cn_launch_status();
+    SizedTexels loc;
+    uint64_t total;
+    if (const int rc = sz_locate(F, R, counts_host, ws, ws_bytes, loc, total)) return rc;
+    if (V >= (1u << 31)) return CNERF_EINVAL;
+    return bake_launch_points(loc, total, verts, normals, V, faces, t0, t1, flags, x, d, max_points, stream);
 }
 
 int cnerf_mesh_atlas_sized_store(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0,
                                  uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host, const uint32_t *flags,
                                  uint8_t *image, void *stream) {
-    SizedPlan pl;
-    SizedPtr p;
-    if (const int rc = sz_check(F, R, counts_host, ws, ws_bytes, pl, p)) return rc;
-    if (t0 > t1 || (uint64_t)t1 > 16 * (uint64_t)pl.tiles || rgb_stride < 3) return CNERF_EINVAL;
-    if (!fill_host) return CNERF_ENULL;
-    if (t1 == t0) return CNERF_OK;
-    if (!rgb || !flags || !image) return CNERF_ENULL;
-    const uchar3 fill = make_uchar3(fill_host[0], fill_host[1], fill_host[2]);
-    hipLaunchKernelGGL(k_sized_store, dim3(cn_div_up(t1 - t0, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), pl, p.owner, t0, t1 - t0, rgb,
-                       rgb_stride, fill, flags, image);
-    return cn_launch_status();
+    SizedTexels loc;
+    uint64_t total;
+    if (const int rc = sz_locate(F, R, counts_host, ws, ws_bytes, loc, total)) return rc;
+    return bake_launch_store(loc, total, t0, t1, rgb, rgb_stride, fill_host, flags, image, stream);
 }
 
 int cnerf_mesh_atlas_sized_fill(uint32_t R, uint32_t tiles, const uint8_t *fill_host, uint8_t *image, void *stream) {
     if (sz_log2(R) < 0 || (uint64_t)tiles > (uint64_t)(R / 4) * (R / 4)) return CNERF_EINVAL;
-    if (!fill_host || !image) return CNERF_ENULL;
-    const uchar3 fill = make_uchar3(fill_host[0], fill_host[1], fill_host[2]);
-    hipLaunchKernelGGL(k_sized_fill, dim3(cn_div_up(R * R, AT_BLOCK)), dim3(AT_BLOCK), 0, CN_STREAM(stream), R, tiles, fill, image);
-    return cn_launch_status();
+    return bake_launch_fill(SizedCells{R, tiles}, fill_host, nullptr, image, stream);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@ import math
 import os
 import struct
 import zlib
+from functools import cached_property
 
 import numpy as np
 import torch
@@ -329,6 +330,45 @@ def atlas_layout(F, resolution):
 
 
 _NO_FIT = "decimate the mesh (target_faces=) or raise the resolution"
+TEXTURE_LAYOUTS = ('uniform', 'area', 'projected')
+
+
+class _BakeLayout:
+    """A texture atlas layout as bake_texture uses it, built from the mesh (v, f, n of _mesh_args), the resolution R and `what`, the name its
+    errors are raised under.  plan: the layout's public plan, if it has one; uvs [F, 3, 2]; flags [1], the device's index check; total,
+    the cell texels.  fill(img, colour) writes the image texels no cell texel lies on, points(t0, t1, x, d) the points and directions of the
+    cell texels [t0, t1), store(t0, t1, val, colour, img) their colours val [t1 - t0, >= 3] (colour: for a cell texel no face owns)."""
+    plan = None
+
+    def __init__(self, v, f, n, R):
+        self.v, self.f, self.n, self.R, self.V, self.F = v, f, n, R, v.shape[0], f.shape[0]
+
+    @staticmethod
+    def precheck(F, R):
+        """what bake_texture reports before it looks at its other arguments"""
+
+
+class _UniformLayout(_BakeLayout):
+    precheck = staticmethod(atlas_layout)
+
+    def __init__(self, v, f, n, R, what, gutter=None):
+        super().__init__(v, f, n, R)
+        self.total = (self.F + 1) // 2 * atlas_layout(self.F, R)[1] ** 2
+        self.uvs = torch.empty(self.F, 3, 2, dtype=torch.float32, device=v.device)
+        self.flags = torch.empty(1, dtype=torch.int32, device=v.device)
+        check(lib.cnerf_mesh_atlas_uvs(_p(f), self.V, self.F, R, _p(self.uvs), self.F, ptr(self.flags), stream()), "mesh_atlas_uvs")
+        _read(self.flags, what, _BAD_INDEX)                                     # the one host read
+
+    def fill(self, img, colour):
+        check(lib.cnerf_mesh_atlas_fill(self.F, self.R, colour, ptr(img), stream()), "mesh_atlas_fill")
+
+    def points(self, t0, t1, x, d):
+        check(lib.cnerf_mesh_atlas_points(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, t0, t1, ptr(self.flags), ptr(x), ptr(d),
+                                          t1 - t0, stream()), "mesh_atlas_points")
+
+    def store(self, t0, t1, val, colour, img):
+        check(lib.cnerf_mesh_atlas_store(self.F, self.R, t0, t1, ptr(val), val.stride(0), colour, ptr(self.flags), ptr(img), stream()),
+              "mesh_atlas_store")
 
 
 class AtlasPlan:
@@ -342,30 +382,51 @@ class AtlasPlan:
         self.__dict__.update(kw)
 
 
-def _atlas_plan(v, f, R, what):
-    """-> (AtlasPlan, flags [1], counts (uint32 * 8), workspace, its size): what bake_texture needs beyond the plan itself"""
-    V, F = v.shape[0], f.shape[0]
-    if R < 16 or R > 16384 or R & (R - 1):
-        raise ValueError(f"{what}: the 'area' layout needs a resolution that is a power of two in [16, 16384], got {R}")
-    no_fit = f"{what}: {F} faces leave cells of fewer than 4 x 4 texels on a {R} x {R} texture; {_NO_FIT}"
-    if (F + 1) // 2 > (R // 4) ** 2:
-        raise ValueError(no_fit)
-    dev = v.device
-    ws, nbytes = _workspace(dev, "mesh_atlas_sized", F)
-    hist = torch.empty(2049, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_atlas_sized_measure(_p(v), V, _p(f), F, ptr(ws), nbytes, ptr(hist), stream()), "mesh_atlas_sized_measure")
-    h = (C.c_uint32 * 2048)(*_read(hist, what, _BAD_INDEX)[:2048])             # the one host read
-    e, tiles, counts = C.c_uint32(0), C.c_uint32(0), (C.c_uint32 * 8)()
-    if lib.cnerf_mesh_atlas_sized_layout(h, R, C.byref(e), counts, C.byref(tiles)) != 0:
-        raise ValueError(no_fit)
-    flags = hist[2048:]
-    cells = torch.empty(F, 4, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_atlas_sized_plan(F, R, e.value, counts, ptr(ws), nbytes, ptr(flags), _p(cells), F, stream()), "mesh_atlas_sized_plan")
-    K = min(7, R.bit_length() - 3)
-    thr = math.inf if e.value >= 2040 else math.sqrt(struct.unpack("<f", struct.pack("<I", e.value << 20))[0])
-    plan = AtlasPlan(resolution=R, e=e.value, threshold=thr, counts=list(counts)[:K + 1], cells=cells, texels=16 * tiles.value,
-                     tiles=tiles.value)
-    return plan, flags, counts, ws, nbytes
+class _AreaLayout(_BakeLayout):
+    def __init__(self, v, f, n, R, what, gutter=None):
+        super().__init__(v, f, n, R)
+        V, F = self.V, self.F
+        if R < 16 or R > 16384 or R & (R - 1):
+            raise ValueError(f"{what}: the 'area' layout needs a resolution that is a power of two in [16, 16384], got {R}")
+        no_fit = f"{what}: {F} faces leave cells of fewer than 4 x 4 texels on a {R} x {R} texture; {_NO_FIT}"
+        if (F + 1) // 2 > (R // 4) ** 2:
+            raise ValueError(no_fit)
+        dev = v.device
+        self.ws, self.nbytes = ws, nbytes = _workspace(dev, "mesh_atlas_sized", F)
+        hist = torch.empty(2049, dtype=torch.int32, device=dev)
+        check(lib.cnerf_mesh_atlas_sized_measure(_p(v), V, _p(f), F, ptr(ws), nbytes, ptr(hist), stream()), "mesh_atlas_sized_measure")
+        h = (C.c_uint32 * 2048)(*_read(hist, what, _BAD_INDEX)[:2048])             # the one host read
+        e, tiles, self.counts = C.c_uint32(0), C.c_uint32(0), (C.c_uint32 * 8)()
+        if lib.cnerf_mesh_atlas_sized_layout(h, R, C.byref(e), self.counts, C.byref(tiles)) != 0:
+            raise ValueError(no_fit)
+        self.flags = hist[2048:]
+        cells = torch.empty(F, 4, dtype=torch.int32, device=dev)
+        check(lib.cnerf_mesh_atlas_sized_plan(F, R, e.value, self.counts, ptr(ws), nbytes, ptr(self.flags), _p(cells), F, stream()),
+              "mesh_atlas_sized_plan")
+        K = min(7, R.bit_length() - 3)
+        thr = math.inf if e.value >= 2040 else math.sqrt(struct.unpack("<f", struct.pack("<I", e.value << 20))[0])
+        self.plan = AtlasPlan(resolution=R, e=e.value, threshold=thr, counts=list(self.counts)[:K + 1], cells=cells, texels=16 * tiles.value,
+                              tiles=tiles.value)
+        self.total = self.plan.texels
+
+    @cached_property
+    def uvs(self):                                                              # computed when first asked for: atlas_plan does not ask
+        uvs = torch.empty(self.F, 3, 2, dtype=torch.float32, device=self.v.device)
+        check(lib.cnerf_mesh_atlas_sized_uvs(self.F, self.R, _p(self.plan.cells), ptr(self.flags), _p(uvs), self.F, stream()),
+              "mesh_atlas_sized_uvs")
+        return uvs
+
+    def fill(self, img, colour):
+        check(lib.cnerf_mesh_atlas_sized_fill(self.R, self.plan.tiles, colour, ptr(img), stream()), "mesh_atlas_sized_fill")
+
+    def points(self, t0, t1, x, d):
+        check(lib.cnerf_mesh_atlas_sized_points(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, self.counts, ptr(self.ws),
+                                                self.nbytes, t0, t1, ptr(self.flags), ptr(x), ptr(d), t1 - t0, stream()),
+              "mesh_atlas_sized_points")
+
+    def store(self, t0, t1, val, colour, img):
+        check(lib.cnerf_mesh_atlas_sized_store(self.F, self.R, self.counts, ptr(self.ws), self.nbytes, t0, t1, ptr(val), val.stride(0), colour,
+                                               ptr(self.flags), ptr(img), stream()), "mesh_atlas_sized_store")
 
 
 def atlas_plan(verts, faces, resolution):
@@ -374,7 +435,7 @@ def atlas_plan(verts, faces, resolution):
     with the face's size (the rules are in include/customnerf_hip.h, cnerf_mesh_atlas_sized_*).  CUDA tensors verts [V, 3], faces [F, 3]
     -> AtlasPlan.  ValueError on a face index outside [0, V), a resolution that is no power of two, or more faces than fit."""
     v, f, _ = _mesh_args(verts, faces, None, "atlas_plan")
-    return _atlas_plan(v, f, int(resolution), "atlas_plan")[0]
+    return _AreaLayout(v, f, None, int(resolution), "atlas_plan").plan
 
 
 class ChartPlan:
@@ -388,41 +449,56 @@ class ChartPlan:
         self.__dict__.update(kw)
 
 
-def _chart_plan(v, f, n, R, gutter, what):
-    """-> (ChartPlan, uvs [F, 3, 2], flags [1], workspace, its size): what bake_texture needs beyond the plan itself"""
-    V, F = v.shape[0], f.shape[0]
-    g = int(gutter)
-    if R < 16 or R > 16384:
-        raise ValueError(f"{what}: the 'projected' layout needs a resolution in [16, 16384], got {R}")
-    if g < 0 or g > 8:
-        raise ValueError(f"{what}: gutter must be in [0, 8], got {gutter}")
-    dev = v.device
-    ws, nbytes = _workspace(dev, "mesh_atlas_proj", V, F, R)
-    counts = torch.empty(2, dtype=torch.int32, device=dev)
-    ext = torch.empty(F, 4, dtype=torch.float32, device=dev)
-    fclass = torch.empty(F, dtype=torch.int32, device=dev)
-    fchart = torch.empty(F, dtype=torch.int32, device=dev)
-    check(lib.cnerf_mesh_atlas_proj_charts(_p(v), _p(n), V, _p(f), F, R, ptr(ws), nbytes, ptr(counts), _p(fclass), _p(fchart), F, _p(ext), F,
-                                           stream()), "mesh_atlas_proj_charts")
-    nc = _read(counts, what, _BAD_INDEX)[0]                                    # host read: C and the flags
-    e = np.ascontiguousarray(ext[:nc].cpu().numpy())                           # host read: exactly the C extents
-    rho = C.c_double(0.0)
-    rects_h = np.zeros((nc, 4), np.int32)
-    rc = lib.cnerf_mesh_atlas_proj_pack(e.ctypes.data_as(C.c_void_p), nc, R, g, C.byref(rho), rects_h.ctypes.data_as(C.c_void_p))
-    if rc == -1:                                                               # CNERF_EINVAL with arguments in range: not even rho = 0 fits
-        raise ValueError(f"{what}: {nc} charts with a gutter of {g} do not fit a {R} x {R} texture; {_NO_FIT}")
-    check(rc, "mesh_atlas_proj_pack")
-    rects = torch.from_numpy(rects_h).to(dev)
-    uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
-    owner = torch.empty(R, R, dtype=torch.int32, device=dev)
-    totals = torch.empty(2, dtype=torch.int64, device=dev)
-    flags = counts[1:]
-    check(lib.cnerf_mesh_atlas_proj_raster(_p(v), V, _p(f), F, R, g, rho.value, _p(rects), nc, ptr(ws), nbytes, ptr(flags), _p(uvs), F,
-                                           None, ptr(owner), ptr(totals), stream()), "mesh_atlas_proj_raster")
-    total, overlap = (int(t) for t in totals.cpu())                            # host read: the totals
-    plan = ChartPlan(resolution=R, gutter=g, charts=nc, density=rho.value, rects=rects, face_chart=fchart, face_class=fclass, owner=owner,
-                     texels=total, overlap_texels=overlap, coverage=total / float(R * R))
-    return plan, uvs, flags, ws, nbytes
+class _ProjectedLayout(_BakeLayout):
+    def __init__(self, v, f, n, R, what, gutter=None):
+        super().__init__(v, f, n, R)
+        V, F = self.V, self.F
+        g = int(gutter)
+        if R < 16 or R > 16384:
+            raise ValueError(f"{what}: the 'projected' layout needs a resolution in [16, 16384], got {R}")
+        if g < 0 or g > 8:
+            raise ValueError(f"{what}: gutter must be in [0, 8], got {gutter}")
+        dev = v.device
+        self.ws, self.nbytes = ws, nbytes = _workspace(dev, "mesh_atlas_proj", V, F, R)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        ext = torch.empty(F, 4, dtype=torch.float32, device=dev)
+        fclass = torch.empty(F, dtype=torch.int32, device=dev)
+        fchart = torch.empty(F, dtype=torch.int32, device=dev)
+        check(lib.cnerf_mesh_atlas_proj_charts(_p(v), _p(n), V, _p(f), F, R, ptr(ws), nbytes, ptr(counts), _p(fclass), _p(fchart), F, _p(ext), F,
+                                               stream()), "mesh_atlas_proj_charts")
+        nc = _read(counts, what, _BAD_INDEX)[0]                                    # host read: C and the flags
+        e = np.ascontiguousarray(ext[:nc].cpu().numpy())                           # host read: exactly the C extents
+        rho = C.c_double(0.0)
+        rects_h = np.zeros((nc, 4), np.int32)
+        rc = lib.cnerf_mesh_atlas_proj_pack(e.ctypes.data_as(C.c_void_p), nc, R, g, C.byref(rho), rects_h.ctypes.data_as(C.c_void_p))
+        if rc == -1:                                                               # CNERF_EINVAL with arguments in range: not even rho = 0 fits
+            raise ValueError(f"{what}: {nc} charts with a gutter of {g} do not fit a {R} x {R} texture; {_NO_FIT}")
+        check(rc, "mesh_atlas_proj_pack")
+        rects = torch.from_numpy(rects_h).to(dev)
+        self.uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
+        owner = torch.empty(R, R, dtype=torch.int32, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        self.flags = counts[1:]
+        check(lib.cnerf_mesh_atlas_proj_raster(_p(v), V, _p(f), F, R, g, rho.value, _p(rects), nc, ptr(ws), nbytes, ptr(self.flags),
+                                               _p(self.uvs), F, None, ptr(owner), ptr(totals), stream()), "mesh_atlas_proj_raster")
+        self.total, overlap = (int(t) for t in totals.cpu())                       # host read: the totals
+        self.plan = ChartPlan(resolution=R, gutter=g, charts=nc, density=rho.value, rects=rects, face_chart=fchart, face_class=fclass,
+                              owner=owner, texels=self.total, overlap_texels=overlap, coverage=self.total / float(R * R))
+
+    def fill(self, img, colour):
+        check(lib.cnerf_mesh_atlas_proj_fill(self.V, self.F, self.R, ptr(self.ws), self.nbytes, colour, ptr(self.flags), ptr(img), stream()),
+              "mesh_atlas_proj_fill")
+
+    def points(self, t0, t1, x, d):
+        check(lib.cnerf_mesh_atlas_proj_points(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, ptr(self.ws), self.nbytes, t0, t1,
+                                               ptr(self.flags), ptr(x), ptr(d), t1 - t0, stream()), "mesh_atlas_proj_points")
+
+    def store(self, t0, t1, val, colour, img):                                  # every listed texel has an owner: no colour for the others
+        check(lib.cnerf_mesh_atlas_proj_store(self.V, self.F, self.R, ptr(self.ws), self.nbytes, t0, t1, ptr(val), val.stride(0),
+                                              ptr(self.flags), ptr(img), stream()), "mesh_atlas_proj_store")
+
+
+_LAYOUTS = dict(zip(TEXTURE_LAYOUTS, (_UniformLayout, _AreaLayout, _ProjectedLayout)))
 
 
 def chart_plan(verts, faces, resolution, normals=None, gutter=2):
@@ -432,7 +508,7 @@ def chart_plan(verts, faces, resolution, normals=None, gutter=2):
     each (the rules are in include/customnerf_hip.h, cnerf_mesh_atlas_proj_*).  CUDA tensors verts [V, 3], faces [F, 3] -> ChartPlan.
     ValueError on a face index outside [0, V), a resolution or gutter out of range, or more charts than fit."""
     v, f, n = _mesh_args(verts, faces, normals, "chart_plan")
-    return _chart_plan(v, f, n, int(resolution), gutter, "chart_plan")[0]
+    return _ProjectedLayout(v, f, n, int(resolution), "chart_plan", gutter).plan
 
 
 def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21, fill=(0, 0, 0), layout='uniform', source=None, reach=None,
@@ -464,64 +540,37 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
         reach = 0.02 * source.diagonal
         if not reach > 0.0:
             raise ValueError("bake_texture: the source has no valid face to take a default reach from")
-    V, F = v.shape[0], f.shape[0]
-    R = int(resolution)
-    if layout not in ('uniform', 'area', 'projected'):
+    F, R = f.shape[0], int(resolution)
+    if layout not in TEXTURE_LAYOUTS:
         raise ValueError(f"bake_texture: layout must be 'uniform', 'area' or 'projected', got {layout!r}")
-    area, proj = layout == 'area', layout == 'projected'
-    if gutter is not None and not proj:
+    if gutter is not None and layout != 'projected':
         raise ValueError(f"bake_texture: gutter belongs to layout='projected', got layout={layout!r}")
-    if not area and not proj:
-        _, s = atlas_layout(F, R)
+    _LAYOUTS[layout].precheck(F, R)                                              # before fill and chunk: of two wrong arguments the uniform
+                                                                                # layout has always reported the resolution first
     fl = tuple(int(c) for c in fill)
     if len(fl) != 3 or min(fl) < 0 or max(fl) > 255:
         raise ValueError(f"bake_texture: fill must be 3 values in [0, 255], got {fill}")
     chunk = int(chunk)
     if chunk < 1:
         raise ValueError(f"bake_texture: chunk must be >= 1, got {chunk}")
-    fill_c = (C.c_uint8 * 3)(*fl)
     dev = v.device
-    if proj:
-        plan, uvs, flags, ws, nbytes = _chart_plan(v, f, n, R, 2 if gutter is None else gutter, "bake_texture")
-    else:
-        uvs = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
     tex = torch.empty(R, R, 3, dtype=torch.uint8, device=dev)
-    images = [(tex, fill_c)]                                                   # every image goes through the same fill and store
+    images = [(tex, (C.c_uint8 * 3)(*fl))]                                      # every image goes through the same fill and store
     if normal_map:
         images.append((torch.empty(R, R, 3, dtype=torch.uint8, device=dev), (C.c_uint8 * 3)(128, 128, 128)))
     kinds = torch.zeros(4, dtype=torch.int64, device=dev)
-    if proj:
-        for img, fc in images:
-            check(lib.cnerf_mesh_atlas_proj_fill(V, F, R, ptr(ws), nbytes, fc, ptr(flags), ptr(img), stream()), "mesh_atlas_proj_fill")
-        total = plan.texels
-    elif area:
-        plan, flags, counts, ws, nbytes = _atlas_plan(v, f, R, "bake_texture")
-        check(lib.cnerf_mesh_atlas_sized_uvs(F, R, _p(plan.cells), ptr(flags), _p(uvs), F, stream()), "mesh_atlas_sized_uvs")
-        for img, fc in images:
-            check(lib.cnerf_mesh_atlas_sized_fill(R, plan.tiles, fc, ptr(img), stream()), "mesh_atlas_sized_fill")
-        total = plan.texels
-    else:
-        flags = torch.empty(1, dtype=torch.int32, device=dev)
-        check(lib.cnerf_mesh_atlas_uvs(_p(f), V, F, R, _p(uvs), F, ptr(flags), stream()), "mesh_atlas_uvs")
-        _read(flags, "bake_texture", _BAD_INDEX)
-        for img, fc in images:
-            check(lib.cnerf_mesh_atlas_fill(F, R, fc, ptr(img), stream()), "mesh_atlas_fill")
-        total = (F + 1) // 2 * s * s
+    # the layout last: it ends in a host read, and what is allocated after that read keeps the device waiting for the fill
+    lay = _LAYOUTS[layout](v, f, n, R, "bake_texture", 2 if gutter is None else gutter)
+    uvs, total = lay.uvs, lay.total
+    for img, fc in images:
+        lay.fill(img, fc)
     m = max(1, min(chunk, total))
     x = torch.empty(m, 3, dtype=torch.float32, device=dev)
     d = torch.empty(m, 3, dtype=torch.float32, device=dev)
     for t0 in range(0, total, m):
         t1 = min(t0 + m, total)
         k = t1 - t0
-        if proj:
-            check(lib.cnerf_mesh_atlas_proj_points(ptr(v), _p(n), V, ptr(f), F, R, ptr(ws), nbytes, t0, t1, ptr(flags), ptr(x), ptr(d), k,
-                                                   stream()), "mesh_atlas_proj_points")
-        elif area:
-            check(lib.cnerf_mesh_atlas_sized_points(ptr(v), _p(n), V, ptr(f), F, R, counts, ptr(ws), nbytes, t0, t1, ptr(flags), ptr(x), ptr(d),
-                                                    k, stream()), "mesh_atlas_sized_points")
-        else:
-            check(lib.cnerf_mesh_atlas_points(ptr(v), _p(n), V, ptr(f), F, R, t0, t1, ptr(flags), ptr(x), ptr(d), k,
-                                              stream()), "mesh_atlas_points")
+        lay.points(t0, t1, x, d)
         if source is not None:
             pr = project_to_surface(source, x[:k], -d[:k], reach)
             look = -pr['normal']
@@ -537,15 +586,7 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
         if rgb.stride(1) != 1 or rgb.device != dev:
             rgb = rgb.to(dev).contiguous()
         for (img, fc), val in zip(images, (rgb, look * -0.5 + 0.5 if normal_map else None)):
-            if proj:
-                check(lib.cnerf_mesh_atlas_proj_store(V, F, R, ptr(ws), nbytes, t0, t1, ptr(val), val.stride(0), ptr(flags), ptr(img),
-                                                      stream()), "mesh_atlas_proj_store")
-            elif area:
-                check(lib.cnerf_mesh_atlas_sized_store(F, R, counts, ptr(ws), nbytes, t0, t1, ptr(val), val.stride(0), fc, ptr(flags), ptr(img),
-                                                       stream()), "mesh_atlas_sized_store")
-            else:
-                check(lib.cnerf_mesh_atlas_store(F, R, t0, t1, ptr(val), val.stride(0), fc, ptr(flags), ptr(img), stream()),
-                      "mesh_atlas_store")
+            lay.store(t0, t1, val, fc, img)
     if source is None and not normal_map:
         return uvs, tex
     return uvs, tex, {'normal_map': images[1][0] if normal_map else None, 'kinds': kinds}

@@ -540,7 +540,7 @@ class NeRFRenderer(nn.Module):
         tex_r = int(texture)
         if tex_r < 0:
             raise ValueError(f"extract_mesh: texture must be 0 (off) or a texture resolution, got {texture}")
-        if texture_layout not in ('uniform', 'area', 'projected'):
+        if texture_layout not in _mesh.TEXTURE_LAYOUTS:
             raise ValueError(f"extract_mesh: texture_layout must be 'uniform', 'area' or 'projected', got {texture_layout!r}")
         n_smooth = int(smooth)
         if n_smooth < 0:

@@ -228,18 +228,22 @@ def shell_colour(x, d):
     return ((x.norm(dim=1, keepdim=True) - 0.9) / 0.2).clamp(0, 1).expand(-1, 3)
 
 
-@pytest.mark.parametrize("layout", ["uniform", "area"])
+@pytest.mark.parametrize("layout", ["uniform", "area", "projected"])
 def test_bake_from_source(layout):
     """bake_texture of the 80-face icosphere with the 1280-face one as its source: every owned texel's colour is that of a point of the
     source's surface, radius in [r_in, 1], within 1 of the store's rounding; the bake without a source is not (its texels lie down to
-    radius 0.934).  The normal map is the restatement's normals through the store's rounding, bit for bit; the kinds are its counts"""
+    radius 0.934).  The normal map is the restatement's normals through the store's rounding, bit for bit; the kinds are its counts.
+    Where the chunks fall changes no byte.  The projected layout is baked without a gutter: grown texels extrapolate beyond the reach"""
     from customnerf_amd import mesh
     s = L.sphere()
     lv, lf = cuda(s['lv']), cuda(s['lf'])
     src = mesh.bake_source(cuda(s['sv']), cuda(s['sf']), cuda(s['sv']))
     R = L.R_SPHERE
-    uvs, tex, extra = mesh.bake_texture(lv, lf, R, shell_colour, normals=lv, source=src, reach=0.25, normal_map=True, layout=layout, chunk=1000)
-    plain = mesh.bake_texture(lv, lf, R, shell_colour, normals=lv, layout=layout)
+    kw = dict(normals=lv, layout=layout, **({'gutter': 0} if layout == 'projected' else {}))
+    uvs, tex, extra = mesh.bake_texture(lv, lf, R, shell_colour, source=src, reach=0.25, normal_map=True, chunk=1000, **kw)
+    _, tex1, extra1 = mesh.bake_texture(lv, lf, R, shell_colour, source=src, reach=0.25, normal_map=True, **kw)
+    assert torch.equal(tex1, tex) and torch.equal(extra1['normal_map'], extra['normal_map']) and torch.equal(extra1['kinds'], extra['kinds'])
+    plain = mesh.bake_texture(lv, lf, R, shell_colour, **kw)
     assert len(plain) == 2 and torch.equal(plain[0], uvs)
     lo, hi = round(255 * (s['inradius'] - 0.9) / 0.2), 128
     tex, nmap, old = tex.cpu().numpy(), extra['normal_map'].cpu().numpy(), plain[1].cpu().numpy()
@@ -260,7 +264,7 @@ def test_bake_from_source(layout):
     assert old[owned].min() < lo - 1                                              # what the feature changes
     assert (tex[~owned] == 0).all() and (nmap[~owned] == 128).all()
     # without a source the normal map holds the mesh's own interpolated normals
-    _, tex2, extra2 = mesh.bake_texture(lv, lf, R, shell_colour, normals=lv, normal_map=True, layout=layout)
+    _, tex2, extra2 = mesh.bake_texture(lv, lf, R, shell_colour, normal_map=True, **kw)
     assert np.array_equal(tex2.cpu().numpy(), old) and extra2['kinds'].cpu().tolist() == [0, 0, 0, 0]
     if layout == 'uniform':
         own_map = np.full((R, R, 3), 128, np.uint8)
