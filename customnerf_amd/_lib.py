@@ -107,6 +107,7 @@ SIGNATURES = {
     "cnerf_mesh_atlas_layout": [u32, u32, vp, vp],
     "cnerf_mesh_atlas_uvs": [vp, u32, u32, u32, vp, u32, vp, vp],
     "cnerf_mesh_atlas_points": [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, vp, u32, vp],
+    "cnerf_mesh_atlas_tspace": [vp, vp, u32, vp, u32, u32, vp, u32, u32, vp, u32, vp, vp, u32, vp],
     "cnerf_mesh_atlas_store": [u32, u32, u32, u32, vp, u32, vp, vp, vp, vp],
     "cnerf_mesh_atlas_fill": [u32, u32, vp, vp, vp],
     "cnerf_mesh_atlas_sized_workspace_bytes": [u32, vp],
@@ -115,6 +116,7 @@ SIGNATURES = {
     "cnerf_mesh_atlas_sized_plan": [u32, u32, u32, vp, vp, u64, vp, vp, u32, vp],
     "cnerf_mesh_atlas_sized_uvs": [u32, u32, vp, vp, vp, u32, vp],
     "cnerf_mesh_atlas_sized_points": [vp, vp, u32, vp, u32, u32, vp, vp, u64, u32, u32, vp, vp, vp, u32, vp],
+    "cnerf_mesh_atlas_sized_tspace": [vp, vp, u32, vp, u32, u32, vp, vp, u64, vp, u32, u32, vp, u32, vp, vp, u32, vp],
     "cnerf_mesh_atlas_sized_store": [u32, u32, vp, vp, u64, u32, u32, vp, u32, vp, vp, vp, vp],
     "cnerf_mesh_atlas_sized_fill": [u32, u32, vp, vp, vp],
     "cnerf_mesh_atlas_proj_workspace_bytes": [u32, u32, u32, vp],
@@ -122,8 +124,13 @@ SIGNATURES = {
     "cnerf_mesh_atlas_proj_pack": [vp, u32, u32, u32, vp, vp],
     "cnerf_mesh_atlas_proj_raster": [vp, u32, vp, u32, u32, u32, C.c_double, vp, u32, vp, u64, vp, vp, u32, vp, vp, vp, vp],
     "cnerf_mesh_atlas_proj_points": [vp, vp, u32, vp, u32, u32, vp, u64, u32, u32, vp, vp, vp, u32, vp],
+    "cnerf_mesh_atlas_proj_tspace": [vp, vp, u32, vp, u32, u32, vp, u64, vp, u32, u32, vp, u32, vp, vp, u32, vp],
     "cnerf_mesh_atlas_proj_store": [u32, u32, u32, vp, u64, u32, u32, vp, u32, vp, vp, vp],
     "cnerf_mesh_atlas_proj_fill": [u32, u32, u32, vp, u64, vp, vp, vp, vp],
+    "cnerf_mesh_tangent_workspace_bytes": [u32, u32, vp],
+    "cnerf_mesh_tangent_weld": [vp, vp, u32, u32, vp, u64, vp, vp, u32, vp, u32, vp],
+    "cnerf_mesh_tangent_frames": [vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp],
+    "cnerf_mesh_tangent_vertices": [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp],
     "cnerf_mesh_raster_workspace_bytes": [u32, u32, u32, u32, vp],
     "cnerf_mesh_raster_visibility": [vp, u32, vp, u32, vp, f32, f32, f32, f32, u32, u32, i32, f32, i32, vp, u64, vp, vp, vp, vp, vp],
     "cnerf_mesh_raster_shade": [vp, vp, vp, u32, u32, vp, u32, u32, i32, vp, vp, vp, u32, vp, vp, f32, f32, vp, vp, vp, vp],

@@ -649,6 +649,14 @@ int cnerf_mesh_atlas_proj_points(const float *verts, const float *normals, uint3
     return bake_launch_points(loc, (uint64_t)R * R, verts, normals, V, faces, t0, t1, flags, x, d, max_points, stream);
 }
 
+int cnerf_mesh_atlas_proj_tspace(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, void *ws,
+                                 uint64_t ws_bytes, const float *tangents, uint32_t t0, uint32_t t1, const float *m, uint32_t m_stride,
+                                 const uint32_t *flags, float *rgb, uint32_t max_points, void *stream) {
+    PjTexels loc;
+    if (const int rc = pj_locate(V, F, R, ws, ws_bytes, loc)) return rc;
+    return bake_launch_tspace(loc, (uint64_t)R * R, verts, normals, V, faces, tangents, t0, t1, m, m_stride, flags, rgb, max_points, stream);
+}
+
 int cnerf_mesh_atlas_proj_store(uint32_t V, uint32_t F, uint32_t R, void *ws, uint64_t ws_bytes, uint32_t t0, uint32_t t1, const float *rgb,
                                 uint32_t rgb_stride, const uint32_t *flags, uint8_t *image, void *stream) {
     PjTexels loc;

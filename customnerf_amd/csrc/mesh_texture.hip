@@ -411,6 +411,16 @@ int cnerf_mesh_atlas_points(const float *verts, const float *normals, uint32_t V
     return bake_launch_points(g, (uint64_t)g.P * g.s * g.s, verts, normals, V, faces, t0, t1, flags, x, d, max_points, stream);
 }
 
+int cnerf_mesh_atlas_tspace(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R,
+                            const float *tangents, uint32_t t0, uint32_t t1, const float *m, uint32_t m_stride, const uint32_t *flags, float *rgb,
+                            uint32_t max_points, void *stream) {
+    AtlasGeom g;
+    if (const int rc = at_layout(F, R, &g)) return rc;
+    if (V >= (1u << 31)) return CNERF_EINVAL;
+    return bake_launch_tspace(g, (uint64_t)g.P * g.s * g.s, verts, normals, V, faces, tangents, t0, t1, m, m_stride, flags, rgb, max_points,
+                              stream);
+}
+
 int cnerf_mesh_atlas_store(uint32_t F, uint32_t R, uint32_t t0, uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host,
                            const uint32_t *flags, uint8_t *image, void *stream) {
     AtlasGeom g;
@@ -506,6 +516,16 @@ int cnerf_mesh_atlas_sized_points(const float *verts, const float *normals, uint
     if (const int rc = sz_locate(F, R, counts_host, ws, ws_bytes, loc, total)) return rc;
     if (V >= (1u << 31)) return CNERF_EINVAL;
     return bake_launch_points(loc, total, verts, normals, V, faces, t0, t1, flags, x, d, max_points, stream);
+}
+
+int cnerf_mesh_atlas_sized_tspace(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R,
+                                  const uint32_t *counts_host, void *ws, uint64_t ws_bytes, const float *tangents, uint32_t t0, uint32_t t1,
+                                  const float *m, uint32_t m_stride, const uint32_t *flags, float *rgb, uint32_t max_points, void *stream) {
+    SizedTexels loc;
+    uint64_t total;
+    if (const int rc = sz_locate(F, R, counts_host, ws, ws_bytes, loc, total)) return rc;
+    if (V >= (1u << 31)) return CNERF_EINVAL;
+    return bake_launch_tspace(loc, total, verts, normals, V, faces, tangents, t0, t1, m, m_stride, flags, rgb, max_points, stream);
 }
 
 int cnerf_mesh_atlas_sized_store(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0,

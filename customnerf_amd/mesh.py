@@ -4,8 +4,9 @@ face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex norm
 uniform or with cells sized by the faces' edges (csrc/mesh_texture.hip), or into an atlas of axis-projected charts (csrc/mesh_charts.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
 shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them,
 watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them, the projection of a low-polygon mesh's
-texels onto the full-resolution surface for baking colour and normal maps (csrc/mesh_bvh.hip), a binary PLY writer and an OBJ + MTL + PNG
-writer.
+texels onto the full-resolution surface for baking colour and normal maps (csrc/mesh_bvh.hip), welded vertices with tangent frames and
+tangent-space normal maps through the same bake (csrc/mesh_tangent.hip, k_bake_tspace of csrc/mesh_bake.h), a binary PLY writer, an
+OBJ + MTL + PNG writer and a glTF 2.0 binary (.glb) writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -337,7 +338,9 @@ class _BakeLayout:
     """A texture atlas layout as bake_texture uses it, built from the mesh (v, f, n of _mesh_args), the resolution R and `what`, the name its
     errors are raised under.  plan: the layout's public plan, if it has one; uvs [F, 3, 2]; flags [1], the device's index check; total,
     the cell texels.  fill(img, colour) writes the image texels no cell texel lies on, points(t0, t1, x, d) the points and directions of the
-    cell texels [t0, t1), store(t0, t1, val, colour, img) their colours val [t1 - t0, >= 3] (colour: for a cell texel no face owns)."""
+    cell texels [t0, t1), store(t0, t1, val, colour, img) their colours val [t1 - t0, >= 3] (colour: for a cell texel no face owns),
+    tspace(t0, t1, tangents, m, out) the tangent-space codes out [t1 - t0, 3] of the object-space normals m [t1 - t0, >= 3] (None: the mesh's
+    own normal at the texel) in the frames of tangents [F, 3, 4], for store."""
     plan = None
 
     def __init__(self, v, f, n, R):
@@ -365,6 +368,10 @@ class _UniformLayout(_BakeLayout):
     def points(self, t0, t1, x, d):
         check(lib.cnerf_mesh_atlas_points(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, t0, t1, ptr(self.flags), ptr(x), ptr(d),
                                           t1 - t0, stream()), "mesh_atlas_points")
+
+    def tspace(self, t0, t1, tangents, m, out):
+        check(lib.cnerf_mesh_atlas_tspace(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, ptr(tangents), t0, t1, _p(m),
+                                          m.stride(0) if m is not None else 0, ptr(self.flags), ptr(out), t1 - t0, stream()), "mesh_atlas_tspace")
 
     def store(self, t0, t1, val, colour, img):
         check(lib.cnerf_mesh_atlas_store(self.F, self.R, t0, t1, ptr(val), val.stride(0), colour, ptr(self.flags), ptr(img), stream()),
@@ -423,6 +430,11 @@ class _AreaLayout(_BakeLayout):
         check(lib.cnerf_mesh_atlas_sized_points(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, self.counts, ptr(self.ws),
                                                 self.nbytes, t0, t1, ptr(self.flags), ptr(x), ptr(d), t1 - t0, stream()),
               "mesh_atlas_sized_points")
+
+    def tspace(self, t0, t1, tangents, m, out):
+        check(lib.cnerf_mesh_atlas_sized_tspace(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, self.counts, ptr(self.ws),
+                                                self.nbytes, ptr(tangents), t0, t1, _p(m), m.stride(0) if m is not None else 0,
+                                                ptr(self.flags), ptr(out), t1 - t0, stream()), "mesh_atlas_sized_tspace")
 
     def store(self, t0, t1, val, colour, img):
         check(lib.cnerf_mesh_atlas_sized_store(self.F, self.R, self.counts, ptr(self.ws), self.nbytes, t0, t1, ptr(val), val.stride(0), colour,
@@ -493,6 +505,11 @@ class _ProjectedLayout(_BakeLayout):
         check(lib.cnerf_mesh_atlas_proj_points(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, ptr(self.ws), self.nbytes, t0, t1,
                                                ptr(self.flags), ptr(x), ptr(d), t1 - t0, stream()), "mesh_atlas_proj_points")
 
+    def tspace(self, t0, t1, tangents, m, out):
+        check(lib.cnerf_mesh_atlas_proj_tspace(ptr(self.v), _p(self.n), self.V, ptr(self.f), self.F, self.R, ptr(self.ws), self.nbytes,
+                                               ptr(tangents), t0, t1, _p(m), m.stride(0) if m is not None else 0, ptr(self.flags), ptr(out),
+                                               t1 - t0, stream()), "mesh_atlas_proj_tspace")
+
     def store(self, t0, t1, val, colour, img):                                  # every listed texel has an owner: no colour for the others
         check(lib.cnerf_mesh_atlas_proj_store(self.V, self.F, self.R, ptr(self.ws), self.nbytes, t0, t1, ptr(val), val.stride(0),
                                               ptr(self.flags), ptr(img), stream()), "mesh_atlas_proj_store")
@@ -528,9 +545,13 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
     source's normal there: color_fn(point, -normal).  A texel that finds no surface within reach keeps its own point and normal.
     normal_map=True also writes an object-space normal map [R, R, 3] uint8 with the same layout and store: 0.5 + 0.5 n of the source's
     normal at the projected point, or without a source of the mesh's own interpolated normal (-d); texels no face owns get
-    (128, 128, 128).  With source or normal_map the result is (uvs, texture, extra), extra = {'normal_map': the map or None, 'kinds':
-    [4] int64 on the device, the cell texels handed to color_fn by the kind of their projection (project_to_surface; zeros without a
-    source)}; with neither it is (uvs, texture) as above."""
+    (128, 128, 128).  normal_map='tangent' writes a tangent-space map instead, the kind glTF takes: the same normal in the frame (t, B, N)
+    of its texel, N = -d, t and B from corner_tangents(verts, faces, uvs, normals) (the rule is in include/customnerf_hip.h,
+    cnerf_mesh_tangent_*: red along +u, green along +v with v up); without a source every owned texel is (128, 128, 255), which is also
+    the colour of the texels no face owns.  With source or normal_map the result is (uvs, texture, extra), extra = {'normal_map': the map or
+    None, 'kinds': [4] int64 on the device, the cell texels handed to color_fn by the kind of their projection (project_to_surface; zeros
+    without a source)} and, with a normal map, 'normal_space': 'object' or 'tangent' and for the latter 'tangents' [F, 3, 4] float32; with
+    neither it is (uvs, texture) as above."""
     v, f, n = _mesh_args(verts, faces, normals, "bake_texture")
     if source is not None and not isinstance(source, BakeSource):
         raise ValueError("bake_texture: source must come from bake_source")
@@ -541,6 +562,9 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
         if not reach > 0.0:
             raise ValueError("bake_texture: the source has no valid face to take a default reach from")
     F, R = f.shape[0], int(resolution)
+    if isinstance(normal_map, str) and normal_map != 'tangent':
+        raise ValueError(f"bake_texture: normal_map must be False, True (object space) or 'tangent', got {normal_map!r}")
+    tangent = isinstance(normal_map, str)
     if layout not in TEXTURE_LAYOUTS:
         raise ValueError(f"bake_texture: layout must be 'uniform', 'area' or 'projected', got {layout!r}")
     if gutter is not None and layout != 'projected':
@@ -557,7 +581,7 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
     tex = torch.empty(R, R, 3, dtype=torch.uint8, device=dev)
     images = [(tex, (C.c_uint8 * 3)(*fl))]                                      # every image goes through the same fill and store
     if normal_map:
-        images.append((torch.empty(R, R, 3, dtype=torch.uint8, device=dev), (C.c_uint8 * 3)(128, 128, 128)))
+        images.append((torch.empty(R, R, 3, dtype=torch.uint8, device=dev), (C.c_uint8 * 3)(128, 128, 255 if tangent else 128)))
     kinds = torch.zeros(4, dtype=torch.int64, device=dev)
     # the layout last: it ends in a host read, and what is allocated after that read keeps the device waiting for the fill
     lay = _LAYOUTS[layout](v, f, n, R, "bake_texture", 2 if gutter is None else gutter)
@@ -567,6 +591,10 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
     m = max(1, min(chunk, total))
     x = torch.empty(m, 3, dtype=torch.float32, device=dev)
     d = torch.empty(m, 3, dtype=torch.float32, device=dev)
+    tangents = code = None
+    if tangent:
+        tangents = _tangents(v, f, uvs, n, "bake_texture")[0]
+        code = torch.empty(m, 3, dtype=torch.float32, device=dev)
     for t0 in range(0, total, m):
         t1 = min(t0 + m, total)
         k = t1 - t0
@@ -585,11 +613,102 @@ def bake_texture(verts, faces, resolution, color_fn, normals=None, chunk=2 ** 21
         rgb = rgb.detach()[:, :3].float()
         if rgb.stride(1) != 1 or rgb.device != dev:
             rgb = rgb.to(dev).contiguous()
-        for (img, fc), val in zip(images, (rgb, look * -0.5 + 0.5 if normal_map else None)):
+        if tangent:                                                             # without a source the encoded normal is the texel's own N
+            lay.tspace(t0, t1, tangents, -look if source is not None else None, code)
+        for (img, fc), val in zip(images, (rgb, code if tangent else look * -0.5 + 0.5 if normal_map else None)):
             lay.store(t0, t1, val, fc, img)
     if source is None and not normal_map:
         return uvs, tex
-    return uvs, tex, {'normal_map': images[1][0] if normal_map else None, 'kinds': kinds}
+    extra = {'normal_map': images[1][0] if normal_map else None, 'kinds': kinds}
+    if normal_map:
+        extra['normal_space'] = 'tangent' if tangent else 'object'
+    if tangent:
+        extra['tangents'] = tangents
+    return uvs, tex, extra
+
+
+def tangent_workspace_bytes(V, F):
+    return _bytes("mesh_tangent", int(V), int(F))
+
+
+def _uv_args(f, uvs, what):
+    require_cuda(uvs)
+    if tuple(uvs.shape) != (f.shape[0], 3, 2):
+        raise ValueError(f"{what}: uvs must be [F, 3, 2] for F = {f.shape[0]} faces, got {tuple(uvs.shape)}")
+    return uvs.detach().contiguous().float()
+
+
+def _weld(f, uv, V, what):
+    """the weld pass -> (corner_vertex [F, 3], vertex_corner [W], the workspace and its size); the one host read: W and the flags"""
+    F, dev = f.shape[0], f.device
+    ws, nbytes = _workspace(dev, "mesh_tangent", V, F)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    cv = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    vc = torch.empty(3 * F, dtype=torch.int32, device=dev)
+    check(lib.cnerf_mesh_tangent_weld(_p(f), _p(uv), V, F, ptr(ws), nbytes, ptr(counts), _p(cv), F, _p(vc), 3 * F, stream()),
+          "mesh_tangent_weld")
+    W, _ = _read(counts, what, _BAD_INDEX)
+    return cv, vc[:W], ws, nbytes
+
+
+def _tangents(v, f, uv, n, what):
+    """weld, then frames -> (tangents [F, 3, 4], corner_vertex, vertex_corner, the workspace and its size)"""
+    V, F = v.shape[0], f.shape[0]
+    cv, vc, ws, nbytes = _weld(f, uv, V, what)
+    tan = torch.empty(F, 3, 4, dtype=torch.float32, device=v.device)
+    check(lib.cnerf_mesh_tangent_frames(_p(v), _p(f), _p(uv), _p(n), V, F, ptr(ws), nbytes, _p(tan), F, stream()), "mesh_tangent_frames")
+    return tan, cv, vc, ws, nbytes
+
+
+def weld_corners(faces, uvs, V=None):
+    """Weld the face corners of a UV-mapped mesh into vertices, on the device (csrc/mesh_tangent.hip; the rules are in
+    include/customnerf_hip.h, cnerf_mesh_tangent_*): corners with the same vertex index and the same UV (bit for bit) are one output vertex;
+    a vertex on a seam becomes one per chart.  Output vertices are numbered by ascending vertex index, within a vertex by their smallest
+    corner (corner c = 3 f + k).  CUDA tensors faces [F, 3] (int), uvs [F, 3, 2] float32; V: the number of vertices the faces index
+    (default: the largest index + 1).  -> (corner_vertex [F, 3] int32, vertex_corner [W] int32: the smallest corner of every output
+    vertex).  A face index outside [0, V) raises ValueError."""
+    require_cuda(faces)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"weld_corners: faces must be [F, 3], got {tuple(faces.shape)}")
+    f = faces.detach().contiguous().to(torch.int32)
+    uv = _uv_args(f, uvs, "weld_corners")
+    if V is None:
+        V = int(f.max()) + 1 if f.numel() else 0
+    V = int(V)
+    if V < 0:
+        raise ValueError("weld_corners: a face index lies outside [0, V)")
+    return _weld(f, uv, V, "weld_corners")[:2]
+
+
+def corner_tangents(verts, faces, uvs, normals=None):
+    """Tangent frames of a UV-mapped mesh, one per face corner, on the device (csrc/mesh_tangent.hip; the rules are in
+    include/customnerf_hip.h): the corners weld_corners joins share one frame, the area-weighted sum of their faces' unit tangents
+    (the direction of +u on the surface), made orthogonal to the vertex normal (without `normals`: to the area-weighted face normal of
+    the group) and normalised, computed in float64 in a fixed order; w = +1 or -1 says whether the bitangent w (n x t) follows +v (v up).
+    Faces without UV area or without area give nothing; a vertex left without a tangent takes the axis most orthogonal to its normal.
+    CUDA tensors verts [V, 3], faces [F, 3] (int), uvs [F, 3, 2], normals [V, 3] or None -> tangents [F, 3, 4] float32 (x, y, z, w).
+    A face index outside [0, V) raises ValueError."""
+    v, f, n = _mesh_args(verts, faces, normals, "corner_tangents")
+    return _tangents(v, f, _uv_args(f, uvs, "corner_tangents"), n, "corner_tangents")[0]
+
+
+def gltf_vertices(verts, faces, uvs, normals=None):
+    """The vertex and index buffers of a glTF primitive for a UV-mapped mesh, on the device: weld_corners, corner_tangents, then a
+    gather.  -> dict: positions [W, 3], normals [W, 3] (the vertex normals as given, or without them the unit normal each frame was built
+    on), uvs [W, 2] stored as (u, 1 - v) (glTF's v points down), tangents [W, 4] float32 and indices [F, 3] uint32 (= corner_vertex),
+    for write_glb.  One host read (W and the index check)."""
+    v, f, n = _mesh_args(verts, faces, normals, "gltf_vertices")
+    uv = _uv_args(f, uvs, "gltf_vertices")
+    V, F, dev = v.shape[0], f.shape[0], v.device
+    tan, cv, vc, ws, nbytes = _tangents(v, f, uv, n, "gltf_vertices")
+    W = vc.shape[0]
+    out = {'positions': torch.empty(W, 3, dtype=torch.float32, device=dev), 'normals': torch.empty(W, 3, dtype=torch.float32, device=dev),
+           'uvs': torch.empty(W, 2, dtype=torch.float32, device=dev), 'tangents': torch.empty(W, 4, dtype=torch.float32, device=dev)}
+    idx = torch.empty(F, 3, dtype=torch.int32, device=dev)                      # the kernel writes uint32 < 2^31: the same bits
+    check(lib.cnerf_mesh_tangent_vertices(_p(v), _p(f), _p(uv), _p(n), _p(tan), _p(cv), _p(vc), V, F, W, ptr(ws), nbytes, _p(out['positions']),
+                                          _p(out['normals']), _p(out['uvs']), _p(out['tangents']), _p(idx), stream()), "mesh_tangent_vertices")
+    out['indices'] = idx.view(torch.uint32) if hasattr(torch, 'uint32') else idx
+    return out
 
 
 _CONVENTIONS = {'nerfstudio': 0, 'ngp': 1}
@@ -1074,11 +1193,12 @@ def distance(verts_a, faces_a, verts_b, faces_b, spacing=None, symmetric=True, i
     return out
 
 
-def write_png(path, image):
-    """8-bit RGB PNG (no interlace, filter 0 on every row), standard library only.  image: [H, W, 3] uint8 tensor (any device) or array."""
+def png_bytes(image, what="png_bytes"):
+    """The bytes of an 8-bit RGB PNG (no interlace, filter 0 on every row), standard library only.  image: [H, W, 3] uint8 tensor (any
+    device) or array."""
     a = _host(image, np.uint8)
     if a.ndim != 3 or a.shape[2] != 3:
-        raise ValueError(f"write_png: image must be [H, W, 3] uint8, got {a.shape}")
+        raise ValueError(f"{what}: image must be [H, W, 3] uint8, got {a.shape}")
     H, W = a.shape[:2]
     raw = np.zeros((H, 1 + 3 * W), dtype=np.uint8)                              # a filter-type byte (0) in front of every row
     raw[:, 1:] = a.reshape(H, 3 * W)
@@ -1086,11 +1206,107 @@ def write_png(path, image):
     def chunk(tag, data):
         return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
 
+    return b"".join((b"\x89PNG\r\n\x1a\n", chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)),
+                     chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)), chunk(b"IEND", b"")))
+
+
+def write_png(path, image):
+    """8-bit RGB PNG (png_bytes) written to `path`.  image: [H, W, 3] uint8 tensor (any device) or array."""
+    data = png_bytes(image, "write_png")
     with open(path, "wb") as fh:
-        fh.write(b"\x89PNG\r\n\x1a\n")
-        fh.write(chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)))
-        fh.write(chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)))
-        fh.write(chunk(b"IEND", b""))
+        fh.write(data)
+
+
+def write_glb(path, positions, indices, normals=None, uvs=None, tangents=None, colors=None, texture=None, normal_map=None, unlit=None):
+    """glTF 2.0 binary (.glb): one mesh with one indexed triangle primitive and one material, everything in one file; json, struct and
+    zlib only.  positions [W, 3] float32, indices [F, 3] (any int type; written as UNSIGNED_INT), and per vertex, all optional: normals
+    [W, 3], uvs [W, 2] (already (u, 1 - v), as gltf_vertices gives them), tangents [W, 4] (xyz and the sign), colors [W, 3] uint8
+    (COLOR_0, normalised RGBA8 with alpha 255).  texture and normal_map [R, R, 3] uint8 are embedded as PNG images (png_bytes): the
+    material's baseColorTexture (metallicFactor 0, roughnessFactor 1) and its normalTexture, a tangent-space map as
+    bake_texture(normal_map='tangent') makes it.  unlit=None: KHR_materials_unlit when there is no normal map (a NeRF's radiance already
+    holds the shading), lit with one; a bool decides.  The file is a 12-byte header, the JSON chunk padded with spaces and the BIN chunk
+    padded with zeros; every bufferView starts on a multiple of 4.  Accepts tensors (any device) or arrays.  ValueError: a normal map
+    without tangents and uvs, a texture without uvs, a per-vertex array whose first dimension is not W, an index outside [0, W)."""
+    import json
+    pos = _host(positions, np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"write_glb: positions must be [W, 3], got {pos.shape}")
+    W = len(pos)
+    idx = _host(indices.view(torch.int32) if torch.is_tensor(indices) and indices.dtype == getattr(torch, 'uint32', None) else indices,
+                np.int64).reshape(-1, 3)
+    if idx.size and (idx.min() < 0 or idx.max() >= W):
+        raise ValueError(f"write_glb: an index lies outside [0, W) for W = {W}")
+    per_vertex = {}
+    for name, a, cols, dt in (("normals", normals, 3, np.float32), ("uvs", uvs, 2, np.float32), ("tangents", tangents, 4, np.float32),
+                              ("colors", colors, 3, np.uint8)):
+        if a is None:
+            continue
+        a = _host(a, dt)
+        if a.ndim != 2 or a.shape != (W, cols):
+            raise ValueError(f"write_glb: {name} must be [W, {cols}] for W = {W} vertices, got {a.shape}")
+        per_vertex[name] = a
+    if texture is not None and "uvs" not in per_vertex:
+        raise ValueError("write_glb: a texture needs uvs")
+    if normal_map is not None and not ("uvs" in per_vertex and "tangents" in per_vertex):
+        raise ValueError("write_glb: a normal map needs tangents and uvs (glTF takes tangent-space maps only)")
+    if unlit is None:
+        unlit = normal_map is None
+    views, accessors, blob = [], [], bytearray()
+
+    def view(data, target=None):
+        blob.extend(b"\0" * (-len(blob) % 4))
+        views.append({"buffer": 0, "byteOffset": len(blob), "byteLength": len(data)})
+        if target is not None:
+            views[-1]["target"] = target
+        blob.extend(data)
+        return len(views) - 1
+
+    def accessor(a, ctype, kind, target, **extra):
+        accessors.append(dict({"bufferView": view(a.tobytes(), target), "componentType": ctype, "count": len(a), "type": kind}, **extra))
+        return len(accessors) - 1
+
+    prim = {"mode": 4, "indices": accessor(idx.astype("<u4").reshape(-1), 5125, "SCALAR", 34963)}
+    bounds = {"min": pos.min(0).astype(np.float64).tolist(), "max": pos.max(0).astype(np.float64).tolist()} if W else \
+        {"min": [0.0, 0.0, 0.0], "max": [0.0, 0.0, 0.0]}
+    attr = {"POSITION": accessor(pos.astype("<f4"), 5126, "VEC3", 34962, **bounds)}
+    for name, key, kind in (("normals", "NORMAL", "VEC3"), ("uvs", "TEXCOORD_0", "VEC2"), ("tangents", "TANGENT", "VEC4")):
+        if name in per_vertex:
+            attr[key] = accessor(per_vertex[name].astype("<f4"), 5126, kind, 34962)
+    if "colors" in per_vertex:
+        rgba = np.full((W, 4), 255, np.uint8)
+        rgba[:, :3] = per_vertex["colors"]
+        attr["COLOR_0"] = accessor(rgba, 5121, "VEC4", 34962, normalized=True)
+    prim["attributes"] = attr
+    pbr = {"metallicFactor": 0.0, "roughnessFactor": 1.0}
+    material = {"pbrMetallicRoughness": pbr}
+    images = []
+    for img, what in ((texture, "texture"), (normal_map, "normal_map")):
+        if img is None:
+            continue
+        images.append({"bufferView": view(png_bytes(img, f"write_glb: {what}")), "mimeType": "image/png"})
+        slot = {"index": len(images) - 1, "texCoord": 0}
+        if what == "texture":
+            pbr["baseColorTexture"] = slot
+        else:
+            material["normalTexture"] = slot
+    doc = {"asset": {"version": "2.0", "generator": "customnerf_amd"}, "scene": 0, "scenes": [{"nodes": [0]}], "nodes": [{"mesh": 0}],
+           "meshes": [{"primitives": [prim]}], "materials": [material], "accessors": accessors, "bufferViews": views}
+    prim["material"] = 0
+    if unlit:
+        material["extensions"] = {"KHR_materials_unlit": {}}
+        doc["extensionsUsed"] = ["KHR_materials_unlit"]
+    if images:
+        doc["images"] = images
+        doc["samplers"] = [{"magFilter": 9729, "minFilter": 9729, "wrapS": 33071, "wrapT": 33071}]
+        doc["textures"] = [{"sampler": 0, "source": i} for i in range(len(images))]
+    blob.extend(b"\0" * (-len(blob) % 4))
+    doc["buffers"] = [{"byteLength": len(blob)}]
+    js = json.dumps(doc, separators=(",", ":")).encode("utf-8")
+    js += b" " * (-len(js) % 4)
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<4sII", b"glTF", 2, 12 + 8 + len(js) + 8 + len(blob)))
+        fh.write(struct.pack("<I4s", len(js), b"JSON") + js)
+        fh.write(struct.pack("<I4s", len(blob), b"BIN\0") + bytes(blob))
 
 
 def _lines(fmt, a):

@@ -525,7 +525,11 @@ class NeRFRenderer(nn.Module):
         kind of their projection (0 nothing within reach, 1 along the normal, 2 against it, 3 the closest point past a rim).
         normal_map=True (needs texture=R) adds 'normal_map' [R, R, 3] uint8, an object-space normal map in the texture's layout: the
         normals of the full-resolution surface under bake_from='source' — the detail decimation removed, in a form a viewer can use —
-        else the final mesh's own interpolated normals.  With the defaults neither key is present."""
+        else the final mesh's own interpolated normals.  normal_map='tangent' makes it a tangent-space map, the kind glTF takes and the
+        one that stays valid when the object is rotated or instanced (mesh.bake_texture(normal_map='tangent'), csrc/mesh_tangent.hip):
+        'tangents' [F, 3, 4] float32, the frame of every face corner, joins the dict; without bake_from='source' the map is flat,
+        (128, 128, 255).  'normal_space' ('object' or 'tangent') joins the dict with either.  With the defaults none of these keys is
+        present."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -551,8 +555,10 @@ class NeRFRenderer(nn.Module):
         if bake_from not in ('mesh', 'source'):
             raise ValueError(f"extract_mesh: bake_from must be 'mesh' or 'source', got {bake_from!r}")
         from_source = bake_from == 'source'
+        if isinstance(normal_map, str) and normal_map != 'tangent':
+            raise ValueError(f"extract_mesh: normal_map must be False, True (object space) or 'tangent', got {normal_map!r}")
         if normal_map and not tex_r:
-            raise ValueError("extract_mesh: normal_map=True needs texture=R, the resolution of the atlas it shares")
+            raise ValueError(f"extract_mesh: normal_map={normal_map!r} needs texture=R, the resolution of the atlas it shares")
         reach = 4.0 * float(step.max()) if bake_reach is None else float(bake_reach)
         if from_source and not reach > 0.0:
             raise ValueError(f"extract_mesh: bake_reach must be > 0, got {bake_reach}")
@@ -583,18 +589,22 @@ class NeRFRenderer(nn.Module):
                         kinds += (pr['kind'][:, None] == torch.arange(4, dtype=torch.uint8, device=x.device)).sum(0)
                 rgb = self(x, look)[1][:, :3].float()
                 colors[s:s + chunk] = (rgb.clamp(0, 1) * 255).round().to(torch.uint8)
-        uvs = tex = nmap = None
+        uvs = tex = nmap = tangents = None
         if tex_r:
             baked = _mesh.bake_texture(verts, faces, tex_r, lambda x, d: self(x, d)[1][:, :3], normals=normals, chunk=chunk,
                                        layout=texture_layout, source=source, reach=reach if source is not None else None,
-                                       normal_map=bool(normal_map))
+                                       normal_map=normal_map if isinstance(normal_map, str) else bool(normal_map))
             uvs, tex = baked[:2]
             if len(baked) > 2:
                 nmap, kinds = baked[2]['normal_map'], baked[2]['kinds'] if source is not None else kinds
+                tangents = baked[2].get('tangents')
         m = {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
              'uvs': uvs, 'texture': tex, 'texture_layout': texture_layout}
         if normal_map:
             m['normal_map'] = nmap
+            m['normal_space'] = 'tangent' if isinstance(normal_map, str) else 'object'
+        if isinstance(normal_map, str):
+            m['tangents'] = tangents
         if from_source:
             m['bake_kinds'] = kinds
         if deviation:
@@ -610,19 +620,38 @@ class NeRFRenderer(nn.Module):
     def save_mesh(self, path, **kw):
         """extract_mesh(**kw) written to `path` -> the mesh dict.  A path ending in .obj writes a Wavefront OBJ (mesh.write_obj: positions,
         normals, and with texture=R the UVs, <stem>.mtl and the R x R <stem>.png beside it; vertex colours are not written to OBJ); any other
+        .glb a binary glTF 2.0 (mesh.write_glb: one file that holds the welded vertices of mesh.gltf_vertices — positions, normals, UVs,
+        tangents — the texture and, with normal_map='tangent', the tangent-space normal map; without texture= the indexed vertices with
+        their normals and colours, or the ambient occlusion as grey, as for PLY; unlit unless it carries a normal map); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
         extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), texture_layout, deviation /
         deviation_spacing, ao, bake_from and bake_reach pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
-        in the material) and, like texture=, needs an .obj path.  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
+        in the material) and, like texture=, needs an .obj path; normal_map='tangent' needs a .glb path (OBJ carries no tangents) and
+        normal_map=True is refused for .glb (glTF has no object-space slot).  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written
         unchanged (a NeRF's radiance already contains its shading, so AO is never multiplied into baked colour or texture)."""
-        obj = str(path).lower().endswith(".obj")
-        if int(kw.get('texture', 0) or 0) and not obj:
-            raise ValueError(f"save_mesh: texture= needs an .obj path (PLY carries no texture), got {path!r}")
-        if kw.get('normal_map') and not obj:
-            raise ValueError(f"save_mesh: normal_map=True needs an .obj path (PLY carries no normal map), got {path!r}")
+        obj, glb = (str(path).lower().endswith(e) for e in (".obj", ".glb"))
+        nm = kw.get('normal_map')
+        if int(kw.get('texture', 0) or 0) and not (obj or glb):
+            raise ValueError(f"save_mesh: texture= needs an .obj or .glb path (PLY carries no texture), got {path!r}")
+        if nm and not (obj or glb):
+            raise ValueError(f"save_mesh: normal_map={nm!r} needs an .obj or .glb path (PLY carries no normal map), got {path!r}")
+        if glb and nm and nm != 'tangent':
+            raise ValueError("save_mesh: glTF has no slot for an object-space normal map; use normal_map='tangent' with a .glb path")
+        if obj and nm == 'tangent':
+            raise ValueError("save_mesh: OBJ carries no tangents; normal_map='tangent' needs a .glb path")
         m = self.extract_mesh(**kw)
-        if obj:
+        if glb:
+            colors = m['colors']
+            if colors is None and 'ao' in m:
+                colors = (m['ao'] * 255).round().to(torch.uint8)[:, None].expand(-1, 3)
+            if m['uvs'] is not None:
+                g = _mesh.gltf_vertices(m['verts'], m['faces'], m['uvs'], m['normals'])
+                _mesh.write_glb(path, g['positions'], g['indices'], normals=g['normals'], uvs=g['uvs'], tangents=g['tangents'],
+                                texture=m['texture'], normal_map=m.get('normal_map'))
+            else:
+                _mesh.write_glb(path, m['verts'], m['faces'], normals=m['normals'], colors=colors)
+        elif obj:
             _mesh.write_obj(path, m['verts'], m['faces'], uvs=m['uvs'], normals=m['normals'], texture=m['texture'],
                             normal_map=m.get('normal_map'))
         else:
@@ -636,7 +665,7 @@ class NeRFRenderer(nn.Module):
         """Preview of an exported mesh from a camera pose, rasterised on the device (mesh.render_mesh, csrc/mesh_raster.hip).  `mesh` is the
         dict extract_mesh / save_mesh return: its verts, faces, normals, colors, uvs and texture are forwarded (so the texture is shown
         when the mesh has one, else the vertex colours, else the normals); the camera is generate_rays' (c2w [3, 4] or [4, 4], intrinsics
-        (fx, fy, cx, cy), convention= in **kw).  map='normal_map' shows the mesh's normal map (extract_mesh(normal_map=True)) in place of
+        (fx, fy, cx, cy), convention= in **kw).  map='normal_map' shows the mesh's normal map (extract_mesh(normal_map=True or 'tangent'), whichever it holds) in place of
         its texture, through the same 'texture' shading.  With `path` the image is also written as a PNG (mesh.write_png).
         -> (image [H, W, 3] uint8, mask [H, W] bool, the visibility dict of mesh.rasterize)."""
         if map not in ('texture', 'normal_map'):

@@ -45,7 +45,9 @@ extern "C" {
  *    (additive, same version) — cnerf_mesh_bvh_raycast / _occluded; the area-proportional atlas (additive, same version) —
  *    cnerf_mesh_atlas_sized_workspace_bytes / _measure / _layout / _plan / _uvs / _points / _store / _fill; projection onto a source
  *    mesh (additive, same version) — cnerf_mesh_bvh_project; the chart-based atlas (additive, same version) —
- *    cnerf_mesh_atlas_proj_workspace_bytes / _charts / _pack / _raster / _points / _store / _fill. */
+ *    cnerf_mesh_atlas_proj_workspace_bytes / _charts / _pack / _raster / _points / _store / _fill; welded vertices, tangent frames and
+ *    tangent-space normal maps (additive, same version) — cnerf_mesh_tangent_workspace_bytes / _weld / _frames / _vertices and
+ *    cnerf_mesh_atlas_tspace / cnerf_mesh_atlas_sized_tspace / cnerf_mesh_atlas_proj_tspace. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -645,6 +647,9 @@ int cnerf_mesh_atlas_uvs(const int32_t *faces, uint32_t V, uint32_t F, uint32_t 
                          void *stream);
 int cnerf_mesh_atlas_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, uint32_t t0,
                             uint32_t t1, const uint32_t *flags, float *x, float *d, uint32_t max_points, void *stream);
+int cnerf_mesh_atlas_tspace(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R,
+                            const float *tangents, uint32_t t0, uint32_t t1, const float *m, uint32_t m_stride, const uint32_t *flags, float *rgb,
+                            uint32_t max_points, void *stream);
 int cnerf_mesh_atlas_store(uint32_t F, uint32_t R, uint32_t t0, uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host,
                            const uint32_t *flags, uint8_t *image, void *stream);
 int cnerf_mesh_atlas_fill(uint32_t F, uint32_t R, const uint8_t *fill_host, uint8_t *image, void *stream);
@@ -695,6 +700,9 @@ int cnerf_mesh_atlas_sized_uvs(uint32_t F, uint32_t R, const int32_t *cells, con
 int cnerf_mesh_atlas_sized_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R,
                                   const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0, uint32_t t1,
                                   const uint32_t *flags, float *x, float *d, uint32_t max_points, void *stream);
+int cnerf_mesh_atlas_sized_tspace(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R,
+                                  const uint32_t *counts_host, void *ws, uint64_t ws_bytes, const float *tangents, uint32_t t0, uint32_t t1,
+                                  const float *m, uint32_t m_stride, const uint32_t *flags, float *rgb, uint32_t max_points, void *stream);
 int cnerf_mesh_atlas_sized_store(uint32_t F, uint32_t R, const uint32_t *counts_host, void *ws, uint64_t ws_bytes, uint32_t t0,
                                  uint32_t t1, const float *rgb, uint32_t rgb_stride, const uint8_t *fill_host, const uint32_t *flags,
                                  uint8_t *image, void *stream);
@@ -777,10 +785,60 @@ int cnerf_mesh_atlas_proj_raster(const float *verts, uint32_t V, const int32_t *
 int cnerf_mesh_atlas_proj_points(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, void *ws,
                                  uint64_t ws_bytes, uint32_t t0, uint32_t t1, const uint32_t *flags, float *x, float *d, uint32_t max_points,
                                  void *stream);
+int cnerf_mesh_atlas_proj_tspace(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t R, void *ws,
+                                 uint64_t ws_bytes, const float *tangents, uint32_t t0, uint32_t t1, const float *m, uint32_t m_stride,
+                                 const uint32_t *flags, float *rgb, uint32_t max_points, void *stream);
 int cnerf_mesh_atlas_proj_store(uint32_t V, uint32_t F, uint32_t R, void *ws, uint64_t ws_bytes, uint32_t t0, uint32_t t1, const float *rgb,
                                 uint32_t rgb_stride, const uint32_t *flags, uint8_t *image, void *stream);
 int cnerf_mesh_atlas_proj_fill(uint32_t V, uint32_t F, uint32_t R, void *ws, uint64_t ws_bytes, const uint8_t *fill_host,
                                const uint32_t *flags, uint8_t *image, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Welded vertices, tangent frames and tangent-space normal maps (customnerf_amd/mesh.py weld_corners / corner_tangents / gltf_vertices /
+ * bake_texture(normal_map='tangent'); csrc/mesh_tangent.hip, k_bake_tspace of csrc/mesh_bake.h; restatement: tests/tangent_restatement.py).
+ * What a glTF primitive and its normalTexture need.  verts / normals float32 [V][3], faces int32 [F][3], uvs float32 [F][3][2] (v up, as the
+ * atlas passes write them); V < 2^31, F <= 0x2AAAAAAA, else CNERF_EINVAL.  Corner c = 3 f + k.  The caller's stream and workspace (16-byte
+ * aligned, >= workspace_bytes(V, F), about 16 bytes per vertex + 60 per face); no allocation, no float atomics, every sum in a stated order:
+ * bit-reproducible.  Red runs along +u and green along +v with v up (the OpenGL and glTF convention once v is flipped for the file).
+ *   weld     : the key of a corner is (vertex index, bits of u, bits of v); corners with equal keys are one output vertex.  Output vertices
+ *              are numbered by ascending vertex index and, within a vertex, by ascending smallest corner of the group.  corner_vertex int32
+ *              [F][3] (rows >= max_faces are not written), vertex_corner int32 [W] (the smallest corner of each group; entries >= max_verts
+ *              are not written; W <= 3 F), counts (device uint32 [2]) = (W, flags): the one host read.  flags bit 0: a face index outside
+ *              [0, V); W is then 0 and weld, frames and vertices write nothing else.
+ *   frames   : after weld on the same stream with the same ws, V, F, faces and uvs.  Per face, from float32 e1 = p1 - p0, e2 = p2 - p0,
+ *              du1 = u1 - u0, dv1 = v1 - v0, du2 = u2 - u0, dv2 = v2 - v0, then in float64 with one rounding per written operation (products
+ *              of two float32 values are exact): det = du1 dv2 - du2 dv1, s = -1 if det < 0 else 1, Tf = s (e1 dv2 - e2 dv1),
+ *              Bf = s (e2 du1 - e1 du2), c = e1 x e2 (as cnerf_mesh_smooth_normals), A2 = sqrt((c0 c0 + c1 c1) + c2 c2), |x| =
+ *              sqrt((x0 x0 + x1 x1) + x2 x2).  A face contributes unless det is 0 or non-finite or one of A2, |Tf|, |Bf| is not in
+ *              (0, inf): (A2 Tf) / |Tf| to S_T, (A2 Bf) / |Bf| to S_B and c to S_N of the group of each of its corners; the sums start at
+ *              0 and run in ascending corner index.  Per group: n = the vertex's normal read as float64, or S_N when normals is NULL,
+ *              divided by sqrt(q), q = (n0 n0 + n1 n1) + n2 n2, when q is in (0, inf); else n = 0.  t = S_T - n (n . S_T) (dot products
+ *              summed (a0 b0 + a1 b1) + a2 b2); when |t|^2 is not in [DBL_MIN, inf): t = c - n n_a, c the unit axis a of the smallest
+ *              |n_a|, the lowest on ties (n = 0 gives t = (1, 0, 0)).  tangent xyz = (float) (t / sqrt(|t|^2)), w = -1 if
+ *              (n x t) . S_B < 0 else +1.  tangents float32 [F][3][4]: every corner of a group gets the group's frame; rows >=
+ *              max_faces are not written.  The workspace keeps (float) n per group for vertices.
+ *   vertices : after frames.  For output vertex i with corner c = vertex_corner[i] of vertex v: positions [W][3] = verts[v], normals_out
+ *              [W][3] = normals[v] as given, or the group's n when normals is NULL, uvs_out [W][2] = (u, 1 - v) of corner c in float32,
+ *              tangents_out [W][4] = tangents[c]; indices uint32 [F][3] = corner_vertex.  W must be weld's (W > 3 F: CNERF_EINVAL).
+ *   tspace   : cnerf_mesh_atlas_tspace / _sized_tspace / _proj_tspace, with the arguments of the layout's points pass: for cell texels
+ *              [t0, t1) the float32 code rgb [N][3] (rows >= max_points are neither read nor written) of the object-space normals
+ *              m [N][m_stride >= 3] in the texel's frame, for the layout's store pass.  N = -d of the points pass, bit for bit, with its
+ *              weights w1, w2 and corner; float32, one rounding per written operation: T' = T0 + w1 (T1 - T0) + w2 (T2 - T0) of the corners'
+ *              tangent xyz (a corner texel: that corner's), t = T' - N (N . T'); when |t|^2 is not in [FLT_MIN, inf): t = c - N N_a as
+ *              above; t = t / sqrt(|t|^2); w = that of the corner with the largest of (1 - w1) - w2, w1, w2 (the lowest on ties; a corner
+ *              texel: that corner's; a face without area in the layout: corner 0's); B = w (N x t); rgb = 0.5 + 0.5 (m . t, m . B, m . N).
+ *              m == NULL encodes N itself: (0.5, 0.5, 1) exactly.  An un-owned cell texel gets (0.5, 0.5, 1); the fill colour of a
+ *              tangent-space map is (128, 128, 255).
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_tangent_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_tangent_weld(const int32_t *faces, const float *uvs, uint32_t V, uint32_t F, void *ws, uint64_t ws_bytes, uint32_t *counts,
+                            int32_t *corner_vertex, uint32_t max_faces, int32_t *vertex_corner, uint32_t max_verts, void *stream);
+int cnerf_mesh_tangent_frames(const float *verts, const int32_t *faces, const float *uvs, const float *normals, uint32_t V, uint32_t F,
+                              void *ws, uint64_t ws_bytes, float *tangents, uint32_t max_faces, void *stream);
+int cnerf_mesh_tangent_vertices(const float *verts, const int32_t *faces, const float *uvs, const float *normals, const float *tangents,
+                                const int32_t *corner_vertex, const int32_t *vertex_corner, uint32_t V, uint32_t F, uint32_t W, void *ws,
+                                uint64_t ws_bytes, float *positions, float *normals_out, float *uvs_out, float *tangents_out,
+                                uint32_t *indices, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Taubin lambda|mu smoothing with uniform weights and area-weighted vertex normals (customnerf_amd/mesh.py smooth / vertex_normals;
