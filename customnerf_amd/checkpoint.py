@@ -5,7 +5,12 @@ File = torch.save of {'epoch', 'global_step', 'stats', ['mean_count', 'mean_dens
 ['optimizer', 'lr_scheduler', 'scaler', 'ema' when full]}.  The model's state-dict keys are the reference's:
 aabb_train / aabb_infer / density_grid / density_bitfield / step_counter buffers, pos_en.embeddings / pos_en.offsets,
 network.params / density_network.params / rgb_network.params — `*.params` is the flat float32 vector of tinycudann.Network
-(row-major [out, in] matrices, widths padded to 16: the layout assumption is stated in DESIGN.md §2, tinycudann being unpinned)."""
+(row-major [out, in] matrices, widths padded to 16: the layout assumption is stated in DESIGN.md §2, tinycudann being unpinned).
+
+Adam's 'step' in 'optimizer' is the number of APPLIED steps in both directions: torch.optim.Adam under a GradScaler never sees a skipped step, and
+optim.FusedAdam.state_dict() writes the loss scaler's on-device count of non-skipped steps, which is what its kernels use for the bias correction.
+load_checkpoint hands that count to an optim.DynamicLossScaler whose 'scaler' entry (a GradScaler's) does not carry it.  trainer.load_checkpoint is
+the trainer-level counterpart (global_step, fp16 shadow, sharded state, graphs)."""
 import glob
 import os
 
@@ -81,9 +86,11 @@ def load_checkpoint(model, checkpoint, model_only=False, optimizer=None, map_loc
     if model_only:
         return out
     out['stats'], out['epoch'], out['global_step'] = ck.get('stats'), ck.get('epoch'), ck.get('global_step')
+    loaded_optimizer = False
     if optimizer is not None and 'optimizer' in ck:
         try:
             optimizer.load_state_dict(ck['optimizer'])
+            loaded_optimizer = True
         except Exception as e:                                          # the reference swallows this too (:885-890)
             log(f"[WARN] Failed to load optimizer: {e!r}")
     if lr_scheduler is not None and 'lr_scheduler' in ck:               # :889-894
@@ -91,9 +98,23 @@ def load_checkpoint(model, checkpoint, model_only=False, optimizer=None, map_loc
             lr_scheduler.load_state_dict(ck['lr_scheduler'])
         except Exception as e:
             log(f"[WARN] Failed to load scheduler: {e!r}")
+    # optim.DynamicLossScaler counts the applied (non-skipped) steps on the device, and the fused Adam kernels take their bias correction from
+    # that count.  A torch GradScaler's state dict (a reference-written 'scaler' entry) has no such key: the loaded optimiser's Adam step is the
+    # same number (torch.optim.Adam under a GradScaler never sees a skipped step; FusedAdam.state_dict writes the scaler's count).
+    steps = _adam_steps(optimizer) if (loaded_optimizer and hasattr(scaler, 'set_good_steps')) else None
     if scaler is not None and 'scaler' in ck:                           # :896-901
         try:
-            scaler.load_state_dict(ck['scaler'])
+            if steps is not None:
+                scaler.load_state_dict(ck['scaler'], good_steps=steps)
+            else:
+                scaler.load_state_dict(ck['scaler'])
         except Exception as e:
             log(f"[WARN] Failed to load scaler: {e!r}")
+    elif steps is not None:                                             # (a run without a scaler resumed with one: the moments are `steps` old)
+        scaler.set_good_steps(steps)
     return out
+
+
+def _adam_steps(optimizer):
+    """the largest Adam 'step' in an optimiser's state: an int (FusedAdam) or a 0-dim tensor (newer torch.optim.Adam); 0 without state"""
+    return max((int(st['step']) for st in optimizer.state.values() if 'step' in st), default=0)

@@ -196,25 +196,28 @@ class ShardedExchange:
             entry['step'] = st['step']
 
     @torch.no_grad()
-    def import_optimizer_state(self, optimizer, drop=True):
+    def import_optimizer_state(self, optimizer, drop=True, moments=True):
         """the inverse, after `optimizer.load_state_dict(...)` and the model's `load_state_dict`: this rank's slice of the loaded moments,
-        the master shard and the shadow are taken from the full tensors; `drop` frees the full moments again."""
+        the master shard and the shadow are taken from the full tensors; `drop` frees the full moments again.  `moments=False` (a model-only
+        load: trainer.load_checkpoint(..., model_only=True)) re-cuts the master shard and the shadow only and keeps the Adam state."""
         for st in self.state:
             p, n, s = st['p'], st['n'], st['shard']
             lo, hi = self.rank * s, min((self.rank + 1) * s, n)
-            entry = optimizer.state.get(p, {})
-            for key, dst in (('exp_avg', st['m']), ('exp_avg_sq', st['v'])):
+            entry = optimizer.state.get(p, {}) if moments else {}
+            for key, dst in (('exp_avg', st['m']), ('exp_avg_sq', st['v'])) if moments else ():
                 dst.zero_()
                 if key in entry and hi > lo:
                     dst[:hi - lo].copy_(entry[key].reshape(-1)[lo:hi])
-            st['step'] = int(entry.get('step', 0))
+            if moments:
+                st['step'] = int(entry.get('step', 0))
             st['master'].zero_()
             if hi > lo:
                 st['master'][:hi - lo].copy_(p.detach().reshape(-1)[lo:hi])
             if 'shadow' in st:
                 st['shadow'][:n].copy_(p.detach().reshape(-1))
-            if drop and p in optimizer.state:
+            if moments and drop and p in optimizer.state:
                 del optimizer.state[p]
+            p._cnerf_stale = False
             p._cnerf_epoch = getattr(p, '_cnerf_epoch', 0) + 1
 
     @torch.no_grad()

@@ -66,10 +66,15 @@ class DynamicLossScaler:
         return {"scale": st[0], "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor, "growth_interval": self.growth_interval,
                 "_growth_tracker": int(st[1]), "_good_steps": int(st[3])}
 
-    def load_state_dict(self, sd):
-        good = sd.get("_good_steps", int(self.state[3]))
-        self.state.copy_(torch.tensor([float(sd["scale"]), float(sd.get("_growth_tracker", 0)), 0.0, float(good)]))
+    def load_state_dict(self, sd, good_steps=None):
+        """`good_steps`: the count to resume with when `sd` carries none (a torch GradScaler's state dict: checkpoint.load_checkpoint passes the
+        loaded optimiser's Adam step, which is the same number); without either the current count stays."""
+        good = sd.get("_good_steps", int(self.state[3]) if good_steps is None else int(good_steps))
+        self.state.copy_(torch.tensor([float(sd["scale"]), float(sd.get("_growth_tracker", 0)), 0.0, float(good)]))     # in place: kernels and graphs hold its address
         self.growth_factor, self.backoff_factor, self.growth_interval = sd["growth_factor"], sd["backoff_factor"], sd["growth_interval"]
+
+    def set_good_steps(self, n):
+        self.state[3:4].fill_(float(n))
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -77,7 +82,9 @@ class FusedAdam(torch.optim.Optimizer):
     `half_shadows`: {param: fp16 tensor} refreshed in the same pass (GridEncoder.set_half_table)."""
 
     def __init__(self, params, lr=5e-4, betas=(0.9, 0.99), eps=1e-15, zero_grad_in_step=True):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        # (weight_decay / amsgrad: not implemented, carried at torch.optim.Adam's defaults so that torch.optim.Adam.load_state_dict accepts a
+        # param group this class saved — it fills in its other defaults itself, but reads these two without one)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False))
         self.zero_grad_in_step = zero_grad_in_step
         self.half_shadows = {}
         self.grad_scale_inv = 1.0
@@ -183,6 +190,28 @@ class FusedAdam(torch.optim.Optimizer):
                                                    float(sc.backoff_factor), int(sc.growth_interval), stream()), "adam_step_scaled_multi")
             self.updates_scaler = True
             sc._update_consumed = True                # ... so the caller's scaler.update() for this step does nothing
+
+    # ---- checkpoints: torch.optim.Adam's state dict, with Adam's step defined as the number of steps that were APPLIED ----------------------------
+    def state_dict(self):
+        """torch.optim.Adam.state_dict().  Under the on-device loss scaler 'step' is the scaler's count of non-skipped steps — the number the kernels
+        used for the bias correction (optim_common.h cn_scaler_step) and the one torch.optim.Adam under a GradScaler holds, which never sees a
+        skipped step.  The host-side counter advances on every call of step() (it cannot know about a skip without a host sync), so it is
+        brought back in line here, with the one host read a save costs anyway."""
+        if self.scaler is not None:
+            good = self.scaler.good_steps()
+            for st in self.state.values():
+                if 'step' in st:
+                    st['step'] = good
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.Adam's or this class's state dict.  The moments are NEW tensors afterwards: an armed table step (arm_in_backward) holds the
+        old ones' addresses and is dropped.  'step' becomes a plain int whatever the file held (newer torch.optim.Adam saves a 0-dim tensor)."""
+        self.disarm_in_backward()
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            if 'step' in st:
+                st['step'] = int(st['step'])
 
     def zero_grad(self, set_to_none=False):
         if self.zero_grad_in_step and not set_to_none:

@@ -214,6 +214,51 @@ class CheckpointMixin:
         return checkpoint.save_checkpoint(path, self.model, epoch=epoch, global_step=self.global_step, stats=stats, optimizer=self.optimizer, full=full,
                                           scaler=self.scaler)
 
+    def _graph_inputs(self):
+        """addresses of everything a captured step (train_step_graphed) reads or writes that a load could move: the parameters, their persistent
+        gradients, the model's buffers, the fp16 shadow of the grid table, the loss scaler's state"""
+        enc = getattr(self.model, 'pos_en', None)
+        shadow = getattr(enc, '_half_table', None)
+        ts = [t for p in self.model.parameters() for t in (p, p.grad)] + list(self.model.buffers()) + [shadow, getattr(self.scaler, 'state', None)]
+        return [None if t is None else (t.data_ptr(), t.dtype, tuple(t.shape)) for t in ts]
+
+    def load_checkpoint(self, path_or_dict, model_only=False):
+        """Counterpart of save_checkpoint (checkpoint.load_checkpoint with this trainer's optimiser and loss scaler; Trainer_Nerf.load_checkpoint,
+        utils_init_nerf.py:837-901) for a fresh trainer and for rolling a live one back.  -> checkpoint.load_checkpoint's info dict.
+        The parameter values are copied IN PLACE (the flat gradient buffer, the fp16 shadow and captured graphs are bound to the parameter storage);
+        `global_step` — which the learning-rate decay is a function of — is restored (and `epoch` / `stats` on a trainer that keeps them); the Adam
+        moments are new tensors afterwards, so an armed table step is dropped; in dp_mode 'sharded' the shards are re-cut from the loaded tensors
+        (every rank calls this).  Captured graphs survive unless something they reference moved."""
+        from . import checkpoint
+        opt_ = self.optimizer
+        if hasattr(opt_, 'disarm_in_backward'):
+            opt_.disarm_in_backward()                                 # (FusedAdam.load_state_dict does it too; a model_only load never gets there)
+        before = self._graph_inputs()
+        dev = next(self.model.parameters()).device
+        info = checkpoint.load_checkpoint(self.model, path_or_dict, model_only=model_only, optimizer=opt_, scaler=self.scaler, map_location=dev)
+        if not model_only:
+            if info['global_step'] is not None:
+                self.global_step = int(info['global_step'])
+            for k in ('epoch', 'stats'):
+                if hasattr(self, k) and info[k] is not None:
+                    setattr(self, k, info[k])
+        enc = getattr(self.model, 'pos_en', None)
+        dp = getattr(self, '_dp', None)
+        if dp is not None:
+            dp.import_optimizer_state(opt_, moments=not model_only)  # master shards, sharded moments and the shadow table from the loaded tensors
+            refresh_half_shadow(opt_, self.model)
+        else:
+            sh = getattr(opt_, 'half_shadows', {}).get(enc.embeddings) if enc is not None else None
+            if sh is not None:
+                # the shadow the fused Adam step writes IS the encoder's: re-cast it now from the loaded table
+                enc.set_half_table(sh)
+                enc.invalidate_half_table()
+                enc.half_table()
+        if self._graph_inputs() != before:
+            self.__dict__.pop('_graphs', None)
+            self.__dict__.pop('_graph_pool', None)
+        return info
+
 
 class EvalMixin:
     """Trainer_Nerf.eval_step / test_step (nerf/utils_init_nerf.py:396-434, 436-485): one full view rendered without perturbation and the image
