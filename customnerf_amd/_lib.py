@@ -258,10 +258,17 @@ def dtype_id(t):
     raise ValueError(f"unsupported dtype {t.dtype}")
 
 
+def query_u64(fn, *args):
+    """fn(*args, &n) for an entry point whose last parameter is a uint64 out-parameter (the cnerf_*_bytes size queries, mostly) -> int n"""
+    out = u64(0)
+    check(fn(*args, C.byref(out)), fn.__name__.removeprefix("cnerf_"))
+    return out.value
+
+
 def scratch_key(device):
-    """Key of a per-device scratch buffer that must not be shared between concurrently running streams (the micro-batch pipeline of
-    trainer.ReconTrainer runs two half-batches on two streams): (device, stream handle)."""
-    import torch
+    """Key of a per-device scratch buffer that streams must not share: (device, stream handle).  torch.cuda.graph captures on a stream of
+    its own, so a buffer first needed inside a capture is allocated there, from the graph's pool, and the eager step's buffer (which a
+    later eager call may replace) never enters a graph; two streams that run the same op at once do not share partial results either."""
     return (device, torch.cuda.current_stream(device).cuda_stream)
 
 
@@ -269,14 +276,51 @@ _SCRATCH_GENERATION = [0]
 
 
 def scratch_reallocated():
-    """Call whenever a cached grow-on-demand scratch buffer (scatter workspaces, field / MLP partial-gradient rows, the march's probe list)
-    is replaced: captured hipGraphs hold the OLD buffer's address, so their owners (trainer.ReconTrainer.train_step_graphed) compare
-    scratch_generation() with the value at capture and drop every cached graph when it moved."""
+    """Called by ScratchCache, and by nothing else, whenever it replaces or drops a buffer: captured hipGraphs hold the OLD buffer's
+    address, so their owners (trainer.ReconTrainer.train_step_graphed) compare scratch_generation() with the value their graphs are valid
+    for and drop every cached graph when it moved."""
     _SCRATCH_GENERATION[0] += 1
 
 
 def scratch_generation():
     return _SCRATCH_GENERATION[0]
+
+
+class ScratchCache(dict):
+    """key -> cached device buffer that grows on demand: THE owner of every such workspace of the package (scatter workspaces, field / MLP
+    partial-gradient rows, the march's probe list, the split-K scratch).  A plain dict to its users (tests clear, pop and assign).
+
+    The one hazard: a captured hipGraph replays with the buffer address it was captured with, so a buffer that a graph may hold must
+    never silently go back to the allocator.  Each cache picks one of the two answers:
+      * releasing (retire=False): the outgrown buffer is freed — dropped BEFORE the new one is allocated, so the peak is one buffer —
+        and scratch_reallocated() tells the graph owners to recapture;
+      * retiring (retire=True): the outgrown buffer stays alive in `retired` for the life of the process and the generation does not
+        move (sd.unet.UNet.graphed keeps its graphs).
+    A buffer is (re)allocated with max(int(count * factor) + pad, floor) elements of `dtype` when there is none, when it is too small,
+    or — `shrink` set — when it holds more than shrink * count elements (one huge call must not pin its worst case)."""
+
+    def __init__(self, factor=1, pad=0, floor=0, dtype=torch.uint8, shrink=None, retire=False):
+        super().__init__()
+        self.factor, self.pad, self.floor, self.dtype, self.shrink, self.retire = factor, pad, floor, dtype, shrink, retire
+        self.retired = []
+
+    def reserve(self, key, count, device):
+        """-> the buffer of `key`, at least `count` elements"""
+        buf = self.get(key)
+        if buf is None or buf.numel() < count or (self.shrink is not None and buf.numel() > self.shrink * count):
+            if not self.retire:
+                self.pop(key, None)
+                scratch_reallocated()
+            elif buf is not None:
+                self.retired.append(buf)
+            buf = None                                               # (the old block goes before the new one is asked for)
+            buf = self[key] = torch.empty(max(int(count * self.factor) + self.pad, self.floor), dtype=self.dtype, device=device)
+        return buf
+
+    def drop(self, key):
+        """release the buffer of `key`, if one is held"""
+        if self.pop(key, None) is not None:
+            scratch_reallocated()
 
 
 _GRAD_CHAIN = {}
@@ -287,7 +331,6 @@ def grad_chain_wait(device):
     overlap each other across streams: wait for the previous one ...  On ONE stream the launch order already is that order, and nothing is
     enqueued (round 6: an event record per producer was a 5.8 us bubble on the queue, two per step — scratch/recon_gaps.sh); a producer on
     another stream waits for the tail of the previous producer's stream (a later point than the producer itself: conservative)."""
-    import torch
     cur = torch.cuda.current_stream(device)
     last = _GRAD_CHAIN.get(device)
     if last is not None and last.cuda_stream != cur.cuda_stream:
@@ -296,5 +339,4 @@ def grad_chain_wait(device):
 
 def grad_chain_record(device):
     """... and remember which stream the next one has to order itself after."""
-    import torch
     _GRAD_CHAIN[device] = torch.cuda.current_stream(device)

@@ -3,15 +3,12 @@ cnerf_field_forward / cnerf_field_backward.  Mirrors NeRFNetwork.forward/.densit
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check, ptr, stream, F16, F32, require_cuda, scratch_key, grad_chain_wait, grad_chain_record, scratch_reallocated
+from ._lib import lib, check, ptr, stream, F16, F32, require_cuda, scratch_key, grad_chain_wait, grad_chain_record, query_u64, ScratchCache
 
 
 def capture_id():
     """capture sequence id of the current stream while it records a hipGraph, else 0"""
-    import ctypes
-    cid = ctypes.c_uint64(0)
-    check(lib.cnerf_stream_capture_id(stream(), ctypes.addressof(cid)), "stream_capture_id")
-    return cid.value
+    return query_u64(lib.cnerf_stream_capture_id, stream())
 
 
 def packed_weights(cache, enc_dim, n_hidden_geo, n_rgb_out, p_net, p_den, p_rgb):
@@ -25,15 +22,13 @@ def packed_weights(cache, enc_dim, n_hidden_geo, n_rgb_out, p_net, p_den, p_rgb)
     Under stream capture a pack is RECORDED, not executed: the first use inside a capture (and any use after a parameter moved inside it)
     records one, so every replay starts from the parameters as they are then; the eager freshness is dropped, because the replays rewrite
     the image at times this cache does not see."""
-    import ctypes
     require_cuda(p_net, p_den, p_rgb)
     key = tuple((p.data_ptr(), p._version, getattr(p, '_cnerf_epoch', 0)) for p in (p_net, p_den, p_rgb))
     slot = (scratch_key(p_net.device), enc_dim, n_hidden_geo, n_rgb_out)
     ent = cache.get(slot)
     if ent is None:
-        need = ctypes.c_uint64(0)
-        check(lib.cnerf_field_weight_image_bytes(int(enc_dim), int(n_hidden_geo), int(n_rgb_out), ctypes.addressof(need)), "field_weight_image_bytes")
-        ent = cache[slot] = {'img': torch.empty(need.value, dtype=torch.uint8, device=p_net.device), 'key': None, 'cap': 0, 'cap_key': None}
+        need = query_u64(lib.cnerf_field_weight_image_bytes, int(enc_dim), int(n_hidden_geo), int(n_rgb_out))
+        ent = cache[slot] = {'img': torch.empty(need, dtype=torch.uint8, device=p_net.device), 'key': None, 'cap': 0, 'cap_key': None}
     cap = capture_id()
     if cap:
         fresh = ent['cap'] == cap and ent['cap_key'] == key
@@ -79,20 +74,12 @@ def field_forward_rows(enc, row0, xyz_rows, dirs, dir_group, enc_dim, n_hidden_g
           "field_forward")
 
 
-_WS = {}
+_WS = ScratchCache(factor=1.1, pad=256)          # the backward's per-workgroup partial-gradient rows
 
 
 def _workspace(P, enc_dim, n_hidden_geo, n_rgb_out, dt, device):
-    import ctypes
-    need = ctypes.c_uint64(0)
-    check(lib.cnerf_field_backward_workspace_bytes(P, enc_dim, n_hidden_geo, n_rgb_out, dt, ctypes.addressof(need)), "field_backward_workspace_bytes")
-    key = scratch_key(device)
-    buf = _WS.get(key)
-    if buf is None or buf.numel() < need.value:
-        buf = torch.empty(int(need.value * 1.1) + 256, dtype=torch.uint8, device=device)
-        _WS[key] = buf
-        scratch_reallocated()
-    return buf
+    need = query_u64(lib.cnerf_field_backward_workspace_bytes, P, enc_dim, n_hidden_geo, n_rgb_out, dt)
+    return _WS.reserve(scratch_key(device), need, device)
 
 
 class FieldFunction(Function):

@@ -9,6 +9,7 @@ Deliberate differences:
     counter, so writes through `.data` must be followed by invalidate_half_table();
   * gradients are accumulated in float32 for both table dtypes (the reference scatters __half2 atomics for fp16).
 """
+import ctypes
 import os
 import weakref
 
@@ -17,7 +18,7 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from .._lib import lib, check, ptr, stream, dtype_id, require_cuda, scratch_key, grad_chain_wait, grad_chain_record, scratch_reallocated
+from .._lib import lib, check, ptr, stream, dtype_id, require_cuda, scratch_key, grad_chain_wait, grad_chain_record, query_u64, ScratchCache
 
 # Optional in-stream timing of the gather kernel (bench.py's roofline leg): when a list is installed with
 # set_profile(), every forward launch is bracketed by a pair of events recorded on the launch stream.
@@ -103,23 +104,15 @@ def _offsets_host(offsets):
     return cached
 
 
-_WS_CACHE = {}
+_WS_CACHE = ScratchCache(factor=1.25, pad=256)
 
 
 def _bwd_workspace(offsets_host, B, D, C, L, max_level, S, H, dt, device):
-    """Scratch for the atomic-free binned scatter (one buffer per device, grown on demand, reused every step)."""
-    import ctypes
-    need = ctypes.c_uint64(0)
-    check(lib.cnerf_grid_encode_backward_workspace_bytes(offsets_host.ctypes.data, B, D, C, L, max_level, S, H, dt, ctypes.addressof(need)),
-          "grid_encode_backward_workspace_bytes")
-    if need.value == 0:
+    """Scratch for the atomic-free binned scatter (one buffer per device and stream, grown on demand, reused every step)."""
+    need = query_u64(lib.cnerf_grid_encode_backward_workspace_bytes, offsets_host.ctypes.data, B, D, C, L, max_level, S, H, dt)
+    if need == 0:
         return None, 0
-    key = scratch_key(device)
-    buf = _WS_CACHE.get(key)
-    if buf is None or buf.numel() < need.value:
-        buf = torch.empty(int(need.value * 1.25) + 256, dtype=torch.uint8, device=device)
-        _WS_CACHE[key] = buf
-        scratch_reallocated()
+    buf = _WS_CACHE.reserve(scratch_key(device), need, device)
     return buf, buf.numel()
 
 
@@ -187,7 +180,7 @@ def set_pre_scatter_hook(fn):
     _PRE_SCATTER_HOOK = fn
 
 
-_SIDE = {}          # device -> {'stream': side stream, 'ws': workspace of the prepared plan, 'owner': weakref to the plan waiting for its backward}
+_SIDE = {}          # scratch_key -> _side_entry
 
 
 class _Plan:
@@ -198,11 +191,19 @@ class _Plan:
         self.ws, self.event, self.inputs_ptr, self.rows = ws, event, inputs_ptr, rows
 
 
+def _side_entry(side_stream):
+    """'ws': the workspace of the prepared plan, a one-key cache that leaves with the entry (_SIDE.clear() releases it);
+    'owner': weakref to the plan waiting for its backward"""
+    return {'stream': side_stream, 'ws': ScratchCache(factor=1.25, pad=256), 'owner': None}
+
+
 def _side(device):
-    key = scratch_key(device)                                # one side stream + plan slot per compute stream (micro-batch pipeline)
+    # one side stream + plan slot per compute stream: a capture runs on a stream of its own, so the plan workspace a graph holds is the
+    # one allocated inside the capture (graph pool), never the eager step's
+    key = scratch_key(device)
     st = _SIDE.get(key)
     if st is None:
-        st = _SIDE[key] = {'stream': torch.cuda.Stream(device=device), 'ws': None, 'owner': None}
+        st = _SIDE[key] = _side_entry(torch.cuda.Stream(device=device))
     return st
 
 
@@ -217,7 +218,6 @@ def _needs_plan(offsets_host, B, D, C, L, S, H, dt, gridtype):
     """does the backward scatter of this shape use a plan prepared ahead of time?  (cnerf_grid_encode_backward_needs_plan, cached per shape: only
     the first form of the binned scatter takes one — float32 records, and fp16 tables the third form does not take; the third form, which
     serves the fp16 tables of the run() path, counts inside its emit kernel and prepares nothing)"""
-    import ctypes
     key = (offsets_host.ctypes.data, B, D, C, L, S, H, dt, gridtype)
     v = _NEEDS_PLAN.get(key)
     if v is None:
@@ -234,21 +234,15 @@ def _prepare_plan(inputs, offsets_host, B, D, C, L, S, H, gridtype, align_corner
     """Issue the coordinate-only half of the binned backward scatter's first form (histogram + scans) for `inputs` [B, D] on the side stream of
     the current compute stream -> _Plan, or None when the side stream still holds an earlier plan / the shape takes no plan (atomic kernel,
     third form)."""
-    import ctypes
     if not _needs_plan(offsets_host, B, D, C, L, S, H, dt, gridtype):
         return None
     side = _side(device)
     if _side_busy(side):
         return None
-    need = ctypes.c_uint64(0)
-    check(lib.cnerf_grid_encode_backward_workspace_bytes(offsets_host.ctypes.data, B, D, C, L, L, S, H, dt, ctypes.addressof(need)),
-          "grid_encode_backward_workspace_bytes")
-    if not need.value:
+    need = query_u64(lib.cnerf_grid_encode_backward_workspace_bytes, offsets_host.ctypes.data, B, D, C, L, L, S, H, dt)
+    if not need:
         return None
-    if side['ws'] is None or side['ws'].numel() < need.value:
-        side['ws'] = torch.empty(int(need.value * 1.25) + 256, dtype=torch.uint8, device=device)
-        scratch_reallocated()
-    ws = side['ws']
+    ws = side['ws'].reserve('plan', need, device)
     cur = torch.cuda.current_stream()
     side['stream'].wait_stream(cur)                              # the coordinates were produced on the current stream
     ok = ctypes.c_int(0)

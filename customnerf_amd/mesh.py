@@ -23,7 +23,7 @@ from functools import cached_property
 import numpy as np
 import torch
 
-from ._lib import lib, check, ptr, stream, require_cuda
+from ._lib import lib, check, ptr, stream, require_cuda, query_u64
 
 
 def _triple(v, name):
@@ -35,9 +35,7 @@ def _triple(v, name):
 
 def _bytes(name, *args):
     """cnerf_<name>_workspace_bytes(*args): the size of a pass's workspace"""
-    out = C.c_uint64(0)
-    check(getattr(lib, f"cnerf_{name}_workspace_bytes")(*args, C.byref(out)), f"{name}_workspace_bytes")
-    return out.value
+    return query_u64(getattr(lib, f"cnerf_{name}_workspace_bytes"), *args)
 
 
 def _workspace(dev, name, *args):

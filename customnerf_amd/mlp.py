@@ -4,27 +4,19 @@ be built and the tensors must live on the GPU.
 
 Reference call sites: nerf/network_grid.py:18-54 (RGB_network), :98-139.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check, ptr, stream, F16, F32, require_cuda, scratch_reallocated
+from ._lib import lib, check, ptr, stream, F16, F32, require_cuda, scratch_key, query_u64, ScratchCache
 
 _ACT = {"None": 0, "Sigmoid": 1}
-_WS = {}
+_WS = ScratchCache(factor=1.1, pad=256)          # the backward's per-workgroup partial-gradient rows
 
 
 def _workspace(P, cfg, dt, device):
-    need = ctypes.c_uint64(0)
     n_in, n_out, n_neurons, n_hidden, _ = cfg
-    check(lib.cnerf_mlp_backward_workspace_bytes(P, n_in, n_out, n_neurons, n_hidden, dt, ctypes.addressof(need)), "mlp_backward_workspace_bytes")
-    buf = _WS.get(device)
-    if buf is None or buf.numel() < need.value:
-        buf = torch.empty(int(need.value * 1.1) + 256, dtype=torch.uint8, device=device)
-        _WS[device] = buf
-        scratch_reallocated()
-    return buf
+    need = query_u64(lib.cnerf_mlp_backward_workspace_bytes, P, n_in, n_out, n_neurons, n_hidden, dt)
+    return _WS.reserve(scratch_key(device), need, device)
 
 
 def _rows(x):

@@ -15,7 +15,7 @@ Differences that are deliberate:
 import torch
 from torch.autograd import Function
 
-from .._lib import lib, check, ptr, stream, scratch_key, scratch_reallocated
+from .._lib import lib, check, ptr, stream, scratch_key, ScratchCache
 
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits", "march_rays_train",
            "composite_rays_train", "composite_rays_train_sdf", "march_rays", "composite_rays", "compact_rays_alive"]
@@ -85,7 +85,7 @@ def packbits(grid, thresh, bitfield=None):
 
 
 # ---------------------------------------------------------------------------------------------- training
-_HITS = {}
+_HITS = ScratchCache(dtype=torch.float32, shrink=4)
 _HITS_MAX_BYTES = 512 << 20          # above this the write pass re-marches (cnerf_march_rays_train_write) instead of keeping a probe list
 
 
@@ -97,16 +97,9 @@ def _hits_scratch(N, max_steps, device):
     need = N * max_steps * 2
     key = scratch_key(device)
     if need * 4 > _HITS_MAX_BYTES:
-        if _HITS.pop(key, None) is not None:
-            scratch_reallocated()
+        _HITS.drop(key)
         return None
-    buf = _HITS.get(key)
-    if buf is None or buf.numel() < need or buf.numel() > 4 * need:
-        _HITS.pop(key, None)
-        buf = None                                                  # drop the old block before asking for the new one
-        buf = _HITS[key] = torch.empty(need, dtype=torch.float32, device=device)
-        scratch_reallocated()
-    return buf
+    return _HITS.reserve(key, need, device)
 
 
 def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars, step_counter=None, mean_count=-1,

@@ -6,13 +6,12 @@ import ctypes
 
 import torch
 
-from .._lib import lib, check, ptr, stream, require_cuda, SdGemmDesc
+from .._lib import lib, check, ptr, stream, require_cuda, SdGemmDesc, query_u64, ScratchCache
 
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU, ACT_GEGLU = 0, 1, 2, 3, 4
 # round 6: GroupNorm statistics / LayerNorm riding on the split-K tail kernel and on the channel concat.  False restores the round-5 launches
 # (stand-alone k_gn_stats / k_layernorm) — the A side of scratch/edit_ab.py's same-box comparison; nothing else reads it.
 TAIL_FUSION = True
-_WS = {}
 _PROFILE = None
 
 
@@ -23,28 +22,22 @@ def set_profile(records):
     _PROFILE = records
 
 
-_WS_RETIRED = []          # outgrown workspaces stay allocated: HIP graphs captured earlier (UNet.graphed) hold their addresses
+_WS = ScratchCache(floor=64 << 20, retire=True)
+_WS_RETIRED = _WS.retired          # outgrown workspaces stay allocated: HIP graphs captured earlier (UNet.graphed) hold their addresses
 
 
 def _workspace(nbytes, device):
     """Split-K scratch shared by all GEMM launches on `device`.  When a later GEMM needs more than the current buffer, the old one is
     RETIRED, not freed: a captured graph replays its GEMM nodes with the pointer it was captured with, and a freed block would be
     handed to some other tensor by the caching allocator while those replays keep writing partial sums into it."""
-    buf = _WS.get(device)
-    if buf is None or buf.numel() < nbytes:
-        if buf is not None:
-            _WS_RETIRED.append(buf)
-        buf = torch.empty(max(int(nbytes), 64 << 20), dtype=torch.uint8, device=device)
-        _WS[device] = buf
-    return buf
+    return _WS.reserve(device, int(nbytes), device)
 
 
 def _launch(d, device):
     """-> True when the library ran the problem split-K (round 6: its tail kernel fills desc.gn_sums like the one-launch epilogue does)"""
-    need = ctypes.c_uint64(0)
-    check(lib.cnerf_sd_gemm_workspace_bytes(ctypes.byref(d), ctypes.byref(need)), "sd_gemm_workspace_bytes")
-    ws = _workspace(need.value, device) if need.value else None
-    if not TAIL_FUSION and need.value:
+    need = query_u64(lib.cnerf_sd_gemm_workspace_bytes, ctypes.byref(d))
+    ws = _workspace(need, device) if need else None
+    if not TAIL_FUSION and need:
         d.gn_sums = None
     if _PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -53,7 +46,7 @@ def _launch(d, device):
     if _PROFILE is not None:
         e1.record()
         _PROFILE.append((e0, e1, 2.0 * d.M * d.N * d.K * d.batch_outer * d.batch_inner, (int(d.M), int(d.N), int(d.K), int(d.mode), int(d.batch_outer * d.batch_inner), int(d.H_in), int(d.Cin), int(d.tstride), int(d.ups))))
-    return need.value > 0
+    return need > 0
 
 
 def _attach_gn(d, gn, M, N):

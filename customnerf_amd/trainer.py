@@ -257,6 +257,7 @@ class CheckpointMixin:
         if self._graph_inputs() != before:
             self.__dict__.pop('_graphs', None)
             self.__dict__.pop('_graph_pool', None)
+            self.__dict__.pop('_graph_gen', None)
         return info
 
 
@@ -441,7 +442,8 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
     def train_step_graphed(self, rays_o, rays_d, rgbs, mask, **render_kw):
         """Buffer ownership: everything a captured graph reads is either one of the view's four resident tensors (pinned by the cache entry), a
         parameter / its .grad / optimiser state (never reallocated), an allocation made during capture (graph pool), or a cached scratch buffer
-        — and the cache is flushed whenever one of those is reallocated (_lib.scratch_generation).
+        (_lib.ScratchCache) — and the graph cache is flushed whenever one of those is reallocated: self._graph_gen is the _lib.scratch_generation()
+        the cached graphs are valid for.
 
         train_step with render + loss + backward replayed as ONE hipGraph per view (opt-in).  A view is recognised by the addresses of its four
         resident tensors (a dataset keeps its rays on the GPU and hands the same tensors out every epoch); the first visit runs two eager steps
@@ -458,7 +460,7 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
         tensors = (rays_o, rays_d, rgbs, mask)
         key = tuple((t.data_ptr(), tuple(t.shape), t.dtype) for t in tensors) + (tuple(sorted(render_kw.items())),)
         cache = self.__dict__.setdefault('_graphs', {})
-        if cache and any(e[3] != scratch_generation() for e in cache.values()):
+        if cache and self._graph_gen != scratch_generation():
             # a grow-on-demand workspace (scatter plan, partial-gradient rows) was reallocated since a cached graph was captured — e.g. by an
             # eval_step on a larger view: it holds the freed buffer's address.  Drop them all (and their pool); every view recaptures.
             cache.clear()
@@ -482,17 +484,15 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
                     loss = loss.detach()
             finally:
                 self.scaler.watch(False)
-            gen1 = scratch_generation()
-            if gen1 != gen0 and cache:
+            if scratch_generation() != gen0 and cache:
                 # The workspaces are keyed by (device, stream): the ones a graph references belong to the CAPTURE stream and are allocated
                 # (graph pool) or re-grown during a capture.  This view grew one — in its warm-up or in its capture — so every graph captured
                 # before holds the address of a block that went back to the shared pool and may alias this view's allocations: drop them
                 # (they recapture on their next visit); the new graph, captured against the buffers as they are now, stays.
                 cache.clear()
             self._graph_pool = graph.pool()
-            ent = cache[key] = (graph, loss, tensors, gen1)          # (the tensors keep the captured addresses alive; gen1: the scratch generation this graph is valid for)
-            for k_ in list(cache):                                   # (entries that survived are valid for the current generation too)
-                cache[k_] = cache[k_][:3] + (gen1,)
+            self._graph_gen = scratch_generation()                   # (entries that survived are valid for the current generation too)
+            ent = cache[key] = (graph, loss, tensors)                # (the tensors keep the captured addresses alive)
         self.model.train()
         self._inf_folded = inf_check_is_folded(self)                 # (the captured kernels carry the pointer they were captured with: this scaler's)
         ent[0].replay()

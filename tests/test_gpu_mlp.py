@@ -77,6 +77,36 @@ def test_mlp_backward(n_in, n_out, nh, act, half):
     assert torch.all(go[n_out:] == 0)
 
 
+def test_mlp_backward_workspace_is_per_stream():
+    """two streams running a Network backward do not share one set of partial-gradient rows: mlp._WS is keyed like field._WS, by
+    (device, stream), and the gradients do not depend on the stream (the kernels are deterministic: bit-equal)"""
+    from customnerf_amd import mlp, tcnn
+    from customnerf_amd._lib import scratch_key
+    net = tcnn.Network(32, 16, {"n_neurons": 64, "n_hidden_layers": 1}).cuda()
+    g = torch.Generator().manual_seed(5)
+    x = (torch.rand(512, 32, generator=g) * 2 - 1).cuda()
+    gy = torch.randn(512, 16, generator=g).cuda()
+
+    def run():
+        net.params.grad = None
+        xg = x.clone().requires_grad_(True)
+        y = net(xg)
+        y.backward(gy.to(y.dtype))
+        return scratch_key(x.device), net.params.grad.clone(), xg.grad.clone()
+
+    mlp._WS.clear()
+    k0, gp0, gx0 = run()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        k1, gp1, gx1 = run()
+    torch.cuda.current_stream().wait_stream(s)
+    assert k0 != k1 and set(mlp._WS) == {k0, k1}
+    assert mlp._WS[k0].data_ptr() != mlp._WS[k1].data_ptr()
+    assert gp0.abs().max() > 0 and gx0.abs().max() > 0
+    assert torch.equal(gp0, gp1) and torch.equal(gx0, gx1)
+
+
 def test_mlp_strided_input_empty_and_errors():
     from customnerf_amd import tcnn
     net = _net(27, 3, 1, "Sigmoid", torch.float32)
