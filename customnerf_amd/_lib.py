@@ -90,6 +90,9 @@ SIGNATURES = {
     "cnerf_marching_cubes_workspace_bytes": [u32, u32, u32, vp],
     "cnerf_marching_cubes_count": [vp, u32, u32, u32, f32, vp, u64, vp, vp],
     "cnerf_marching_cubes_emit": [vp, u32, u32, u32, f32, vp, vp, vp, u64, vp, vp, vp, u32, u32, vp],
+    "cnerf_marching_cubes_sparse_workspace_bytes": [u32, vp],
+    "cnerf_marching_cubes_sparse_count": [vp, vp, vp, u32, u32, u32, u32, f32, vp, u64, vp, vp, vp],
+    "cnerf_marching_cubes_sparse_emit": [vp, vp, vp, u32, u32, u32, u32, f32, vp, vp, vp, u64, vp, vp, vp, vp, u32, u32, vp],
     "cnerf_mesh_components_workspace_bytes": [u32, u32, vp],
     "cnerf_mesh_components_count": [vp, u32, u32, u32, i32, vp, u64, vp, vp],
     "cnerf_mesh_components_emit": [vp, vp, u32, vp, u32, u32, i32, vp, u64, vp, vp, vp, vp, u32, u32, vp],

@@ -10,35 +10,16 @@
 //
 // Vertices are ordered by (linear point index, axis), triangles by (linear cell index, table order): the output does not depend on
 // scheduling.  Workspace: header (overflow flag) | case bytes [N] | mask bytes [N] | vertex bases uint32 [N] | workgroup totals uint2 [N/256].
-#include "common.h"
-#include "mc_tables.h"
-#include "mesh_common.h"        // MC_BLOCK, mc_block_prefix / mc_block_total, mc_scan_totals, MeshCarve
+#include "mesh_mc.h"            // the arithmetic and workspace regions shared with mesh_sparse.hip; mc_tables.h, mesh_common.h
 
 namespace {
-
-struct McPtr {
-    uint32_t *flag;                                  // header: the overflow flag
-    uint8_t *cases, *masks;
-    uint32_t *vbase;
-    uint2 *sums;
-};
 
 // the workspace of n grid points: its regions in order -> total bytes (ws == nullptr: the size only)
 uint64_t mc_carve(void *ws, uint64_t n, McPtr &p) {
     MeshCarve c(ws);
-    p.flag = c.header();
-    p.cases = c.take<uint8_t>(n);
-    p.masks = c.take<uint8_t>(n);
-    p.vbase = c.take<uint32_t>(n);
-    p.sums = c.take<uint2>(cn_div_up64(n, MC_BLOCK));
+    mc_take(c, n, p);
     return c.total();
 }
-
-struct McGeom {
-    float org[3], sp[3];
-};
-
-__device__ __forceinline__ bool mc_in(float v, float level) { return v >= level; }   // NaN: outside
 
 __global__ __launch_bounds__(MC_BLOCK) void k_mc_count(const float *__restrict__ vol, uint32_t nx, uint32_t ny, uint32_t nz, float level,
                                                        uint8_t *__restrict__ cases, uint8_t *__restrict__ masks, uint2 *__restrict__ sums) {
@@ -75,22 +56,15 @@ __global__ __launch_bounds__(MC_SCAN_BLOCK) void k_mc_scan(uint2 *__restrict__ s
                                                            uint32_t *__restrict__ flag) {
     uint64_t cv, ct;
     mc_scan_totals(sums, nblk, cv, ct);
-    if (threadIdx.x == 0) {
-        const bool over = cv > 0x7fffffffull || ct > 0x7fffffffull;
-        counts[0] = over ? 0xffffffffu : (uint32_t)cv;
-        counts[1] = over ? 0xffffffffu : (uint32_t)ct;
-        flag[0] = over ? 1u : 0u;
-    }
+    if (threadIdx.x == 0) mc_store_counts(cv, ct, counts, flag);
 }
 
-// d(vol)/d(axis b) at point p: central difference inside, one-sided at the volume's faces, divided by the spacing
-__device__ __forceinline__ float mc_grad(const float *__restrict__ vol, uint32_t p, uint32_t idx, uint32_t len, uint32_t stride, float sp) {
-    const bool lo = idx > 0, hi = idx + 1 < len;
-    const float vp = hi ? vol[p + stride] : vol[p];
-    const float vm = lo ? vol[p - stride] : vol[p];
-    const float h = (lo && hi) ? 2.0f : 1.0f;
-    return (vp - vm) / (h * sp);
-}
+// mc_grad's fetch for a dense volume: the value d steps of `stride` from point p
+struct McDenseVal {
+    const float *__restrict__ vol;
+    uint32_t p, stride;
+    __device__ __forceinline__ float operator()(int d) const { return d > 0 ? vol[p + stride] : d < 0 ? vol[p - stride] : vol[p]; }
+};
 
 __global__ __launch_bounds__(MC_BLOCK) void k_mc_verts(const float *__restrict__ vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, McGeom g,
                                                        const uint8_t *__restrict__ masks, const uint2 *__restrict__ sums,
@@ -114,33 +88,25 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_verts(const float *__restrict__
         if (!((m >> a) & 1u)) continue;
         const uint32_t j = i + stride[a];
         if (vid < max_verts) {
-            const float v1 = vol[j];
-            float t = (level - v0) / (v1 - v0);
-            t = t != t ? 0.5f : fminf(fmaxf(t, 0.0f), 1.0f);
+            const float t = mc_cross_t(level, v0, vol[j]);
             float p[3];
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const float fi = (float)idx[b];
-                p[b] = b == a ? g.org[b] + (fi + t) * g.sp[b] : g.org[b] + fi * g.sp[b];
-            }
+            mc_vertex_pos(g, idx, a, t, p);
             const uint64_t o = 3 * (uint64_t)vid;
             verts[o] = p[0];
             verts[o + 1] = p[1];
             verts[o + 2] = p[2];
             if (normals) {
-                float nv[3];
+                float g0[3], g1[3], nv[3];
 #pragma unroll
                 for (int b = 0; b < 3; ++b) {
                     const uint32_t jb = b == a ? idx[b] + 1 : idx[b];
-                    const float g0 = mc_grad(vol, i, idx[b], len[b], stride[b], g.sp[b]);
-                    const float g1 = mc_grad(vol, j, jb, len[b], stride[b], g.sp[b]);
-                    nv[b] = -(g0 + t * (g1 - g0));
+                    g0[b] = mc_grad(McDenseVal{vol, i, stride[b]}, idx[b], len[b], g.sp[b]);
+                    g1[b] = mc_grad(McDenseVal{vol, j, stride[b]}, jb, len[b], g.sp[b]);
                 }
-                const float l = sqrtf(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
-                const float s = l > 0.0f ? l : 1.0f;
-                normals[o] = nv[0] / s;
-                normals[o + 1] = nv[1] / s;
-                normals[o + 2] = nv[2] / s;
+                mc_normal(g0, g1, t, nv);
+                normals[o] = nv[0];
+                normals[o + 1] = nv[1];
+                normals[o + 2] = nv[2];
             }
         }
         ++vid;
@@ -164,10 +130,10 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_faces(uint32_t nx, uint32_t ny,
         int32_t tri[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const uint32_t e = (uint32_t)cn_mc_tri[c][3 * k + q];
-            const uint32_t corner = cn_mc_edge_corner[e], axis = cn_mc_edge_axis[e];
+            uint32_t corner, axis;
+            mc_edge_owner((uint32_t)cn_mc_tri[c][3 * k + q], corner, axis);
             const uint32_t owner = i + (corner & 1u ? nyz : 0u) + (corner & 2u ? nz : 0u) + (corner & 4u ? 1u : 0u);
-            tri[q] = (int32_t)(vbase[owner] + (uint32_t)__popc(masks[owner] & ((1u << axis) - 1u)));
+            tri[q] = mc_vertex_id(vbase[owner], masks[owner], axis);
         }
         const uint64_t o = 3 * (uint64_t)f;
         faces[o] = tri[0];
@@ -214,11 +180,7 @@ int cnerf_marching_cubes_emit(const float *vol, uint32_t nx, uint32_t ny, uint32
     const uint32_t n = nx * ny * nz;
     McPtr p;
     if (const int rc = mesh_check_ws(ws, ws_bytes, mc_carve(ws, n, p))) return rc;
-    McGeom g;
-    for (int b = 0; b < 3; ++b) {
-        g.org[b] = origin_host[b];
-        g.sp[b] = spacing_host[b];
-    }
+    const McGeom g = mc_geom(origin_host, spacing_host);
     hipLaunchKernelGGL(k_mc_verts, mesh_grid(n), dim3(MC_BLOCK), 0, CN_STREAM(stream), vol, nx, ny, nz, level, g, (const uint8_t *)p.masks,
                        (const uint2 *)p.sums, (const uint32_t *)p.flag, p.vbase, verts, max_verts ? normals : nullptr, max_verts);
     hipLaunchKernelGGL(k_mc_faces, mesh_grid(n), dim3(MC_BLOCK), 0, CN_STREAM(stream), nx, ny, nz, (const uint8_t *)p.cases,

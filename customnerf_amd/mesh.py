@@ -1,4 +1,6 @@
-"""Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*), mesh cleanup on the GPU (csrc/mesh_clean.hip:
+"""Mesh export: marching cubes on the GPU (csrc/mesh.hip, cnerf_marching_cubes_*) over a dense volume, or over the 8^3-point bricks around
+the surface only (csrc/mesh_sparse.hip, cnerf_marching_cubes_sparse_*; sparse_volume finds the bricks from a field without evaluating the
+whole lattice, and the mesh is the dense one bit for bit in another order), mesh cleanup on the GPU (csrc/mesh_clean.hip:
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
 face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU,
 uniform or with cells sized by the faces' edges (csrc/mesh_texture.hip), or into an atlas of axis-projected charts (csrc/mesh_charts.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
@@ -96,6 +98,238 @@ def marching_cubes(volume, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0
     check(lib.cnerf_marching_cubes_emit(ptr(vol), nx, ny, nz, level, org, sp, ptr(ws), nbytes, _p(verts), _p(nrm), _p(faces), V, F, stream()),
           "marching_cubes_emit")
     return verts, faces, nrm
+
+
+# ------------------------------------------------------------------------------------------------ brick-sparse extraction
+BRICK = 8                                                                      # lattice points per brick and axis (csrc/mesh_sparse.hip)
+_BRICK_POINTS = BRICK ** 3
+
+
+class SparseVolume:
+    """A lattice of `shape` points of which only some bricks of 8 x 8 x 8 points hold values (include/customnerf_hip.h, the sparse
+    marching-cubes section): coords [n, 3] int32, unique and sorted; values [n, 512] float32, point (x, y, z) in brick
+    (x >> 3, y >> 3, z >> 3) at ((x & 7) * 8 + (y & 7)) * 8 + (z & 7); nbr [n, 27] int32, the brick at every offset of {-1, 0, 1}^3 or -1.
+    origin / spacing are 3 floats.  Counters of how it was made: `evaluations` field values asked for (probe lattice + bricks),
+    `rounds` passes of the growth loop (the last one found nothing missing), `probe` the seeding stride."""
+
+    def __init__(self, shape, origin, spacing, coords, values, nbr, evaluations=0, rounds=0, probe=1):
+        self.shape = tuple(int(s) for s in shape)
+        self.origin, self.spacing = tuple(float(x) for x in origin), tuple(float(x) for x in spacing)
+        self.coords, self.values, self.nbr = coords, values, nbr
+        self.evaluations, self.rounds, self.probe = int(evaluations), int(rounds), int(probe)
+
+    @property
+    def n_bricks(self):
+        return int(self.coords.shape[0])
+
+
+def sparse_workspace_bytes(n_bricks):
+    return _bytes("marching_cubes_sparse", int(n_bricks))
+
+
+def _brick_grid(shape):
+    return tuple(-(-int(s) // BRICK) for s in shape)
+
+
+def _brick_coords(keys, gb):
+    """brick keys (bx * gby + by) * gbz + bz, int64 -> [n, 3] int64"""
+    return torch.stack([keys // (gb[1] * gb[2]), (keys // gb[2]) % gb[1], keys % gb[2]], dim=1)
+
+
+def _brick_offsets(dev):
+    o = torch.arange(27, device=dev)
+    return torch.stack([o // 9 - 1, (o // 3) % 3 - 1, o % 3 - 1], dim=1)        # slot (dx + 1) 9 + (dy + 1) 3 + dz + 1
+
+
+def _around(keys, gb):
+    """-> (keys of the 27 bricks around each brick [n, 27], whether each lies inside the brick grid [n, 27])"""
+    c = _brick_coords(keys, gb)[:, None, :] + _brick_offsets(keys.device)[None]
+    inside = ((c >= 0) & (c < torch.tensor(gb, device=keys.device))).all(-1)
+    return (c[..., 0] * gb[1] + c[..., 1]) * gb[2] + c[..., 2], inside
+
+
+def _find(keys, k):
+    """position of every k in the sorted unique keys, and whether it is there"""
+    if not keys.numel():
+        return torch.zeros_like(k), torch.zeros_like(k, dtype=torch.bool)
+    pos = torch.searchsorted(keys, k.clamp(min=0)).clamp(max=keys.numel() - 1)
+    return pos, keys[pos] == k
+
+
+def _brick_nbr(keys, gb):
+    k, inside = _around(keys, gb)
+    pos, found = _find(keys, k)
+    return torch.where(found & inside, pos, torch.full_like(pos, -1)).to(torch.int32).contiguous()
+
+
+def _brick_values(fetch, keys, gb, chunk):
+    """values [n, 512] of the bricks `keys`: fetch(ijk [m, 3] int64 global lattice indices) -> [m] float32"""
+    dev = keys.device
+    loc = torch.arange(_BRICK_POINTS, device=dev)
+    loc = torch.stack([loc >> 6, (loc >> 3) & 7, loc & 7], dim=1)
+    out = torch.empty(keys.numel(), _BRICK_POINTS, dtype=torch.float32, device=dev)
+    per = max(1, int(chunk) // _BRICK_POINTS)
+    for s in range(0, keys.numel(), per):
+        ijk = (_brick_coords(keys[s:s + per], gb)[:, None, :] * BRICK + loc[None]).reshape(-1, 3)
+        out[s:s + per] = fetch(ijk).reshape(-1, _BRICK_POINTS)
+    return out
+
+
+def _probe_index(n, probe, dev):
+    """the multiples of `probe` below n, plus the last index"""
+    idx = list(range(0, n, probe))
+    if idx[-1] != n - 1:
+        idx.append(n - 1)
+    return torch.tensor(idx, dtype=torch.int64, device=dev)
+
+
+def _seed_keys(inside, pidx, probe, gb):
+    """Keys of the seed bricks: brick b is one when the probe points with index in [8 b - probe, 8 b + 8 + probe] on every axis are not
+    all on one side.  inside [Px, Py, Pz] bool (value >= level), pidx the three probe index lists."""
+    def box_any(a):
+        for ax in range(3):
+            lo = torch.arange(gb[ax], device=a.device)[:, None] * BRICK
+            m = ((pidx[ax][None] >= lo - probe) & (pidx[ax][None] <= lo + BRICK + probe)).float()
+            a = (torch.tensordot(m, a.movedim(ax, 0), dims=1) > 0).float().movedim(0, ax)
+        return a > 0
+    seed = box_any(inside.float()) & box_any((~inside).float())
+    return torch.nonzero(seed.reshape(-1)).reshape(-1)
+
+
+def _sparse_count(values, coords, nbr, shape, level, want_state):
+    """cnerf_marching_cubes_sparse_count -> (workspace, its bytes, counts [3] on the device, state [n] uint8 or None)"""
+    dev, n = values.device, int(coords.shape[0])
+    ws, nbytes = _workspace(dev, "marching_cubes_sparse", n)
+    counts = torch.zeros(3, dtype=torch.int32, device=dev)
+    state = torch.empty(n, dtype=torch.uint8, device=dev) if want_state else None
+    check(lib.cnerf_marching_cubes_sparse_count(ptr(values), ptr(coords), ptr(nbr), n, *shape, float(level), ptr(ws), nbytes, ptr(state),
+                                                ptr(counts), stream()), "marching_cubes_sparse_count")
+    return ws, nbytes, counts, state
+
+
+def _grow(fetch, keys, shape, origin, spacing, level, chunk, max_rounds, evaluations, probe, what):
+    """Seeds -> the SparseVolume at the fixed point of: mesh state of the bricks (the count pass), need = the 26 neighbours of the
+    crossing bricks that are not there yet, fetch and merge them."""
+    gb, dev = _brick_grid(shape), keys.device
+    values = _brick_values(fetch, keys, gb, chunk)
+    evaluations += values.numel()
+    rounds = 0
+    nbr = torch.empty(0, 27, dtype=torch.int32, device=dev)
+    while keys.numel():
+        if rounds >= max_rounds:
+            raise ValueError(f"{what}: the surface's bricks were still growing after max_rounds={max_rounds} rounds")
+        rounds += 1                                                             # a round: one count pass; the last finds nothing missing
+        nbr = _brick_nbr(keys, gb)
+        state = _sparse_count(values, _brick_coords(keys, gb).to(torch.int32).contiguous(), nbr, shape, level, True)[3]
+        k, inside = _around(keys[(state & 1).bool()], gb)
+        cand = torch.unique(k[inside])
+        need = cand[~_find(keys, cand)[1]]
+        if not need.numel():                                                    # (the host read of a round)
+            break
+        more = _brick_values(fetch, need, gb, chunk)
+        evaluations += more.numel()
+        keys, perm = torch.sort(torch.cat([keys, need]))
+        values = torch.cat([values, more])[perm]
+    return SparseVolume(shape, origin, spacing, _brick_coords(keys, gb).to(torch.int32).contiguous(), values.contiguous(), nbr,
+                        evaluations=evaluations, rounds=rounds, probe=probe)
+
+
+def _shape3(shape, what):
+    s = tuple(int(x) for x in shape)
+    if len(s) != 3 or min(s) < 2 or max(s) > 1 << 20:
+        raise ValueError(f"{what}: shape must be 3 sizes in [2, 2^20], got {tuple(shape)}")
+    return s
+
+
+def sparse_volume(sigma_fn, shape, origin, spacing, level, probe=4, chunk=2 ** 21, max_rounds=64, device=None):
+    """The bricks of a `shape` lattice that the isosurface {field == level} passes through, found without evaluating the whole lattice.
+    sigma_fn(x [m, 3] float32 on the device) -> [m] values, elementwise; lattice point ijk sits at origin + ijk.float() * spacing, computed
+    on the device in float32 (what NeRFRenderer.density_volume computes, so both ask the field at identical points).
+    Seeding: the field on the probe lattice — the indices that are multiples of `probe` on each axis plus the last one; a brick is a seed
+    when the probe values around it (index box [8 b - probe, 8 b + 8 + probe]^3) are not all on one side of `level`.  Growth: evaluate
+    the seeds, then repeat: the count pass of marching_cubes_sparse says which bricks cross; their 26 neighbours that are missing are
+    evaluated and merged; stop when none is missing (ValueError when max_rounds such rounds have not got there).  At that fixed point every crossing brick has
+    all its neighbours, which is what marching_cubes_sparse needs, and every piece of surface connected — through cells whose corners
+    lie on both sides — to something the seeding saw is covered, so the mesh equals marching_cubes of the full lattice.
+    probe=1 examines every lattice point: nothing can be missed.  With probe=k only surface components that lie wholly between probe
+    points — no probe point inside them or no probe point outside a hole — can be missed: the class of loss of an extraction at
+    resolution / k, and nothing that is connected to a seen crossing is lost.
+    -> SparseVolume; .evaluations counts the calls' points (probe lattice + 512 per brick)."""
+    what = "sparse_volume"
+    shape, probe = _shape3(shape, what), int(probe)
+    if probe < 1:
+        raise ValueError(f"{what}: probe must be >= 1, got {probe}")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    org = torch.as_tensor(origin, dtype=torch.float32).reshape(3).to(dev)
+    sp = torch.as_tensor(spacing, dtype=torch.float32).reshape(3).to(dev)
+
+    def fetch(ijk):
+        return sigma_fn((org + ijk.float() * sp).contiguous()).reshape(-1).float()
+
+    pidx = [_probe_index(n, probe, dev) for n in shape]
+    P = tuple(len(p) for p in pidx)
+    n = P[0] * P[1] * P[2]
+    inside = torch.empty(n, dtype=torch.bool, device=dev)
+    for s in range(0, n, chunk):
+        i = torch.arange(s, min(s + chunk, n), device=dev, dtype=torch.int64)
+        ijk = torch.stack([pidx[0][i // (P[1] * P[2])], pidx[1][(i // P[2]) % P[1]], pidx[2][i % P[2]]], dim=1)
+        inside[s:s + len(i)] = fetch(ijk) >= float(level)
+    keys = _seed_keys(inside.view(P), pidx, probe, _brick_grid(shape))
+    return _grow(fetch, keys, shape, org.tolist(), sp.tolist(), level, chunk, max_rounds, n, probe, what)
+
+
+def sparse_volume_from_dense(volume, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """The SparseVolume of a CUDA float32 tensor [X, Y, Z] that is already there: the bricks sparse_volume(probe=1) selects, their values
+    gathered from the tensor."""
+    what = "sparse_volume_from_dense"
+    require_cuda(volume)
+    if volume.dim() != 3:
+        raise ValueError(f"{what}: volume must be [X, Y, Z], got {tuple(volume.shape)}")
+    vol = volume.detach().contiguous().float()
+    shape = _shape3(vol.shape, what)
+    hi = torch.tensor(shape, device=vol.device) - 1
+
+    def fetch(ijk):
+        i = torch.minimum(ijk, hi)                                             # entries past the lattice's end are never read
+        return vol[i[:, 0], i[:, 1], i[:, 2]]
+
+    pidx = [torch.arange(n, device=vol.device) for n in shape]
+    keys = _seed_keys(vol >= float(level), pidx, 1, _brick_grid(shape))
+    sp, org = _triple(spacing, "spacing"), _triple(origin, "origin")
+    return _grow(fetch, keys, shape, list(org), list(sp), level, 2 ** 21, 1 << 30, vol.numel(), 1, what)
+
+
+def marching_cubes_sparse(sv, level, normals=True, want_keys=False):
+    """marching_cubes over the bricks of a SparseVolume (csrc/mesh_sparse.hip): -> (verts, faces, normals or None[, keys]) on the device,
+    the mesh marching_cubes gives on the full lattice wherever the bricks cover the surface — the same bits; vertices ordered by (brick,
+    point in the brick, axis), triangles by (brick, cell in the brick, table order).  keys [V] int64 = ((x * ny + y) * nz + z) * 3 + axis
+    of every vertex: torch.argsort(keys) is the permutation into marching_cubes' order.  A brick through which the surface passes and
+    that lacks a neighbour is open and raises ValueError (sparse_volume never returns one); the three counts are the only host read."""
+    what = "marching_cubes_sparse"
+    require_cuda(sv.values, sv.coords, sv.nbr)
+    n, dev = sv.n_bricks, sv.values.device
+    if tuple(sv.values.shape) != (n, _BRICK_POINTS) or tuple(sv.coords.shape) != (n, 3) or tuple(sv.nbr.shape) != (n, 27):
+        raise ValueError(f"{what}: need values [n, 512], coords [n, 3] and nbr [n, 27], got {tuple(sv.values.shape)}, "
+                         f"{tuple(sv.coords.shape)} and {tuple(sv.nbr.shape)}")
+    values = sv.values.detach().contiguous().float()
+    coords, nbr = sv.coords.contiguous().to(torch.int32), sv.nbr.contiguous().to(torch.int32)
+    shape = _shape3(sv.shape, what)
+    sp, org = _triple(sv.spacing, "spacing"), _triple(sv.origin, "origin")
+    level = float(level)
+    V = F = 0
+    if n:
+        ws, nbytes, counts, _ = _sparse_count(values, coords, nbr, shape, level, False)
+        V, F, n_open = (int(c) & 0xffffffff for c in counts.cpu())             # the one host read
+        if n_open:
+            raise ValueError(f"{what}: {n_open} open bricks: the surface passes through them and a neighbour brick is missing")
+        if V == 0xffffffff:
+            raise ValueError(f"marching_cubes: the mesh of a {shape[0]}x{shape[1]}x{shape[2]} volume has more than 2^31 - 1 vertices or triangles")
+    verts, nrm, faces, _ = _outputs(dev, V, F, normals, old_index=False)
+    keys = torch.empty(V, dtype=torch.int64, device=dev) if want_keys else None
+    if n:
+        check(lib.cnerf_marching_cubes_sparse_emit(ptr(values), ptr(coords), ptr(nbr), n, *shape, level, org, sp, ptr(ws), nbytes, _p(verts),
+                                                   _p(nrm), _p(faces), _p(keys), V, F, stream()), "marching_cubes_sparse_emit")
+    return (verts, faces, nrm, keys) if want_keys else (verts, faces, nrm)
 
 
 def _mesh_args(verts, faces, normals, what):

@@ -449,6 +449,24 @@ class NeRFRenderer(nn.Module):
             raise ValueError(f"extract_mesh: need resolution >= 2 and a non-empty box, got {resolution} and {aabb.tolist()}")
         return lo, (hi - lo) / (resolution - 1)
 
+    def _mesh_sigma(self, x, part='all', view_dir=(0.0, 0.0, -1.0)):
+        """The field that mesh extraction takes the isosurface of, at positions x [m, 3] -> [m] float32 (density_volume's docstring says
+        what `part` selects); elementwise, so the dense lattice and the bricks of a sparse extraction ask it alike."""
+        if part not in ('all', 'fg', 'bg'):
+            raise ValueError(f"extract_mesh: part must be 'all', 'fg' or 'bg', got {part!r}")
+        if part == 'all':
+            return self.density(x)['sigma'].reshape(-1).float()
+        d = torch.tensor(view_dir, dtype=torch.float32, device=x.device).reshape(1, 3)
+        sigma, rgbc = self(x, d.expand(len(x), 3).contiguous())[:2]
+        if rgbc.shape[-1] < 4:
+            raise ValueError("extract_mesh: part='fg' / 'bg' needs a field with a confidence channel (opt.train_conf)")
+        sigma, conf = sigma.reshape(-1).float(), rgbc[:, 3].float()
+        if bool(getattr(self.opt, 'soft_mask', False)):
+            m = torch.sigmoid((conf - float(getattr(self.opt, 'conf_thr', 0.5))) * 100)
+            return sigma * m if part == 'fg' else sigma * (1 - m)
+        m = conf > 0.5
+        return torch.where(m if part == 'fg' else ~m, sigma, torch.zeros_like(sigma))
+
     @torch.no_grad()
     def density_volume(self, resolution=256, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0)):
         """sigma on a resolution^3 lattice over `aabb` (default aabb_infer), [R, R, R] float32 in meshgrid('ij') order (z fastest).
@@ -463,32 +481,17 @@ class NeRFRenderer(nn.Module):
         lo, step = lo.to(dev), step.to(dev)
         n = R ** 3
         vol = torch.empty(n, dtype=torch.float32, device=dev)
-        d = torch.tensor(view_dir, dtype=torch.float32, device=dev).reshape(1, 3)
-        soft, thr = bool(getattr(self.opt, 'soft_mask', False)), float(getattr(self.opt, 'conf_thr', 0.5))
         for s in range(0, n, chunk):
             i = torch.arange(s, min(s + chunk, n), device=dev, dtype=torch.int64)
             ijk = torch.stack([i // (R * R), (i // R) % R, i % R], dim=1).float()
-            x = (lo + ijk * step).contiguous()
-            if part == 'all':
-                vol[s:s + len(i)] = self.density(x)['sigma'].reshape(-1).float()
-                continue
-            sigma, rgbc = self(x, d.expand(len(i), 3).contiguous())[:2]
-            if rgbc.shape[-1] < 4:
-                raise ValueError("extract_mesh: part='fg' / 'bg' needs a field with a confidence channel (opt.train_conf)")
-            sigma, conf = sigma.reshape(-1).float(), rgbc[:, 3].float()
-            if soft:
-                m = torch.sigmoid((conf - thr) * 100)
-                vol[s:s + len(i)] = sigma * m if part == 'fg' else sigma * (1 - m)
-            else:
-                m = conf > 0.5
-                vol[s:s + len(i)] = torch.where(m if part == 'fg' else ~m, sigma, torch.zeros_like(sigma))
+            vol[s:s + len(i)] = self._mesh_sigma((lo + ijk * step).contiguous(), part, view_dir)
         return vol.view(R, R, R)
 
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
                      smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0,
-                     texture_layout='uniform', bake_from='mesh', bake_reach=None, normal_map=False):
+                     texture_layout='uniform', bake_from='mesh', bake_reach=None, normal_map=False, sparse=False, sparse_probe=4):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -529,7 +532,16 @@ class NeRFRenderer(nn.Module):
         one that stays valid when the object is rotated or instanced (mesh.bake_texture(normal_map='tangent'), csrc/mesh_tangent.hip):
         'tangents' [F, 3, 4] float32, the frame of every face corner, joins the dict; without bake_from='source' the map is flat,
         (128, 128, 255).  'normal_space' ('object' or 'tangent') joins the dict with either.  With the defaults none of these keys is
-        present."""
+        present.
+        sparse=True extracts the same surface without the dense volume, which is what makes resolutions of 1024 and beyond affordable
+        (the dense path holds resolution^3 values plus 6 bytes of workspace per point and refuses more than 2^31 points): the field is
+        evaluated on a probe lattice of every sparse_probe-th point, then only in the bricks of 8^3 points around the surface found
+        there, grown until the surface is covered (mesh.sparse_volume), and marching cubes runs over that brick list
+        (mesh.marching_cubes_sparse, csrc/mesh_sparse.hip).  Same lattice, threshold and part, the same arithmetic: the mesh has the
+        dense path's vertices and triangles, bit for bit, in brick order in place of lattice order — except that, with sparse_probe=k > 1,
+        a surface component small enough to lie wholly between the probe points (as an extraction at resolution / k would lose it) can be
+        missed; sparse_probe=1 misses nothing.  'volume' is then None and 'sparse' joins the dict: {'bricks', 'evaluations', 'rounds',
+        'points': resolution^3}.  Every later stage works on the mesh and is the same.  With sparse=False the key is absent."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -562,8 +574,18 @@ class NeRFRenderer(nn.Module):
         reach = 4.0 * float(step.max()) if bake_reach is None else float(bake_reach)
         if from_source and not reach > 0.0:
             raise ValueError(f"extract_mesh: bake_reach must be > 0, got {bake_reach}")
-        vol = self.density_volume(R, aabb, chunk, part, view_dir)
-        verts, faces, normals = _mesh.marching_cubes(vol, threshold, spacing=step.tolist(), origin=lo.tolist())
+        if int(sparse_probe) < 1:
+            raise ValueError(f"extract_mesh: sparse_probe must be >= 1 (every how many lattice points the field is probed), got {sparse_probe}")
+        sparse_info = None
+        if sparse:
+            vol = None
+            sv = _mesh.sparse_volume(lambda x: self._mesh_sigma(x, part, view_dir), (R, R, R), lo, step, threshold, probe=int(sparse_probe),
+                                     chunk=chunk, device=self.aabb_infer.device)
+            verts, faces, normals = _mesh.marching_cubes_sparse(sv, threshold)
+            sparse_info = {'bricks': sv.n_bricks, 'evaluations': sv.evaluations, 'rounds': sv.rounds, 'points': R ** 3}
+        else:
+            vol = self.density_volume(R, aabb, chunk, part, view_dir)
+            verts, faces, normals = _mesh.marching_cubes(vol, threshold, spacing=step.tolist(), origin=lo.tolist())
         if int(min_component_faces) > 0 or keep_largest:
             verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
                                                                      largest=bool(keep_largest))
@@ -600,6 +622,8 @@ class NeRFRenderer(nn.Module):
                 tangents = baked[2].get('tangents')
         m = {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
              'uvs': uvs, 'texture': tex, 'texture_layout': texture_layout}
+        if sparse_info is not None:
+            m['sparse'] = sparse_info
         if normal_map:
             m['normal_map'] = nmap
             m['normal_space'] = 'tangent' if isinstance(normal_map, str) else 'object'
@@ -625,7 +649,7 @@ class NeRFRenderer(nn.Module):
         their normals and colours, or the ambient occlusion as grey, as for PLY; unlit unless it carries a normal map); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
         extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), texture_layout, deviation /
-        deviation_spacing, ao, bake_from and bake_reach pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
+        deviation_spacing, ao, bake_from, bake_reach, sparse and sparse_probe pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
         in the material) and, like texture=, needs an .obj path; normal_map='tangent' needs a .glb path (OBJ carries no tangents) and
         normal_map=True is refused for .glb (glTF has no object-space slot).  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written

@@ -47,7 +47,8 @@ extern "C" {
  *    mesh (additive, same version) — cnerf_mesh_bvh_project; the chart-based atlas (additive, same version) —
  *    cnerf_mesh_atlas_proj_workspace_bytes / _charts / _pack / _raster / _points / _store / _fill; welded vertices, tangent frames and
  *    tangent-space normal maps (additive, same version) — cnerf_mesh_tangent_workspace_bytes / _weld / _frames / _vertices and
- *    cnerf_mesh_atlas_tspace / cnerf_mesh_atlas_sized_tspace / cnerf_mesh_atlas_proj_tspace. */
+ *    cnerf_mesh_atlas_tspace / cnerf_mesh_atlas_sized_tspace / cnerf_mesh_atlas_proj_tspace; marching cubes over a list of bricks
+ *    (additive, same version) — cnerf_marching_cubes_sparse_workspace_bytes / _count / _emit. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -533,6 +534,42 @@ int cnerf_marching_cubes_count(const float *vol, uint32_t nx, uint32_t ny, uint3
 int cnerf_marching_cubes_emit(const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, const float *origin_host,
                               const float *spacing_host, void *ws, uint64_t ws_bytes, float *verts, float *normals, int32_t *faces,
                               uint32_t max_verts, uint32_t max_faces, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Marching cubes over a brick-sparse volume (customnerf_amd/mesh.py sparse_volume / marching_cubes_sparse; csrc/mesh_sparse.hip; the
+ * reference has none): the passes above over a list of n_bricks bricks of 8 x 8 x 8 lattice points in place of every point of an
+ * nx x ny x nz lattice, so that a fine lattice costs memory and field evaluations only near the surface.  Same table, same arithmetic
+ * (csrc/mesh_mc.h holds the one definition of both): where the bricks cover the surface the mesh is the dense one, bit for bit, in
+ * another order.
+ *   values float32 [n][512]: lattice point (x, y, z) lives in brick (x >> 3, y >> 3, z >> 3) at ((x & 7) 8 + (y & 7)) 8 + (z & 7);
+ *                            entries past the lattice's end are never read.
+ *   coords int32 [n][3]    : the bricks, unique and sorted lexicographically.
+ *   nbr    int32 [n][27]   : index of the brick at offset (dx, dy, dz) in {-1, 0, 1}^3, slot (dx + 1) 9 + (dy + 1) 3 + dz + 1, or -1 when
+ *                            it is not in the list (an index outside [0, n) counts as -1); slot 13 is the brick itself.
+ * A point past the lattice's end does not exist (the dense pass's faces); a point inside it whose brick is absent is unavailable.
+ *   workspace_bytes : bytes of `ws` (about 6 per point of the n bricks).  n_bricks < 2^22, else CNERF_EINVAL.
+ *   count           : counts[3] (device uint32) = (vertices, triangles, open bricks); state (NULL: none) uint8 [n]: bit 0 the brick
+ *                     crosses — an edge it owns with both ends available changes side, or a cell it owns with 8 available corners is
+ *                     mixed; bit 1 it is complete — every one of its 26 neighbours that lies inside the lattice is in the list.  Only
+ *                     complete bricks are meshed, the others add nothing to the counts; a crossing brick that is not complete is open.
+ *                     Both counts 0xffffffff if either exceeds INT32_MAX.
+ *   emit            : after count on the same stream with the same ws and arguments; writes nothing after an overflow or when any
+ *                     brick is open.  verts / normals / faces as the dense emit; vertices in (brick index, local point index, axis)
+ *                     order, triangles in (brick index, local cell index, table order); positions and gradients use the GLOBAL
+ *                     lattice index, one-sided gradients at the lattice's faces only.  vert_keys (NULL: none) int64 [V] =
+ *                     ((x ny + y) nz + z) 3 + axis of every vertex: sorting by it gives the dense pass's order.
+ * n_bricks == 0: CNERF_OK without a launch.  Then NULL values / coords / nbr / ws / counts (emit: origin_host, spacing_host, verts or
+ * faces with a non-zero max): CNERF_ENULL.  Then a dimension < 2 or > 2^20, n_bricks >= 2^22, ws short or not 16-byte aligned:
+ * CNERF_EINVAL.  No atomics: the output is bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_marching_cubes_sparse_workspace_bytes(uint32_t n_bricks, uint64_t *bytes_host);
+int cnerf_marching_cubes_sparse_count(const float *values, const int32_t *coords, const int32_t *nbr, uint32_t n_bricks, uint32_t nx,
+                                      uint32_t ny, uint32_t nz, float level, void *ws, uint64_t ws_bytes, uint8_t *state, uint32_t *counts,
+                                      void *stream);
+int cnerf_marching_cubes_sparse_emit(const float *values, const int32_t *coords, const int32_t *nbr, uint32_t n_bricks, uint32_t nx,
+                                     uint32_t ny, uint32_t nz, float level, const float *origin_host, const float *spacing_host, void *ws,
+                                     uint64_t ws_bytes, float *verts, float *normals, int32_t *faces, int64_t *vert_keys, uint32_t max_verts,
+                                     uint32_t max_faces, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Mesh cleanup (customnerf_amd/mesh.py remove_small_components / simplify; csrc/mesh_clean.hip; the reference has none — NeRF-to-mesh tools
