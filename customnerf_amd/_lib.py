@@ -137,6 +137,9 @@ SIGNATURES = {
     "cnerf_mesh_raster_workspace_bytes": [u32, u32, u32, u32, vp],
     "cnerf_mesh_raster_visibility": [vp, u32, vp, u32, vp, f32, f32, f32, f32, u32, u32, i32, f32, i32, vp, u64, vp, vp, vp, vp, vp],
     "cnerf_mesh_raster_shade": [vp, vp, vp, u32, u32, vp, u32, u32, i32, vp, vp, vp, u32, vp, vp, f32, f32, vp, vp, vp, vp],
+    "cnerf_tsdf_integrate": [vp, u32, u32, u32, vp, vp, f32, vp, vp, u32, u32, u32, vp, f32, f32, f32, f32, i32, f32, i32, vp],
+    "cnerf_tsdf_finalize": [vp, u32, u32, u32, f32, vp, vp, vp],
+    "cnerf_tsdf_face_keep": [vp, u32, u32, u32, vp, vp, vp, u32, vp, u32, vp, vp],
     "cnerf_mesh_bvh_workspace_bytes": [u32, u32, vp],
     "cnerf_mesh_bvh_build": [vp, u32, vp, u32, vp, u64, vp, vp],
     "cnerf_mesh_bvh_closest": [vp, u64, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp],

@@ -14,7 +14,7 @@
 //   k_raster_shade   : one thread per pixel: vertex colours, texture, normals or depth -> RGB8 and the mask
 //
 // Coverage and the winner are exact (int64 edge functions on the snapped positions); depth is float32 in the header's operation order.
-#include "mesh_common.h"
+#include "mesh_camera.h"          // the camera and its vertex transform, shared with mesh_tsdf.hip; mesh_common.h
 
 #define RS_SMALL 16
 #define RS_TILE 32
@@ -23,12 +23,6 @@
 #define RS_EMPTY (~0ull)
 
 namespace {
-
-struct RasterCam {
-    float m[3][4];
-    float fx, fy, cx, cy, near;
-    int convention;
-};
 
 struct RasterWs {
     uint32_t *header;                                            // [0]: faces on the large list
@@ -50,18 +44,13 @@ uint64_t rs_carve(void *ws, uint64_t V, uint64_t F, uint64_t HW, RasterWs *w) {
     return c.total();
 }
 
-__global__ __launch_bounds__(MC_BLOCK) void k_raster_vertex(const float *__restrict__ verts, uint32_t V, RasterCam cam, int4 *__restrict__ vrec) {
+__global__ __launch_bounds__(MC_BLOCK) void k_raster_vertex(const float *__restrict__ verts, uint32_t V, MeshCam cam, int4 *__restrict__ vrec) {
     const uint32_t v = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (v >= V) return;
     const uint64_t o = 3 * (uint64_t)v;
     const float d0 = verts[o] - cam.m[0][3], d1 = verts[o + 1] - cam.m[1][3], d2 = verts[o + 2] - cam.m[2][3];
-    float c[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) c[k] = (cam.m[0][k] * d0 + cam.m[1][k] * d1) + cam.m[2][k] * d2;
-    const float z = cam.convention == 0 ? -c[2] : c[2];
-    const float sy = cam.convention == 0 ? -1.0f : 1.0f;
-    const float X = cam.cx + cam.fx * (c[0] / z);
-    const float Y = cam.cy + sy * (cam.fy * (c[1] / z));
+    float z, X, Y;
+    mesh_cam_project(cam, d0, d1, d2, z, X, Y);
     const float rx = rintf(X * 256.0f), ry = rintf(Y * 256.0f);
     const bool ok = fabsf(z) < INFINITY && z >= cam.near && fabsf(X) < INFINITY && fabsf(Y) < INFINITY && fabsf(rx) < RS_LIMIT &&
                     fabsf(ry) < RS_LIMIT;                        // every comparison is false on a NaN
@@ -356,22 +345,12 @@ int cnerf_mesh_raster_workspace_bytes(uint32_t V, uint32_t F, uint32_t H, uint32
 int cnerf_mesh_raster_visibility(const float *verts, uint32_t V, const int32_t *faces, uint32_t F, const float *c2w_host, float fx, float fy,
                                  float cx, float cy, uint32_t H, uint32_t W, int convention, float near, int cull, void *ws, uint64_t ws_bytes,
                                  int32_t *face_out, float *depth_out, float *bary_out, uint32_t *counts, void *stream) {
-    if (!rs_sizes_ok(V, F, H, W) || !(fabsf(fx) < INFINITY) || !(fabsf(fy) < INFINITY) || fx == 0.0f || fy == 0.0f || !(fabsf(cx) < INFINITY) ||
-        !(fabsf(cy) < INFINITY) || !(fabsf(near) < INFINITY) || convention < 0 || convention > 1 || cull < 0 || cull > 2)
-        return CNERF_EINVAL;
+    if (!rs_sizes_ok(V, F, H, W) || !mesh_cam_ok(fx, fy, cx, cy, near, convention) || cull < 0 || cull > 2) return CNERF_EINVAL;
     const uint64_t HW = (uint64_t)H * W;
     if (!c2w_host || !counts || !ws || (F && (!faces || (V && !verts))) || (HW && (!face_out || !depth_out || !bary_out))) return CNERF_ENULL;
     RasterWs w;
     if (const int rc = mesh_check_ws(ws, ws_bytes, rs_carve(ws, V, F, HW, &w))) return rc;
-    RasterCam cam;
-    for (int r = 0; r < 3; ++r)
-        for (int k = 0; k < 4; ++k) cam.m[r][k] = c2w_host[4 * r + k];
-    cam.fx = fx;
-    cam.fy = fy;
-    cam.cx = cx;
-    cam.cy = cy;
-    cam.near = near;
-    cam.convention = convention;
+    const MeshCam cam = mesh_cam(c2w_host, fx, fy, cx, cy, near, convention);
     hipStream_t st = CN_STREAM(stream);
     if (const int rc = (int)hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), st)) return rc;
     if (const int rc = (int)hipMemsetAsync(w.header, 0, 64 * sizeof(uint32_t), st)) return rc;

@@ -7,8 +7,9 @@ uniform or with cells sized by the faces' edges (csrc/mesh_texture.hip), or into
 shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them,
 watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them, the projection of a low-polygon mesh's
 texels onto the full-resolution surface for baking colour and normal maps (csrc/mesh_bvh.hip), welded vertices with tangent frames and
-tangent-space normal maps through the same bake (csrc/mesh_tangent.hip, k_bake_tspace of csrc/mesh_bake.h), a binary PLY writer, an
-OBJ + MTL + PNG writer and a glTF 2.0 binary (.glb) writer.
+tangent-space normal maps through the same bake (csrc/mesh_tangent.hip, k_bake_tspace of csrc/mesh_bake.h), TSDF fusion of rendered or
+rasterised depth maps into a volume whose zero level is the surface the views show (TSDFVolume, csrc/mesh_tsdf.hip), a binary PLY writer,
+an OBJ + MTL + PNG writer and a glTF 2.0 binary (.glb) writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
 (nerf/renderer.py:128-196).  Here the surface is extracted by three passes on the device; the two counts are the only host read.
@@ -1051,6 +1052,128 @@ def render_mesh(verts, faces, c2w, intrinsics, H, W, *, colors=None, uvs=None, t
                                       _p(tex), R, _p(v), _p(n), d0, d1, (C.c_uint8 * 3)(*b), _p(image), _p(mask), stream()),
           "mesh_raster_shade")
     return image, mask != 0, vis
+
+
+# ------------------------------------------------------------------------------------------------ TSDF fusion of depth maps
+_DEPTH_KINDS = {'z': 0, 'ray': 1}
+
+
+class TSDFVolume:
+    """Depth maps fused into a truncated signed distance volume on marching cubes' lattice, on the device (csrc/mesh_tsdf.hip; the rules
+    are in include/customnerf_hip.h, cnerf_tsdf_*): the zero level is the surface the views show, with no density threshold to tune.
+    shape (nx, ny, nz) >= 2 each and at most 2^31 - 1 points, origin / spacing 3 floats as marching_cubes takes them, trunc > 0 the
+    truncation distance in world units (a few lattice steps: below about 3 the observed band round the surface has holes).  The state
+    [n, 2] float32 = (sum of w s, sum of w) per point, s positive inside, lives on `device` (default: that of the first depth map) and is
+    allocated by the first integrate.  `views` counts the integrated views."""
+
+    def __init__(self, shape, origin, spacing, trunc, device=None):
+        self.shape = _shape3(shape, "TSDFVolume")
+        if math.prod(self.shape) >= 2 ** 31:
+            raise ValueError(f"TSDFVolume: a lattice of {self.shape} has 2^31 points or more")
+        self._org, self._sp = _triple(origin, "origin"), _triple(spacing, "spacing")
+        self.origin, self.spacing = tuple(self._org), tuple(self._sp)
+        self.trunc = float(trunc)
+        if not (math.isfinite(self.trunc) and self.trunc > 0.0):
+            raise ValueError(f"TSDFVolume: trunc must be finite and > 0, got {trunc}")
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != 'cuda':
+            raise RuntimeError("customnerf_amd: tensors must live on the GPU (HIP device memory); there is no CPU path")
+        self.views = 0
+        self._state = None
+        self._seen = None                                                       # (views, fill) -> (volume, observed points) of the last finalize
+
+    @property
+    def state(self):
+        """[n, 2] float32 on the device: (acc, weight) per lattice point, z fastest"""
+        if self._state is None:
+            self._state = torch.zeros(math.prod(self.shape), 2, dtype=torch.float32, device=self.device or torch.device('cuda'))
+            self.device = self._state.device
+        return self._state
+
+    def integrate(self, depth, c2w, intrinsics, convention='nerfstudio', depth_kind='ray', weights=None, near=0.01):
+        """Fuse N views: depth [N, H, W] or [H, W] float32 CUDA ('ray': metric distance along the pixel's ray, what a renderer returns;
+        'z': camera-axis depth, what rasterize returns; +inf: the ray hit nothing, free space all the way; NaN, 0 or negative: the pixel
+        says nothing), c2w [N, 3|4, 4] or one [3|4, 4] (tensor or array), intrinsics (fx, fy, cx, cy) and convention as generate_rays and
+        rasterize take them, weights None or like depth (a pixel with weight 0 says nothing).  Points nearer than `near` along the camera
+        axis are not touched.  The views are summed in index order: any split into calls gives the same state.  -> self."""
+        require_cuda(depth, weights)
+        if depth.dim() == 2:
+            depth = depth[None]
+        if depth.dim() != 3:
+            raise ValueError(f"TSDFVolume.integrate: depth must be [N, H, W] or [H, W], got {tuple(depth.shape)}")
+        N, H, W = depth.shape
+        if weights is not None:
+            if weights.dim() == 2:
+                weights = weights[None]
+            if tuple(weights.shape) != (N, H, W):
+                raise ValueError(f"TSDFVolume.integrate: weights must be shaped like depth, got {tuple(weights.shape)} and {(N, H, W)}")
+        m = _host(c2w, np.float32)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.shape[0] != N:
+            raise ValueError(f"TSDFVolume.integrate: need one c2w per depth map, got {m.shape} for {N} views")
+        _, k, H, W = _camera(np.zeros((3, 4), np.float32), intrinsics, H, W, "TSDFVolume.integrate")
+        cams = (C.c_float * (12 * max(N, 1)))()
+        for v in range(N):
+            cams[12 * v:12 * v + 12] = list(_camera(m[v], intrinsics, H, W, "TSDFVolume.integrate")[0])
+        if convention not in _CONVENTIONS:
+            raise ValueError(f"TSDFVolume.integrate: convention must be 'nerfstudio' or 'ngp', got {convention!r}")
+        if depth_kind not in _DEPTH_KINDS:
+            raise ValueError(f"TSDFVolume.integrate: depth_kind must be 'ray' or 'z', got {depth_kind!r}")
+        near = float(near)
+        if not (math.isfinite(near) and all(math.isfinite(x) for x in k) and k[0] != 0.0 and k[1] != 0.0):
+            raise ValueError(f"TSDFVolume.integrate: need finite intrinsics with fx, fy != 0 and a finite near, got {k}, near = {near}")
+        if self.device is not None and depth.device != self.device:
+            raise ValueError(f"TSDFVolume.integrate: the volume lives on {self.device}, depth on {depth.device}")
+        self.device = depth.device
+        d = depth.detach().contiguous().float()
+        w = None if weights is None else weights.detach().contiguous().float()
+        check(lib.cnerf_tsdf_integrate(ptr(self.state), *self.shape, self._org, self._sp, self.trunc, _p(d), _p(w), N, H, W, cams, *k,
+                                       _CONVENTIONS[convention], near, _DEPTH_KINDS[depth_kind], stream()), "tsdf_integrate")
+        self.views += N
+        return self
+
+    def _finalize(self, fill):
+        fill = float(fill)
+        if self._seen is None or self._seen[0] != (self.views, fill):
+            vol = torch.empty(self.shape, dtype=torch.float32, device=self.state.device)
+            count = torch.empty(1, dtype=torch.int32, device=vol.device)
+            check(lib.cnerf_tsdf_finalize(ptr(self.state), *self.shape, fill, ptr(vol), ptr(count), stream()), "tsdf_finalize")
+            self._seen = ((self.views, fill), vol, int(count.item()) & 0xffffffff)
+        return self._seen[1], self._seen[2]
+
+    def volume(self, fill=-1.0):
+        """[nx, ny, nz] float32: acc / weight where a view said something, `fill` elsewhere (-1: free space); positive inside"""
+        return self._finalize(fill)[0]
+
+    @property
+    def observed(self):
+        """share of the lattice points with weight > 0"""
+        return self._finalize(-1.0)[1] / math.prod(self.shape)
+
+    def face_keep(self, verts, faces):
+        """[F] bool: the lattice cell that holds the face's centroid has eight observed corners"""
+        v, f, _ = _mesh_args(verts, faces, None, "TSDFVolume.face_keep")
+        keep = torch.empty(f.shape[0], dtype=torch.uint8, device=f.device)
+        check(lib.cnerf_tsdf_face_keep(ptr(self.state), *self.shape, self._org, self._sp, _p(v), v.shape[0], _p(f), f.shape[0], _p(keep),
+                                       stream()), "tsdf_face_keep")
+        return keep != 0
+
+    def extract(self, fill=-1.0):
+        """The fused surface: marching_cubes(volume(fill), 0.0) without its gradient normals (they would read `fill` next to unobserved
+        points), minus the faces whose cell has an unobserved corner — the shell where "behind the surface" meets "never observed" — and
+        the vertices only they used; face order is kept.  -> (verts [V, 3] float32, faces [F, 3] int32 wound outwards, normals [V, 3]
+        float32: vertex_normals of the result, info {'observed': share of observed points, 'dropped_faces'})."""
+        vol, seen = self._finalize(fill)
+        verts, faces, _ = marching_cubes(vol, 0.0, spacing=self.spacing, origin=self.origin, normals=False)
+        keep = self.face_keep(verts, faces)
+        kept = faces[keep]
+        used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+        used[kept.reshape(-1).long()] = True
+        new_index = (torch.cumsum(used, 0) - 1).to(torch.int32)
+        verts, faces = verts[used].contiguous(), new_index[kept.long()].contiguous()
+        info = {'observed': seen / math.prod(self.shape), 'dropped_faces': int(keep.numel() - kept.shape[0])}
+        return verts, faces, vertex_normals(verts, faces), info
 
 
 def bvh_workspace_bytes(V, F):

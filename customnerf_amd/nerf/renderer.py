@@ -3,6 +3,7 @@
 Implemented (reference lines): sample_pdf (21-55), NeRFRenderer.__init__ (199-243), reset_extra_state (266-276),
 run (278-405), weights_sum_i (407-474), run_cuda (597-718), update_extra_state (1658-1715), render (1719-1733),
 convert_sigma_samples_to_ply (128-196) and the density_mesh hook (251) as NeRFRenderer.extract_mesh / save_mesh (marching cubes in mesh.hip).
+render_depth (metric depth maps; no reference counterpart) feeds extract_mesh(tsdf=...), the TSDF fusion of mesh_tsdf.hip.
 Out of scope: the SDF/NeuS paths, the unused run_cuda2 / render_cuda duplicates.
 Every function here ends in HIP kernels (render.hip, raymarching.hip, occupancy.hip): there is no torch restatement of the
 reference's bodies in the product — that lives in oracle/torch_oracle.py, for the tests.
@@ -487,11 +488,52 @@ class NeRFRenderer(nn.Module):
             vol[s:s + len(i)] = self._mesh_sigma((lo + ijk * step).contiguous(), part, view_dir)
         return vol.view(R, R, R)
 
+    _TSDF_KEYS = {'poses': None, 'intrinsics': None, 'H': None, 'W': None, 'convention': 'nerfstudio', 'trunc': None, 'min_opacity': 0.5,
+                  'carve': True, 'render': None}
+
+    @staticmethod
+    def _tsdf_options(tsdf, sparse, part, max_step):
+        """extract_mesh's tsdf= dict with its defaults filled in; everything wrong with it raises ValueError before any render"""
+        if not isinstance(tsdf, dict):
+            raise ValueError(f"extract_mesh: tsdf must be None or a dict of options, got {type(tsdf).__name__}")
+        if sparse:
+            raise ValueError("extract_mesh: tsdf and sparse=True exclude each other (a brick-sparse TSDF is not built)")
+        if part != 'all':
+            raise ValueError(f"extract_mesh: tsdf fuses renders of the whole field; part must be 'all', got {part!r}")
+        unknown = sorted(set(tsdf) - set(NeRFRenderer._TSDF_KEYS))
+        if unknown:
+            raise ValueError(f"extract_mesh: unknown tsdf keys {unknown}; known: {sorted(NeRFRenderer._TSDF_KEYS)}")
+        missing = [k for k in ('poses', 'intrinsics', 'H', 'W') if tsdf.get(k) is None]
+        if missing:
+            raise ValueError(f"extract_mesh: tsdf needs {missing}")
+        cfg = {**NeRFRenderer._TSDF_KEYS, **tsdf}
+        p = cfg['poses']
+        p = torch.as_tensor(np.asarray(p.detach().cpu() if torch.is_tensor(p) else p, dtype=np.float32))
+        if p.dim() != 3 or tuple(p.shape[1:]) not in ((3, 4), (4, 4)):
+            raise ValueError(f"extract_mesh: tsdf['poses'] must be [N, 3, 4] or [N, 4, 4], got {tuple(p.shape)}")
+        if p.shape[0] == 0:
+            raise ValueError("extract_mesh: tsdf['poses'] holds no view")
+        if cfg['convention'] not in ('nerfstudio', 'ngp'):
+            raise ValueError(f"extract_mesh: tsdf['convention'] must be 'nerfstudio' or 'ngp', got {cfg['convention']!r}")
+        k = tuple(float(x) for x in cfg['intrinsics'])
+        if len(k) != 4:
+            raise ValueError(f"extract_mesh: tsdf['intrinsics'] must be (fx, fy, cx, cy), got {len(k)} values")
+        trunc = 4.0 * max_step if cfg['trunc'] is None else float(cfg['trunc'])
+        if not (math.isfinite(trunc) and trunc > 0.0):
+            raise ValueError(f"extract_mesh: tsdf['trunc'] must be finite and > 0, got {cfg['trunc']}")
+        H, W = int(cfg['H']), int(cfg['W'])
+        if H < 1 or W < 1:
+            raise ValueError(f"extract_mesh: tsdf needs H, W >= 1, got {H}, {W}")
+        cfg.update(poses=p, intrinsics=k, trunc=trunc, H=H, W=W, min_opacity=float(cfg['min_opacity']), carve=bool(cfg['carve']),
+                   render=dict(cfg['render'] or {}))
+        return cfg
+
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
                      smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0,
-                     texture_layout='uniform', bake_from='mesh', bake_reach=None, normal_map=False, sparse=False, sparse_probe=4):
+                     texture_layout='uniform', bake_from='mesh', bake_reach=None, normal_map=False, sparse=False, sparse_probe=4,
+                     tsdf=None):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -541,7 +583,17 @@ class NeRFRenderer(nn.Module):
         dense path's vertices and triangles, bit for bit, in brick order in place of lattice order — except that, with sparse_probe=k > 1,
         a surface component small enough to lie wholly between the probe points (as an extraction at resolution / k would lose it) can be
         missed; sparse_probe=1 misses nothing.  'volume' is then None and 'sparse' joins the dict: {'bricks', 'evaluations', 'rounds',
-        'points': resolution^3}.  Every later stage works on the mesh and is the same.  With sparse=False the key is absent."""
+        'points': resolution^3}.  Every later stage works on the mesh and is the same.  With sparse=False the key is absent.
+        tsdf=dict(...) takes the surface from rendered views in place of a density level: render_depth from every pose, the depth maps
+        fused into a truncated signed distance volume on the same lattice (mesh.TSDFVolume, csrc/mesh_tsdf.hip) and its zero level
+        meshed (TSDFVolume.extract: faces whose cell has a corner no view observed are dropped; area-weighted normals).  The surface is
+        the one the renders show: no threshold to tune, and haze that never shows in a render leaves no floaters.  Keys: 'poses'
+        [N, 3|4, 4], 'intrinsics' (fx, fy, cx, cy), 'H', 'W' (required); 'convention' ('nerfstudio'), 'trunc' (the truncation distance,
+        default 4 x the largest lattice step), 'min_opacity' (0.5: below it a pixel is free space), 'carve' (True; False turns
+        transparent pixels into "no information" — NaN — in place of "free" — +inf), 'render' (kwargs of render()).  `threshold` and
+        `part` play no role (part must be 'all', sparse False); 'threshold' in the result is 0.0, 'volume' the finalised TSDF (positive
+        inside), and 'tsdf' joins the dict: {'views', 'trunc', 'observed': share of observed lattice points, 'dropped_faces'}.  Every
+        later stage is the same.  With tsdf=None the key is absent."""
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -576,8 +628,22 @@ class NeRFRenderer(nn.Module):
             raise ValueError(f"extract_mesh: bake_reach must be > 0, got {bake_reach}")
         if int(sparse_probe) < 1:
             raise ValueError(f"extract_mesh: sparse_probe must be >= 1 (every how many lattice points the field is probed), got {sparse_probe}")
-        sparse_info = None
-        if sparse:
+        sparse_info = tsdf_info = None
+        if tsdf is not None:
+            cfg = self._tsdf_options(tsdf, sparse, part, float(step.max()))
+            poses = cfg['poses']
+            tv = _mesh.TSDFVolume((R, R, R), lo.tolist(), step.tolist(), cfg['trunc'], device=self.aabb_infer.device)
+            for s in range(0, poses.shape[0], 16):                               # a launch of the fusion takes 16 views: the volume is read once for them
+                maps = []
+                for pose in poses[s:s + 16]:
+                    d = self.render_depth(pose, cfg['intrinsics'], cfg['H'], cfg['W'], convention=cfg['convention'],
+                                          min_opacity=cfg['min_opacity'], **cfg['render'])['depth']
+                    maps.append(d if cfg['carve'] else torch.where(torch.isinf(d), torch.full_like(d, math.nan), d))
+                tv.integrate(torch.stack(maps), poses[s:s + 16], cfg['intrinsics'], convention=cfg['convention'], depth_kind='ray')
+            threshold, vol = 0.0, tv.volume()
+            verts, faces, normals, info = tv.extract()
+            tsdf_info = {'views': tv.views, 'trunc': tv.trunc, 'observed': info['observed'], 'dropped_faces': info['dropped_faces']}
+        elif sparse:
             vol = None
             sv = _mesh.sparse_volume(lambda x: self._mesh_sigma(x, part, view_dir), (R, R, R), lo, step, threshold, probe=int(sparse_probe),
                                      chunk=chunk, device=self.aabb_infer.device)
@@ -624,6 +690,8 @@ class NeRFRenderer(nn.Module):
              'uvs': uvs, 'texture': tex, 'texture_layout': texture_layout}
         if sparse_info is not None:
             m['sparse'] = sparse_info
+        if tsdf_info is not None:
+            m['tsdf'] = tsdf_info
         if normal_map:
             m['normal_map'] = nmap
             m['normal_space'] = 'tangent' if isinstance(normal_map, str) else 'object'
@@ -649,7 +717,7 @@ class NeRFRenderer(nn.Module):
         their normals and colours, or the ambient occlusion as grey, as for PLY; unlit unless it carries a normal map); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
         extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), texture_layout, deviation /
-        deviation_spacing, ao, bake_from, bake_reach, sparse and sparse_probe pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
+        deviation_spacing, ao, bake_from, bake_reach, sparse, sparse_probe and tsdf pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
         in the material) and, like texture=, needs an .obj path; normal_map='tangent' needs a .glb path (OBJ carries no tangents) and
         normal_map=True is refused for .glb (glTF has no object-space slot).  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written
@@ -701,6 +769,44 @@ class NeRFRenderer(nn.Module):
         if path is not None:
             _mesh.write_png(path, image)
         return image, mask, vis
+
+    @torch.no_grad()
+    def render_depth(self, c2w, intrinsics, H, W, convention='nerfstudio', min_opacity=0.5, max_ray_batch=1 << 16, **render_kw):
+        """Depth map of one pinhole view (the camera of provider_utils.generate_rays and mesh.rasterize: c2w [3, 4] or [4, 4], intrinsics
+        (fx, fy, cx, cy)), rendered through render(..., staged=True, perturb=False, **render_kw) in batches of max_ray_batch rays.
+        -> {'depth': [H, W] float32, 'opacity': [H, W] float32}.  depth is the METRIC DISTANCE ALONG THE RAY of the expected termination,
+        sum(w t) / sum(w), whichever path rendered it; pixels whose opacity sum(w) is below min_opacity get +inf (nothing was hit), which
+        is what mesh.TSDFVolume.integrate(depth_kind='ray') reads as free space.  The two paths return different things under 'depth':
+        run_cuda sum(w t), and run() sum(w clamp((t - near) / (far - near), 0, 1)) as the reference does (nerf/renderer.py:435-436), so
+        the latter is mapped back with the ray's own near / far (near_far_from_aabb with the box and min_near that run() used)."""
+        m = torch.as_tensor(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, dtype=np.float32))
+        if tuple(m.shape) not in ((3, 4), (4, 4)):
+            raise ValueError(f"render_depth: c2w must be [3, 4] or [4, 4], got {tuple(m.shape)}")
+        k = tuple(float(x) for x in intrinsics)
+        H, W, batch = int(H), int(W), int(max_ray_batch)
+        if len(k) != 4 or H < 1 or W < 1 or batch < 1:
+            raise ValueError(f"render_depth: need intrinsics (fx, fy, cx, cy), H, W >= 1 and max_ray_batch >= 1, got {k}, {H}, {W}, {batch}")
+        from .provider_utils import generate_rays
+        dev = self.aabb_infer.device
+        o, d = generate_rays(m[None, :3].to(dev), *k, H, W, 1.0, convention)
+        o, d = o.view(-1, 3), d.view(-1, 3)
+        depth = torch.empty(H * W, dtype=torch.float32, device=dev)
+        opacity = torch.empty_like(depth)
+        aabb = self.aabb_train if self.training else self.aabb_infer
+        for s in range(0, H * W, batch):
+            ro, rd = o[s:s + batch].contiguous(), d[s:s + batch].contiguous()
+            res = self.render(ro[None], rd[None], staged=True, perturb=False, **render_kw)
+            if 'depth' not in res:
+                raise ValueError("render_depth: render() returned no depth (run() fills its results only under opt.train_conf)")
+            acc = res['weights_sum'].reshape(-1).float()
+            t = res['depth'].reshape(-1).float() / acc                          # 0 / 0 where nothing was hit: below min_opacity anyway
+            if not self.cuda_ray:
+                near, far = raymarching.near_far_from_aabb(ro, rd, aabb, self.min_near)
+                t = near + t * (far - near)
+            depth[s:s + batch] = t * rd.norm(dim=-1)
+            opacity[s:s + batch] = acc
+        depth = torch.where(opacity >= float(min_opacity), depth, torch.full_like(depth, math.inf))
+        return {'depth': depth.view(H, W), 'opacity': opacity.view(H, W)}
 
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=2048, **kwargs):
         """renderer.py:1719-1733."""

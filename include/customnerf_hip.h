@@ -48,7 +48,8 @@ extern "C" {
  *    cnerf_mesh_atlas_proj_workspace_bytes / _charts / _pack / _raster / _points / _store / _fill; welded vertices, tangent frames and
  *    tangent-space normal maps (additive, same version) — cnerf_mesh_tangent_workspace_bytes / _weld / _frames / _vertices and
  *    cnerf_mesh_atlas_tspace / cnerf_mesh_atlas_sized_tspace / cnerf_mesh_atlas_proj_tspace; marching cubes over a list of bricks
- *    (additive, same version) — cnerf_marching_cubes_sparse_workspace_bytes / _count / _emit. */
+ *    (additive, same version) — cnerf_marching_cubes_sparse_workspace_bytes / _count / _emit; TSDF fusion of depth maps (additive, same
+ *    version) — cnerf_tsdf_integrate / _finalize / _face_keep. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -956,6 +957,52 @@ int cnerf_mesh_raster_shade(const int32_t *face, const float *depth, const float
                             uint32_t F, int mode, const uint8_t *colors, const float *uvs, const uint8_t *texture, uint32_t R,
                             const float *verts, const float *normals, float d0, float d1, const uint8_t *bg_host, uint8_t *image, uint8_t *mask,
                             void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * TSDF fusion: depth maps of a set of views fused into a truncated signed distance volume on marching cubes' lattice, whose zero level is
+ * the surface the views show (customnerf_amd/mesh.py TSDFVolume; csrc/mesh_tsdf.hip; the reference has none — NeRF exporters do it on the
+ * host).  All float arithmetic is float32, one rounding per written operation, in the order written (the build has -ffp-contract=off);
+ * divisions and square roots are correctly rounded: the rasteriser's rules above.
+ *   State: float32 [n][2] on the device, n = nx ny nz points in cnerf_marching_cubes_*'s order (z fastest): (acc, weight) = (sum of w s,
+ *   sum of w) over the views integrated so far; all zero at first (the caller clears it).  origin_host / spacing_host float32 [3] on the
+ *   host as cnerf_marching_cubes_emit takes them: lattice point idx sits at p_b = org_b + (float) idx_b sp_b.
+ *   Cameras: those of cnerf_mesh_raster_visibility, one c2w_host float32 [3][4] per view ([n_views][3][4] on the host), shared fx, fy, cx,
+ *   cy, convention and near; the vertex transform is the rasteriser's own code (csrc/mesh_camera.h).
+ *   integrate, per point, for each view v in index order:
+ *      1. d = p - t                          2. c_k = (m[0][k] d0 + m[1][k] d1) + m[2][k] d2
+ *      3. z = -c_2 (convention 0) or c_2 (convention 1)             4. skip unless z >= near (a NaN z fails the test)
+ *      5. X = cx + fx (c_0 / z)              6. Y = cy + (-1) (fy (c_1 / z)) (convention 0) or cy + fy (c_1 / z) (convention 1)
+ *      7. skip unless 0 <= X < (float) W and 0 <= Y < (float) H, tested on the floats (non-finite values fail)
+ *      8. ix = (int) floorf(X), iy = (int) floorf(Y): the pixel whose centre (ix + .5, iy + .5) carries that ray; skip unless ix < W and
+ *         iy < H (which can fail only where (float) W rounds up, W > 2^24)
+ *      9. D = depth[v][iy][ix]; skip if D is NaN or D <= 0.  +inf is valid: nothing was hit, the ray is free space all the way
+ *     10. w = pixel_weight ? pixel_weight[v][iy][ix] : 1; skip unless 0 < w < inf
+ *     11. r = z (depth_kind 0: camera-axis depth, what cnerf_mesh_raster_visibility writes) or sqrtf((d0 d0 + d1 d1) + d2 d2)
+ *         (depth_kind 1: distance along the ray, what a renderer returns)
+ *     12. sdf = D - r; skip if sdf < -trunc: the point is hidden behind the surface and this view says nothing about it
+ *     13. s = -fminf(1, sdf / trunc): positive inside like a density, -1 in free space, so that marching cubes (inside: value >= level)
+ *         winds the faces outwards at level 0
+ *     14. acc += w s (the product rounded, then the sum); weight += w
+ *   The views go to the device in launches of at most 16, the cameras by value; a point's sums run in view order within and across
+ *   launches and calls, so the state does not depend on how the views are cut: n_views = 33 at once, 33 calls of one and 16 + 17 give the
+ *   same bytes.  depth / pixel_weight: device float32 [n_views][H][W]; pixel_weight may be NULL.
+ *   finalize : volume[i] = weight[i] > 0 ? acc[i] / weight[i] : fill (device float32 [n]); observed (device uint32 [1]) = the number of
+ *              points with weight > 0 (an integer count: any order of arrival gives the same value).
+ *   face_keep: keep[f] (device uint8 [F]) = 1 when the lattice cell that holds face f's centroid has eight corners with weight > 0, else 0:
+ *              c_b = ((v0_b + v1_b) + v2_b) / 3, q_b = clamp(floorf((c_b - org_b) / sp_b), 0, n_b - 2) (NaN -> 0), the cell's corners are
+ *              q + {0, 1}^3.  A face with an index outside [0, V) gets 0.  It removes the shell where "behind the surface" meets "never
+ *              observed" from the zero-level mesh of finalize's volume.
+ *   CNERF_EINVAL: a lattice extent < 2 or more than 2^31 points; (integrate) trunc not finite or <= 0, fx or fy zero or non-finite, cx / cy /
+ *   near non-finite, convention or depth_kind outside {0, 1}, H W >= 2^31; (face_keep) V or F >= 2^31.  Then n_views == 0 / F == 0:
+ *   CNERF_OK without a launch.  Then CNERF_ENULL: a NULL state, depth, c2w_host, origin_host, spacing_host, volume, observed, faces, keep,
+ *   or verts with V > 0.  All return before any launch.  No workspace; no float atomics: the output is bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_tsdf_integrate(float *state, uint32_t nx, uint32_t ny, uint32_t nz, const float *origin_host, const float *spacing_host, float trunc,
+                         const float *depth, const float *pixel_weight, uint32_t n_views, uint32_t H, uint32_t W, const float *c2w_host,
+                         float fx, float fy, float cx, float cy, int convention, float near, int depth_kind, void *stream);
+int cnerf_tsdf_finalize(const float *state, uint32_t nx, uint32_t ny, uint32_t nz, float fill, float *volume, uint32_t *observed, void *stream);
+int cnerf_tsdf_face_keep(const float *state, uint32_t nx, uint32_t ny, uint32_t nz, const float *origin_host, const float *spacing_host,
+                         const float *verts, uint32_t V, const int32_t *faces, uint32_t F, uint8_t *keep, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Closest-point queries against a triangle mesh and a deterministic surface sampler: what the deviation report is made of
