@@ -2,7 +2,8 @@
 the surface only (csrc/mesh_sparse.hip, cnerf_marching_cubes_sparse_*; sparse_volume finds the bricks from a field without evaluating the
 whole lattice, and the mesh is the dense one bit for bit in another order), mesh cleanup on the GPU (csrc/mesh_clean.hip:
 removal of small connected components, simplification by vertex clustering; csrc/mesh_decimate.hip: quadric edge-collapse decimation to a
-face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals), texture baking into a per-face-pair atlas on the GPU,
+face count; csrc/mesh_smooth.hip: Taubin smoothing and area-weighted vertex normals; csrc/mesh_holes.hip: the topology report — edges,
+boundary loops, Euler characteristic, watertightness — and the filling of simple boundary loops), texture baking into a per-face-pair atlas on the GPU,
 uniform or with cells sized by the faces' edges (csrc/mesh_texture.hip), or into an atlas of axis-projected charts (csrc/mesh_charts.hip), a rasteriser for previews of the exported mesh from a camera pose (csrc/mesh_raster.hip: visibility buffer and
 shaded images), closest-point queries through a bounding-volume hierarchy with a surface sampler and the mesh-to-mesh distance built on them,
 watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them, the projection of a low-polygon mesh's
@@ -451,6 +452,86 @@ def decimate(verts, faces, target_faces, normals=None, rounds=None):
     vo, no, fo, old = _outputs(dev, nv, nf, n is not None)
     check(lib.cnerf_mesh_decimate_emit(_p(n), V, nf, ptr(ws), nbytes, _p(vo), _p(no), _p(fo), _p(old), nv, nf, stream()), "mesh_decimate_emit")
     return vo, fo, no, old
+
+
+def holes_workspace_bytes(V, F):
+    return _bytes("mesh_holes", int(V), int(F))
+
+
+_TOPOLOGY_COUNTS = ("vertices_used", "edges", "boundary_edges", "nonmanifold_edges", "pinched_vertices", "boundary_loops", "simple_loops",
+                    "components", "degenerate_faces")
+
+
+def topology(verts, faces):
+    """What kind of surface a triangle mesh is, counted on the device (csrc/mesh_holes.hip; the rules are in include/customnerf_hip.h,
+    cnerf_mesh_topology*).  Any triangle mesh (it need not be manifold): CUDA tensors verts [V, 3], faces [F, 3] (int).  -> dict of
+    Python ints and bools from one host read, plus one device tensor:
+    vertices_used (vertices in a face), faces, edges (distinct unordered vertex pairs; a face repeating an index adds no edge between the
+    equal ones); boundary_edges (in one face), nonmanifold_edges (in more than two faces, or in two that use them in one direction);
+    pinched_vertices (more than one boundary half-edge leaves them, or ends in them); boundary_loops (connected components of the graph
+    of boundary edges) and simple_loops (those without a pinched vertex or an end of a non-manifold edge: the ones fill_holes closes);
+    components (vertices joined by a face, labelled as by remove_small_components; vertices no face references are not counted);
+    euler = vertices_used - edges + faces; degenerate_faces (faces repeating an index); watertight (at least one face and no boundary
+    edge, non-manifold edge or degenerate face); loop_lengths [boundary_loops] int32 on the device, the edges of every loop in the order
+    of the loops' labels (the smallest half-edge id 3 f + k on each).  A face index outside [0, V) raises ValueError."""
+    v, f, _ = _mesh_args(verts, faces, None, "topology")
+    V, F = v.shape[0], f.shape[0]
+    dev = v.device
+    r = [0] * len(_TOPOLOGY_COUNTS)
+    if F:                                                                       # (no face: nothing to launch)
+        ws, nbytes = _workspace(dev, "mesh_holes", V, F)
+        counts = torch.empty(len(_TOPOLOGY_COUNTS) + 1, dtype=torch.int32, device=dev)
+        check(lib.cnerf_mesh_topology(_p(f), V, F, ptr(ws), nbytes, ptr(counts), stream()), "mesh_topology")
+        r = _read(counts, "topology", _BAD_INDEX)[:-1]                          # the one host read
+    t = dict(zip(_TOPOLOGY_COUNTS, r))
+    t["faces"] = F
+    t["euler"] = t["vertices_used"] - t["edges"] + F
+    t["watertight"] = F > 0 and not (t["boundary_edges"] or t["nonmanifold_edges"] or t["degenerate_faces"])
+    t["loop_lengths"] = torch.empty(t["boundary_loops"], dtype=torch.int32, device=dev)
+    if t["boundary_loops"]:
+        check(lib.cnerf_mesh_topology_loops(V, F, ptr(ws), nbytes, ptr(t["loop_lengths"]), t["boundary_loops"], stream()), "mesh_topology_loops")
+    return t
+
+
+def _max_edges(max_edges, what):
+    """max_edges of fill_holes as the entry points take it: 0 for None (no limit), else an int >= 3"""
+    if max_edges is None:
+        return 0
+    if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not 3 <= max_edges < 2 ** 32:
+        raise ValueError(f"{what}: max_edges must be None (no limit) or an int >= 3, got {max_edges!r}")
+    return int(max_edges)
+
+
+def fill_holes(verts, faces, normals=None, max_edges=None):
+    """Close the boundary loops of a mesh on the device (csrc/mesh_holes.hip; the rules are in include/customnerf_hip.h,
+    cnerf_mesh_holes_*).  The mesh must be edge-manifold and consistently oriented with no face repeating an index, as marching cubes,
+    remove_small_components, decimate and TSDFVolume.extract give; anything else raises ValueError, as decimate does.  Every simple loop
+    (topology()) of 3 <= n <= max_edges edges (None: no limit) is filled: a loop of 3 with the one face that reverses its half-edges, a
+    longer one with a new vertex at the centroid of its vertices and a fan of n faces wound like the surface round it.  Loops through a
+    pinched vertex and longer loops stay open and are counted.  A centroid fan across a large or non-planar hole is a coarse patch; the
+    new vertex is an interior one, so smooth() moves it and decimate() may remove it.
+    CUDA tensors verts [V, 3], faces [F, 3] (int), normals [V, 3] or None.  -> (verts [V', 3] float32, faces [F', 3] int32, normals
+    [V', 3] or None, info).  The input vertices and faces (unreferenced vertices included) are the prefix of the output, bit for bit;
+    new vertices follow in the order of the loops' labels, new faces in that order and, within a loop, in loop order from its label.
+    The new vertex's normal is the normalised sum of its fan's face normals.  info: {'filled', 'skipped_pinched', 'skipped_long',
+    'new_vertices', 'new_faces'}.  A mesh with nothing to fill comes back equal to the input."""
+    me = _max_edges(max_edges, "fill_holes")
+    v, f, n = _mesh_args(verts, faces, normals, "fill_holes")
+    V, F = v.shape[0], f.shape[0]
+    dev = v.device
+    nv = nf = filled = pinched = long_ = 0
+    if F:
+        ws, nbytes = _workspace(dev, "mesh_holes", V, F)
+        counts = torch.empty(6, dtype=torch.int32, device=dev)
+        check(lib.cnerf_mesh_holes_count(_p(f), V, F, me, ptr(ws), nbytes, ptr(counts), stream()), "mesh_holes_count")
+        nv, nf, filled, pinched, long_, _ = _read(counts, "fill_holes", _DECIMATE_FLAGS)          # the one host read
+    info = {'filled': filled, 'skipped_pinched': pinched, 'skipped_long': long_, 'new_vertices': nv, 'new_faces': nf}
+    if not F:
+        return v.clone(), f.clone(), None if n is None else n.clone(), info
+    vo, no, fo, _ = _outputs(dev, V + nv, F + nf, n is not None, old_index=False)
+    check(lib.cnerf_mesh_holes_emit(_p(v), _p(n), V, _p(f), F, me, ptr(ws), nbytes, _p(vo), _p(no), _p(fo), V + nv, F + nf, stream()),
+          "mesh_holes_emit")
+    return vo, fo, no, info
 
 
 def smooth_workspace_bytes(V, F):

@@ -533,7 +533,7 @@ class NeRFRenderer(nn.Module):
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
                      smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0,
                      texture_layout='uniform', bake_from='mesh', bake_reach=None, normal_map=False, sparse=False, sparse_probe=4,
-                     tsdf=None):
+                     tsdf=None, fill_holes=False, topology=False):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -593,7 +593,25 @@ class NeRFRenderer(nn.Module):
         transparent pixels into "no information" — NaN — in place of "free" — +inf), 'render' (kwargs of render()).  `threshold` and
         `part` play no role (part must be 'all', sparse False); 'threshold' in the result is 0.0, 'volume' the finalised TSDF (positive
         inside), and 'tsdf' joins the dict: {'views', 'trunc', 'observed': share of observed lattice points, 'dropped_faces'}.  Every
-        later stage is the same.  With tsdf=None the key is absent."""
+        later stage is the same.  With tsdf=None the key is absent.
+        fill_holes=True closes the boundary loops the extraction leaves — where the surface leaves the lattice (an aabb tighter than
+        the object, an object standing on the box floor), where the TSDF's face rule drops the unobserved side, where component removal
+        kept a rim — with mesh.fill_holes (csrc/mesh_holes.hip): every simple loop gets a fan round a new vertex at its centroid (a loop
+        of three edges one face); an int >= 3 fills only the loops of at most that many edges.  It runs after component removal and
+        before smoothing, clustering and decimation, so the patches are smoothed and decimated with the rest (and belong to the mesh
+        'deviation' and bake_from='source' compare with); a fan across a large, non-planar hole is a coarse patch, and loops through a
+        pinched vertex stay open.  Not with simplify, whose output need not be manifold; it works with sparse=True and with tsdf=.
+        'holes' joins the dict: mesh.fill_holes' info.  topology=True adds 'topology': mesh.topology of the final mesh (edges, boundary
+        loops, Euler characteristic, 'watertight', ...).  With the defaults neither key is present."""
+        if fill_holes is True or fill_holes is False:
+            fill_edges = None
+        elif isinstance(fill_holes, (int, np.integer)) and fill_holes >= 3:
+            fill_edges = int(fill_holes)
+        else:
+            raise ValueError(f"extract_mesh: fill_holes must be False, True (no length limit) or an int >= 3 (the longest loop filled), "
+                             f"got {fill_holes!r}")
+        if fill_holes is not False and int(simplify):
+            raise ValueError("extract_mesh: fill_holes and simplify exclude each other (clustered meshes need not be manifold)")
         threshold = float(self.opt.density_thresh if threshold is None else threshold)
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
@@ -655,7 +673,10 @@ class NeRFRenderer(nn.Module):
         if int(min_component_faces) > 0 or keep_largest:
             verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
                                                                      largest=bool(keep_largest))
-        kept = (verts, faces, normals) if deviation or from_source else None     # held only for the report and the projection
+        holes_info = None
+        if fill_holes is not False:
+            verts, faces, normals, holes_info = _mesh.fill_holes(verts, faces, normals, max_edges=fill_edges)
+        kept =(verts, faces, normals) if deviation or from_source else None     # held only for the report and the projection
         if n_smooth:
             verts, normals = _mesh.smooth(verts, faces, n_smooth, smooth_lambda, smooth_mu, normals=normals)
         if k >= 2:
@@ -692,6 +713,10 @@ class NeRFRenderer(nn.Module):
             m['sparse'] = sparse_info
         if tsdf_info is not None:
             m['tsdf'] = tsdf_info
+        if holes_info is not None:
+            m['holes'] = holes_info
+        if topology:
+            m['topology'] = _mesh.topology(verts, faces)
         if normal_map:
             m['normal_map'] = nmap
             m['normal_space'] = 'tangent' if isinstance(normal_map, str) else 'object'
@@ -717,7 +742,7 @@ class NeRFRenderer(nn.Module):
         their normals and colours, or the ambient occlusion as grey, as for PLY; unlit unless it carries a normal map); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
         extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), texture_layout, deviation /
-        deviation_spacing, ao, bake_from, bake_reach, sparse, sparse_probe and tsdf pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
+        deviation_spacing, ao, bake_from, bake_reach, sparse, sparse_probe, tsdf, fill_holes and topology pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
         in the material) and, like texture=, needs an .obj path; normal_map='tangent' needs a .glb path (OBJ carries no tangents) and
         normal_map=True is refused for .glb (glTF has no object-space slot).  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written

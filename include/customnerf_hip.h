@@ -49,7 +49,8 @@ extern "C" {
  *    tangent-space normal maps (additive, same version) — cnerf_mesh_tangent_workspace_bytes / _weld / _frames / _vertices and
  *    cnerf_mesh_atlas_tspace / cnerf_mesh_atlas_sized_tspace / cnerf_mesh_atlas_proj_tspace; marching cubes over a list of bricks
  *    (additive, same version) — cnerf_marching_cubes_sparse_workspace_bytes / _count / _emit; TSDF fusion of depth maps (additive, same
- *    version) — cnerf_tsdf_integrate / _finalize / _face_keep. */
+ *    version) — cnerf_tsdf_integrate / _finalize / _face_keep; topology report and hole filling (additive, same version) —
+ *    cnerf_mesh_holes_workspace_bytes / _count / _emit and cnerf_mesh_topology / _loops. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -1003,6 +1004,50 @@ int cnerf_tsdf_integrate(float *state, uint32_t nx, uint32_t ny, uint32_t nz, co
 int cnerf_tsdf_finalize(const float *state, uint32_t nx, uint32_t ny, uint32_t nz, float fill, float *volume, uint32_t *observed, void *stream);
 int cnerf_tsdf_face_keep(const float *state, uint32_t nx, uint32_t ny, uint32_t nz, const float *origin_host, const float *spacing_host,
                          const float *verts, uint32_t V, const int32_t *faces, uint32_t F, uint8_t *keep, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Topology report and hole filling (customnerf_amd/mesh.py topology / fill_holes; csrc/mesh_holes.hip; the reference has none).  verts
+ * float32 [V][3], optional normals float32 [V][3] (NULL: none), faces int32 [F][3].  V < 2^31 and F <= 0x2AAAAAAA (half-edge ids 3 f + k
+ * and loop lengths stay below 2^31), else CNERF_EINVAL; F = 0 returns CNERF_OK without a launch and writes nothing; ws 16-byte aligned and
+ * >= workspace_bytes, else CNERF_EINVAL.  The caller's stream and workspace; no allocation, no host sync; the counts are the one host read.
+ * The output does not depend on scheduling: integer atomics only, compaction by scan, lists sorted.  flags bit 0: some face index lies
+ * outside [0, V), and nothing else is then counted or written.
+ *   Definitions: half-edge 3 f + k runs from a = f[k] to b = f[(k + 1) % 3]; with a == b (a face repeating an index) it is no edge.  For
+ *   an undirected edge {a, b}, same and opp count the half-edges a -> b and b -> a.  Interior: one of each.  Boundary: one in all.  Every
+ *   other edge is non-manifold (more than two faces, or two that use it in one direction).  A boundary half-edge is the half-edge of a
+ *   boundary edge.  A vertex is pinched when more than one boundary half-edge leaves it, or more than one ends in it.  Boundary loops
+ *   are the connected components of the graph of boundary edges; a loop's label is the smallest half-edge id on it.  A loop is simple
+ *   when it holds no pinched vertex and no end of a non-manifold edge: a cycle, and next(a -> b) is the one boundary half-edge leaving b.
+ *   topology       : counts (device uint32 [10]) = vertices in a face, undirected edges, boundary edges, non-manifold edges, pinched
+ *                    vertices, boundary loops, simple loops, components (vertices joined by a face, as cnerf_mesh_components_*; those
+ *                    that hold a face), faces repeating an index, flags.  Any triangle mesh.
+ *   topology_loops : after topology on the same stream with the same ws, V and F: loop_lengths [max_loops] int32, the edges of every
+ *                    loop in increasing label; entries at or past max_loops are not written.
+ *   holes_count    : the mesh must be edge-manifold and consistently oriented with no face repeating an index — flags bit 1: a
+ *                    non-manifold edge, bit 2: a face repeating an index; after a flag the counts are 0 and emit writes nothing.
+ *                    max_edges: 0 for no limit, else >= 3 (1 and 2: CNERF_EINVAL).  A simple loop of 3 <= n <= max_edges edges is
+ *                    filled, every other loop is left open.  counts (device uint32 [6]) = new vertices, new faces, loops filled, loops
+ *                    left open as not simple, loops left open as too long, flags.
+ *   holes_emit     : after holes_count on the same stream with the same ws and arguments.  verts_out [V + new vertices][3], faces_out
+ *                    [F + new faces][3], normals_out (written when normals != NULL): the input is their prefix, bit for bit (vertices
+ *                    no face references included).  Then, per filled loop in increasing label: n = 3, a -> b -> c -> a from the label:
+ *                    the face (b, a, c), no vertex.  n > 3: one vertex c and, in loop order from the label, the face (b, a, c) for
+ *                    every half-edge a -> b — the winding of that half-edge's missing twin.  c = the sum of the loop's positions
+ *                    (the a of every half-edge) in fp64 in loop order, divided by n, rounded once to float32.  Its normal: the sum over
+ *                    the fan's faces, in loop order, of (p1 - p0) x (p2 - p0) in fp64 from the float32 positions (c as rounded), m;
+ *                    l = sqrt((mx mx + my my) + mz mz); (float)(m / l) when l > 0, else 0.  One rounding per written operation, nothing
+ *                    fused; division and square root are correctly rounded.  Entries at or past max_verts / max_faces are not written
+ *                    (a loop whose fan would cross either is not written at all).
+ *   workspace_bytes : about 17 bytes per vertex + 51 per face + 36 per 256 of max(V, 3 F).
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_holes_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_topology(const int32_t *faces, uint32_t V, uint32_t F, void *ws, uint64_t ws_bytes, uint32_t *counts, void *stream);
+int cnerf_mesh_topology_loops(uint32_t V, uint32_t F, void *ws, uint64_t ws_bytes, int32_t *loop_lengths, uint32_t max_loops, void *stream);
+int cnerf_mesh_holes_count(const int32_t *faces, uint32_t V, uint32_t F, uint32_t max_edges, void *ws, uint64_t ws_bytes, uint32_t *counts,
+                           void *stream);
+int cnerf_mesh_holes_emit(const float *verts, const float *normals, uint32_t V, const int32_t *faces, uint32_t F, uint32_t max_edges,
+                          void *ws, uint64_t ws_bytes, float *verts_out, float *normals_out, int32_t *faces_out, uint32_t max_verts,
+                          uint32_t max_faces, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Closest-point queries against a triangle mesh and a deterministic surface sampler: what the deviation report is made of
