@@ -140,6 +140,8 @@ SIGNATURES = {
     "cnerf_tsdf_integrate": [vp, u32, u32, u32, vp, vp, f32, vp, vp, u32, u32, u32, vp, f32, f32, f32, f32, i32, f32, i32, vp],
     "cnerf_tsdf_finalize": [vp, u32, u32, u32, f32, vp, vp, vp],
     "cnerf_tsdf_face_keep": [vp, u32, u32, u32, vp, vp, vp, u32, vp, u32, vp, vp],
+    "cnerf_view_colors_accumulate": [vp, vp, u32, vp, vp, vp, u32, u32, u32, vp, f32, f32, f32, f32, i32, f32, i32, f32, f32, i32, vp, vp, vp],
+    "cnerf_view_colors_resolve": [vp, vp, u32, vp, vp, vp, vp, vp],
     "cnerf_mesh_holes_workspace_bytes": [u32, u32, vp],
     "cnerf_mesh_topology": [vp, u32, u32, vp, u64, vp, vp],
     "cnerf_mesh_topology_loops": [u32, u32, vp, u64, vp, u32, vp],

@@ -9,7 +9,8 @@ shaded images), closest-point queries through a bounding-volume hierarchy with a
 watertight ray casts through the same hierarchy and the per-vertex ambient occlusion built on them, the projection of a low-polygon mesh's
 texels onto the full-resolution surface for baking colour and normal maps (csrc/mesh_bvh.hip), welded vertices with tangent frames and
 tangent-space normal maps through the same bake (csrc/mesh_tangent.hip, k_bake_tspace of csrc/mesh_bake.h), TSDF fusion of rendered or
-rasterised depth maps into a volume whose zero level is the surface the views show (TSDFVolume, csrc/mesh_tsdf.hip), a binary PLY writer,
+rasterised depth maps into a volume whose zero level is the surface the views show (TSDFVolume, csrc/mesh_tsdf.hip), the colour of
+texels and vertices blended from the rendered views that see them (ViewColors, csrc/mesh_view_colors.hip), a binary PLY writer,
 an OBJ + MTL + PNG writer and a glTF 2.0 binary (.glb) writer.
 
 The reference turns a density volume into a mesh with skimage.measure.marching_cubes on the host and writes it with plyfile
@@ -1255,6 +1256,146 @@ class TSDFVolume:
         verts, faces = verts[used].contiguous(), new_index[kept.long()].contiguous()
         info = {'observed': seen / math.prod(self.shape), 'dropped_faces': int(keep.numel() - kept.shape[0])}
         return verts, faces, vertex_normals(verts, faces), info
+
+
+# ------------------------------------------------------------------------------------------------ colour fused from rendered views
+_VIEW_BATCH = 16                                                                # views per launch of cnerf_view_colors_accumulate
+
+
+class ViewColors:
+    """Colour of surface points blended from the rendered views that see them, on the device (csrc/mesh_view_colors.hip; the rules are
+    in include/customnerf_hip.h, cnerf_view_colors_*): a bake_texture color_fn that returns what the renders show — the composited
+    colour along camera rays — in place of one point query of the field.  images [N, H, W, 3] float32 CUDA, depth [N, H, W] float32
+    CUDA: the depth of THE SURFACE THE QUERIED POINTS LIE ON from each camera (rasterize(...)['depth'] of that mesh with depth_kind='z';
+    'ray' takes a distance along the ray), never a NeRF's own depth; c2w [N, 3|4, 4] (tensor or array), intrinsics (fx, fy, cx, cy)
+    and convention as generate_rays and rasterize take them; weights None or like depth (a rendered opacity: a pixel with weight 0 says
+    nothing).  A view sees a point when the point lies at least `near` in front of it, the 2 x 2 pixels round its projection lie in
+    the image and all four depths are finite and within depth_tol of the point's — required: a geometric scale only the caller knows,
+    a few times the pixel footprint on the surface — and the cosine between the normal and the direction to the camera exceeds
+    min_cos; its bilinear colour enters with weight cos^power times the bilinear pixel weight.  power (an integer 1..8) and min_cos
+    (in [0, 1)) are documented defaults, not measured optima.  Pinhole views only, and no exposure compensation between views.
+    vc(x [M, 3], d [M, 3]) -> [M, 3] float32 is the color_fn: the normal is -d.  Where no view saw the point the row comes from
+    `fallback`, another color_fn evaluated for the whole chunk (no host read), else it is `fill` (3 floats).  vc.counts [3] int64 on the
+    device adds up, over the calls, the points seen by 0, 1 and >= 2 views; reset_counts() clears it.  The views are summed in index
+    order with no atomics: the result does not depend on how they are cut into launches.  Bad arguments raise ValueError before any
+    launch."""
+
+    def __init__(self, images, depth, c2w, intrinsics, depth_tol, convention='nerfstudio', depth_kind='z', weights=None, power=2, min_cos=0.2,
+                 near=0.01, fallback=None, fill=(0, 0, 0)):
+        if images.dim() != 4 or images.shape[3] != 3:
+            raise ValueError(f"ViewColors: images must be [N, H, W, 3], got {tuple(images.shape)}")
+        N, H, W = images.shape[:3]
+        if tuple(depth.shape) != (N, H, W):
+            raise ValueError(f"ViewColors: depth must be [N, H, W] like images, got {tuple(depth.shape)} and {(N, H, W)}")
+        if weights is not None and tuple(weights.shape) != (N, H, W):
+            raise ValueError(f"ViewColors: weights must be shaped like depth, got {tuple(weights.shape)} and {(N, H, W)}")
+        for name, t in (("images", images), ("depth", depth), ("weights", weights)):
+            if t is not None and t.dtype != torch.float32:
+                raise ValueError(f"ViewColors: {name} must be float32, got {t.dtype}")
+            if t is not None and t.device != images.device:
+                raise ValueError(f"ViewColors: {name} lives on {t.device}, images on {images.device}")
+        m = _host(c2w, np.float32)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.shape[0] != N:
+            raise ValueError(f"ViewColors: need one c2w per image, got {m.shape} for {N} views")
+        _, k, H, W = _camera(np.zeros((3, 4), np.float32), intrinsics, H, W, "ViewColors")
+        self._cams = [_camera(m[v], intrinsics, H, W, "ViewColors")[0] for v in range(N)]
+        if not np.isfinite(m[:, :3]).all():
+            raise ValueError("ViewColors: c2w holds non-finite values")
+        if convention not in _CONVENTIONS:
+            raise ValueError(f"ViewColors: convention must be 'nerfstudio' or 'ngp', got {convention!r}")
+        if depth_kind not in _DEPTH_KINDS:
+            raise ValueError(f"ViewColors: depth_kind must be 'ray' or 'z', got {depth_kind!r}")
+        near = float(near)
+        if not (math.isfinite(near) and all(math.isfinite(x) for x in k) and k[0] != 0.0 and k[1] != 0.0):
+            raise ValueError(f"ViewColors: need finite intrinsics with fx, fy != 0 and a finite near, got {k}, near = {near}")
+        self.depth_tol = float(depth_tol)
+        if not (math.isfinite(self.depth_tol) and self.depth_tol > 0.0):
+            raise ValueError(f"ViewColors: depth_tol must be finite and > 0, got {depth_tol}")
+        if isinstance(power, bool) or not isinstance(power, (int, np.integer)) or not 1 <= power <= 8:
+            raise ValueError(f"ViewColors: power must be an integer in 1..8, got {power!r}")
+        self.min_cos = float(min_cos)
+        if not 0.0 <= self.min_cos < 1.0:
+            raise ValueError(f"ViewColors: min_cos must lie in [0, 1), got {min_cos}")
+        if fallback is not None and not callable(fallback):
+            raise ValueError(f"ViewColors: fallback must be None or a color_fn(x, d), got {type(fallback).__name__}")
+        fl = tuple(float(c) for c in fill)
+        if len(fl) != 3 or not all(math.isfinite(c) for c in fl):
+            raise ValueError(f"ViewColors: fill must be 3 finite values, got {fill}")
+        require_cuda(images, depth, weights)                                    # last: everything above is checked without a device
+        self.images, self.depth = images.detach().contiguous(), depth.detach().contiguous()
+        self.weights = None if weights is None else weights.detach().contiguous()
+        self.views, self.H, self.W, self.device = N, H, W, images.device
+        self.intrinsics, self.near, self.power = k, near, int(power)
+        self.convention, self.depth_kind = convention, depth_kind
+        self.fallback, self._fill = fallback, (C.c_float * 3)(*fl)
+        self.counts = torch.zeros(3, dtype=torch.int64, device=self.device)
+
+    def reset_counts(self):
+        self.counts.zero_()
+
+    def _points(self, x, normals, what):
+        require_cuda(x, normals)
+        if x.dim() != 2 or x.shape[1] != 3 or tuple(normals.shape) != tuple(x.shape):
+            raise ValueError(f"{what}: points and normals must both be [M, 3], got {tuple(x.shape)} and {tuple(normals.shape)}")
+        if x.shape[0] >= 2 ** 31:
+            raise ValueError(f"{what}: at most 2^31 - 1 points a call, got {x.shape[0]}")
+        if x.device != self.device or normals.device != self.device:
+            raise ValueError(f"{what}: the views live on {self.device}, the points on {x.device}")
+        return x.detach().contiguous().float(), normals.detach().contiguous().float()
+
+    def accumulate(self, x, normals, state=None, seen=None, views=None):
+        """Add the views `views` (a slice of the view indices; default all) to the sums of the points x [M, 3] with unit normals [M, 3]:
+        state [M, 4] float32 (sum of w r, w g, w b, w) and seen [M] int32 (the views that added), both zero when not given, updated in
+        place, one launch per 16 views.  -> (state, seen)"""
+        x, n = self._points(x, normals, "ViewColors.accumulate")
+        M = x.shape[0]
+        if state is None:
+            state = torch.zeros(M, 4, dtype=torch.float32, device=self.device)
+        if seen is None:
+            seen = torch.zeros(M, dtype=torch.int32, device=self.device)
+        if tuple(state.shape) != (M, 4) or state.dtype != torch.float32 or tuple(seen.shape) != (M,) or seen.dtype != torch.int32 or \
+                not state.is_contiguous() or not seen.is_contiguous() or state.device != self.device or seen.device != self.device:
+            raise ValueError(f"ViewColors.accumulate: state must be contiguous [M, 4] float32 and seen [M] int32 for M = {M} on {self.device}")
+        idx = range(self.views)[slice(None) if views is None else views]
+        if not isinstance(idx, range) or (len(idx) and idx.step != 1):
+            raise ValueError(f"ViewColors.accumulate: views must be a slice of consecutive views, got {views!r}")
+        for b in range(idx.start, idx.start + len(idx), _VIEW_BATCH):
+            nb = min(_VIEW_BATCH, idx.start + len(idx) - b)
+            cams = (C.c_float * (12 * nb))()
+            for v in range(nb):
+                cams[12 * v:12 * v + 12] = list(self._cams[b + v])
+            check(lib.cnerf_view_colors_accumulate(_p(x), _p(n), M, _p(self.images[b:b + nb]), _p(self.depth[b:b + nb]),
+                                                   None if self.weights is None else _p(self.weights[b:b + nb]), nb, self.H, self.W, cams,
+                                                   *self.intrinsics, _CONVENTIONS[self.convention], self.near, _DEPTH_KINDS[self.depth_kind],
+                                                   self.depth_tol, self.min_cos, self.power, _p(state), _p(seen), stream()),
+                  "view_colors_accumulate")
+        return state, seen
+
+    def resolve(self, state, seen, fallback=None):
+        """[M, 3] float32: acc / weight where a view saw the point, else the row of `fallback` ([M, 3] float32 tensor or None), else
+        `fill`; the points seen by 0, 1 and >= 2 views are added to `counts`."""
+        M = state.shape[0]
+        if fallback is not None and (tuple(fallback.shape) != (M, 3) or fallback.dtype != torch.float32 or not fallback.is_contiguous() or
+                                     fallback.device != self.device):
+            raise ValueError(f"ViewColors.resolve: fallback must be contiguous [M, 3] float32 for M = {M} on {self.device}")
+        out = torch.empty(M, 3, dtype=torch.float32, device=self.device)
+        check(lib.cnerf_view_colors_resolve(_p(state), _p(seen), M, _p(fallback), self._fill, _p(out), ptr(self.counts), stream()),
+              "view_colors_resolve")
+        return out
+
+    def __call__(self, x, d):
+        x, n = self._points(x, -d, "ViewColors")
+        state, seen = self.accumulate(x, n)
+        fb = None
+        if self.fallback is not None:
+            fb = self.fallback(x, d)
+            if not torch.is_tensor(fb) or fb.dim() != 2 or fb.shape[0] != x.shape[0] or fb.shape[1] < 3 or not fb.is_floating_point():
+                raise ValueError(f"ViewColors: fallback must return a floating tensor [N, >= 3] for N = {x.shape[0]} points, got "
+                                 f"{tuple(fb.shape) if torch.is_tensor(fb) else type(fb).__name__}")
+            fb = fb.detach()[:, :3].float().to(self.device).contiguous()
+        return self.resolve(state, seen, fb)
 
 
 def bvh_workspace_bytes(V, F):

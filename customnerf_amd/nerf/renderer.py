@@ -528,12 +528,79 @@ class NeRFRenderer(nn.Module):
                    render=dict(cfg['render'] or {}))
         return cfg
 
+    _COLOR_VIEW_KEYS = {'poses': None, 'intrinsics': None, 'H': None, 'W': None, 'convention': 'nerfstudio', 'min_opacity': 0.5,
+                        'render': None, 'depth_tol': None, 'power': 2, 'min_cos': 0.2}
+
+    @staticmethod
+    def _color_view_options(color_views, tsdf, wanted, max_step):
+        """extract_mesh's color_views= (a dict, or 'tsdf' for the cameras of `tsdf`) with its defaults filled in; everything wrong with it
+        raises ValueError before any render.  `wanted`: color=True or texture=R was asked for."""
+        keys = NeRFRenderer._COLOR_VIEW_KEYS
+        if isinstance(color_views, str):
+            if color_views != 'tsdf':
+                raise ValueError(f"extract_mesh: color_views must be None, a dict of options or 'tsdf', got {color_views!r}")
+            if not isinstance(tsdf, dict):
+                raise ValueError("extract_mesh: color_views='tsdf' reuses the cameras of tsdf=, which is not given")
+            color_views = {k: tsdf[k] for k in ('poses', 'intrinsics', 'H', 'W', 'convention', 'min_opacity', 'render') if k in tsdf}
+        if not isinstance(color_views, dict):
+            raise ValueError(f"extract_mesh: color_views must be None, a dict of options or 'tsdf', got {type(color_views).__name__}")
+        if not wanted:
+            raise ValueError("extract_mesh: color_views colours the vertices or a texture; it needs color=True or texture=R")
+        unknown = sorted(set(color_views) - set(keys))
+        if unknown:
+            raise ValueError(f"extract_mesh: unknown color_views keys {unknown}; known: {sorted(keys)}")
+        missing = [k for k in ('poses', 'intrinsics', 'H', 'W') if color_views.get(k) is None]
+        if missing:
+            raise ValueError(f"extract_mesh: color_views needs {missing}")
+        cfg = {**keys, **color_views}
+        p = cfg['poses']
+        p = torch.as_tensor(np.asarray(p.detach().cpu() if torch.is_tensor(p) else p, dtype=np.float32))
+        if p.dim() != 3 or tuple(p.shape[1:]) not in ((3, 4), (4, 4)):
+            raise ValueError(f"extract_mesh: color_views['poses'] must be [N, 3, 4] or [N, 4, 4], got {tuple(p.shape)}")
+        if p.shape[0] == 0:
+            raise ValueError("extract_mesh: color_views['poses'] holds no view")
+        if not bool(torch.isfinite(p).all()):
+            raise ValueError("extract_mesh: color_views['poses'] holds non-finite values")
+        if cfg['convention'] not in ('nerfstudio', 'ngp'):
+            raise ValueError(f"extract_mesh: color_views['convention'] must be 'nerfstudio' or 'ngp', got {cfg['convention']!r}")
+        k = tuple(float(x) for x in cfg['intrinsics'])
+        if len(k) != 4:
+            raise ValueError(f"extract_mesh: color_views['intrinsics'] must be (fx, fy, cx, cy), got {len(k)} values")
+        tol = 2.0 * max_step if cfg['depth_tol'] is None else float(cfg['depth_tol'])
+        if not (math.isfinite(tol) and tol > 0.0):
+            raise ValueError(f"extract_mesh: color_views['depth_tol'] must be finite and > 0, got {cfg['depth_tol']}")
+        power, min_cos = cfg['power'], float(cfg['min_cos'])
+        if isinstance(power, bool) or not isinstance(power, (int, np.integer)) or not 1 <= power <= 8:
+            raise ValueError(f"extract_mesh: color_views['power'] must be an integer in 1..8, got {power!r}")
+        if not 0.0 <= min_cos < 1.0:
+            raise ValueError(f"extract_mesh: color_views['min_cos'] must lie in [0, 1), got {cfg['min_cos']}")
+        H, W = int(cfg['H']), int(cfg['W'])
+        if H < 2 or W < 2:
+            raise ValueError(f"extract_mesh: color_views needs H, W >= 2, got {H}, {W}")
+        cfg.update(poses=p, intrinsics=k, depth_tol=tol, power=int(power), min_cos=min_cos, H=H, W=W, min_opacity=float(cfg['min_opacity']),
+                   render=dict(cfg['render'] or {}))
+        return cfg
+
+    def _view_colors(self, cfg, verts, faces, fallback):
+        """mesh.ViewColors of the views of cfg (_color_view_options) on the surface (verts, faces): every pose rendered with render_view —
+        its opacity is the pixel weight, zero below min_opacity — and the surface rasterised from it for the visibility depth"""
+        images, depths, weights = [], [], []
+        for pose in cfg['poses']:
+            rv = self.render_view(pose, cfg['intrinsics'], cfg['H'], cfg['W'], convention=cfg['convention'], min_opacity=cfg['min_opacity'],
+                                  **cfg['render'])
+            images.append(rv['image'])
+            weights.append(torch.where(rv['opacity'] >= cfg['min_opacity'], rv['opacity'], torch.zeros_like(rv['opacity'])))
+            depths.append(_mesh.rasterize(verts, faces, pose, cfg['intrinsics'], cfg['H'], cfg['W'], convention=cfg['convention'])['depth'])
+        return _mesh.ViewColors(torch.stack(images), torch.stack(depths), cfg['poses'], cfg['intrinsics'], cfg['depth_tol'],
+                                convention=cfg['convention'], depth_kind='z', weights=torch.stack(weights), power=cfg['power'],
+                                min_cos=cfg['min_cos'], fallback=fallback)
+
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
                      smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0,
                      texture_layout='uniform', bake_from='mesh', bake_reach=None, normal_map=False, sparse=False, sparse_probe=4,
-                     tsdf=None, fill_holes=False, topology=False):
+                     tsdf=None, fill_holes=False, topology=False, color_views=None):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -602,7 +669,20 @@ class NeRFRenderer(nn.Module):
         'deviation' and bake_from='source' compare with); a fan across a large, non-planar hole is a coarse patch, and loops through a
         pinched vertex stay open.  Not with simplify, whose output need not be manifold; it works with sparse=True and with tsdf=.
         'holes' joins the dict: mesh.fill_holes' info.  topology=True adds 'topology': mesh.topology of the final mesh (edges, boundary
-        loops, Euler characteristic, 'watertight', ...).  With the defaults neither key is present."""
+        loops, Euler characteristic, 'watertight', ...).  With the defaults neither key is present.
+        color_views=dict(...) takes the colour of color=True and texture=R (one of which it needs) from rendered views in place of one
+        field query per point — forward(x, -normal) reads the radiance of a single point in a direction no training ray had, while what
+        the renders show is the colour composited along camera rays.  Every pose is rendered with render_view; the surface the
+        queried points lie on — the final mesh, or with bake_from='source' the mesh as it stood after marching cubes and component
+        removal — is rasterised from the same pose (mesh.rasterize) for the visibility depth, never the field's own depth; and
+        mesh.ViewColors (csrc/mesh_view_colors.hip) blends, per point, the views that see it, weighted by cos^power of the viewing
+        angle and by the rendered opacity (zero below min_opacity).  Points no view sees fall back to the field query.  Keys: 'poses'
+        [N, 3|4, 4], 'intrinsics' (fx, fy, cx, cy), 'H', 'W' (required); 'convention' ('nerfstudio'), 'min_opacity' (0.5), 'render'
+        (kwargs of render()), 'depth_tol' (how far a point may lie from the rasterised depth and still count as seen; default twice
+        the largest lattice step), 'power' (2) and 'min_cos' (0.2) — documented defaults, not measured optima.  color_views='tsdf'
+        reuses the cameras of tsdf= (ValueError without it).  Pinhole views only, and no exposure compensation between views.
+        'view_colors' joins the dict: {'views', 'seen': [3] int64 on the device, the points asked (vertices and texels) that 0, 1 and
+        >= 2 views saw, 'depth_tol'}.  With color_views=None the key is absent and every output is what it was."""
         if fill_holes is True or fill_holes is False:
             fill_edges = None
         elif isinstance(fill_holes, (int, np.integer)) and fill_holes >= 3:
@@ -646,6 +726,9 @@ class NeRFRenderer(nn.Module):
             raise ValueError(f"extract_mesh: bake_reach must be > 0, got {bake_reach}")
         if int(sparse_probe) < 1:
             raise ValueError(f"extract_mesh: sparse_probe must be >= 1 (every how many lattice points the field is probed), got {sparse_probe}")
+        cv_cfg = None
+        if color_views is not None:
+            cv_cfg = self._color_view_options(color_views, tsdf, bool(color) or bool(tex_r), float(step.max()))
         sparse_info = tsdf_info = None
         if tsdf is not None:
             cfg = self._tsdf_options(tsdf, sparse, part, float(step.max()))
@@ -686,6 +769,10 @@ class NeRFRenderer(nn.Module):
             verts, faces, normals, _ = _mesh.decimate(verts, faces, tf, normals=normals)
         source = _mesh.bake_source(*kept) if from_source and (color or tex_r) else None
         kinds = torch.zeros(4, dtype=torch.int64, device=verts.device) if from_source else None
+        field_color = lambda x, d: self(x, d)[1][:, :3]                         # noqa: E731
+        color_fn = field_color
+        if cv_cfg is not None:                                                   # the views on the surface the queried points lie on
+            color_fn = self._view_colors(cv_cfg, *(kept[:2] if source is not None else (verts, faces)), field_color)
         colors = None
         if color:
             colors = torch.empty(verts.shape[0], 3, dtype=torch.uint8, device=verts.device)
@@ -696,11 +783,11 @@ class NeRFRenderer(nn.Module):
                     x, look = pr['point'], -pr['normal']
                     if not tex_r:
                         kinds += (pr['kind'][:, None] == torch.arange(4, dtype=torch.uint8, device=x.device)).sum(0)
-                rgb = self(x, look)[1][:, :3].float()
+                rgb = color_fn(x, look).float()
                 colors[s:s + chunk] = (rgb.clamp(0, 1) * 255).round().to(torch.uint8)
         uvs = tex = nmap = tangents = None
         if tex_r:
-            baked = _mesh.bake_texture(verts, faces, tex_r, lambda x, d: self(x, d)[1][:, :3], normals=normals, chunk=chunk,
+            baked = _mesh.bake_texture(verts, faces, tex_r, color_fn, normals=normals, chunk=chunk,
                                        layout=texture_layout, source=source, reach=reach if source is not None else None,
                                        normal_map=normal_map if isinstance(normal_map, str) else bool(normal_map))
             uvs, tex = baked[:2]
@@ -715,6 +802,8 @@ class NeRFRenderer(nn.Module):
             m['tsdf'] = tsdf_info
         if holes_info is not None:
             m['holes'] = holes_info
+        if cv_cfg is not None:
+            m['view_colors'] = {'views': color_fn.views, 'seen': color_fn.counts, 'depth_tol': color_fn.depth_tol}
         if topology:
             m['topology'] = _mesh.topology(verts, faces)
         if normal_map:
@@ -742,7 +831,7 @@ class NeRFRenderer(nn.Module):
         their normals and colours, or the ambient occlusion as grey, as for PLY; unlit unless it carries a normal map); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
         extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), texture_layout, deviation /
-        deviation_spacing, ao, bake_from, bake_reach, sparse, sparse_probe, tsdf, fill_holes and topology pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
+        deviation_spacing, ao, bake_from, bake_reach, sparse, sparse_probe, tsdf, fill_holes, topology and color_views pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
         in the material) and, like texture=, needs an .obj path; normal_map='tangent' needs a .glb path (OBJ carries no tangents) and
         normal_map=True is refused for .glb (glTF has no object-space slot).  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written
@@ -832,6 +921,42 @@ class NeRFRenderer(nn.Module):
             opacity[s:s + batch] = acc
         depth = torch.where(opacity >= float(min_opacity), depth, torch.full_like(depth, math.inf))
         return {'depth': depth.view(H, W), 'opacity': opacity.view(H, W)}
+
+    @torch.no_grad()
+    def render_view(self, c2w, intrinsics, H, W, convention='nerfstudio', min_opacity=0.5, max_ray_batch=1 << 16, **render_kw):
+        """render_depth's view with its colour, from the same one pass per ray batch: -> {'image': [H, W, 3] float32, the composited
+        colour render() returns (over its background, where one is set), 'depth', 'opacity'}; depth and opacity are render_depth's, bit
+        for bit.  What extract_mesh(color_views=...) projects onto the mesh."""
+        m = torch.as_tensor(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, dtype=np.float32))
+        if tuple(m.shape) not in ((3, 4), (4, 4)):
+            raise ValueError(f"render_view: c2w must be [3, 4] or [4, 4], got {tuple(m.shape)}")
+        k = tuple(float(x) for x in intrinsics)
+        H, W, batch = int(H), int(W), int(max_ray_batch)
+        if len(k) != 4 or H < 1 or W < 1 or batch < 1:
+            raise ValueError(f"render_view: need intrinsics (fx, fy, cx, cy), H, W >= 1 and max_ray_batch >= 1, got {k}, {H}, {W}, {batch}")
+        from .provider_utils import generate_rays
+        dev = self.aabb_infer.device
+        o, d = generate_rays(m[None, :3].to(dev), *k, H, W, 1.0, convention)
+        o, d = o.view(-1, 3), d.view(-1, 3)
+        image = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
+        depth = torch.empty(H * W, dtype=torch.float32, device=dev)
+        opacity = torch.empty_like(depth)
+        aabb = self.aabb_train if self.training else self.aabb_infer
+        for s in range(0, H * W, batch):
+            ro, rd = o[s:s + batch].contiguous(), d[s:s + batch].contiguous()
+            res = self.render(ro[None], rd[None], staged=True, perturb=False, **render_kw)
+            if 'depth' not in res or 'image' not in res:
+                raise ValueError("render_view: render() returned no image or depth (run() fills its results only under opt.train_conf)")
+            acc = res['weights_sum'].reshape(-1).float()
+            t = res['depth'].reshape(-1).float() / acc                          # the arithmetic of render_depth, in its order
+            if not self.cuda_ray:
+                near, far = raymarching.near_far_from_aabb(ro, rd, aabb, self.min_near)
+                t = near + t * (far - near)
+            depth[s:s + batch] = t * rd.norm(dim=-1)
+            opacity[s:s + batch] = acc
+            image[s:s + batch] = res['image'].reshape(-1, 3).float()
+        depth = torch.where(opacity >= float(min_opacity), depth, torch.full_like(depth, math.inf))
+        return {'image': image.view(H, W, 3), 'depth': depth.view(H, W), 'opacity': opacity.view(H, W)}
 
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=2048, **kwargs):
         """renderer.py:1719-1733."""

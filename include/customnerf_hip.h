@@ -1006,6 +1006,55 @@ int cnerf_tsdf_face_keep(const float *state, uint32_t nx, uint32_t ny, uint32_t 
                          const float *verts, uint32_t V, const int32_t *faces, uint32_t F, uint8_t *keep, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Multi-view colour fusion: the colour of surface points (the texels of a bake, the vertices of a mesh) blended from the rendered views
+ * that see them (customnerf_amd/mesh.py ViewColors; csrc/mesh_view_colors.hip; the reference has none — NeRF-to-mesh exporters project
+ * their renders onto the surface on the host).  All float arithmetic is float32, one rounding per written operation, in the order
+ * written (the build has -ffp-contract=off); divisions and square roots are correctly rounded: the rasteriser's rules above.
+ *   Points: points / normals device float32 [M][3], p and its unit normal n (not normalised here), in any order; M < 2^31.
+ *   Views: images device float32 [n_views][H][W][3], depth device float32 [n_views][H][W] — the depth of THE SURFACE THE POINTS LIE ON
+ *   from each camera (cnerf_mesh_raster_visibility: camera-axis depth, depth_kind 0; or a distance along the ray, depth_kind 1) —
+ *   pixel_weight device float32 [n_views][H][W] or NULL.  Cameras: those of cnerf_tsdf_integrate, one c2w_host float32 [3][4] per view
+ *   on the host, shared fx, fy, cx, cy, convention and near; the vertex transform is the rasteriser's own code (csrc/mesh_camera.h).
+ *   State: float32 [M][4] on the device, 16-byte aligned: (sum of w r, sum of w g, sum of w b, sum of w) over the views so far, and seen
+ *   uint32 [M], the number of views that added to the point; all zero at first (the caller clears them).
+ *   accumulate, per point, for each view v in index order ("skip": this view adds nothing to this point):
+ *      1. d = p - t; c_k = (m[0][k] d0 + m[1][k] d1) + m[2][k] d2; z = -c_2 (convention 0) or c_2 (convention 1); skip unless z >= near
+ *         (a NaN z fails the test); X = cx + fx (c_0 / z); Y = cy + (-1) (fy (c_1 / z)) (convention 0) or cy + fy (c_1 / z)
+ *         (convention 1): steps 1-6 of cnerf_tsdf_integrate
+ *      2. pixels are sampled at their centres: u = X - 0.5, v = Y - 0.5, x0 = floorf(u), y0 = floorf(v), ax = u - x0, ay = v - y0; skip
+ *         unless the whole 2 x 2 footprint lies in the image: 0 <= x0 <= (float)(W - 2) and 0 <= y0 <= (float)(H - 2), tested on the
+ *         floats (non-finite values fail), then (int) x0 + 1 < W and (int) y0 + 1 < H (which can fail only where the float rounds up,
+ *         W > 2^24).  A point that projects into the half-pixel border of the image is skipped
+ *      3. len = sqrtf((d0 d0 + d1 d1) + d2 d2); r = z (depth_kind 0) or len (depth_kind 1); skip unless ALL FOUR footprint depths
+ *         D = depth[v][y0 + j][x0 + i] satisfy D > 0, D < inf and fabsf(D - r) <= depth_tol (NaN fails).  Conservative at silhouettes on
+ *         purpose — a footprint that straddles an occluding edge or the background is dropped whole, another view covers that point —
+ *         so background never bleeds in
+ *      4. cos = -((n0 d0 + n1 d1) + n2 d2) / len; skip unless cos > min_cos; w = cos, then power - 1 times w = w cos (power 1..8).  With
+ *         pixel_weight: w = w q, q the bilinear value of the four weights as in 5.  Skip unless 0 < w < inf
+ *      5. per channel, with gx = 1 - ax, gy = 1 - ay and c_ij = images[v][y0 + j][x0 + i]:
+ *         c = (c00 gx + c10 ax) gy + (c01 gx + c11 ax) ay
+ *      6. acc_k += w c_k (the product rounded, then the sum) for k = r, g, b; wsum += w; seen += 1
+ *   One launch takes at most 16 views, the cameras by value; n_views > 16 is CNERF_EINVAL and the caller cuts the views.  A point's sums
+ *   run in view order within and across launches and calls, so the state does not depend on the cut: 33 views as 16 + 16 + 1, as
+ *   1 + 32 or one by one give the same bytes.  Colour and pixel weight are read only where the depth test passed.
+ *   resolve: out[i] (device float32 [M][3]) = acc / wsum per channel where wsum > 0, else fallback[i] (device float32 [M][3]) when
+ *            fallback != NULL, else fill_host (float32 [3] on the host).  counts (device uint64 [3]) += the number of points with seen
+ *            == 0, == 1 and >= 2: resolve adds to what counts holds (the caller clears it), integer adds, so any order of arrival gives
+ *            the same value.
+ *   CNERF_EINVAL: M >= 2^31; (accumulate) n_views > 16, fx or fy zero or non-finite, cx / cy / near non-finite, convention or depth_kind
+ *   outside {0, 1}, depth_tol not finite or <= 0, min_cos outside [0, 1), power outside 1..8, H W >= 2^31.  Then M == 0 or n_views == 0:
+ *   CNERF_OK without a launch.  Then CNERF_ENULL: a NULL points, normals, images, depth, c2w_host, state, seen, fill_host, out or
+ *   counts; then CNERF_EINVAL for a state that is not 16-byte aligned.  H < 2 or W < 2: CNERF_OK without a launch (no footprint fits).
+ *   All return before any launch.  No workspace; no float atomics: the output is bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_view_colors_accumulate(const float *points, const float *normals, uint32_t M, const float *images, const float *depth,
+                                 const float *pixel_weight, uint32_t n_views, uint32_t H, uint32_t W, const float *c2w_host, float fx, float fy,
+                                 float cx, float cy, int convention, float near, int depth_kind, float depth_tol, float min_cos, int power,
+                                 float *state, uint32_t *seen, void *stream);
+int cnerf_view_colors_resolve(const float *state, const uint32_t *seen, uint32_t M, const float *fallback, const float *fill_host, float *out,
+                              uint64_t *counts, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Topology report and hole filling (customnerf_amd/mesh.py topology / fill_holes; csrc/mesh_holes.hip; the reference has none).  verts
  * float32 [V][3], optional normals float32 [V][3] (NULL: none), faces int32 [F][3].  V < 2^31 and F <= 0x2AAAAAAA (half-edge ids 3 f + k
  * and loop lengths stay below 2^31), else CNERF_EINVAL; F = 0 returns CNERF_OK without a launch and writes nothing; ws 16-byte aligned and
