@@ -282,13 +282,26 @@ def attention_apply(P, v, heads):
 
 def attention(q, k, v, heads, causal=False):
     """softmax(q k^T / sqrt(d)) v per head; q [B, Tq, C], k / v [B, Tk, C] half (strided views of a fused projection are fine).
-    Head dims <= 160: the fused kernel (scores never materialised); larger heads: explicit scores (attention_scores / _apply)."""
+    Head dims <= 160: the fused kernel (scores never materialised); larger heads, and head dims that are no multiple of 8: explicit scores
+    (attention_scores / _apply)."""
     B, Tq, C = q.shape
     Tk = k.shape[1]
     d_ = C // heads
     if d_ > 160 or d_ % 8:
         assert not causal
-        return attention_apply(attention_scores(q, k, heads, 1.0 / float(d_) ** 0.5), v, heads)
+        alpha = 1.0 / float(d_) ** 0.5
+        if d_ % 8 == 0:
+            return attention_apply(attention_scores(q, k, heads, alpha), v, heads)
+        # the GEMMs read their operands in 16-byte chunks (K % 8, 16-byte aligned head slices): every head padded to pad8(d) channels with
+        # zeros, which add nothing to a score and give zero output channels
+        dp = pad8(d_)
+
+        def padded(t):
+            p = torch.zeros(t.shape[0], t.shape[1], heads, dp, dtype=t.dtype, device=t.device)
+            p[..., :d_].copy_(t.unflatten(2, (heads, d_)))
+            return p.flatten(2)
+        o = attention_apply(attention_scores(padded(q), padded(k), heads, alpha), padded(v), heads)
+        return o.unflatten(2, (heads, dp))[..., :d_].reshape(B, Tq, C)
     assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
     if v.stride(1) % 8 == 0 and v.stride(0) % 8 == 0 and v.data_ptr() % 16 == 0:
         # V as the projection leaves it (e.g. the last third of a fused qkv GEMM): the kernel transposes its key tiles in LDS
