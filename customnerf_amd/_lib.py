@@ -156,6 +156,10 @@ SIGNATURES = {
     "cnerf_mesh_bvh_raycast": [vp, u64, u32, u32, vp, vp, u32, f32, f32, vp, vp, i32, vp, vp, vp, vp, vp],
     "cnerf_mesh_bvh_occluded": [vp, u64, u32, u32, vp, vp, u32, f32, f32, vp, vp, i32, vp, vp, vp],
     "cnerf_mesh_bvh_project": [vp, u64, u32, u32, vp, vp, vp, vp, u32, f32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "cnerf_mesh_winding_workspace_bytes": [u32, u32, vp],
+    "cnerf_mesh_winding_build": [vp, u64, u32, u32, vp, u64, vp],
+    "cnerf_mesh_winding_query": [vp, u64, u32, u32, vp, u64, vp, u32, f32, vp, vp, vp],
+    "cnerf_mesh_bvh_signed_distance": [vp, u64, u32, u32, vp, u64, vp, u32, f32, vp, vp, vp, vp, vp],
     # ---- include/customnerf_sd.h (score-distillation primitives)
     "cnerf_sd_gemm": [vp, vp, u64, vp],
     "cnerf_sd_gemm_workspace_bytes": [vp, vp],

@@ -1,7 +1,8 @@
 // Closest-point and ray queries against a triangle mesh through a bounding-volume hierarchy, and a deterministic surface sampler
 // (cnerf_mesh_bvh_*, cnerf_mesh_sample_*): what mesh.distance() measures the deviation between two meshes with, and what mesh.ray_cast(),
 // mesh.occluded() and mesh.ambient_occlusion() ask, and what mesh.project_to_surface() moves the texels of a decimated mesh onto the
-// full-resolution surface with (cnerf_mesh_bvh_project).  Same conventions as the other mesh passes: the
+// full-resolution surface with (cnerf_mesh_bvh_project), and the inside test and signed distance of mesh.winding_number(),
+// mesh.contains() and mesh.signed_distance() (cnerf_mesh_winding_*, cnerf_mesh_bvh_signed_distance).  Same conventions as the other mesh passes: the
 // caller's stream, buffers and workspace, no allocation, no host synchronisation, no float atomics.  The rules (which faces take part, the
 // point-triangle rule, the ray-triangle rule, the sampler's enumeration) are in include/customnerf_hip.h; tests/bvh_restatement.py and
 // tests/ray_restatement.py restate them bit for bit.
@@ -70,6 +71,18 @@
 //                   a wave that hit idle meanwhile; on a baker's input, where the low mesh lies within reach of its source, those are the
 //                   texels past a rim).  The walks keep a face, its record's slot and its barycentrics; the point, the interpolated
 //                   normal (the one place the source's faces and normals are read) and the offset are made once, after the walks.
+// Winding number
+//   k_bvh_moments_leaf / k_bvh_moments_fit : per node of the same implicit tree a centre, the radius of a ball about it that holds the
+//                   node's vertices, the sum of the faces' area vectors and of their areas — two float4 per heap index in a buffer of
+//                   their own, built like the boxes: the deepest level from the records, then one launch per level from the children.
+//                   The BVH workspace is read only.
+//   k_bvh_winding : one thread per query, the generalized winding number: a depth-first walk, left child first, whose whole state is the
+//                   heap index and its depth (the next node: up while a right child, then the right sibling).  A node further away
+//                   than beta radii adds its dipole (Barill et al. 2018) from the moments alone — the boxes are never read —
+//                   otherwise the walk descends, and a leaf adds the solid angles of its records.  The result depends on the tree,
+//                   unlike the queries above: the header fixes every operation, tests/winding_restatement.py restates them.
+//   k_bvh_signed  : bv_nearest, unchanged, for the distance and the face; then the winding walk for the sign.  The walks run one after
+//                   the other and share only the query point.
 // Sampler
 //   k_sample_count / k_sample_scan / k_sample_emit : k^2 per face -> workgroup totals -> offsets -> one thread per sample (a binary search in
 //                   the workgroup's 256 prefix sums finds its face), so the writes are coalesced whatever the mix of face sizes.
@@ -906,6 +919,211 @@ __global__ __launch_bounds__(MC_BLOCK) void k_bvh_project(BvPtr ws, uint32_t V, 
     if (stats) bv_add_stats(stats, visits, tests);
 }
 
+// ------------------------------------------------------------------------------------------------ winding number
+__device__ __forceinline__ void bv_cross(const float u[3], const float v[3], float c[3]) {
+    c[0] = u[1] * v[2] - u[2] * v[1];
+    c[1] = u[2] * v[0] - u[0] * v[2];
+    c[2] = u[0] * v[1] - u[1] * v[0];
+}
+
+__device__ __forceinline__ float bv_len(const float u[3]) { return sqrtf(bv_dot(u, u)); }
+
+// the leaves [l0, l1) of node j of the deepest level D (none or one)
+__device__ __forceinline__ void bv_leaf_range(uint32_t j, uint32_t NL, uint32_t D, uint32_t &l0, uint32_t &l1) {
+    l0 = (uint32_t)(((uint64_t)j * NL) >> D);
+    l1 = (uint32_t)((((uint64_t)j + 1) * NL) >> D);
+}
+
+// The moments of the deepest level's nodes, by the leaf rule of the header.  One thread per node; the records are read twice (the
+// sums, then the radius about the centre the sums give).
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_moments_leaf(BvPtr p, uint32_t F, float4 *__restrict__ mom) {
+    const uint32_t j = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = min(p.hdr[H_N], F);
+    uint32_t NL, D, l0, l1;
+    bv_shape(n, NL, D);
+    if (j >= (1u << D)) return;
+    bv_leaf_range(j, NL, D, l0, l1);
+    float A = 0.0f, N[3] = {0.0f, 0.0f, 0.0f}, S[3] = {0.0f, 0.0f, 0.0f}, M[3] = {0.0f, 0.0f, 0.0f}, a[3], b[3], c[3];
+    uint32_t cnt = 0;
+    if (l0 < l1)
+        for (uint32_t t = 0; t < BV_LEAF; ++t) {
+            if (bv_record(p.tri, (uint64_t)l0 * BV_LEAF + t, a, b, c) == BV_NOFACE) continue;
+            const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+            float x[3];
+            bv_cross(e1, e2, x);
+            const float Ai = 0.5f * bv_len(x);
+            A = A + Ai;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float ck = ((a[k] + b[k]) + c[k]) / 3.0f;
+                N[k] = N[k] + 0.5f * x[k];
+                S[k] = S[k] + Ai * ck;
+                M[k] = M[k] + ck;
+            }
+            ++cnt;
+        }
+    float pt[3] = {0.0f, 0.0f, 0.0f}, r = -1.0f;
+    if (cnt) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pt[k] = A == 0.0f ? M[k] / (float)cnt : S[k] / A;
+        r = 0.0f;
+        for (uint32_t t = 0; t < BV_LEAF; ++t) {
+            if (bv_record(p.tri, (uint64_t)l0 * BV_LEAF + t, a, b, c) == BV_NOFACE) continue;
+            const float da[3] = {a[0] - pt[0], a[1] - pt[1], a[2] - pt[2]}, db[3] = {b[0] - pt[0], b[1] - pt[1], b[2] - pt[2]};
+            const float dc[3] = {c[0] - pt[0], c[1] - pt[1], c[2] - pt[2]};
+            r = fmaxf(fmaxf(r, bv_len(da)), fmaxf(bv_len(db), bv_len(dc)));
+        }
+    }
+    const uint64_t idx = ((uint64_t)1 << D) + j;
+    mom[2 * idx] = make_float4(pt[0], pt[1], pt[2], r);
+    mom[2 * idx + 1] = make_float4(N[0], N[1], N[2], A);
+}
+
+// The moments of level d < D from the two children, by the inner rule of the header.  One launch per level, deepest first.
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_moments_fit(uint32_t d, BvPtr p, uint32_t F, float4 *__restrict__ mom) {
+    const uint32_t j = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = min(p.hdr[H_N], F);
+    uint32_t NL, D;
+    bv_shape(n, NL, D);
+    if (d >= D || j >= (1u << d)) return;
+    const uint64_t idx = ((uint64_t)1 << d) + j;
+    const float4 l0 = mom[4 * idx], l1 = mom[4 * idx + 1], r0 = mom[4 * idx + 2], r1 = mom[4 * idx + 3];
+    float4 o0, o1;
+    if (l0.w < 0.0f) {                                           // an empty child: the other one (empty or not) as it is
+        o0 = r0;
+        o1 = r1;
+    } else if (r0.w < 0.0f) {
+        o0 = l0;
+        o1 = l1;
+    } else {
+        const float A = l1.w + r1.w;
+        const float pl[3] = {l0.x, l0.y, l0.z}, pr[3] = {r0.x, r0.y, r0.z};
+        float pt[3], dl[3], dr[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            pt[k] = A == 0.0f ? 0.5f * (pl[k] + pr[k]) : (l1.w * pl[k] + r1.w * pr[k]) / A;
+            dl[k] = pt[k] - pl[k];
+            dr[k] = pt[k] - pr[k];
+        }
+        o0 = make_float4(pt[0], pt[1], pt[2], fmaxf(bv_len(dl) + l0.w, bv_len(dr) + r0.w));
+        o1 = make_float4(l1.x + r1.x, l1.y + r1.y, l1.z + r1.z, A);
+    }
+    mom[2 * idx] = o0;
+    mom[2 * idx + 1] = o1;
+}
+
+#define BV_FOURPI 12.566370614359172f
+
+// Omega / 4 pi of the triangle (a, b, c) seen from q (Van Oosterom and Strackee 1983), by the rule of the header
+__device__ __forceinline__ float bv_solid(const float q[3], const float A[3], const float B[3], const float C[3]) {
+    const float a[3] = {A[0] - q[0], A[1] - q[1], A[2] - q[2]}, b[3] = {B[0] - q[0], B[1] - q[1], B[2] - q[2]};
+    const float c[3] = {C[0] - q[0], C[1] - q[1], C[2] - q[2]};
+    float x[3];
+    bv_cross(b, c, x);
+    const float num = bv_dot(a, x);
+    if (num == 0.0f) return 0.0f;                                // in the triangle's plane as far as float32 can tell
+    const float la = bv_len(a), lb = bv_len(b), lc = bv_len(c);
+    const float den = (((la * lb) * lc + bv_dot(a, b) * lc) + bv_dot(b, c) * la) + bv_dot(c, a) * lb;
+    return (2.0f * atan2f(num, den)) / BV_FOURPI;
+}
+
+// The winding number of the tree's faces about q (finite, of a tree with n > 0 faces): a depth-first walk over the implicit tree, left
+// child first; the state is the heap index and its depth.  A node far enough for its radius is taken whole as a dipole (Barill et al.
+// 2018, the first term of the expansion), read from the moments alone: the boxes are never touched.  Terms add up in the order met.
+__device__ __forceinline__ float bv_winding(const BvPtr &ws, const float4 *__restrict__ mom, uint32_t n, const float q[3], float beta2,
+                                            uint32_t &accepted, uint32_t &tests) {
+    uint32_t NL, D;
+    bv_shape(n, NL, D);
+    uint32_t node = 1, depth = 0;
+    float w = 0.0f;
+    for (;;) {
+        const float4 m0 = mom[2 * (uint64_t)node];
+        bool down = false;
+        if (m0.w >= 0.0f) {                                      // not empty
+            const float d[3] = {m0.x - q[0], m0.y - q[1], m0.z - q[2]};
+            const float d2 = bv_dot(d, d);
+            if (d2 > beta2 * (m0.w * m0.w)) {                    // false for beta = inf, whatever the radius (inf * 0 is NaN)
+                const float4 m1 = mom[2 * (uint64_t)node + 1];
+                const float nn[3] = {m1.x, m1.y, m1.z};
+                w = w + bv_dot(nn, d) / (BV_FOURPI * (d2 * sqrtf(d2)));
+                ++accepted;
+            } else if (depth == D) {
+                uint32_t l0, l1;
+                bv_leaf_range(node - (1u << D), NL, D, l0, l1);
+                if (l0 < l1) {                                   // always: the node is not empty
+#pragma unroll
+                    for (uint32_t t = 0; t < BV_LEAF; ++t) {
+                        float a[3], b[3], c[3];
+                        if (bv_record(ws.tri, (uint64_t)l0 * BV_LEAF + t, a, b, c) == BV_NOFACE) continue;
+                        ++tests;
+                        w = w + bv_solid(q, a, b, c);
+                    }
+                }
+            } else {
+                node = 2 * node;
+                ++depth;
+                down = true;
+            }
+        }
+        if (!down) {                                             // the next node in depth-first order: up while a right child, then right
+            while (node & 1u) {
+                node >>= 1;
+                --depth;
+            }
+            if (!node) break;                                    // came up from the root
+            node += 1;
+        }
+    }
+    return w;
+}
+
+// the query point of thread q; false: no walk (q >= Q, no face in the tree, a non-finite point)
+__device__ __forceinline__ bool bv_point_load(const float *__restrict__ points, uint32_t q, uint32_t Q, uint32_t n, float p[3]) {
+    bool live = q < Q && n;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        p[k] = q < Q ? points[3 * (uint64_t)q + k] : 0.0f;
+        live &= bv_finite(p[k]);
+    }
+    return live;
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_winding(BvPtr ws, uint32_t F, const float4 *__restrict__ mom, const float *__restrict__ points,
+                                                          uint32_t Q, float beta, float *__restrict__ winding,
+                                                          unsigned long long *__restrict__ stats) {
+    const uint32_t q = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = min(ws.hdr[H_N], F);
+    float p[3], w = 0.0f;
+    uint32_t accepted = 0, tests = 0;
+    if (bv_point_load(points, q, Q, n, p)) w = bv_winding(ws, mom, n, p, beta * beta, accepted, tests);
+    if (q < Q) winding[q] = w;
+    if (stats) bv_add_stats(stats, accepted, tests);
+}
+
+// The signed distance: the closest-point walk for the magnitude and the face, then the winding walk for the sign (negative inside).
+// The two walks run one after the other and share nothing but the query point, so the live state is that of the larger one.
+__global__ __launch_bounds__(MC_BLOCK) void k_bvh_signed(BvPtr ws, uint32_t F, const float4 *__restrict__ mom, const float *__restrict__ points,
+                                                         uint32_t Q, float beta, float *__restrict__ signed_dist, int32_t *__restrict__ face,
+                                                         float *__restrict__ winding, unsigned long long *__restrict__ stats) {
+    const uint32_t q = blockIdx.x * MC_BLOCK + threadIdx.x;
+    const uint32_t n = min(ws.hdr[H_N], F);
+    float p[3], best = INFINITY, w = 0.0f;
+    uint32_t bestf = BV_NOFACE, bests = 0, visits = 0, ctests = 0, tests = 0, accepted = 0;
+    if (bv_point_load(points, q, Q, n, p)) {
+        bv_nearest(ws, n, p, best, bestf, bests, visits, ctests);
+        w = bv_winding(ws, mom, n, p, beta * beta, accepted, tests);
+    }
+    if (q < Q) {
+        const float dist = sqrtf(best);
+        signed_dist[q] = w >= 0.5f ? -dist : dist;
+        face[q] = bestf != BV_NOFACE ? (int32_t)bestf : -1;
+        if (winding) winding[q] = w;
+    }
+    if (stats) bv_add_stats(stats, accepted, tests);
+}
+
+inline uint64_t bv_moment_bytes(uint64_t F) { return sizeof(float4) * (2ull << (bv_max_depth(F) + 1)); }
+
 // ------------------------------------------------------------------------------------------------ sampler
 struct SmpPtr {
     uint32_t *hdr;
@@ -1094,6 +1312,54 @@ int cnerf_mesh_bvh_project(const void *ws, uint64_t ws_bytes, uint32_t V, uint32
     if (!Q) return CNERF_OK;
     hipLaunchKernelGGL(k_bvh_project, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, V, F, faces, normals, x, n, Q, reach,
                        reach_per_query, point, normal, offset, face, kind, (unsigned long long *)stats);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_winding_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host) {
+    if (!bytes_host) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F)) return CNERF_EINVAL;
+    *bytes_host = bv_moment_bytes(F);
+    return CNERF_OK;
+}
+
+int cnerf_mesh_winding_build(const void *bvh_ws, uint64_t bvh_bytes, uint32_t V, uint32_t F, void *mom, uint64_t mom_bytes, void *stream) {
+    if (!bvh_ws || !mom) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F)) return CNERF_EINVAL;
+    BvPtr p;
+    if (const int rc = mesh_check_ws(bvh_ws, bvh_bytes, bv_carve((void *)bvh_ws, F, p))) return rc;
+    if (const int rc = mesh_check_ws(mom, mom_bytes, bv_moment_bytes(F))) return rc;
+    hipStream_t st = CN_STREAM(stream);
+    const int Dmax = (int)bv_max_depth(F);
+    hipLaunchKernelGGL(k_bvh_moments_leaf, mesh_grid(1ull << Dmax), dim3(MC_BLOCK), 0, st, p, F, (float4 *)mom);
+    for (int d = Dmax - 1; d >= 0; --d)
+        hipLaunchKernelGGL(k_bvh_moments_fit, mesh_grid(1ull << d), dim3(MC_BLOCK), 0, st, (uint32_t)d, p, F, (float4 *)mom);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_winding_query(const void *bvh_ws, uint64_t bvh_bytes, uint32_t V, uint32_t F, const void *mom, uint64_t mom_bytes,
+                             const float *points, uint32_t Q, float beta, float *winding, uint64_t *stats, void *stream) {
+    if (!bvh_ws || !mom || (Q && (!points || !winding))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F) || Q >= (1u << 31) || !(beta >= 1.0f)) return CNERF_EINVAL;
+    BvPtr p;
+    if (const int rc = mesh_check_ws(bvh_ws, bvh_bytes, bv_carve((void *)bvh_ws, F, p))) return rc;
+    if (const int rc = mesh_check_ws(mom, mom_bytes, bv_moment_bytes(F))) return rc;
+    if (!Q) return CNERF_OK;
+    hipLaunchKernelGGL(k_bvh_winding, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, F, (const float4 *)mom, points, Q, beta, winding,
+                       (unsigned long long *)stats);
+    return cn_launch_status();
+}
+
+int cnerf_mesh_bvh_signed_distance(const void *bvh_ws, uint64_t bvh_bytes, uint32_t V, uint32_t F, const void *mom, uint64_t mom_bytes,
+                                   const float *points, uint32_t Q, float beta, float *signed_dist, int32_t *face, float *winding,
+                                   uint64_t *stats, void *stream) {
+    if (!bvh_ws || !mom || (Q && (!points || !signed_dist || !face))) return CNERF_ENULL;
+    if (!bv_sizes_ok(V, F) || Q >= (1u << 31) || !(beta >= 1.0f)) return CNERF_EINVAL;
+    BvPtr p;
+    if (const int rc = mesh_check_ws(bvh_ws, bvh_bytes, bv_carve((void *)bvh_ws, F, p))) return rc;
+    if (const int rc = mesh_check_ws(mom, mom_bytes, bv_moment_bytes(F))) return rc;
+    if (!Q) return CNERF_OK;
+    hipLaunchKernelGGL(k_bvh_signed, mesh_grid(Q), dim3(MC_BLOCK), 0, CN_STREAM(stream), p, F, (const float4 *)mom, points, Q, beta, signed_dist,
+                       face, winding, (unsigned long long *)stats);
     return cn_launch_status();
 }
 

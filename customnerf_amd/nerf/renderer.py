@@ -600,7 +600,7 @@ class NeRFRenderer(nn.Module):
                      min_component_faces=0, keep_largest=False, simplify=0, target_faces=0, texture=0, smooth=0, smooth_lambda=0.5,
                      smooth_mu=-0.53, deviation=False, deviation_spacing=None, deviation_max_samples=1 << 26, ao=0,
                      texture_layout='uniform', bake_from='mesh', bake_reach=None, normal_map=False, sparse=False, sparse_probe=4,
-                     tsdf=None, fill_holes=False, topology=False, color_views=None):
+                     tsdf=None, fill_holes=False, topology=False, color_views=None, remesh=None):
         """Isosurface sigma == threshold (default opt.density_thresh) of the field on a resolution^3 lattice over `aabb` (default
         aabb_infer): density_volume, then marching cubes on the device (mesh.marching_cubes).  color=True: forward(verts, -normals) gives
         each vertex the colour seen looking at the surface, as uint8 RGB.  -> dict of device tensors: verts [V, 3] float32 (world
@@ -622,8 +622,8 @@ class NeRFRenderer(nn.Module):
         deviation=True reports what the lossy passes cost in geometry: 'deviation' joins the dict — mesh.distance(final mesh, the mesh as it
         stood after marching cubes and component removal), both directions (max, mean, rms per direction and 'hausdorff', in world units),
         sampled deviation_spacing apart (default: half the smallest lattice step; at most deviation_max_samples samples per direction,
-        ValueError beyond), plus 'step', the lattice step, so that the error reads in voxels; None when neither smooth, simplify nor
-        target_faces ran.  Without deviation=True the key is absent.
+        ValueError beyond), plus 'step', the lattice step, so that the error reads in voxels; None when neither smooth, simplify,
+        target_faces nor remesh ran.  Without deviation=True the key is absent.
         ao=K > 0 adds 'ao' [V] float32 in [0, 1]: the per-vertex ambient occlusion of the final mesh from K rays per vertex
         (mesh.ambient_occlusion: the share of the rays that escape), a shading cue for geometry-only previews — render_mesh(colors=) shows
         it as grey.  It is never multiplied into colors or texture: the field's radiance already contains the scene's shading.  With ao=0
@@ -682,7 +682,16 @@ class NeRFRenderer(nn.Module):
         the largest lattice step), 'power' (2) and 'min_cos' (0.2) — documented defaults, not measured optima.  color_views='tsdf'
         reuses the cameras of tsdf= (ValueError without it).  Pinhole views only, and no exposure compensation between views.
         'view_colors' joins the dict: {'views', 'seen': [3] int64 on the device, the points asked (vertices and texels) that 0, 1 and
-        >= 2 views saw, 'depth_tol'}.  With color_views=None the key is absent and every output is what it was."""
+        >= 2 views saw, 'depth_tol'}.  With color_views=None the key is absent and every output is what it was.
+        remesh=R2 (an int) or remesh=dict(resolution=.. | voxel=.., offset=0.0, beta=2.0, probe=2) rebuilds the surface as the zero level
+        (with offset: the level `offset`, > 0 thicker, < 0 thinner, in world units) of the mesh's own signed distance on a cubic lattice
+        of R2 points along the longest side of its box (mesh.voxel_remesh; the sign is the generalized winding number, csrc/mesh_bvh.hip,
+        so the input may have holes, overlapping parts and non-manifold edges).  The output is closed and manifold wherever that level
+        set is regular: holes are capped, the faces inside overlapping parts vanish, and detail below a voxel of the new lattice is lost.
+        It runs after component removal and fill_holes and before smooth, simplify and target_faces; 'deviation' and bake_from='source'
+        compare with the surface as extracted, so they report what the remesh cost, and deviation=True counts it as a lossy pass.
+        'remesh' joins the dict: voxel_remesh's info (shape, origin, spacing, bricks, evaluations, rounds, offset, beta).  With
+        remesh=None the key is absent and every output is what it was."""
         if fill_holes is True or fill_holes is False:
             fill_edges = None
         elif isinstance(fill_holes, (int, np.integer)) and fill_holes >= 3:
@@ -726,6 +735,18 @@ class NeRFRenderer(nn.Module):
             raise ValueError(f"extract_mesh: bake_reach must be > 0, got {bake_reach}")
         if int(sparse_probe) < 1:
             raise ValueError(f"extract_mesh: sparse_probe must be >= 1 (every how many lattice points the field is probed), got {sparse_probe}")
+        remesh_kw = None
+        if remesh is not None:
+            if isinstance(remesh, dict):
+                remesh_kw = dict(remesh)
+            elif isinstance(remesh, (int, np.integer)) and not isinstance(remesh, bool):
+                remesh_kw = {'resolution': int(remesh)}
+            else:
+                raise ValueError(f"extract_mesh: remesh must be None, a resolution (int) or a dict of mesh.voxel_remesh's options, got {remesh!r}")
+            unknown = set(remesh_kw) - {'resolution', 'voxel', 'offset', 'beta', 'probe'}
+            if unknown or (remesh_kw.get('resolution') is None) == (remesh_kw.get('voxel') is None):
+                raise ValueError(f"extract_mesh: remesh takes exactly one of 'resolution' and 'voxel', and 'offset', 'beta', 'probe'; "
+                                 f"got {sorted(remesh_kw)}")
         cv_cfg = None
         if color_views is not None:
             cv_cfg = self._color_view_options(color_views, tsdf, bool(color) or bool(tex_r), float(step.max()))
@@ -760,6 +781,9 @@ class NeRFRenderer(nn.Module):
         if fill_holes is not False:
             verts, faces, normals, holes_info = _mesh.fill_holes(verts, faces, normals, max_edges=fill_edges)
         kept =(verts, faces, normals) if deviation or from_source else None     # held only for the report and the projection
+        remesh_info = None
+        if remesh_kw is not None:
+            verts, faces, normals, remesh_info = _mesh.voxel_remesh(verts, faces, chunk=chunk, **remesh_kw)
         if n_smooth:
             verts, normals = _mesh.smooth(verts, faces, n_smooth, smooth_lambda, smooth_mu, normals=normals)
         if k >= 2:
@@ -802,6 +826,8 @@ class NeRFRenderer(nn.Module):
             m['tsdf'] = tsdf_info
         if holes_info is not None:
             m['holes'] = holes_info
+        if remesh_info is not None:
+            m['remesh'] = remesh_info
         if cv_cfg is not None:
             m['view_colors'] = {'views': color_fn.views, 'seen': color_fn.counts, 'depth_tol': color_fn.depth_tol}
         if topology:
@@ -815,7 +841,7 @@ class NeRFRenderer(nn.Module):
             m['bake_kinds'] = kinds
         if deviation:
             m['deviation'] = None
-            if n_smooth or k >= 2 or tf:
+            if n_smooth or k >= 2 or tf or remesh_info is not None:
                 sp = 0.5 * float(step.min()) if deviation_spacing is None else float(deviation_spacing)
                 m['deviation'] = dict(_mesh.distance(verts, faces, kept[0], kept[1], spacing=sp, max_samples=deviation_max_samples),
                                       step=tuple(step.tolist()))
@@ -831,7 +857,7 @@ class NeRFRenderer(nn.Module):
         their normals and colours, or the ambient occlusion as grey, as for PLY; unlit unless it carries a normal map); any other
         path a binary PLY (mesh.write_ply: positions, normals, and colours when color=True), which takes no texture.  The cleanup options of
         extract_mesh (min_component_faces, keep_largest, smooth, smooth_lambda, smooth_mu, simplify, target_faces), texture_layout, deviation /
-        deviation_spacing, ao, bake_from, bake_reach, sparse, sparse_probe, tsdf, fill_holes, topology and color_views pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
+        deviation_spacing, ao, bake_from, bake_reach, sparse, sparse_probe, tsdf, fill_holes, topology, color_views and remesh pass through; normal_map=True writes <stem>_normal.png beside a .obj (a `norm` line
         in the material) and, like texture=, needs an .obj path; normal_map='tangent' needs a .glb path (OBJ carries no tangents) and
         normal_map=True is refused for .glb (glTF has no object-space slot).  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written

@@ -50,7 +50,9 @@ extern "C" {
  *    cnerf_mesh_atlas_tspace / cnerf_mesh_atlas_sized_tspace / cnerf_mesh_atlas_proj_tspace; marching cubes over a list of bricks
  *    (additive, same version) — cnerf_marching_cubes_sparse_workspace_bytes / _count / _emit; TSDF fusion of depth maps (additive, same
  *    version) — cnerf_tsdf_integrate / _finalize / _face_keep; topology report and hole filling (additive, same version) —
- *    cnerf_mesh_holes_workspace_bytes / _count / _emit and cnerf_mesh_topology / _loops. */
+ *    cnerf_mesh_holes_workspace_bytes / _count / _emit and cnerf_mesh_topology / _loops; winding number and signed distance on the
+ *    closest-point tree (additive, same version) — cnerf_mesh_winding_workspace_bytes / _build / _query and
+ *    cnerf_mesh_bvh_signed_distance. */
 #define CNERF_ABI_VERSION 7
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -1233,6 +1235,55 @@ int cnerf_mesh_bvh_occluded(const void *ws, uint64_t ws_bytes, uint32_t V, uint3
 int cnerf_mesh_bvh_project(const void *ws, uint64_t ws_bytes, uint32_t V, uint32_t F, const int32_t *faces, const float *normals,
                            const float *x, const float *n, uint32_t Q, float reach, const float *reach_per_query, float *point,
                            float *normal, float *offset, int32_t *face, uint8_t *kind, uint64_t *stats, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Inside or outside: the generalized winding number of a point about the faces of the tree of cnerf_mesh_bvh_build, and the signed
+ * distance made of it and the closest-point rule (customnerf_amd/mesh.py winding_number / contains / signed_distance / voxel_remesh;
+ * csrc/mesh_bvh.hip; the reference has none).  The winding number tolerates holes, self-intersections and non-manifold edges (Jacobson,
+ * Kavan and Sorkine-Hornung 2013); far parts of the mesh are taken whole through the first (dipole) term of the expansion of Barill,
+ * Dym, Kazhdan, Schneider and Jacobson 2018, kept per tree node in a buffer of its own: bvh_ws is read only, its layout and
+ * cnerf_mesh_bvh_workspace_bytes are what they were.  float32, one rounding per written operation in the order written, divisions and
+ * square roots correctly rounded, dot(u, v) = (ux vx + uy vy) + uz vz, exactly as above; cross(u, v) = (uy vz - uz vy, uz vx - ux vz,
+ * ux vy - uy vx), len(u) = sqrt(dot(u, u)); tests/winding_restatement.py restates the rules.  Unlike the results above, these DO depend on
+ * the tree: its shape is the one the build gives — the records in sorted order, BV_LEAF = 4 to a leaf, NL = ceil(n / 4) leaves, depth
+ * D = ceil(log2 NL), node (d, j) at heap index 2^d + j covering the leaves [j NL >> d, (j + 1) NL >> d), children 2 i and 2 i + 1.
+ *   moments (cnerf_mesh_winding_build, after cnerf_mesh_bvh_build with the same bvh_ws, V and F): mom holds two float4 per heap index i, at
+ *     [2 i] = (p.x, p.y, p.z, r) — a centre and the radius of a ball about it that holds the node's vertices — and at [2 i + 1] =
+ *     (N.x, N.y, N.z, A) — the sum of the faces' area vectors and of their areas.  Indices 1 .. 2^(D + 1) - 1 are written, nothing else.
+ *     leaf (a node of level D), over the valid records of its leaf (at most one leaf, at most four records) in slot order, with the sums
+ *       started at 0: e1 = b - a, e2 = c - a, x = cross(e1, e2), A_i = 0.5 len(x), c_i = ((a + b) + c) / 3 per component;
+ *       A = A + A_i, N = N + 0.5 x, S = S + A_i c_i, M = M + c_i per component.  Then p = S / A, or M / (float) count when A == 0, per
+ *       component, and r = the largest len(v - p) over the records' vertices v, started at 0.
+ *     inner node, from the left child (p_l, r_l, N_l, A_l) and the right one: A = A_l + A_r, N = N_l + N_r,
+ *       p = (A_l p_l + A_r p_r) / A, or 0.5 (p_l + p_r) when A == 0, per component, r = max(len(p - p_l) + r_l, len(p - p_r) + r_r).
+ *     empty node (no valid record below it: the NaN padding, a node of level D that covers no leaf): p = N = 0, A = 0, r = -1.  A node with
+ *       an empty left child is a copy of its right child, bit for bit; otherwise one with an empty right child is a copy of its left.
+ *   winding (cnerf_mesh_winding_query): per query q, a depth-first walk from the root, the left child before the right, w started at 0:
+ *     an empty node (r < 0) is passed over.  With d = p - q per component and d2 = dot(d, d), a node is accepted whole when
+ *     d2 > (beta beta) (r r) (false when that product is NaN, as for beta = +inf and r = 0): w = w + dot(N, d) / (FOURPI (d2 sqrt(d2))),
+ *     FOURPI = 12.566370614359172f.  Otherwise the walk descends, and at level D each valid record of the leaf, in slot order, adds
+ *     the solid angle of Van Oosterom and Strackee 1983: a = A - q, b = B - q, c = C - q per component (A, B, C the record's vertices),
+ *     num = dot(a, cross(b, c)); a term of 0 when num == 0; la = len(a), lb = len(b), lc = len(c),
+ *     den = (((la lb) lc + dot(a, b) lc) + dot(b, c) la) + dot(c, a) lb, w = w + (2 atan2f(num, den)) / FOURPI.
+ *     atan2f is the device library's (a few ulp, not correctly rounded): the one step that is not restated bit for bit.  A mesh wound
+ *     outwards — (b - a) x (c - a) points out, the convention of the rasteriser and the ray queries — has w = 1 inside and 0 outside.
+ *     beta = +inf accepts nothing: w is the sum over all the faces in tree order.  A non-finite q or a tree without faces: w = 0.
+ *     stats (NULL or device uint64 [2], ADDED to, so zero it first): nodes accepted and triangles evaluated, summed over the call.
+ *   signed distance (cnerf_mesh_bvh_signed_distance): dist2 and face by the rule of cnerf_mesh_bvh_closest, unchanged, w as above (stored
+ *     when winding is not NULL); signed_dist [Q] = -sqrt(dist2) when w >= 0.5, else sqrt(dist2): negative inside.  A non-finite q or a tree
+ *     without faces: signed_dist = +inf, face = -1, w = 0.  stats as for the winding query.
+ *   CNERF_ENULL: a required pointer (bvh_ws, mom; with Q > 0 points and winding, or signed_dist and face) is NULL.  CNERF_EINVAL: V, F or
+ *   Q >= 2^31, a short or misaligned (16 bytes) bvh_ws or mom, beta < 1 or NaN.  Both return before any launch; Q = 0 is accepted.  The
+ *   caller's stream and buffers; no allocation, no host sync, no float atomics: a query's terms add up in the order of its own walk, so
+ *   every output is bit-reproducible.  workspace_bytes: 32 bytes per heap index, 32 * 2^(Dmax + 1) with Dmax the depth of a tree of F faces.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_mesh_winding_workspace_bytes(uint32_t V, uint32_t F, uint64_t *bytes_host);
+int cnerf_mesh_winding_build(const void *bvh_ws, uint64_t bvh_bytes, uint32_t V, uint32_t F, void *mom, uint64_t mom_bytes, void *stream);
+int cnerf_mesh_winding_query(const void *bvh_ws, uint64_t bvh_bytes, uint32_t V, uint32_t F, const void *mom, uint64_t mom_bytes,
+                             const float *points, uint32_t Q, float beta, float *winding, uint64_t *stats, void *stream);
+int cnerf_mesh_bvh_signed_distance(const void *bvh_ws, uint64_t bvh_bytes, uint32_t V, uint32_t F, const void *mom, uint64_t mom_bytes,
+                                   const float *points, uint32_t Q, float beta, float *signed_dist, int32_t *face, float *winding,
+                                   uint64_t *stats, void *stream);
 
 #ifdef __cplusplus
 }
