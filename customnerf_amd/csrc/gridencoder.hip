@@ -212,21 +212,35 @@ __global__ void __launch_bounds__(GE_BLOCK) k_grid_fwd_fast(const float *__restr
     *out = gf_eval_level(in, table, lv.size[level], lv.resolution[level], lv.scale[level], gridtype);
 }
 
-// Sample-major traversal: a workgroup evaluates ALL levels of a tile of 256 SPT consecutive samples (level loop outside, the tile's samples
-// inside).  Every XCD touches every table, so this loses to the level-major list when the samples are spread over the volume (the 16 tables
-// do not fit an L2) and wins when neighbours of the list are neighbours in space — the importance samples of a fitted field, whose rows are
-// re-used from L1 / L2 across the tile (scratch/fused_fwd_lab.hip, profiles/r05_fused_fwd_lab.log: 153 vs 188 us).  Bit-identical results.
-template <int SPT>
-__global__ void __launch_bounds__(GE_BLOCK) k_grid_fwd_fast_sm(const float *__restrict__ inputs, const __half *__restrict__ grid, const GridLevels lv,
-                                                               __half *__restrict__ outputs, uint32_t B, uint32_t n_levels, uint32_t gridtype,
-                                                               uint32_t ostride) {
-    const uint32_t t0 = blockIdx.x * (GE_BLOCK * SPT) + threadIdx.x;
-    if (t0 >= B) return;
+// Sample-major traversal: a workgroup evaluates ALL levels of a tile of THREADS x SPT consecutive samples (level loop outside, the tile's
+// samples inside; thread t0 takes samples t0 + s THREADS).  Every XCD touches every table, so this loses to the level-major list when the
+// samples are spread over the volume (the 16 tables do not fit an L2) and wins when neighbours of the list are neighbours in space — the
+// importance samples of a fitted field, whose rows are re-used from L1 / L2 across the tile (scratch/fused_fwd_lab.hip,
+// profiles/r05_fused_fwd_lab.log: 153 vs 188 us).  Bit-identical results.
+// What keeps a level's table in the L2s is that the whole device is on the same level at the same time: the workgroups start together and
+// every level costs them about the same.  One wave per SIMD (256 x 16) keeps that by itself.  Four waves per SIMD on the same 4096-sample
+// tile (1024 x 4) drift apart — 315 / 247 us per launch (coarse / importance pass) against 223 / 187 — unless a barrier per level holds them
+// together: 219 / 180 us, the form that ships.  With one wave per SIMD the barrier only costs (234 / 201), so it is tied to the workgroup
+// size.  profiles/gather_tiles_ab.txt has every form.
+// xcd_tiles: XCD x (= blockIdx % 8 as dispatched) takes a contiguous run of tiles instead of every eighth one (see ge_fwd_C).
+template <int SPT, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_grid_fwd_fast_sm(const float *__restrict__ inputs, const __half *__restrict__ grid, const GridLevels lv,
+                                                              __half *__restrict__ outputs, uint32_t B, uint32_t n_levels, uint32_t gridtype,
+                                                              uint32_t ostride, int xcd_tiles) {
+    static_assert(THREADS % 64 == 0 && THREADS <= 1024, "whole waves, one workgroup");
+    constexpr bool SYNC = THREADS > GE_BLOCK;              // more than one wave per SIMD: level barrier
+    uint32_t tile = blockIdx.x;
+    if (xcd_tiles) {                                      // bijective for any grid: XCD x gets q + 1 tiles if x < r, else q (as ge_work_item)
+        const uint32_t q = gridDim.x / CN_NXCD, r = gridDim.x % CN_NXCD, xcd = blockIdx.x % CN_NXCD, k = blockIdx.x / CN_NXCD;
+        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+    }
+    const uint32_t t0 = tile * (THREADS * SPT) + threadIdx.x;
+    if (!SYNC && t0 >= B) return;                         // (with the barrier every thread stays: loads are clamped to B - 1, stores guarded)
     float in[SPT][3];
     bool ok[SPT];
 #pragma unroll
     for (int s = 0; s < SPT; s++) {
-        ge_load_coords<3>(inputs, min(t0 + s * GE_BLOCK, B - 1), in[s]);
+        ge_load_coords<3>(inputs, min(t0 + s * THREADS, B - 1), in[s]);
         ok[s] = !(in[s][0] < 0 || in[s][0] > 1 || in[s][1] < 0 || in[s][1] > 1 || in[s][2] < 0 || in[s][2] > 1);
 #pragma unroll
         for (int d = 0; d < 3; d++) in[s][d] = ok[s] ? in[s][d] : 0.5f;
@@ -237,9 +251,10 @@ __global__ void __launch_bounds__(GE_BLOCK) k_grid_fwd_fast_sm(const float *__re
         const unsigned char *__restrict__ table = reinterpret_cast<const unsigned char *>(grid) + (size_t)lv.offset[level] * 4;
         const uint32_t size = lv.size[level], res = lv.resolution[level];
         const float scale = lv.scale[level];
+        if constexpr (SYNC) __syncthreads();
 #pragma unroll
         for (int s = 0; s < SPT; s++) {
-            const uint32_t b = t0 + s * GE_BLOCK;
+            const uint32_t b = t0 + s * THREADS;
             const uint32_t r = gf_eval_level(in[s], table, size, res, scale, gridtype);
             if (b < B) out[(size_t)level * ostride + b] = ok[s] ? r : 0u;
         }
@@ -405,8 +420,33 @@ static bool ge_fast_eligible(const GridLevels &lv, uint32_t nl, uint32_t gridtyp
 #define GE_TRAV_LEVEL 0u
 #define GE_TRAV_SAMPLE 1u
 #ifndef GE_FAST_SPT
-#define GE_FAST_SPT 16                              // samples per thread of the sample-major kernel (tuning builds: CNERF_GRID_SPT)
+#define GE_FAST_SPT 4                               // samples per thread of the sample-major kernel (tuning builds: CNERF_GRID_SPT)
 #endif
+#ifndef GE_FAST_THREADS
+#define GE_FAST_THREADS 1024                        // its workgroup size (tuning builds: CNERF_GRID_THREADS); the tile is the product
+#endif
+// (tests/test_gpu_gridencoder_tiles.py places its batch sizes around GE_FAST_THREADS x GE_FAST_SPT = 4096 samples: TILE there follows these two)
+
+// the sample-major launch.  xcd_tiles: see ge_fwd_C.  The release library holds the shipped shape only; tuning builds can also select the
+// one-wave-per-SIMD shapes of the round-6 sweep, and refuse a pair that is not built instead of running another one under its name.
+static int ge_launch_sm(const float *inputs, const __half *emb, const GridLevels &lv, __half *out, uint32_t B, uint32_t nl, uint32_t gridtype,
+                        uint32_t ostride, int xcd_tiles, hipStream_t st) {
+#define GE_SM(THR_, SPT_) hipLaunchKernelGGL((k_grid_fwd_fast_sm<SPT_, THR_>), dim3(cn_div_up(B, THR_ * SPT_)), dim3(THR_), 0, st, inputs, emb, lv, out, B, nl, gridtype, ostride, xcd_tiles)
+#ifdef CNERF_TUNING
+    static const int spt = cn_tune_env("CNERF_GRID_SPT", GE_FAST_SPT), thr = cn_tune_env("CNERF_GRID_THREADS", GE_FAST_THREADS);
+    // (256 x 12 / 20 / 24 measured: 292 / 220 / 256 us against 187 at 16 — tiles that do not align with the 64-sample rays)
+    if (thr == 256 && spt == 4) GE_SM(256, 4);
+    else if (thr == 256 && spt == 8) GE_SM(256, 8);
+    else if (thr == 256 && spt == 16) GE_SM(256, 16);
+    else if (thr == 256 && spt == 32) GE_SM(256, 32);
+    else if (thr == GE_FAST_THREADS && spt == GE_FAST_SPT) GE_SM(GE_FAST_THREADS, GE_FAST_SPT);
+    else return CNERF_EINVAL;
+#else
+    GE_SM(GE_FAST_THREADS, GE_FAST_SPT);
+#endif
+#undef GE_SM
+    return cn_launch_status();
+}
 
 template <typename T, int D>
 static int ge_fwd_C(const float *inputs, const T *emb, const GridLevels &lv, T *out, uint32_t B, uint32_t C, uint32_t L, uint32_t nl, T *dy_dx,
@@ -418,22 +458,21 @@ static int ge_fwd_C(const float *inputs, const T *emb, const GridLevels &lv, T *
     // reference field's own table (T = 2^21: 8 MiB per level) does not: there the plain order — consecutive workgroups, i.e. all eight XCDs, on
     // the same level at the same time, each L2 holding what its neighbours also fetch through the Infinity Cache — is faster: coarse pass
     // 364 -> 283 us, importance pass 229 -> 215 us (profiles/r06_bear_gather_ab.txt).
-    if (sw == 2 && cn_tune_env("CNERF_GRID_SWIZZLE", -1) < 0) {
-        uint64_t biggest = 0;
-        for (uint32_t l = 0; l < nl; l++) biggest = biggest > lv.size[l] ? biggest : lv.size[l];
-        if (biggest * C * sizeof(T) > (4ull << 20)) sw = 0;
-    }
+    // The sample-major kernel takes the opposite turn on such a table: every XCD walks every level there, so what an L2 can keep is the part of a
+    // level that ITS tiles touch — consecutive tiles (neighbouring rays) go to one XCD instead of round-robin over the eight: coarse pass
+    // 287 -> 257 us, importance pass 212 -> 194 us, both now ahead of the level-major list (276 / 207); on the 2 MiB levels, which an L2 holds
+    // whole, the same assignment costs 4 us (profiles/gather_tiles_ab.txt).
+    uint64_t biggest = 0;
+    for (uint32_t l = 0; l < nl; l++) biggest = biggest > lv.size[l] ? biggest : lv.size[l];
+    const bool big = biggest * C * sizeof(T) > (4ull << 20);
+    if (sw == 2 && cn_tune_env("CNERF_GRID_SWIZZLE", -1) < 0 && big) sw = 0;
     GridLevels lvb = lv;
     if constexpr (std::is_same<T, __half>::value && D == 3) {
         if (C == 2 && !dy_dx && interp == 0 && !ac && ge_fast_eligible(lvb, nl, gridtype)) {
             static const int force = cn_tune_env("CNERF_GRID_TRAV", -1);       // tuning builds: override the caller's traversal
             if (force >= 0) traversal = (uint32_t)force;
             if (traversal == GE_TRAV_SAMPLE) {
-                static const int spt = cn_tune_env("CNERF_GRID_SPT", GE_FAST_SPT);
-#define GE_SM(SPT_) case SPT_: hipLaunchKernelGGL(k_grid_fwd_fast_sm<SPT_>, dim3(cn_div_up(B, GE_BLOCK * SPT_)), block, 0, st, inputs, emb, lvb, out, B, nl, gridtype, ostride); break;
-                switch (spt) { GE_SM(4) GE_SM(8) GE_SM(32) default: GE_SM(16) }      // (12 / 20 / 24 measured: 292 / 220 / 256 us against 187 at 16 — tiles that do not align with the 64-sample rays)
-#undef GE_SM
-                return cn_launch_status();
+                return ge_launch_sm(inputs, emb, lvb, out, B, nl, gridtype, ostride, big ? 1 : 0, st);
             }
         }
     }

@@ -45,7 +45,8 @@ class TraversalTuner:
     sample-major wins, on those of a fitted field level-major does (a real surface does not cluster them like the lab's samples: DESIGN.md
     §4a).  On a trial call the caller runs BOTH forms back to back on the same samples (the second overwrites the first's identical output)
     between event pairs; the events are read without blocking on a later call, and the faster form is used until the next trial.  Two trial
-    calls (order swapped) at calls `first` / `first + 1`, then every `period` calls: 2 extra gathers per `period` steps."""
+    calls (order swapped) at calls `first` / `first + 1`, then every `period` calls: 2 extra gathers per `period` steps.  One tuner per call
+    site: the renderer keeps one for its stratified and one for its importance samples."""
 
     def __init__(self, first=2, period=256, margin=0.02):
         self.choice = LEVEL_MAJOR

@@ -172,11 +172,14 @@ class NeRFNetwork(NeRFRenderer):
             torch.add(x, self.opt.bound, out=u)                                     # grid.py:156: (x + bound) / (2 bound)
             u.div_(2 * self.opt.bound)
         trav = 0
-        if importance and getattr(self.opt, 'tune_gather_traversal', True):
-            trav = self.__dict__.get('_fine_tuner')
+        if getattr(self.opt, 'tune_gather_traversal', True):
+            # one tuner per call site: the stratified coarse samples tie on a table whose levels fit an L2 (the tuner then stays level-major)
+            # and take the sample-major form on the reference field's own 8 MiB levels
+            key = '_fine_tuner' if importance else '_coarse_tuner'
+            trav = self.__dict__.get(key)
             if trav is None:
                 from ..gridencoder.grid import TraversalTuner
-                trav = self.__dict__['_fine_tuner'] = TraversalTuner()
+                trav = self.__dict__[key] = TraversalTuner()
         self.pos_en.encode_into(u, enc, row0, half=self._half(), traversal=trav)
 
     @torch.no_grad()
