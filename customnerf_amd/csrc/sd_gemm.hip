@@ -70,7 +70,9 @@ __device__ __forceinline__ void sg_epilogue_phase2(const CnerfSdGemm &g, const f
     constexpr int SG_EPI_THREADS = NTHREADS;
     // ---- phase 2: 8 consecutive columns per lane
     // optional: GroupNorm statistics of the output for the norm that reads it next.  A thread's column chunk is fixed over its rows, so
-    // the (<= 2) groups' sums live in registers; flushed per image into a small LDS table, then one global atomic per (image, group) and tile.
+    // the (<= 3) groups' sums live in registers; flushed per image into a small LDS table, then one global atomic per (image, group) and tile.
+    // (Three: with 5 channels per group the chunk at n = 8 holds columns of groups 1, 2 and 3.  No other width >= 4 puts two group boundaries
+    // strictly inside an 8-aligned chunk.)
     const bool do_gn = !SPLIT && g.gn_sums != nullptr;
     constexpr int GI = 4;                                // images a tile can touch (gn_rows >= 64)
     const uint32_t gn_cg = do_gn ? g.N / g.gn_groups : 1u;
@@ -80,6 +82,8 @@ __device__ __forceinline__ void sg_epilogue_phase2(const CnerfSdGemm &g, const f
         __syncthreads();
     }
     float gs[2][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
+    float gs3[2] = {0.0f, 0.0f};                         // the third group of a chunk (gn3 only)
+    const bool gn3 = do_gn && gn_cg == 5;                // tile-uniform, an instantiation of its own: the common widths keep the two-bucket loop as it was
     uint32_t gn_img = 0xFFFFFFFFu;
     _Float16 *C = (!SPLIT && g.C) ? reinterpret_cast<_Float16 *>(g.C) + g.sc_o * zo + g.sc_i * zi : nullptr;
     float *C32 = SPLIT ? partial + (size_t)split * g.M * g.N : (g.C32 ? g.C32 + g.sc_o * zo + g.sc_i * zi : nullptr);
@@ -97,8 +101,9 @@ __device__ __forceinline__ void sg_epilogue_phase2(const CnerfSdGemm &g, const f
 #pragma unroll
         for (int e = 0; e < 8; e++) bias8[e] = (!SPLIT && g.bias && nb_ + e < g.N) ? g.bias[nb_ + e] : 0.0f;
     }
-    auto phase2 = [&](auto inside_c) __attribute__((always_inline)) {
+    auto phase2 = [&](auto inside_c, auto gn3_c) __attribute__((always_inline)) {
     constexpr bool INSIDE = decltype(inside_c)::value;   // the whole tile is inside [M, N]
+    constexpr bool GN3 = decltype(gn3_c)::value;         // statistics with 5 channels per group: three buckets
     constexpr int NIT = BM * CPR / SG_EPI_THREADS;            // items per thread (8 | 4): fixed trip count, unrolled — the LDS reads of all items
 #pragma unroll                                           // are in flight together instead of one read -> convert -> store chain per item
     for (int k = 0; k < NIT; k++) {
@@ -168,17 +173,38 @@ __device__ __forceinline__ void sg_epilogue_phase2(const CnerfSdGemm &g, const f
                     gn_add(&gn_lds[gn_img - gn_i0][gl][1], gs[0][1]);
                     gn_add(&gn_lds[gn_img - gn_i0][gl + 1][0], gs[1][0]);
                     gn_add(&gn_lds[gn_img - gn_i0][gl + 1][1], gs[1][1]);
+                    if constexpr (GN3) {
+                        gn_add(&gn_lds[gn_img - gn_i0][gl + 2][0], gs3[0]);
+                        gn_add(&gn_lds[gn_img - gn_i0][gl + 2][1], gs3[1]);
+                        gs3[0] = gs3[1] = 0.0f;
+                    }
                     gs[0][0] = gs[0][1] = gs[1][0] = gs[1][1] = 0.0f;
                 }
                 gn_img = img;
             }
+            if constexpr (!GN3) {
 #pragma unroll
-            for (int e = 0; e < 8; e++) {
-                if (INSIDE || n + e < g.N) {
-                    const float xf = (float)(_Float16)v[e];                         // what the consumer will read
-                    const int k = ((uint32_t)e < split_c) ? 0 : 1;
-                    gs[k][0] += xf;
-                    gs[k][1] += xf * xf;
+                for (int e = 0; e < 8; e++) {
+                    if (INSIDE || n + e < g.N) {
+                        const float xf = (float)(_Float16)v[e];                     // what the consumer will read
+                        const int k = ((uint32_t)e < split_c) ? 0 : 1;
+                        gs[k][0] += xf;
+                        gs[k][1] += xf * xf;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    if (INSIDE || n + e < g.N) {
+                        const float xf = (float)(_Float16)v[e], xq = xf * xf;
+                        const bool b1 = (uint32_t)e >= split_c, b2 = (uint32_t)e >= split_c + gn_cg;      // columns [split_c + gn_cg, 8): g_lo + 2
+                        gs[0][0] += b1 ? 0.0f : xf;
+                        gs[0][1] += b1 ? 0.0f : xq;
+                        gs[1][0] += (b1 && !b2) ? xf : 0.0f;
+                        gs[1][1] += (b1 && !b2) ? xq : 0.0f;
+                        gs3[0] += b2 ? xf : 0.0f;
+                        gs3[1] += b2 ? xq : 0.0f;
+                    }
                 }
             }
         }
@@ -203,8 +229,11 @@ __device__ __forceinline__ void sg_epilogue_phase2(const CnerfSdGemm &g, const f
         }
     }
     };
-    if (m0 + BM <= g.M && n0 + BN <= g.N) phase2(std::true_type{});
-    else phase2(std::false_type{});
+    const bool inside = m0 + BM <= g.M && n0 + BN <= g.N;
+    if (!gn3) {
+        if (inside) phase2(std::true_type{}, std::false_type{});
+        else phase2(std::false_type{}, std::false_type{});
+    } else phase2(std::false_type{}, std::true_type{});      // (no SD shape has 5-channel groups: the guarded form serves inside tiles too)
     if (do_gn) {
         if (gn_img != 0xFFFFFFFFu) {
             const uint32_t gl = (n0 + (tid % CPR) * 8) / gn_cg - gn_g0;
@@ -212,6 +241,10 @@ __device__ __forceinline__ void sg_epilogue_phase2(const CnerfSdGemm &g, const f
             gn_add(&gn_lds[gn_img - gn_i0][gl][1], gs[0][1]);
             gn_add(&gn_lds[gn_img - gn_i0][gl + 1][0], gs[1][0]);
             gn_add(&gn_lds[gn_img - gn_i0][gl + 1][1], gs[1][1]);
+            if (gn3) {
+                gn_add(&gn_lds[gn_img - gn_i0][gl + 2][0], gs3[0]);
+                gn_add(&gn_lds[gn_img - gn_i0][gl + 2][1], gs3[1]);
+            }
         }
         __syncthreads();
         const uint32_t n_img = g.M / g.gn_rows;
@@ -795,6 +828,10 @@ __global__ void __launch_bounds__(256) k_sd_gemm_splitk_epilogue(const CnerfSdGe
             }
             a = a * g.alpha + (g.bias ? g.bias[n] : 0.0f);
             b = b * g.alpha + (g.bias ? g.bias[n + 1] : 0.0f);
+            if (g.bias_rows) {                                              // per-image bias comes before the activation, as in the one-launch epilogue
+                const float *br = g.bias_rows + (size_t)(m / g.rows_per_bias_row) * (g.ld_bias_rows ? g.ld_bias_rows : g.N) + n;
+                a += br[0]; b += br[1];
+            }
             reinterpret_cast<_Float16 *>(g.C)[(size_t)m * g.ldc + c] = (_Float16)(a * (0.5f * b * (1.0f + erff(b * 0.70710678118654752f))));
         }
         return;

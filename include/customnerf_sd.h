@@ -32,7 +32,7 @@ extern "C" {
  *   forward conv (torch.nn.Conv2d):            stride s, pad p, tstride 1
  *   input-gradient of a conv (frozen weights):  stride 1, pad KH-1-p, tstride s, B = weights flipped and transposed
  * epilogue, in this order:  (+ bias[n])  (+ bias_rows[(m / rows_per_bias_row)][n])  (activation: 0 none, 1 SiLU, 2 GELU(erf), 3 quick-GELU x*sigmoid(1.702x),
- *                           4 GEGLU on interleaved column pairs: C[m][j] = y[2j] * gelu(y[2j+1]), C is N/2 wide, no residual)
+ *                           4 GEGLU on interleaved column pairs: C[m][j] = y[2j] * gelu(y[2j+1]), y after both biases, C is N/2 wide, no residual)
  *                           (+ residual[z][m][n])  -> C (half), and/or C32 (float, optional).
  * batching: z = zo * batch_inner + zi, operand bases advance by s?_o * zo + s?_i * zi elements (attention heads are a strided
  * view of [batch, tokens, heads*dim]); batch = 1 and zero strides for plain GEMMs / convs.
@@ -60,7 +60,8 @@ typedef struct CnerfSdGemm {
     uint32_t Cin, H_in, W_in, H_out, W_out, KH, KW, stride, pad_t, pad_l, ups, tstride;
     /* optional GroupNorm statistics of the OUTPUT (the norm that consumes C next): gn_sums [M / gn_rows][gn_groups][2] int64 fixed point
      * (CNERF_SD_GN_FRAC_BITS fractional bits), pre-zeroed, receives sum and sum of squares of the half-rounded outputs per (image,
-     * channel group); N % gn_groups == 0, gn_rows >= 64.
+     * channel group); N % gn_groups == 0, N / gn_groups >= 4 (any such width: groups of 5 channels put three groups into one 8-column chunk
+     * of the epilogue, which carries a third bucket for them), gn_rows >= 64, M % gn_rows == 0, no batching — else CNERF_EINVAL.
      * Served on every schedule (round 6: the split-K tail kernel accumulates them; a request of more than 512 (image, group) pairs keeps
      * the problem off the split-K path). */
     int64_t *gn_sums;
