@@ -181,6 +181,9 @@ SIGNATURES = {
     "cnerf_sd_timestep_embedding": [vp, u32, u32, vp, vp],
     "cnerf_sd_add_noise": [vp, vp, f32, u32, vp, vp],
     "cnerf_sd_sds_grad": [vp, u32, vp, f32, f32, f32, u32, vp, vp],
+    "cnerf_sd_decoder_input": [vp, u32, u32, f32, vp, vp, vp],
+    "cnerf_sd_decoder_output": [vp, u32, u32, u32, vp, vp, vp],
+    "cnerf_sd_ddim_step": [vp, u32, vp, f32, f32, f32, i32, u32, u32, vp, vp, vp, vp],
     "cnerf_edit_ray_images": [vp, u32, u32, vp, vp, vp, vp],
     "cnerf_edit_ray_images_backward": [vp, vp, vp, u32, u32, vp, vp],
     "cnerf_edit_l1_loss": [vp, vp, u32, f32, vp, vp, vp],

@@ -120,6 +120,34 @@ def vae_encoder_params(cfg):
     return out
 
 
+def vae_decoder_params(cfg):
+    """the decoder half of diffusers' AutoencoderKL (post_quant_conv + Decoder): up block i runs layers_per_block + 1 resnets at
+    reversed(block_out_channels)[i], the first of them coming from the previous block's width, and all but the last block end in a
+    nearest-2x upsample + 3x3 convolution"""
+    boc = cfg["block_out_channels"]
+    rev = tuple(reversed(boc))
+    lc = cfg["latent_channels"]
+    c = rev[0]
+    out = [("post_quant_conv.weight", (lc, lc, 1, 1)), ("post_quant_conv.bias", (lc,)),
+           ("decoder.conv_in.weight", (c, lc, 3, 3)), ("decoder.conv_in.bias", (c,))]
+    a = "decoder.mid_block.attentions.0."
+    out += _resnet("decoder.mid_block.resnets.0.", c, c, 0)
+    out += [(a + "group_norm.weight", (c,)), (a + "group_norm.bias", (c,))]
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        out += [(a + n + ".weight", (c, c)), (a + n + ".bias", (c,))]
+    out += _resnet("decoder.mid_block.resnets.1.", c, c, 0)
+    cin = c
+    for i, c in enumerate(rev):
+        for j in range(cfg["layers_per_block"] + 1):
+            out += _resnet(f"decoder.up_blocks.{i}.resnets.{j}.", cin, c, 0)
+            cin = c
+        if i < len(rev) - 1:
+            out += [(f"decoder.up_blocks.{i}.upsamplers.0.conv.weight", (c, c, 3, 3)), (f"decoder.up_blocks.{i}.upsamplers.0.conv.bias", (c,))]
+    out += [("decoder.conv_norm_out.weight", (c,)), ("decoder.conv_norm_out.bias", (c,)),
+            ("decoder.conv_out.weight", (cfg["in_channels"], c, 3, 3)), ("decoder.conv_out.bias", (cfg["in_channels"],))]
+    return out
+
+
 # older diffusers checkpoints name the VAE attention projections differently
 VAE_ATTN_ALIASES = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
 

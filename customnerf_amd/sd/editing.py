@@ -193,6 +193,38 @@ class EditTrainer(CheckpointMixin, EvalMixin):
             loss_dict['loss_bg'] = loss_bg.detach()
         return pred_rgb, pred_ws, loss, loss_dict
 
+    def guidance_preview(self, data, path=None, t=None, seed=0):
+        """What the SDS term sees of one view, for inspecting a run: render | noised | one-step denoised estimate x0 as an [H, 3W, 3] uint8 strip
+        (written as a PNG when `path` is given).  The view (first of the batch) is rendered without gradients or perturbation, resized and
+        encoded as train_step_sd does, noised at timestep t (default: the middle of the guidance's [min_step, max_step]) and decoded through
+        StableDiffusion.preview under the global prompt.  All draws come from a generator seeded here: no RNG stream, scaler, optimizer or
+        step counter of the training loop is touched (the UNet graph's input buffer is, and every training step rewrites it before use)."""
+        _, _, rays_o, rays_d, H, W, _ = data
+        dev = next(self.model.parameters()).device
+        guide = self.guidance
+        was_training = self.model.training
+        self.model.eval()                                    # a model in training mode draws its importance samples from the global RNG stream
+        try:
+            out = self._render_eval(self.model, rays_o.to(dev)[:1], rays_d.to(dev)[:1])
+        finally:
+            self.model.train(was_training)
+        img = out['image'].reshape(1, H, W, 3).permute(0, 3, 1, 2).float().contiguous()
+        r = self.sds_resolution
+        gen = torch.Generator().manual_seed(seed)
+        sample_noise, noise = torch.randn(2, 1, guide.vae_cfg["latent_channels"], r // 8, r // 8, generator=gen).to(dev).unbind(0)
+        with torch.no_grad():
+            latents = guide.encode_imgs(img, sample_noise=sample_noise, resize=(r, r))
+        t = (guide.min_step + guide.max_step) // 2 if t is None else int(t)
+        text_z = self.text_z[0] if self.clip_view else self.text_z
+        panels = guide.preview(latents, text_z, t, noise=noise, mode='sds')
+        fit = lambda p: p if p.shape[-2:] == (H, W) else F.interpolate(p, (H, W), mode="bilinear", align_corners=False)
+        strip = torch.cat([img, fit(panels['noisy']), fit(panels['x0'])], dim=3)[0].permute(1, 2, 0)
+        strip = (strip.clamp(0, 1) * 255.0).round().to(torch.uint8)
+        if path is not None:
+            from ..mesh import write_png
+            write_png(path, strip)
+        return strip
+
     def allreduce_grads(self):
         self._flat = allreduce_grads_flat(list(self.model.parameters()), self._flat, self.world_size)     # same path the gloo test exercises
 

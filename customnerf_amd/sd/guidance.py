@@ -1,7 +1,9 @@
 """`StableDiffusion` guidance with the reference's surface (nerf/sd.py:35-155) on libcustomnerf_hip.so.
 
 Same constructor arguments, `get_text_embeds`, `encode_imgs`, `train_step(latents, text_embeddings, ..., t_ratio)` and
-`set_system`; the VAE encoder and the UNet are customnerf_amd.sd.vae.VAEEncoder / unet.UNet.  Weights: pass diffusers
+`set_system`; the VAE encoder and the UNet are customnerf_amd.sd.vae.VAEEncoder / unet.UNet.  Beyond the reference (which never
+decodes a latent): `decode_latents`, `produce_latents` (DDIM), `embeds_to_img` / `prompt_to_img` and `preview`, on a VAEDecoder that is
+built on first use.  Weights: pass diffusers
 state dicts (`unet_state`, `vae_state`, float16/float32 tensors keyed as in a `runwayml/stable-diffusion-v1-5` checkpoint);
 without them the networks are seeded-random of the SD-1.5 shapes (synthetic mode: benchmarks and tests — there is no
 network access to fetch the checkpoint), and `data: synthetic` is what bench.py reports.
@@ -10,10 +12,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import arch, ops
+from . import arch, ops, sampler
 from .edit_fn import SDSLoss
 from .unet import UNet
-from .vae import VAEEncoder
+from .vae import VAEDecoder, VAEEncoder
 
 
 class StableDiffusion(nn.Module):
@@ -28,6 +30,9 @@ class StableDiffusion(nn.Module):
         self.unet_cfg = unet_cfg or arch.UNET_SD15
         self.vae_cfg = vae_cfg or arch.VAE_SD15
         self.synthetic = unet_state is None or vae_state is None
+        # the decoder (decode_latents / produce_latents / preview) is built on first use: what it needs of the caller's weights, or the seed
+        self._vae_dec = None
+        self._vae_dec_src = (seed + 3) if vae_state is None else {k: v for k, v in vae_state.items() if k.startswith(("decoder.", "post_quant_conv."))}
         if unet_state is None:
             unet_state = arch.random_state_dict(arch.unet_params(self.unet_cfg), seed + 1)
         if vae_state is None:
@@ -177,3 +182,94 @@ class StableDiffusion(nn.Module):
         if getattr(self.opt, 'log_loss_item', True):
             return loss, dict(loss_sds=loss.item())
         return loss, dict(loss_sds=loss.detach())
+
+    # ---- latents -> images and DDIM sampling: decode_latents / produce_latents / prompt_to_img of the stable-dreamfusion guidance classes.
+    # Inference only; none of it draws from self._gen (the training timesteps) or from a generator the caller did not pass.
+    def _decoder(self):
+        if self._vae_dec is None:
+            src = self._vae_dec_src
+            if isinstance(src, int):
+                src = arch.random_state_dict(arch.vae_decoder_params(self.vae_cfg), src)                 # synthetic mode: its own seed
+            elif not any(k.startswith("decoder.") for k in src):
+                raise ValueError("`vae_state` holds no `decoder.*` / `post_quant_conv.*` weights: decoding latents needs the whole AutoencoderKL state dict, "
+                                 "not the encoder half")
+            self._vae_dec = VAEDecoder(self.vae_cfg, src, self.device)
+            self._vae_dec_src = None
+        return self._vae_dec
+
+    def decode_latents(self, latents):
+        """latents [B, 4, h, w] (as encode_imgs / produce_latents return them) -> imgs [B, 3, 8h, 8w] float32 in [0, 1]"""
+        return self._decoder().decode(latents.to(self.device))[0]
+
+    def _unet_pairs_buffer(self, text_embeddings, B, h, w):
+        """where the UNet input of B (uncond, text) pairs is written: the captured graph's own input (made on first use) when eps_pred replays one"""
+        shape = (2 * B, h, w, 8)
+        if self.use_graph and 2 * B <= 16:
+            return self.unet.graph_inputs(shape, self._ctx_half(text_embeddings, B))[0]
+        return torch.empty(shape, dtype=torch.float16, device=self.device)
+
+    @torch.no_grad()
+    def produce_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None, generator=None,
+                        return_x0=False, batch_size=1):
+        """DDIM (eta = 0; sampler.ddim_schedule) from noise to latents [B, 4, height/8, width/8] under classifier-free guidance.
+        text_embeddings [2, 77, D] (uncond, text) is shared by the batch; `latents`: the initial noise (else drawn with `generator`, batch_size
+        samples).  One UNet call of batch 2B and one cnerf_sd_ddim_step per step, no host synchronisation in between: the step writes the
+        next UNet input where the UNet reads it.  return_x0: also the per-step denoised estimates [steps, B, 4, h, w]."""
+        if height % 64 or width % 64 or height <= 0 or width <= 0:
+            raise ValueError(f"height and width must be positive multiples of 64 (8x VAE, three UNet downsamples), got {height} x {width}")
+        h, w = height // 8, width // 8
+        if latents is None:
+            gdev = generator.device if generator is not None else self.device
+            latents = torch.randn(batch_size, 4, h, w, generator=generator, device=gdev, dtype=torch.float32)
+        if tuple(latents.shape[1:]) != (4, h, w):
+            raise ValueError(f"latents must be [B, 4, {h}, {w}], got {tuple(latents.shape)}")
+        lat = latents.detach().to(self.device, torch.float32).contiguous().clone()
+        B = lat.shape[0]
+        steps = sampler.ddim_schedule(num_inference_steps, self.alphas_host)
+        x0s = torch.empty(len(steps), B, 4, h, w, dtype=torch.float32, device=self.device) if return_x0 else None
+        unet_in = self._unet_pairs_buffer(text_embeddings, B, h, w)
+        for b in range(B):
+            ops.add_noise(lat[b:b + 1], lat[b:b + 1], 1.0, out=unet_in[2 * b:2 * b + 2])           # alpha_bar = 1: the latents themselves, as the UNet's CFG pair
+        for i, (t, ab_t, ab_prev) in enumerate(steps):
+            eps = self.eps_pred(unet_in, t, text_embeddings)
+            ops.ddim_step(eps, lat, ab_t, ab_prev, guidance_scale, ops.DDIM_CFG, latents_out=lat, x0_out=None if x0s is None else x0s[i], unet_in=unet_in)
+        return (lat, x0s) if return_x0 else lat
+
+    def embeds_to_img(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None, generator=None, batch_size=1):
+        """produce_latents + decode -> images uint8 [B, height, width, 3] (device tensor; mesh.write_png takes one image)"""
+        lat = self.produce_latents(text_embeddings, height, width, num_inference_steps, guidance_scale, latents, generator, batch_size=batch_size)
+        return self._decoder().decode(lat, image=False, image_u8=True)[1]
+
+    def prompt_to_img(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None, generator=None,
+                      batch_size=1):
+        """embeds_to_img on get_text_embeds(prompts, negative_prompts): one prompt per call (several samples of it: batch_size)"""
+        prompts = [prompts] if isinstance(prompts, str) else list(prompts)
+        negative_prompts = [negative_prompts] if isinstance(negative_prompts, str) else list(negative_prompts)
+        text_embeddings = self.get_text_embeds(prompts, negative_prompts)
+        if text_embeddings.shape[0] != 2:
+            raise ValueError("prompt_to_img takes one prompt and one negative prompt; use batch_size for several samples")
+        return self.embeds_to_img(text_embeddings, height, width, num_inference_steps, guidance_scale, latents, generator, batch_size)
+
+    @torch.no_grad()
+    def preview(self, latents, text_embeddings, t, noise=None, mode='sds'):
+        """What the guidance sees at timestep t: the latents noised as train_step noises them, and the one-step denoised estimate x0 behind the
+        prediction — mode 'sds': under the combination the SDS gradient uses (e_text + g (e_text - e_uncond), g = opt.cfg), 'cfg': under plain
+        classifier-free guidance.  -> dict(noisy=, x0=), decoded images [B, 3, 8h, 8w] float32.  noise: [B, 4, h, w] (else seeded by t)."""
+        if mode not in ('sds', 'cfg'):
+            raise ValueError(f"mode must be 'sds' or 'cfg', got {mode!r}")
+        t = int(t)
+        g = float(self.opt.cfg)
+        lat = latents.detach().to(self.device, torch.float32).contiguous()
+        B, _, h, w = lat.shape
+        if noise is None:
+            noise = torch.randn(lat.shape, generator=torch.Generator().manual_seed(t))
+        noise = noise.to(self.device, torch.float32).contiguous()
+        ab = float(self.alphas_host[t])
+        unet_in = self._unet_pairs_buffer(text_embeddings, B, h, w)
+        for b in range(B):
+            ops.add_noise(lat[b:b + 1], noise[b:b + 1], ab, out=unet_in[2 * b:2 * b + 2])
+        eps = self.eps_pred(unet_in, t, text_embeddings)
+        noisy = ab ** 0.5 * lat + (1.0 - ab) ** 0.5 * noise                                        # float32 copy of what add_noise rounded to half
+        x0 = torch.empty_like(lat)
+        ops.ddim_step(eps, noisy, ab, ab, g, ops.DDIM_SDS if mode == 'sds' else ops.DDIM_CFG, x0_out=x0)
+        return dict(noisy=self.decode_latents(noisy), x0=self.decode_latents(x0))

@@ -416,6 +416,47 @@ def sds_grad(eps, noise, alpha_bar, guidance, lambda_sd, out=None):
     return grad
 
 
+# ---- image sampling glue, one launch each (csrc/sd_sample.hip)
+DDIM_CFG, DDIM_SDS = 0, 1        # cnerf_sd_ddim_step `mode`: e_uncond + g (e_text - e_uncond) / the SDS gradient's e_text + g (e_text - e_uncond)
+
+
+def decoder_input(latents, post_quant, scaling_factor):
+    """latents [B, 4, h, w] float32, post_quant [20] float32 (W[out][in] | b of the 1x1 post_quant_conv) -> [B, h, w, 8] half NHWC
+    = post_quant_conv(latents / scaling_factor), channels 4..7 zero"""
+    require_cuda(latents, post_quant)
+    B, C, h, w = latents.shape
+    assert C == 4 and latents.dtype == torch.float32 and latents.is_contiguous()
+    assert post_quant.dtype == torch.float32 and post_quant.is_contiguous() and post_quant.numel() == 20
+    out = torch.empty(B, h, w, 8, dtype=torch.float16, device=latents.device)
+    check(lib.cnerf_sd_decoder_input(ptr(latents), B, h * w, float(scaling_factor), ptr(post_quant), ptr(out), stream()), "sd_decoder_input")
+    return out
+
+
+def decoder_output(x, image=True, image_u8=False):
+    """x [B, H, W, ld] half (channels 0..2) -> (imgs [B, 3, H, W] float32 = clamp(x / 2 + 0.5, 0, 1) or None, [B, H, W, 3] uint8 = round(255 imgs) or None)"""
+    require_cuda(x)
+    B, H, W, ld = x.shape
+    assert x.dtype == torch.float16 and x.is_contiguous()
+    img = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device) if image else None
+    u8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=x.device) if image_u8 else None
+    check(lib.cnerf_sd_decoder_output(ptr(x), ld, B, H * W, ptr(img), ptr(u8), stream()), "sd_decoder_output")
+    return img, u8
+
+
+def ddim_step(eps, latents, alpha_bar_t, alpha_bar_prev, guidance, mode=DDIM_CFG, latents_out=None, x0_out=None, unet_in=None):
+    """eps [2B, h, w, ld] half ((uncond, text) per sample), latents [B, 4, h, w] float32.  Writes whichever of latents_out (x_prev; may be
+    `latents`), x0_out (both like latents) and unet_in ([2B, h, w, 8] half: the next UNet input) is given."""
+    require_cuda(eps, latents)
+    B, C, h, w = latents.shape
+    assert C == 4 and latents.dtype == torch.float32 and latents.is_contiguous()
+    assert eps.dtype == torch.float16 and eps.is_contiguous() and eps.shape[:3] == (2 * B, h, w)
+    for o in (latents_out, x0_out):
+        assert o is None or (o.dtype == torch.float32 and o.is_contiguous() and o.shape == latents.shape)
+    assert unet_in is None or (unet_in.dtype == torch.float16 and unet_in.is_contiguous() and unet_in.shape == (2 * B, h, w, 8))
+    check(lib.cnerf_sd_ddim_step(ptr(eps), eps.shape[3], ptr(latents), float(alpha_bar_t), float(alpha_bar_prev), float(guidance), int(mode), B, h * w,
+                                 ptr(latents_out), ptr(x0_out), ptr(unet_in), stream()), "sd_ddim_step")
+
+
 # ---- the small tensors of one editing step, one launch each (csrc/edit_ops.hip)
 def _f32c(t):
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.contiguous().float()

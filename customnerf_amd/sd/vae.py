@@ -6,7 +6,10 @@ through this network's input gradient (sd.py:150-152), so every op is an autogra
 the library's kernels: the input-gradient of a convolution is the same implicit GEMM with flipped/transposed weights (and
 the transposed-stride loader for the three downsampling convs), GroupNorm+SiLU has a fused backward, the single-head
 mid-block attention is differentiated through explicit P = softmax(QK^T) GEMMs.  Weights are frozen (no weight gradients).
-Module tree / parameter names are diffusers' (arch.vae_encoder_params)."""
+Module tree / parameter names are diffusers' (arch.vae_encoder_params).
+
+VAEDecoder (arch.vae_decoder_params) is the other half, for looking at latents (StableDiffusion.decode_latents / produce_latents /
+preview): the same primitives, inference only."""
 import torch
 from torch.autograd import Function
 
@@ -123,10 +126,11 @@ class _ImageInput(Function):
 
 
 class _ConvW:
-    def __init__(self, sd, p, dev):
+    def __init__(self, sd, p, dev, dgrad=True):
+        """dgrad=False: no input-gradient weights (the decoder is inference only)"""
         w = sd[p + ".weight"].to(dev)
         self.k = w.shape[-1]
-        self.w, self.wd, self.b = pack.pack_conv(w), pack.pack_conv_dgrad(w), pack.f32(sd[p + ".bias"].to(dev))
+        self.w, self.wd, self.b = pack.pack_conv(w), (pack.pack_conv_dgrad(w) if dgrad else None), pack.f32(sd[p + ".bias"].to(dev))
 
     def __call__(self, x, stride=1, pad=None, out_hw=None, residual=None, gn=None):
         """gn = (pool, groups): also return the GroupNorm statistics of the output -> (y, (sums, ready)); else -> y"""
@@ -139,13 +143,36 @@ class _ConvW:
 
 
 class _LinW:
-    def __init__(self, sd, p, dev):
+    def __init__(self, sd, p, dev, dgrad=True):
         w = sd[p + ".weight"].to(dev)
         w = w.reshape(w.shape[0], -1)                                    # 1x1 convolutions are linears over NHWC channels
-        self.w, self.wT, self.b = pack.pack_linear(w), pack.pack_linear_T(w), pack.f32(sd[p + ".bias"].to(dev))
+        self.w, self.wT, self.b = pack.pack_linear(w), (pack.pack_linear_T(w) if dgrad else None), pack.f32(sd[p + ".bias"].to(dev))
 
     def __call__(self, x, residual=None):
         return _Linear.apply(x, self.w, self.wT, self.b, residual)
+
+
+def _resnet_forward(x, blk, groups, eps, pool, x_sums, x_ready, out_gn):
+    """norm1 + SiLU -> conv1 -> norm2 + SiLU -> conv2 + shortcut of one residual block (blk: _Resnet).  x_sums: the statistics of x from its
+    producer (x_ready: filled) or None; out_gn: have conv2 accumulate the statistics of y.  -> y, the statistics of y (or None), whether
+    they are filled, and what a backward needs (the statistics of x, conv1's output and its statistics)."""
+    B, H, W, _ = x.shape
+    if x_sums is not None:
+        h, s1 = ops.groupnorm(x, *blk.n1, groups, eps, True, sums=x_sums, sums_ready=x_ready)
+    else:
+        h, s1 = ops.groupnorm(x, *blk.n1, groups, eps, True, pool)
+    c1w, c2w = blk.c1, blk.c2
+    s2 = pool.take()
+    c1, ok1 = ops.conv2d(h, c1w.w, c1w.b, c1w.k, stride=1, pad=c1w.k // 2, gn=(s2, groups, H * W))
+    h, _ = ops.groupnorm(c1, *blk.n2, groups, eps, True, sums=s2, sums_ready=ok1)
+    res = ops.linear(x, blk.sc.w, bias=blk.sc.b) if blk.sc is not None else x
+    so, ok = None, False
+    if out_gn:
+        so = pool.take()
+        y, ok = ops.conv2d(h, c2w.w, c2w.b, c2w.k, stride=1, pad=c2w.k // 2, residual=res, gn=(so, groups, H * W))
+    else:
+        y = ops.conv2d(h, c2w.w, c2w.b, c2w.k, stride=1, pad=c2w.k // 2, residual=res)
+    return y, so, ok, (s1, c1, s2)
 
 
 class _ResnetFn(Function):
@@ -158,21 +185,7 @@ class _ResnetFn(Function):
     def forward(ctx, x, blk, groups, eps, pool, x_sums, x_ready, out_gn):
         ctx.set_materialize_grads(False)                     # (statistics and flag outputs: no zero tensors for them in the backward)
         B, H, W, _ = x.shape
-        if x_sums is not None:
-            h, s1 = ops.groupnorm(x, *blk.n1, groups, eps, True, sums=x_sums, sums_ready=x_ready)
-        else:
-            h, s1 = ops.groupnorm(x, *blk.n1, groups, eps, True, pool)
-        c1w, c2w = blk.c1, blk.c2
-        s2 = pool.take()
-        c1, ok1 = ops.conv2d(h, c1w.w, c1w.b, c1w.k, stride=1, pad=c1w.k // 2, gn=(s2, groups, H * W))
-        h, _ = ops.groupnorm(c1, *blk.n2, groups, eps, True, sums=s2, sums_ready=ok1)
-        res = ops.linear(x, blk.sc.w, bias=blk.sc.b) if blk.sc is not None else x
-        so, ok = None, False
-        if out_gn:
-            so = pool.take()
-            y, ok = ops.conv2d(h, c2w.w, c2w.b, c2w.k, stride=1, pad=c2w.k // 2, residual=res, gn=(so, groups, H * W))
-        else:
-            y = ops.conv2d(h, c2w.w, c2w.b, c2w.k, stride=1, pad=c2w.k // 2, residual=res)
+        y, so, ok, (s1, c1, s2) = _resnet_forward(x, blk, groups, eps, pool, x_sums, x_ready, out_gn)
         ctx.save_for_backward(x, s1, c1, s2, pool.take(), pool.take())       # + two pre-zeroed scratch slices for the backward norms
         ctx.blk, ctx.cfg = blk, (groups, eps, H, W)
         flag = torch.tensor(1 if ok else 0)
@@ -200,11 +213,11 @@ class _ResnetFn(Function):
 
 
 class _Resnet:
-    def __init__(self, sd, p, dev):
+    def __init__(self, sd, p, dev, dgrad=True):
         self.n1 = (pack.f32(sd[p + "norm1.weight"].to(dev)), pack.f32(sd[p + "norm1.bias"].to(dev)))
         self.n2 = (pack.f32(sd[p + "norm2.weight"].to(dev)), pack.f32(sd[p + "norm2.bias"].to(dev)))
-        self.c1, self.c2 = _ConvW(sd, p + "conv1", dev), _ConvW(sd, p + "conv2", dev)
-        self.sc = _LinW(sd, p + "conv_shortcut", dev) if (p + "conv_shortcut.weight") in sd else None
+        self.c1, self.c2 = _ConvW(sd, p + "conv1", dev, dgrad), _ConvW(sd, p + "conv2", dev, dgrad)
+        self.sc = _LinW(sd, p + "conv_shortcut", dev, dgrad) if (p + "conv_shortcut.weight") in sd else None
 
     def __call__(self, x, groups, eps, pool, x_sums=None, out_gn=False):
         """x_sums = (sums, ready) of x from its producer (or None); out_gn: also return the statistics of the output -> (y, (sums, ready) | None)"""
@@ -265,3 +278,80 @@ class VAEEncoder:
         Differentiable w.r.t. imgs."""
         x = _ImageInput.apply(imgs, resize[0], resize[1])
         return SampleLatents.apply(self.moments(x).contiguous(), sample_noise, self.cfg["scaling_factor"])     # clamp / exp / sample / scale: one launch
+
+
+class VAEDecoder:
+    """AutoencoderKL decoder (post_quant_conv + Decoder; arch.vae_decoder_params), inference only: the same NHWC-half primitives,
+    weight packing and statistics plumbing as VAEEncoder, no autograd.  The 2x nearest upsamples are folded into the loader of the
+    convolution that follows them (ops.conv2d ups=2): no upsampled tensor exists."""
+
+    def __init__(self, cfg, state_dict, device="cuda"):
+        self.cfg = cfg
+        dev = torch.device(device)
+        sd = dict(state_dict)
+        a = "decoder.mid_block.attentions.0."
+        for old, new in VAE_ATTN_ALIASES.items():                       # older diffusers checkpoints
+            for suffix in (".weight", ".bias"):
+                if a + old + suffix in sd:
+                    sd[a + new + suffix] = sd.pop(a + old + suffix)
+        lc = cfg["latent_channels"]
+        if lc != 4:
+            raise ValueError("the decoder's input kernel is written for 4 latent channels")
+        rev = tuple(reversed(cfg["block_out_channels"]))
+        # post_quant_conv as 20 floats (W[out][in] | b): applied by cnerf_sd_decoder_input, a K = 4 GEMM is not worth a launch
+        self.post_quant = torch.cat([sd["post_quant_conv.weight"].reshape(lc, lc).flatten(), sd["post_quant_conv.bias"].flatten()]).to(dev, torch.float32).contiguous()
+        self.conv_in = _ConvW(sd, "decoder.conv_in", dev, dgrad=False)
+        self.mid0, self.mid1 = _Resnet(sd, "decoder.mid_block.resnets.0.", dev, False), _Resnet(sd, "decoder.mid_block.resnets.1.", dev, False)
+        self.an = (pack.f32(sd[a + "group_norm.weight"].to(dev)), pack.f32(sd[a + "group_norm.bias"].to(dev)))
+        self.aq, self.ak, self.av, self.ao = (_LinW(sd, a + n, dev, dgrad=False) for n in ("to_q", "to_k", "to_v", "to_out.0"))
+        self.up = []
+        for i in range(len(rev)):
+            res = [_Resnet(sd, f"decoder.up_blocks.{i}.resnets.{j}.", dev, False) for j in range(cfg["layers_per_block"] + 1)]
+            us = _ConvW(sd, f"decoder.up_blocks.{i}.upsamplers.0.conv", dev, dgrad=False) if i < len(rev) - 1 else None
+            self.up.append((res, us))
+        self.no = (pack.f32(sd["decoder.conv_norm_out.weight"].to(dev)), pack.f32(sd["decoder.conv_norm_out.bias"].to(dev)))
+        # conv_out: its 3 output channels padded to 8 with zero filters, the row width the GEMM's other small outputs have (quant_conv)
+        w, b = sd["decoder.conv_out.weight"], sd["decoder.conv_out.bias"]
+        pad = pack.pad8(w.shape[0]) - w.shape[0]
+        self.conv_out = _ConvW({"w.weight": torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, pad)), "w.bias": torch.nn.functional.pad(b, (0, pad))}, "w", dev, dgrad=False)
+
+    @staticmethod
+    def _conv(cw, x, G, pool=None, ups=1):
+        """the convolution `cw` (_ConvW) on x; pool: also ask for the GroupNorm statistics of the output -> (y, (sums, ready))"""
+        if pool is None:
+            return ops.conv2d(x, cw.w, cw.b, cw.k, pad=cw.k // 2, ups=ups)
+        sums = pool.take()
+        y, ok = ops.conv2d(x, cw.w, cw.b, cw.k, pad=cw.k // 2, ups=ups, gn=(sums, G, x.shape[1] * ups * x.shape[2] * ups))
+        return y, (sums, ok)
+
+    @torch.no_grad()
+    def forward(self, latents):
+        """latents [B, 4, h, w] float32 (scaled by scaling_factor, as encode_imgs returns them) -> conv_out's output [B, 8h, 8w, 8] half NHWC
+        (3 channels + zero padding), about [-1, 1]"""
+        G, eps = self.cfg["groups"], self.cfg["eps"]
+        x = ops.decoder_input(latents.detach().float().contiguous(), self.post_quant, self.cfg["scaling_factor"])
+        n_res = 2 + sum(len(res) for res, _ in self.up)
+        pool = ops.SumsPool(3 * n_res + 8, x.shape[0], G, x.device)
+        h, hs = self._conv(self.conv_in, x, G, pool)
+        h, so, ok, _ = _resnet_forward(h, self.mid0, G, eps, pool, hs[0], hs[1], True)
+        B, H, W, C = h.shape
+        n, _ = ops.groupnorm(h, *self.an, G, eps, False, sums=so, sums_ready=ok)
+        n = n.view(B, H * W, C)
+        lin = lambda l, t, residual=None: ops.linear(t, l.w, bias=l.b, residual=residual)
+        P = ops.attention_scores(lin(self.aq, n), lin(self.ak, n), 1, 1.0 / float(C) ** 0.5)
+        h = lin(self.ao, ops.attention_apply(P, lin(self.av, n), 1), residual=h.view(B, H * W, C)).view(B, H, W, C)
+        h, so, ok, _ = _resnet_forward(h, self.mid1, G, eps, pool, None, False, True)
+        for res, us in self.up:
+            for j, r in enumerate(res):
+                feeds_norm = not (us is not None and j == len(res) - 1)       # the last resnet of a block feeds the upsample conv
+                h, so, ok, _ = _resnet_forward(h, r, G, eps, pool, so, ok, feeds_norm)
+            if us is not None:
+                h, (so, ok) = self._conv(us, h, G, pool, ups=2)
+        h, _ = ops.groupnorm(h, *self.no, G, eps, True, sums=so, sums_ready=ok)
+        return self._conv(self.conv_out, h, G)
+
+    __call__ = forward
+
+    def decode(self, latents, image=True, image_u8=False):
+        """-> (imgs [B, 3, 8h, 8w] float32 = clamp(forward / 2 + 0.5, 0, 1) or None, the same as [B, 8h, 8w, 3] uint8 or None)"""
+        return ops.decoder_output(self.forward(latents), image, image_u8)

@@ -167,6 +167,28 @@ int cnerf_sd_add_noise(const float *latents, const float *noise, float alpha_bar
 int cnerf_sd_sds_grad(const void *eps, uint32_t ld_eps, const float *noise, float alpha_bar, float guidance, float lambda_sd,
                       uint32_t pixels, float *grad, void *stream);
 
+/* Image sampling (StableDiffusion.produce_latents / decode_latents / preview): the glue between the UNet, the float32 latents of a
+ * DDIM run and the VAE decoder.  One launch each; every rejected argument, a NULL pointer included, is CNERF_EINVAL.
+ *
+ * cnerf_sd_decoder_input: latents [B][4][hw] float32 -> out [B][hw][8] half (NHWC, channels 4..7 zero, 16-byte aligned)
+ *   = post_quant_conv(latents / scaling_factor); post_quant = 20 DEVICE floats: the 1x1 convolution's W[out][in] row-major, then b[4].
+ * cnerf_sd_decoder_output: x [B][HW][ld] half (decoder.conv_out; channels 0..2 are read, ld >= 3) -> img [B][3][HW] float32
+ *   = clamp(x / 2 + 0.5, 0, 1) and img_u8 [B][HW][3] = round(255 img); either output may be NULL, not both.
+ * cnerf_sd_ddim_step: one DDIM step (eta = 0, no sample clipping) for `pairs` independent samples.
+ *   eps [pairs][2][pixels][ld_eps] half, each pair (uncond, text); latents [pairs][4][pixels] float32; alpha_bar_t, alpha_bar_prev in (0, 1].
+ *     e      = e_uncond + g (e_text - e_uncond)      mode 0: classifier-free guidance
+ *            = e_text   + g (e_text - e_uncond)      mode 1: the combination of cnerf_sd_sds_grad (sd.py:143)
+ *     x0     = (x - sqrt(1 - ab_t) e) / sqrt(ab_t)
+ *     x_prev = sqrt(ab_prev) x0 + sqrt(1 - ab_prev) e
+ *   latents_out (x_prev; may be `latents` itself) and x0_out in the latents' layout, unet_in [pairs][2][pixels][8] half = x_prev written
+ *   twice with zero padding (cnerf_sd_add_noise's layout: the captured UNet graph's own input can be the target).  Each of the three may
+ *   be NULL, not all. */
+int cnerf_sd_decoder_input(const float *latents, uint32_t B, uint32_t hw, float scaling_factor, const float *post_quant, void *out,
+                           void *stream);
+int cnerf_sd_decoder_output(const void *x, uint32_t ld, uint32_t B, uint32_t HW, float *img, uint8_t *img_u8, void *stream);
+int cnerf_sd_ddim_step(const void *eps, uint32_t ld_eps, const float *latents, float alpha_bar_t, float alpha_bar_prev, float guidance,
+                       int mode, uint32_t pairs, uint32_t pixels, float *latents_out, float *x0_out, void *unet_in, void *stream);
+
 /* Generic element-wise helpers on half buffers (n elements): y = a + b ; y = silu(x). */
 int cnerf_sd_add(const void *a, const void *b, uint64_t n, void *y, void *stream);
 int cnerf_sd_silu(const void *x, uint64_t n, void *y, void *stream);
