@@ -23,8 +23,7 @@
 // D = 3, C = 2 only (the configuration CustomNeRF uses); other shapes take the atomic kernel in gridencoder.hip.
 //
 // Two forms live in this file.  The FIRST form described above (k_bin_*: histogram + scans + one 8/12-byte record per corner) serves float32
-// records and the fp16 tables the third form does not take (hashed levels whose size is not a power of two or is below 32 entries); its
-// coordinate-only half (histogram + scans) can be issued ahead of time, on a side stream (cnerf_grid_encode_backward_prepare).  The THIRD form
+// records and the fp16 tables the third form does not take (hashed levels whose size is not a power of two or is below 32 entries).  The THIRD form
 // (k_bin3_*: no histogram, block-local counting, fixed-capacity bin regions with spill, interleaved bins on the hashed levels) serves every fp16
 // table CustomNeRF runs — the benchmark table and the reference field's own 2^21-entry table.  Its records are 8-byte fp16 PAIR records (one per
 // x-pair of corners, see "fp16 pair records" below).  The form numbering follows docs/HISTORY.md.
@@ -1512,14 +1511,6 @@ static int b3_backward(const __half *grad, const float *inputs, const GridLevels
     return cn_launch_status();
 }
 
-// does the binned backward of this shape use a plan prepared ahead of time (histogram + scans on the sample coordinates)?  The third form
-// counts inside its emit kernel: nothing to prepare.
-// (the query has no align_corners argument: a plan is "needed" unless the third form takes the shape either way — a plan prepared for a launch
-// that then does not use it is wasted work, never wrong)
-bool bn_needs_plan(uint32_t B, uint32_t nl, const GridLevels &lv, int dtype, uint32_t gridtype) {
-    return !(b3_enabled(lv, nl, B, dtype, gridtype, 0) && b3_enabled(lv, nl, B, dtype, gridtype, 1));
-}
-
 // used by gridencoder.hip
 bool bn_eligible(uint32_t B, uint32_t D, uint32_t C, uint32_t nl, const GridLevels &lv) {
     if (D != 3 || C != 2 || nl == 0) return false;
@@ -1547,8 +1538,7 @@ uint64_t bn_workspace_bytes(uint32_t B, uint32_t nl, const GridLevels &lv, int d
 
 // First form.  Phase 1 (bn_prepare; needs the sample coordinates only): histogram + scans.  Phase 2 (bn_phase2; needs the gradients): emit +
 // accumulate.
-// The two phases may be issued separately (cnerf_grid_encode_backward_prepare) so that phase 1 overlaps the forward / field backward.
-int bn_prepare(const float *inputs, const GridLevels &lv, uint32_t B, uint32_t nl, uint32_t gridtype, int ac, uint32_t interp, int dtype,
+static int bn_prepare(const float *inputs, const GridLevels &lv, uint32_t B, uint32_t nl, uint32_t gridtype, int ac, uint32_t interp, int dtype,
                void *workspace, hipStream_t st) {
     BinPlan plan;
     bn_plan(lv, nl, B, plan);
@@ -1585,13 +1575,11 @@ static int bn_phase2(const T *grad, const float *inputs, const GridLevels &lv, f
 }
 
 int bn_backward(const void *grad, const float *inputs, const GridLevels &lv, float *gemb, uint32_t B, uint32_t nl, uint32_t gridtype, int ac,
-                uint32_t interp, int dtype, void *workspace, hipStream_t st, bool prepared) {
+                uint32_t interp, int dtype, void *workspace, hipStream_t st) {
     if (b3_enabled(lv, nl, B, dtype, gridtype, ac)) return b3_backward((const __half *)grad, inputs, lv, gemb, B, nl, gridtype, ac, interp, workspace, st);
     if (nl) (void)b3_take_adam(gemb, lv, nl, false);                                 // (the first form does not carry the optimiser step: disarm)
-    if (!prepared) {
-        const int rc = bn_prepare(inputs, lv, B, nl, gridtype, ac, interp, dtype, workspace, st);
-        if (rc) return rc;
-    }
+    const int rc = bn_prepare(inputs, lv, B, nl, gridtype, ac, interp, dtype, workspace, st);
+    if (rc) return rc;
     if (dtype == CNERF_F16) return bn_phase2<__half>((const __half *)grad, inputs, lv, gemb, B, nl, gridtype, ac, interp, dtype, workspace, st);
     return bn_phase2<float>((const float *)grad, inputs, lv, gemb, B, nl, gridtype, ac, interp, dtype, workspace, st);
 }

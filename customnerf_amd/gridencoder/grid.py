@@ -9,10 +9,6 @@ Deliberate differences:
     counter, so writes through `.data` must be followed by invalidate_half_table();
   * gradients are accumulated in float32 for both table dtypes (the reference scatters __half2 atomics for fp16).
 """
-import ctypes
-import os
-import weakref
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -181,106 +177,19 @@ def set_pre_scatter_hook(fn):
     _PRE_SCATTER_HOOK = fn
 
 
-_SIDE = {}          # scratch_key -> _side_entry
-
-
-class _Plan:
-    """a prepared scatter plan (lives on the autograd node: dropped with the graph if the backward never runs)"""
-    __slots__ = ('ws', 'event', 'inputs_ptr', 'rows', '__weakref__')
-
-    def __init__(self, ws, event, inputs_ptr, rows):
-        self.ws, self.event, self.inputs_ptr, self.rows = ws, event, inputs_ptr, rows
-
-
-def _side_entry(side_stream):
-    """'ws': the workspace of the prepared plan, a one-key cache that leaves with the entry (_SIDE.clear() releases it);
-    'owner': weakref to the plan waiting for its backward"""
-    return {'stream': side_stream, 'ws': ScratchCache(factor=1.25, pad=256), 'owner': None}
-
-
-def _side(device):
-    # one side stream + plan slot per compute stream: a capture runs on a stream of its own, so the plan workspace a graph holds is the
-    # one allocated inside the capture (graph pool), never the eager step's
-    key = scratch_key(device)
-    st = _SIDE.get(key)
-    if st is None:
-        st = _SIDE[key] = _side_entry(torch.cuda.Stream(device=device))
-    return st
-
-
-def _side_busy(side):
-    return side['owner'] is not None and side['owner']() is not None
-
-
-_NEEDS_PLAN = {}
-
-
-def _needs_plan(offsets_host, B, D, C, L, S, H, dt, gridtype):
-    """does the backward scatter of this shape use a plan prepared ahead of time?  (cnerf_grid_encode_backward_needs_plan, cached per shape: only
-    the first form of the binned scatter takes one — float32 records, and fp16 tables the third form does not take; the third form, which
-    serves the fp16 tables of the run() path, counts inside its emit kernel and prepares nothing)"""
-    key = (offsets_host.ctypes.data, B, D, C, L, S, H, dt, gridtype)
-    v = _NEEDS_PLAN.get(key)
-    if v is None:
-        n = ctypes.c_int(0)
-        check(lib.cnerf_grid_encode_backward_needs_plan(offsets_host.ctypes.data, B, D, C, L, L, S, H, gridtype, dt, ctypes.addressof(n)),
-              "grid_encode_backward_needs_plan")
-        if len(_NEEDS_PLAN) > 256:
-            _NEEDS_PLAN.clear()
-        v = _NEEDS_PLAN[key] = (bool(n.value), offsets_host)             # (the array reference pins the key's address)
-    return v[0]
-
-
-def _prepare_plan(inputs, offsets_host, B, D, C, L, S, H, gridtype, align_corners, interpolation, dt, device):
-    """Issue the coordinate-only half of the binned backward scatter's first form (histogram + scans) for `inputs` [B, D] on the side stream of
-    the current compute stream -> _Plan, or None when the side stream still holds an earlier plan / the shape takes no plan (atomic kernel,
-    third form)."""
-    if not _needs_plan(offsets_host, B, D, C, L, S, H, dt, gridtype):
-        return None
-    side = _side(device)
-    if _side_busy(side):
-        return None
-    need = query_u64(lib.cnerf_grid_encode_backward_workspace_bytes, offsets_host.ctypes.data, B, D, C, L, L, S, H, dt)
-    if not need:
-        return None
-    ws = side['ws'].reserve('plan', need, device)
-    cur = torch.cuda.current_stream()
-    side['stream'].wait_stream(cur)                              # the coordinates were produced on the current stream
-    ok = ctypes.c_int(0)
-    check(lib.cnerf_grid_encode_backward_prepare(ptr(inputs), offsets_host.ctypes.data, B, D, C, L, L, S, H, gridtype, int(align_corners),
-                                                 interpolation, dt, ptr(ws), ws.numel(), ctypes.addressof(ok), side['stream'].cuda_stream),
-          "grid_encode_backward_prepare")
-    if not ok.value:
-        return None
-    ev = torch.cuda.Event()
-    ev.record(side['stream'])
-    plan = _Plan(ws, ev, inputs.data_ptr(), B)
-    side['owner'] = weakref.ref(plan)
-    return plan
-
-
 class _grid_attach(Function):
     """Backward half of _grid_encode for a feature buffer that was filled by GridEncoder.encode_into calls: forward hands the buffer
-    on unchanged, backward scatters d(loss)/d(features) [L,B,C] into the table gradient for ALL B rows of `inputs`.
-    When the scatter takes the first form of the binned backward (float32 records, see _needs_plan), its coordinate-only half (histogram + scans) is issued
-    here, in the forward, on a second stream: it overlaps the rest of the forward pass and the field backward instead of sitting on the
-    critical path.  The third form (fp16 records) has no such half: nothing is issued."""
+    on unchanged, backward scatters d(loss)/d(features) [L,B,C] into the table gradient for ALL B rows of `inputs`."""
 
     @staticmethod
-    def forward(ctx, enc, inputs, embeddings, offsets_host, per_level_scale, base_resolution, gridtype, align_corners, interpolation, overlap,
-                grad_in_place=False, plan=None):
+    def forward(ctx, enc, inputs, embeddings, offsets_host, per_level_scale, base_resolution, gridtype, align_corners, interpolation,
+                grad_in_place=False):
         ctx.param = embeddings if grad_in_place else None
         L, B, C = enc.shape
         D = inputs.shape[1]
         S, H = float(np.log2(per_level_scale)), int(base_resolution)
-        dt = dtype_id(enc)
         ctx.save_for_backward(inputs)
         ctx.cfg = (offsets_host, B, D, C, L, S, H, gridtype, interpolation, align_corners, tuple(embeddings.shape))
-        if plan is not None and (plan.inputs_ptr != inputs.data_ptr() or plan.rows != B):
-            plan = None                                                          # prepared for other coordinates: not ours
-        if plan is None and overlap:
-            plan = _prepare_plan(inputs, offsets_host, B, D, C, L, S, H, gridtype, align_corners, interpolation, dt, enc.device)
-        ctx.plan = plan
         return enc.detach()
 
     @staticmethod
@@ -298,22 +207,12 @@ class _grid_attach(Function):
         grad_embeddings = tgt if in_place else torch.zeros(eshape, device=grad.device, dtype=torch.float32)
         if in_place:
             grad_chain_wait(grad.device)                                        # read-modify-write of the shared .grad: one scatter at a time
-        if ctx.plan is not None:
-            ws, ev = ctx.plan.ws, ctx.plan.event
-            torch.cuda.current_stream().wait_event(ev)
-            try:
-                check(lib.cnerf_grid_encode_backward_prepared(ptr(grad), ptr(inputs), offsets_host.ctypes.data, ptr(grad_embeddings), B, D, C, L, L, S, H,
-                                                              gridtype, int(align_corners), interpolation, dtype_id(grad), ptr(ws), ws.numel(), stream()),
-                      "grid_encode_backward_prepared")
-            finally:
-                ctx.plan = None                                                 # releases the side workspace for the next plan
-        else:
-            ws, ws_bytes = _bwd_workspace(offsets_host, B, D, C, L, L, S, H, dtype_id(grad), grad.device)
-            check(lib.cnerf_grid_encode_backward(ptr(grad), ptr(inputs), offsets_host.ctypes.data, ptr(grad_embeddings), B, D, C, L, L, S, H, None, None,
-                                                 gridtype, int(align_corners), interpolation, dtype_id(grad), ptr(ws), ws_bytes, stream()), "grid_encode_backward")
+        ws, ws_bytes = _bwd_workspace(offsets_host, B, D, C, L, L, S, H, dtype_id(grad), grad.device)
+        check(lib.cnerf_grid_encode_backward(ptr(grad), ptr(inputs), offsets_host.ctypes.data, ptr(grad_embeddings), B, D, C, L, L, S, H, None, None,
+                                             gridtype, int(align_corners), interpolation, dtype_id(grad), ptr(ws), ws_bytes, stream()), "grid_encode_backward")
         if in_place:
             grad_chain_record(grad.device)
-        return None, None, (None if in_place else grad_embeddings), None, None, None, None, None, None, None, None, None
+        return None, None, (None if in_place else grad_embeddings), None, None, None, None, None, None, None
 
 
 def grid_encode(inputs, embeddings, offsets, per_level_scale, base_resolution, calc_grad_inputs=False, gridtype=0,
@@ -447,23 +346,10 @@ class GridEncoder(nn.Module):
                 if prof is not None and k == len(todo) - 1:
                     prof.append((e0, e1, B, L, table.element_size()))
 
-    def prepare_backward(self, inputs_unit, half):
-        """Issue the coordinate-only half of the backward scatter for inputs_unit [P, D] (float32, contiguous, [0, 1] grid coordinates) NOW, on
-        the side stream — as soon as the coordinates exist, e.g. before the last encode_into, whose gather it then overlaps — and return the
-        plan for attach_backward(..., plan=).  None when nothing was issued: the shape takes no plan (only the first form of the binned
-        scatter does: see _needs_plan), or the side stream is busy (attach_backward then plans by itself)."""
-        assert inputs_unit.is_contiguous() and inputs_unit.dtype == torch.float32
-        P, D = inputs_unit.shape
-        dt = dtype_id(torch.empty(0, dtype=torch.float16 if half else torch.float32))
-        return _prepare_plan(inputs_unit, self._offsets_host, P, D, self.level_dim, self.num_levels, float(np.log2(self.per_level_scale)),
-                             int(self.base_resolution), self.gridtype_id, self.align_corners, self.interp_id, dt, inputs_unit.device)
-
-    def attach_backward(self, enc, inputs_unit, overlap=True, plan=None):
-        """enc [L, P, C] filled by encode_into for the rows of inputs_unit [P, D] -> the same features, differentiable in the table.
-        overlap: issue the coordinate-only half of the backward scatter now, on a second stream, if the shape takes one (see _grid_attach);
-        plan: it was issued earlier by prepare_backward on these coordinates."""
+    def attach_backward(self, enc, inputs_unit):
+        """enc [L, P, C] filled by encode_into for the rows of inputs_unit [P, D] -> the same features, differentiable in the table."""
         return _grid_attach.apply(enc, inputs_unit.contiguous().float(), self.embeddings, self._offsets_host, self.per_level_scale, self.base_resolution,
-                                  self.gridtype_id, self.align_corners, self.interp_id, bool(overlap), bool(getattr(self, 'grad_in_place', False)), plan)
+                                  self.gridtype_id, self.align_corners, self.interp_id, bool(getattr(self, 'grad_in_place', False)))
 
     def forward(self, inputs, bound=1, max_level=None, return_kernel_layout=False):
         """grid.py:151-168: [..., D] -> [..., L*C]."""

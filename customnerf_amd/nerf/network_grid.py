@@ -190,24 +190,11 @@ class NeRFNetwork(NeRFRenderer):
                                      wimg=self._weight_image())
         return sigma
 
-    def _overlap_plan(self):
-        return getattr(self.opt, 'overlap_scatter_plan', True)
-
-    def split_prepare(self, unit, grad_enabled):
-        """As soon as every row of `unit` is written (i.e. before the last split_encode): start the coordinate-only half of the backward
-        scatter on the side stream, where it overlaps that gather instead of the field kernels.  -> plan for split_forward, or None (also
-        whenever the scatter takes no plan: only its float32-record form does, gridencoder.grid._needs_plan)."""
-        if not (grad_enabled and self.pos_en.embeddings.requires_grad and self._overlap_plan()):
-            return None
-        if not getattr(self.opt, 'early_scatter_plan', True):
-            return None
-        return self.pos_en.prepare_backward(unit, self._half())
-
-    def split_forward(self, enc, unit, x, d, dir_group, plan=None):
+    def split_forward(self, enc, unit, x, d, dir_group):
         """forward() on a complete feature buffer: (sigma [P], rgbc [P, 4]); gradients reach the table through attach_backward"""
         enc_dim, n_geo, n_rgb = self._fused_cfg()
         if torch.is_grad_enabled() and self.pos_en.embeddings.requires_grad:
-            enc = self.pos_en.attach_backward(enc, unit, overlap=self._overlap_plan(), plan=plan)
+            enc = self.pos_en.attach_backward(enc, unit)
         sigma, rgbc = field(enc, x, d.reshape(-1, 3), dir_group, enc_dim, n_geo, n_rgb, self.network.params, self.density_network.params,
                             self.rgb_network.params, grad_in_place=bool(getattr(self, 'grad_in_place', False)), wimg=self._weight_image())
         return sigma, rgbc
@@ -226,13 +213,13 @@ class NeRFNetwork(NeRFRenderer):
                            self.density_network.params, self.rgb_network.params, sigma_all[row0:row0 + n], rgbc_all[row0:row0 + n],
                            wimg=self._weight_image())
 
-    def split_attach(self, enc, unit, x, d, dir_group, sigma_all, rgbc_all, plan=None):
+    def split_attach(self, enc, unit, x, d, dir_group, sigma_all, rgbc_all):
         """(sigma [P], rgbc [P, 4]) computed by split_forward_rows -> the same values, differentiable in the table and the MLP parameters"""
         if not torch.is_grad_enabled():
             return sigma_all, rgbc_all
         enc_dim, n_geo, n_rgb = self._fused_cfg()
         if self.pos_en.embeddings.requires_grad:
-            enc = self.pos_en.attach_backward(enc, unit, overlap=self._overlap_plan(), plan=plan)
+            enc = self.pos_en.attach_backward(enc, unit)
         return field_attach(enc, x, d.reshape(-1, 3), dir_group, enc_dim, n_geo, n_rgb, self.network.params, self.density_network.params,
                             self.rgb_network.params, sigma_all, rgbc_all, grad_in_place=bool(getattr(self, 'grad_in_place', False)),
                             wimg=self._weight_image())

@@ -196,7 +196,6 @@ class NeRFRenderer(nn.Module):
         split = (num_steps == upsample_steps and getattr(self.opt, 'split_eval', True) and getattr(self, 'supports_split_eval', False)
                  and not getattr(self.opt, 'eval_fine_density', False))
         grad_on = torch.is_grad_enabled()
-        plan = None
         if not split:
             nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
         with torch.no_grad():
@@ -237,7 +236,6 @@ class NeRFRenderer(nn.Module):
                 z_all, xyz_f, src = render_ops.sample_fine_merge_split(rays_o, rays_d, nears, fars, aabb, z_vals, sig_c, upsample_steps, u_draw(),
                                                                         xyz_fine_out=xyz_list[Pc:].view(N, upsample_steps, 3),
                                                                         unit_fine_out=unit[Pc:].view(N, upsample_steps, 3), bound=bnd)
-                plan = self.split_prepare(unit, grad_on)                     # all coordinates exist: a scatter plan (float32 records) runs beside the gather below
                 self.split_encode(enc, unit, xyz_list[Pc:], Pc, unit_ready=True, importance=True)
                 if blockwise:
                     self.split_forward_rows(enc, Pc, xyz_list[Pc:], rays_d, upsample_steps, sig_all, rgbc_all)
@@ -251,9 +249,9 @@ class NeRFRenderer(nn.Module):
             # both blocks hold num_steps samples per ray, so "one direction per num_steps consecutive samples" covers the list with [d | d]
             dirs2 = self._dirs_twice(rays_d)
             if blockwise:
-                sig_l, rgbc_l = self.split_attach(enc, unit, xyz_list, dirs2, num_steps, sig_all, rgbc_all, plan=plan)
+                sig_l, rgbc_l = self.split_attach(enc, unit, xyz_list, dirs2, num_steps, sig_all, rgbc_all)
             else:
-                sig_l, rgbc_l = self.split_forward(enc, unit, xyz_list, dirs2, num_steps, plan=plan)
+                sig_l, rgbc_l = self.split_forward(enc, unit, xyz_list, dirs2, num_steps)
             # early termination of the backward (north_star; the reference's own is `T < T_thresh` on its march path): only where the gradients
             # go into the half-precision fused field, whose backward rounds them to half anyway
             flush = bool(grad_on and getattr(self.opt, 'early_termination', True) and self._fused_cfg() and self._half())

@@ -461,7 +461,7 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
         key = tuple((t.data_ptr(), tuple(t.shape), t.dtype) for t in tensors) + (tuple(sorted(render_kw.items())),)
         cache = self.__dict__.setdefault('_graphs', {})
         if cache and self._graph_gen != scratch_generation():
-            # a grow-on-demand workspace (scatter plan, partial-gradient rows) was reallocated since a cached graph was captured — e.g. by an
+            # a grow-on-demand workspace (scatter records, partial-gradient rows) was reallocated since a cached graph was captured — e.g. by an
             # eval_step on a larger view: it holds the freed buffer's address.  Drop them all (and their pool); every view recaptures.
             cache.clear()
             self.__dict__.pop('_graph_pool', None)

@@ -52,8 +52,10 @@ extern "C" {
  *    version) — cnerf_tsdf_integrate / _finalize / _face_keep; topology report and hole filling (additive, same version) —
  *    cnerf_mesh_holes_workspace_bytes / _count / _emit and cnerf_mesh_topology / _loops; winding number and signed distance on the
  *    closest-point tree (additive, same version) — cnerf_mesh_winding_workspace_bytes / _build / _query and
- *    cnerf_mesh_bvh_signed_distance. */
-#define CNERF_ABI_VERSION 7
+ *    cnerf_mesh_bvh_signed_distance.
+ * 8: the scatter's ahead-of-time plan is gone — cnerf_grid_encode_backward_prepare / _needs_plan / _prepared (cnerf_grid_encode_backward is
+ *    the one call, on one stream) — and so is cnerf_grid_encode_forward_strided (cnerf_grid_encode_forward_ordered with CNERF_GRID_LEVEL_MAJOR). */
+#define CNERF_ABI_VERSION 8
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
 const char *cnerf_target_arch(void);
@@ -174,14 +176,10 @@ int cnerf_grid_encode_forward(const float *inputs, const void *embeddings, const
 /* Same, writing into a larger output buffer: outputs [L, out_level_stride, C] with out_level_stride >= B rows per level (0 = B);
  * the caller offsets `outputs` to the first row it wants written.  Lets several gathers (the coarse and the importance samples of
  * NeRFRenderer.run, renderer.py:327-363) fill one feature buffer, so that the coarse samples are not gathered a second time. */
-int cnerf_grid_encode_forward_strided(const float *inputs, const void *embeddings, const int32_t *offsets_host, void *outputs,
-                                      uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level, float S, uint32_t H,
-                                      void *dy_dx, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
-                                      uint32_t out_level_stride, void *stream);
-/* Same with the traversal of the sample list chosen by the caller (results are bit-identical either way; only the specialised
+/* ... and with the traversal of the sample list chosen by the caller (results are bit-identical either way; only the specialised
  * fp16 / D = 3 / C = 2 / linear kernel has two forms, every other configuration ignores it):
  *   CNERF_GRID_LEVEL_MAJOR  0  one level at a time per XCD (its table stays in that XCD's L2): right for samples spread over the volume
- *                              — the stratified samples of NeRFRenderer.run (renderer.py:317-325) — and the default of the entry points above;
+ *                              — the stratified samples of NeRFRenderer.run (renderer.py:317-325) — and what cnerf_grid_encode_forward takes;
  *   CNERF_GRID_SAMPLE_MAJOR 1  all levels of a tile of consecutive samples per workgroup: right when neighbours of the list are neighbours
  *                              in space — the importance samples (renderer.py:340-352) of a field that has a surface. */
 #define CNERF_GRID_LEVEL_MAJOR 0
@@ -204,27 +202,6 @@ int cnerf_grid_encode_backward(const void *grad, const float *inputs, const int3
                                uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level, float S, uint32_t H,
                                const void *dy_dx, float *grad_inputs, uint32_t gridtype, int align_corners,
                                uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes, void *stream);
-/* Two-phase form of the binned backward, for the shapes that take its FIRST form (cnerf_grid_encode_backward_needs_plan = 1): that form
- * counts its records per table chunk in a histogram pass over the sample coordinates before it emits them.  _prepare runs that
- * coordinate-only part (histogram + scans) into `workspace` — issue it early, on a second stream, and it overlaps the forward pass and the
- * field backward; *prepared tells whether it launched anything (0: nothing was launched — the shape takes the atomic kernel, or the third
- * form, which counts inside its emit kernel — use cnerf_grid_encode_backward).  _prepared then runs the gradient-dependent part (record
- * emit + LDS accumulation) and must see the same inputs, shape and workspace, after _prepare's work has completed (event / stream order is
- * the caller's). */
-int cnerf_grid_encode_backward_prepare(const float *inputs, const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
-                                       uint32_t max_level, float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp,
-                                       int dtype, void *workspace, uint64_t workspace_bytes, int *prepared, void *stream);
-/* *needs_plan = 1 when cnerf_grid_encode_backward of this shape takes the first form: float32 records, and float16 records on a table the
- * third form does not take (a hashed level whose size is not a power of two, or is below 32 entries).  0 when there is nothing to prepare —
- * the atomic kernel, or the third form (float16 records, hash and tiled grids of up to 512 bins per level: the benchmark table and the
- * reference field's own T = 2^21 table).  _prepare reports *prepared = 0 for such shapes; this query lets a caller skip it (and its
- * workspace) altogether. */
-int cnerf_grid_encode_backward_needs_plan(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level, float S,
-                                          uint32_t H, uint32_t gridtype, int dtype, int *needs_plan);
-int cnerf_grid_encode_backward_prepared(const void *grad, const float *inputs, const int32_t *offsets_host, float *grad_embeddings,
-                                        uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level, float S, uint32_t H,
-                                        uint32_t gridtype, int align_corners, uint32_t interp, int dtype, void *workspace,
-                                        uint64_t workspace_bytes, void *stream);
 /* *bytes = scratch size the binned scatter wants for this problem (0: the atomic path will be used). */
 int cnerf_grid_encode_backward_workspace_bytes(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                                                uint32_t max_level, float S, uint32_t H, int dtype, uint64_t *bytes);

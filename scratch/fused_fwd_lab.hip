@@ -13,9 +13,7 @@
 
 bool bn_eligible(uint32_t, uint32_t, uint32_t, uint32_t, const GridLevels &) { return false; }
 uint64_t bn_workspace_bytes(uint32_t, uint32_t, const GridLevels &, int) { return 0; }
-int bn_backward(const void *, const float *, const GridLevels &, float *, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t, bool) { return -1; }
-int bn_prepare(const float *, const GridLevels &, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t) { return -1; }
-bool bn_needs_plan(uint32_t, uint32_t, const GridLevels &, int, uint32_t) { return false; }
+int bn_backward(const void *, const float *, const GridLevels &, float *, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t) { return -1; }
 void bn_grid_adam_arm(const CnerfGridAdam *) {}
 int bn_grid_adam_consumed() { return 0; }
 float *g_cn_found_inf = nullptr;
@@ -215,7 +213,7 @@ int main() {
         float *d_in; CK(hipMalloc(&d_in, (size_t)B * 12)); CK(hipMemcpy(d_in, sc.unit.data(), (size_t)B * 12, hipMemcpyHostToDevice));
         __half *d_ref, *d_out; CK(hipMalloc(&d_ref, (size_t)L * B * 4)); CK(hipMalloc(&d_out, (size_t)L * B * 4));
         printf("---- %s samples, B = %u\n", fine ? "importance-like (draw order)" : "stratified coarse", B);
-        auto prod = [&] { cnerf_grid_encode_forward_strided(d_in, d_tab, offs.data(), d_ref, B, 3, 2, L, L, S, H, nullptr, 0, 0, 0, CNERF_F16, B, nullptr); };
+        auto prod = [&] { cnerf_grid_encode_forward_ordered(d_in, d_tab, offs.data(), d_ref, B, 3, 2, L, L, S, H, nullptr, 0, 0, 0, CNERF_F16, B, GE_TRAV_LEVEL, nullptr); };
         const float t_all = time_it(prod);
         printf("%-72s %7.1f us  (%.3f of 8 TB/s)\n", "production k_grid_fwd_fast (level-major, XCD-sliced)", t_all, (double)B * 588 / (t_all * 1e-6) / 8e12);
         prod(); CK(hipDeviceSynchronize());

@@ -13,8 +13,7 @@
 // the binned backward lives in another translation unit of the library: not needed here
 bool bn_eligible(uint32_t, uint32_t, uint32_t, uint32_t, const GridLevels &) { return false; }
 uint64_t bn_workspace_bytes(uint32_t, uint32_t, const GridLevels &, int) { return 0; }
-int bn_backward(const void *, const float *, const GridLevels &, float *, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t, bool) { return -1; }
-int bn_prepare(const float *, const GridLevels &, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t) { return -1; }
+int bn_backward(const void *, const float *, const GridLevels &, float *, uint32_t, uint32_t, uint32_t, int, uint32_t, int, void *, hipStream_t) { return -1; }
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 
@@ -422,7 +421,7 @@ int main(int argc, char **argv) {
         float *d_in; CK(hipMalloc(&d_in, (size_t)B * 12)); CK(hipMemcpy(d_in, sc.unit.data(), (size_t)B * 12, hipMemcpyHostToDevice));
         __half *d_ref, *d_out; CK(hipMalloc(&d_ref, (size_t)L * B * 4)); CK(hipMalloc(&d_out, (size_t)L * B * 4));
         printf("---- %s samples, B = %u\n", fine ? "importance-like (draw order)" : "stratified coarse", B);
-        auto prod = [&](uint32_t nl) { cnerf_grid_encode_forward_strided(d_in, d_tab, offs.data(), d_ref, B, 3, 2, L, nl, S, H, nullptr, 0, 0, 0, CNERF_F16, B, nullptr); };
+        auto prod = [&](uint32_t nl) { cnerf_grid_encode_forward_ordered(d_in, d_tab, offs.data(), d_ref, B, 3, 2, L, nl, S, H, nullptr, 0, 0, 0, CNERF_F16, B, GE_TRAV_LEVEL, nullptr); };
         const float t_all = time_it([&] { prod(16); });
         printf("production k_grid_fwd_fast, 16 levels: %7.1f us  (%.2f of 8 TB/s)\n", t_all, (double)B * 588 / (t_all * 1e-6) / 8e12);
         for (uint32_t nl : {5u, 3u, 2u}) printf("production, levels 0..%u only:           %7.1f us\n", nl - 1, time_it([&] { prod(nl); }));

@@ -226,66 +226,41 @@ def test_backward_binned_no_atomics(name, kw, half):
         assert torch.equal(gc, gd)
 
 
-def test_backward_plan_prepared_ahead():
-    """cnerf_grid_encode_backward_prepare, then _prepared, on one stream.  float32 records take the first form, whose histogram + scans
-    _prepare issues before the gradients exist: the result must agree with the one-shot cnerf_grid_encode_backward and with the oracle.
-    float16 records on the benchmark table take the third form, which counts inside its emit kernel: _prepare reports prepared = 0 and
-    leaves the workspace untouched."""
-    from customnerf_amd._lib import lib, ptr, stream, check
-    import ctypes
+def test_attach_backward_first_form_f32():
+    """encode_into + attach_backward on a float32 table above the binned threshold (B x L >= 2^20): float32 records take the first form of the
+    binned scatter.  Into a fresh gradient, and in place into a pre-filled .grad (grad_in_place), it must agree with _grid_encode's backward on
+    the same inputs and with the oracle.  (float32 LDS adds depend on the order of the records: a tolerance, not a bit test.)"""
+    from customnerf_amd.gridencoder import grid as G
     enc = build(CONFIGS[0][1])
     L, C = enc.num_levels, enc.level_dim
-    S, H = float(np.log2(enc.per_level_scale)), enc.base_resolution
-    off, gid, ac, iid = enc._offsets_host.ctypes.data, enc.gridtype_id, int(enc.align_corners), enc.interp_id
-
-    def needs_plan(B, half):
-        n = ctypes.c_int(7)
-        check(lib.cnerf_grid_encode_backward_needs_plan(off, B, 3, C, L, L, S, H, gid, int(half), ctypes.addressof(n)))
-        return n.value
-
-    def workspace(B, half):
-        need = ctypes.c_uint64(0)
-        check(lib.cnerf_grid_encode_backward_workspace_bytes(off, B, 3, C, L, L, S, H, int(half), ctypes.addressof(need)))
-        assert need.value > 0
-        return torch.empty(int(need.value) + 256, dtype=torch.uint8, device='cuda')
-
-    def prepare(x, B, half, ws):
-        ok = ctypes.c_int(7)
-        check(lib.cnerf_grid_encode_backward_prepare(ptr(x), off, B, 3, C, L, L, S, H, gid, ac, iid, int(half), ptr(ws), ws.numel(),
-                                                     ctypes.addressof(ok), stream()))
-        return ok.value
-
-    # float32 records: the first form, planned ahead
     B = 70001
-    assert needs_plan(B, False) == 1
     xn = make_inputs(B, 3, seed=41)
     xn[100:200] = xn[50]
     g = np.random.default_rng(42).standard_normal((B, L * C)).astype(np.float32)
-    ge_ref, _ = co.grid_encode_backward(g, xn, tuple(enc.embeddings.shape), enc._offsets_host, enc.per_level_scale, H, None, gid,
-                                        enc.align_corners, iid)
+    ge_ref, _ = co.grid_encode_backward(g, xn, tuple(enc.embeddings.shape), enc._offsets_host, enc.per_level_scale, enc.base_resolution, None,
+                                        enc.gridtype_id, enc.align_corners, enc.interp_id)
     x = cuda(xn)
     glbc = cuda(g).view(B, L, C).permute(1, 0, 2).contiguous()
-    ws = workspace(B, False)
-    assert prepare(x, B, False, ws) == 1
-    ga = torch.zeros(enc.embeddings.shape, device='cuda')
-    check(lib.cnerf_grid_encode_backward_prepared(ptr(glbc), ptr(x), off, ptr(ga), B, 3, C, L, L, S, H, gid, ac, iid, 0, ptr(ws), ws.numel(),
-                                                  stream()))
-    gb = torch.zeros(enc.embeddings.shape, device='cuda')
-    check(lib.cnerf_grid_encode_backward(ptr(glbc), ptr(x), off, ptr(gb), B, 3, C, L, L, S, H, None, None, gid, ac, iid, 0, ptr(ws), ws.numel(),
-                                         stream()))
-    a = ga.cpu().numpy()
-    np.testing.assert_allclose(a, gb.cpu().numpy(), rtol=1e-4, atol=1e-3)
-    np.testing.assert_allclose(a, ge_ref, rtol=1e-4, atol=1e-3)
-    assert np.abs(a).max() > 1.0
-    # float16 records on the benchmark table (16384 rays x 128 samples): the third form, nothing to prepare
-    B = 1 << 21
-    assert needs_plan(B, True) == 0
-    x = torch.rand(B, 3, device='cuda')
-    ws = workspace(B, True)
-    ws.fill_(0xA5)
-    assert prepare(x, B, True, ws) == 0
-    lo, hi = torch.aminmax(ws)
-    assert int(lo) == int(hi) == 0xA5
+    S = float(np.log2(enc.per_level_scale))
+    assert G._bwd_workspace(enc._offsets_host, B, 3, C, L, L, S, enc.base_resolution, 0, x.device)[1] > 0       # the binned path, not the atomic kernel
+    out = G._grid_encode.apply(x, enc.embeddings, enc.embeddings.detach(), enc._offsets_host, enc.per_level_scale, enc.base_resolution, False,
+                               enc.gridtype_id, enc.align_corners, enc.interp_id, None)
+    out.backward(glbc)
+    want = enc.embeddings.grad.cpu().numpy()
+    assert np.abs(want).max() > 1.0
+    buf = torch.empty(L, B, C, device='cuda')
+    enc.encode_into(x, buf, 0, half=False)
+    assert torch.equal(buf, out.detach())
+    enc.embeddings.grad = None
+    enc.attach_backward(buf, x).backward(glbc)
+    fresh = enc.embeddings.grad.cpu().numpy()
+    enc.grad_in_place = True
+    enc.embeddings.grad = tgt = torch.full(enc.embeddings.shape, 0.5, device='cuda')
+    enc.attach_backward(buf, x).backward(glbc)
+    assert enc.embeddings.grad is tgt                                   # accumulated into the buffer it was given
+    for got in (fresh, tgt.cpu().numpy() - 0.5):
+        np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-3)
+        np.testing.assert_allclose(got, ge_ref, rtol=1e-4, atol=1e-3)
 
 
 def test_scatter_skips_zero_rows_and_recomputes_overflowing_bins():

@@ -779,7 +779,7 @@ def test_graphed_step_owns_its_buffers():
     tcnn.set_default_dtype(torch.float16)
     from customnerf_amd import field as fld
     from customnerf_amd.gridencoder import grid as ge
-    ge._WS_CACHE.clear(); ge._SIDE.clear(); fld._WS.clear()              # earlier tests of the session may have left large workspaces: (2) needs a real growth
+    ge._WS_CACHE.clear(); fld._WS.clear()              # earlier tests of the session may have left large workspaces: (2) needs a real growth
     H = W = 16
     V = 70
 

@@ -114,7 +114,7 @@ def test_recon_training_is_independent_of_recycled_memory():
         from customnerf_amd.gridencoder import grid as ge
         from customnerf_amd import field as fld
         if poison:
-            ge._WS_CACHE.clear(); ge._SIDE.clear(); fld._WS.clear()      # the cached workspaces too: they are re-allocated from the poisoned pools
+            ge._WS_CACHE.clear(); fld._WS.clear()      # the cached workspaces too: they are re-allocated from the poisoned pools
             poison_allocator(8.0)
         torch.manual_seed(0)
         opt = sc.make_opt(fp16=True, **grid_kw)

@@ -204,7 +204,7 @@ def test_argument_validation_without_launch():
 def test_abi_and_python_surface():
     from customnerf_amd import _lib, mesh
     from customnerf_amd.nerf.renderer import NeRFRenderer
-    assert _lib.ABI_VERSION == 7 and _lib.lib.cnerf_abi_version() == 7
+    assert _lib.ABI_VERSION == 8 and _lib.lib.cnerf_abi_version() == 8
     for name in ("cnerf_mesh_bvh_workspace_bytes", "cnerf_mesh_bvh_build", "cnerf_mesh_bvh_closest", "cnerf_mesh_sample_workspace_bytes",
                  "cnerf_mesh_sample_count", "cnerf_mesh_sample_emit"):
         assert name in _lib.SIGNATURES and hasattr(_lib.lib, name)

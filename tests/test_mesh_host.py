@@ -161,7 +161,7 @@ def test_abi_declared_and_bound():
     for name in ("cnerf_marching_cubes_workspace_bytes", "cnerf_marching_cubes_count", "cnerf_marching_cubes_emit"):
         assert re.search(r"\bint " + name + r"\(", src), name
         assert name in _lib.SIGNATURES
-    assert _lib.ABI_VERSION == 7 and _lib.lib.cnerf_abi_version() == 7
+    assert _lib.ABI_VERSION == 8 and _lib.lib.cnerf_abi_version() == 8
 
 
 def test_workspace_bytes():

@@ -181,7 +181,7 @@ def test_argument_validation_without_launch():
 def test_abi_version_and_python_surface():
     from customnerf_amd import _lib, mesh
     from customnerf_amd.nerf.renderer import NeRFRenderer
-    assert _lib.ABI_VERSION == 7 and _lib.lib.cnerf_abi_version() == 7
+    assert _lib.ABI_VERSION == 8 and _lib.lib.cnerf_abi_version() == 8
     assert mesh.raster_workspace_bytes(10, 20, 30, 40) >= 8 * 30 * 40 + 16 * 10 + 20 * 20
     assert callable(mesh.rasterize) and callable(mesh.render_mesh) and callable(NeRFRenderer.render_mesh)
     with pytest.raises(ValueError):

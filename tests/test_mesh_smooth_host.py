@@ -28,7 +28,7 @@ def test_symbols_declared_bound_exported():
         assert re.search(r"\bint " + name + r"\(", src), name
         assert name in _lib.SIGNATURES
         assert hasattr(_lib.lib, name)
-    assert _lib.ABI_VERSION == 7 and _lib.lib.cnerf_abi_version() == 7
+    assert _lib.ABI_VERSION == 8 and _lib.lib.cnerf_abi_version() == 8
 
 
 def test_workspace_bytes_grows():

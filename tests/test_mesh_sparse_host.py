@@ -24,7 +24,7 @@ def test_abi_declared_bound_and_exported():
     for name in NAMES:
         assert re.search(r"\bint " + name + r"\(", src), name
         assert name in _lib.SIGNATURES and hasattr(_lib.lib, name)
-    assert _lib.ABI_VERSION == 7 and _lib.lib.cnerf_abi_version() == 7
+    assert _lib.ABI_VERSION == 8 and _lib.lib.cnerf_abi_version() == 8
 
 
 def test_workspace_bytes():

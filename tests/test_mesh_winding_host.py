@@ -29,11 +29,11 @@ NAMES4 = ("cnerf_mesh_winding_workspace_bytes", "cnerf_mesh_winding_build", "cne
 
 def test_abi_names_and_version():
     from customnerf_amd import _lib
-    assert _lib.lib.cnerf_abi_version() == 7
+    assert _lib.lib.cnerf_abi_version() == 8
     header = open(os.path.join(HERE, "..", "include", "customnerf_hip.h")).read()
     for name in NAMES4:
         assert name in _lib.SIGNATURES and callable(getattr(_lib.lib, name)) and f"int {name}(" in header
-    assert "#define CNERF_ABI_VERSION 7" in header
+    assert "#define CNERF_ABI_VERSION 8" in header
 
 
 def test_return_codes_before_any_launch():

@@ -71,22 +71,17 @@ def test_two_keys_are_independent():
     assert list(c) == ["b"]
 
 
-def _side_ws(grid):
-    return grid._side_entry(None)['ws']          # the per-stream plan workspace lives inside its _SIDE entry
-
-
 # (module, how to reach the cache) -> (factor, pad, floor, dtype, shrink, retire)
 CACHES = [
     ("customnerf_amd.field", lambda m: m._WS, (1.1, 256, 0, torch.uint8, None, False)),
     ("customnerf_amd.mlp", lambda m: m._WS, (1.1, 256, 0, torch.uint8, None, False)),
     ("customnerf_amd.gridencoder.grid", lambda m: m._WS_CACHE, (1.25, 256, 0, torch.uint8, None, False)),
-    ("customnerf_amd.gridencoder.grid", _side_ws, (1.25, 256, 0, torch.uint8, None, False)),
     ("customnerf_amd.raymarching.raymarching", lambda m: m._HITS, (1, 0, 0, torch.float32, 4, False)),
     ("customnerf_amd.sd.ops", lambda m: m._WS, (1, 0, 64 << 20, torch.uint8, None, True)),
 ]
 
 
-@pytest.mark.parametrize("module,get,want", CACHES, ids=["field", "mlp", "grid", "grid_side", "hits", "sd_ops"])
+@pytest.mark.parametrize("module,get,want", CACHES, ids=["field", "mlp", "grid", "hits", "sd_ops"])
 def test_module_caches_carry_their_parameters(module, get, want):
     mod = importlib.import_module(module)
     c = get(mod)
