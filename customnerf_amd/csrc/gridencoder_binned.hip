@@ -366,6 +366,8 @@ __global__ void __launch_bounds__(1024) k_bin_accum(const BinRec<T> *__restrict_
 // the per-corner products are rounded to that grid instead of to binary16 (the reference rounds w*g to half, gridencoder.cu:328: the
 // difference is below one half ulp of each product).
 #define B3_SINGLE 15u                              // pair shift t of a single record (one corner)
+#define B3_ABL_CELL 14u                            // tuning builds only: stand-in record of the cell-record ablation (a pair shift is at most 11)
+#define B3_ABL_TAIL 13u                            // and the slot that stands for the second half of a 16-byte record: loaded, then ignored
 
 
 // the four (y, z) corner pairs of a sample on one level: entries of the x and x+1 corner, the weight of the pair, the x fraction
@@ -442,6 +444,20 @@ __device__ __forceinline__ uint32_t b3_ticket(uint32_t *counters, uint32_t c) {
     }
     return atomicAdd(&counters[c], 1u);
 }
+#ifdef CNERF_TUNING
+// (cell-record ablation of k_bin3_emit: one ticket for n consecutive slots)
+__device__ __forceinline__ uint32_t b3_ticket_n(uint32_t *counters, uint32_t c, uint32_t n) {
+    const uint64_t act = __ballot(1);
+    const uint32_t c_lead = __builtin_amdgcn_readfirstlane(c);
+    if (__ballot(c == c_lead) == act) {
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+        uint32_t base = 0;
+        if (rank == 0) base = atomicAdd(&counters[c_lead], (uint32_t)__popcll(act) * n);
+        return __builtin_amdgcn_readfirstlane(base) + rank * n;
+    }
+    return atomicAdd(&counters[c], n);
+}
+#endif
 
 // The fixed-point sums cannot carry an infinity or a NaN (llrint of one is an arbitrary finite pattern), but the loss scaler finds overflow by
 // looking for exactly those in the gradients (the reference's half2 atomics propagate them: gridencoder.cu:324-337).  A non-finite incoming
@@ -496,6 +512,21 @@ struct B3Pending { uint32_t key; unsigned long long a0, b0, a1, b1; };   // key 
 __device__ __forceinline__ void b3_flush_pending(long long *acc, const B3Pending &c) {
     if (c.key == 0xFFFFFFFFu) return;
     const uint32_t e = c.key & (BN_CHUNK - 1), t = (c.key >> 12) & 15u;
+#ifdef CNERF_TUNING
+    // the stand-in record of the cell-record ablation (CNERF_B3_EMIT_ABL 128 / 256, results wrong) pays the LDS updates of the four pair
+    // records it replaces: four x-pairs at the (y, z) offsets of a 17-line level, wrapped into the image
+    if (t == B3_ABL_CELL) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t ek = (e + (k & 1u) * 289u + (k >> 1) * 17u) & (BN_CHUNK - 1), ek1 = ek ^ 1u;
+            atomicAdd(reinterpret_cast<unsigned long long *>(&acc[ek]), c.a0);
+            atomicAdd(reinterpret_cast<unsigned long long *>(&acc[BN_CHUNK + ek]), c.b0);
+            atomicAdd(reinterpret_cast<unsigned long long *>(&acc[ek1]), c.a1);
+            atomicAdd(reinterpret_cast<unsigned long long *>(&acc[BN_CHUNK + ek1]), c.b1);
+        }
+        return;
+    }
+#endif
     atomicAdd(reinterpret_cast<unsigned long long *>(&acc[e]), c.a0);
     atomicAdd(reinterpret_cast<unsigned long long *>(&acc[BN_CHUNK + e]), c.b0);
     if (t != B3_SINGLE) {
@@ -509,6 +540,9 @@ __device__ __forceinline__ void b3_push_record(long long *acc, B3Pending &c, con
     v.u = r.y;
     const float2 f = __half22float2(v.h);
     const uint32_t key = r.x & 0xFFFFu, t = (r.x >> 12) & 15u;
+#ifdef CNERF_TUNING
+    if (t == B3_ABL_TAIL) return;                                                   // (the pending sums stay: the next stand-in of the same cell still combines)
+#endif
     unsigned long long a0, b0, a1 = 0, b1 = 0;
     if (t == B3_SINGLE) {
         a0 = b3_fix(f.x * 16777216.0f); b0 = b3_fix(f.y * 16777216.0f);
@@ -536,6 +570,8 @@ __device__ __forceinline__ void b3_push_record(long long *acc, B3Pending &c, con
 //   k_bin3_emit   a block (2048 points of one level) derives its corner pairs ONCE, takes an LDS ticket per record against per-bin counters
 //                 that start at zero, scans the 128 counters (the block's own histogram) and sorts the records by bin into the LDS staging area.
 //                 Samples whose gradient is exactly zero on this level emit nothing (they add exactly zero to every fixed-point sum).
+//                 A sample of a dense level of at most 64 bins whose eight corners share a bin takes ONE ticket for its four records
+//                 (b3_emit<true>: the second counter class, see there; k_bin3_emit holds the body with and without it).
 //     hashed levels (interleaved bins, loads near-uniform): every bin owns a slab region of fixed capacity (1.5 x its expected load); the block
 //                 reserves its run in each bin with ONE returning atomic per (block, bin) on the bin's cursor — issued right after the scan,
 //                 consumed at copy-out — and copies its runs there: bin-major, densely packed, exactly the layout the accumulate kernel streams.
@@ -606,13 +642,19 @@ __device__ __forceinline__ bool b3_paired_h(uint32_t i0, uint32_t i1) {
     return m != 0 && m < (1u << B3_K) && (m & (m + 1)) == 0;
 }
 
-__global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3_emit(const __half *__restrict__ grad, const float *__restrict__ inputs, const GridLevels lv,
+template <bool TWO>
+__device__ __forceinline__ void b3_emit(const __half *__restrict__ grad, const float *__restrict__ inputs, const GridLevels lv,
                                                           const Bin3Plan plan, uint32_t *__restrict__ runs, uint32_t *__restrict__ cursor,
                                                           uint2 *__restrict__ hslab, uint2 *__restrict__ dslab, uint32_t B,
                                                           uint32_t gridtype, int align_corners, uint32_t interp, float *__restrict__ grad_grid, uint32_t n_slots,
                                                           uint32_t abl_arg, float *__restrict__ found_inf) {
 #ifdef CNERF_TUNING
     const uint32_t abl = abl_arg;                  // timing aid (results wrong): 1 no reservations, 2 no copy-out, 4 no phase 2, 8 no run-table stores, 16 no tickets, 32 no corner arithmetic, 64 no loads
+    // 128 / 256: the ceiling of a 16-byte CELL record (docs/HISTORY.md B.7 (iv)) — on a dense narrow level of at most 64 bins a sample whose
+    // eight corners share a bin takes ONE ticket and leaves as one stand-in record (128: the least such a record could cost) or as a
+    // stand-in and a tail slot (256: the slots, bytes and records per accumulate thread of a 16-byte record); the accumulate still pays
+    // the sample's sixteen LDS updates, combined in registers over consecutive stand-ins of one cell (b3_flush_pending, b3_push_record)
+    bool cell[B3_PTS / B3_THREADS];
 #else
     constexpr uint32_t abl = 0;
     (void)abl_arg;
@@ -641,11 +683,25 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
     auto bin_of = [&](uint32_t e) { return dense_lvl ? e >> BN_CHUNK_LOG2 : b3_bin_of(e, hb); };
     auto local_of = [&](uint32_t e) { return dense_lvl ? e & (BN_CHUNK - 1) : b3_local_of(e, hb); };
     auto paired = [&](uint32_t a, uint32_t b) { return dense_lvl ? b3_paired_d(a, b) : b3_paired_h(a, b); };
+    // A dense level of at most 64 bins keeps TWO counters per bin: 64 + c counts the SAMPLES whose eight corners all lie in bin c (every cell but
+    // those that straddle a bin border; with align_corners also not the cells whose boundary corner wraps) — such a sample takes ONE ticket
+    // for its four pair records — and c counts records, one ticket each, as everywhere else.  With n such samples in the block, the
+    // record of pair q of the sample with ticket r goes to slot q n + r of the bin's run and the ticketed records follow at 4 n: still one
+    // run per (bin, block) for the accumulate, and pair-major across the WHOLE block — corners are shared between neighbouring cells (the
+    // q = 1 entry of one cell is the q = 0 entry of the next), so a stretch of the run that mixes the pairs of neighbouring samples has the
+    // lanes of one accumulate instruction meet on the same LDS address (pair-major per wave, measured: docs/HISTORY.md B.31).
+    // The class is a COMPILE-TIME property of the body: k_bin3_emit holds the body twice and a workgroup takes the one of its level.  With the
+    // class as a run-time flag of one body, every other level paid for it in code generation (emit +10 us on a fitted field, +14-22 us on the
+    // bear table, also with the flag never set: docs/HISTORY.md B.31).
+    constexpr bool two_class = TWO;
+    if (TWO) __builtin_assume(dense_lvl && nch <= B3_NARROW_CHUNKS / 2);
     if (threadIdx.x < NBN) cnt[threadIdx.x] = 0;
     __syncthreads();
     constexpr int PPT = B3_PTS / B3_THREADS;
     bool ok[PPT];
     uint32_t i0[PPT][4], i1[PPT][4], tk[PPT][4];
+    // (the highest corner is the last to leave the bin, and a wrapped one lies below the lowest)
+    auto one_ticket = [&](int i) { return two_class && !(abl & (16u | 32u | 384u)) && i1[i][3] > i0[i][0] && bin_of(i1[i][3]) == bin_of(i0[i][0]); };
     float wyz[PPT][4], fx[PPT], g0[PPT], g1[PPT];
     // ---- phase 1: corner pairs, gradients, one LDS ticket per record (ticket = rank of the record inside the block's run for its bin)
     // every load of the thread's samples first, unconditionally (clamped row): the coordinates and the gradient of a sample are independent
@@ -675,6 +731,17 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
                 b3_pairs(in, lv, level, gridtype, align_corners, interp, i0[i], i1[i], wyz[i], fx[i]);
             }
             b3_poison(g0[i], g1[i], grad_grid, lv, level, i0[i][0], found_inf);
+#ifdef CNERF_TUNING
+            cell[i] = (abl & 384u) && dense_lvl && nch <= 64 && i1[i][3] > i0[i][0] && bin_of(i1[i][3]) == bin_of(i0[i][0]);
+            if (cell[i]) {
+                tk[i][0] = (abl & 16) ? 0u : b3_ticket_n(cnt, bin_of(i0[i][0]), (abl & 256u) ? 2u : 1u);
+                continue;
+            }
+#endif
+            if (one_ticket(i)) {
+                tk[i][0] = b3_ticket(cnt, B3_NARROW_CHUNKS / 2 + bin_of(i0[i][0]));
+                continue;
+            }
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 if (abl & 16) { tk[i][q] = 0; continue; }
@@ -740,10 +807,21 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
         // 128 counters: lane l takes the bins 2 l and 2 l + 1 (run starts in bin order); their two reservations are ONE 64-bit returning atomic
         // when the pair is aligned (round 6: the memory-side atomic unit is the resource, A.1 item 1 — 1.4 M reservations per step become 0.7 M)
         const uint32_t lane = threadIdx.x;
-        const uint32_t ca = cnt[2 * lane], cb = cnt[2 * lane + 1];
-        const uint32_t incl = cn_wave_incl_scan(ca + cb);
-        const uint32_t oa = incl - (ca + cb), ob = oa + ca;
-        start[2 * lane] = oa; start[2 * lane + 1] = ob;
+        uint32_t ca = cnt[2 * lane], cb = cnt[2 * lane + 1], sa = 0, sb = 0;                 // records; two classes: + four per counted sample, in front of them
+        if (two_class) {
+            constexpr uint32_t H = B3_NARROW_CHUNKS / 2;
+            if (lane < H / 2) { sa = 4u * cnt[H + 2 * lane]; sb = 4u * cnt[H + 2 * lane + 1]; }
+            else ca = cb = 0;                                                          // (the upper half of the counters are the sample counts)
+        }
+        const uint32_t incl = cn_wave_incl_scan(sa + ca + sb + cb);
+        const uint32_t oa = incl - (sa + ca + sb + cb), ob = oa + sa + ca;
+        if (two_class) {
+            constexpr uint32_t H = B3_NARROW_CHUNKS / 2;
+            if (lane < H / 2) { start[H + 2 * lane] = oa; start[2 * lane] = oa + sa; start[H + 2 * lane + 1] = ob; start[2 * lane + 1] = ob + sb; }
+        } else {
+            start[2 * lane] = oa; start[2 * lane + 1] = ob;
+        }
+        ca += sa; cb += sb;
         if (lane == 63) *s_total = incl;
         if (dense_lvl) {
             if (2 * lane < nch && !(abl & 8)) runs[(size_t)(bin0 + 2 * lane) * nb + pb] = ca | (oa << 16);
@@ -782,6 +860,24 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
             if (sl < B3_CAP) { s_rec[sl] = make_uint2(word, val); if (!wide) s_bin[sl] = (uint8_t)c; }
             else region[sl] = make_uint2(word, val);                                // beyond the staging capacity: straight into the block's region
         };
+#ifdef CNERF_TUNING
+        if (cell[i]) {                                                              // (abl 128 / 256: the stand-in records carry the first pair's value)
+            v.h = __floats2half2_rn(wyz[i][0] * g0[i], wyz[i][0] * g1[i]);
+            put(bin_of(i0[i][0]), tk[i][0], local_of(i0[i][0]) | (B3_ABL_CELL << 12) | (fxq << 16), v.u);
+            if (abl & 256u) put(bin_of(i0[i][0]), tk[i][0] + 1, local_of(i0[i][0]) | (B3_ABL_TAIL << 12) | (fxq << 16), v.u);
+            continue;
+        }
+#endif
+        if (one_ticket(i)) {
+            const uint32_t c = B3_NARROW_CHUNKS / 2 + bin_of(i0[i][0]), n = cnt[c];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint32_t t = 31u - (uint32_t)__clz((int)(i0[i][q] ^ i1[i][q]));
+                v.h = __floats2half2_rn(wyz[i][q] * g0[i], wyz[i][q] * g1[i]);
+                put(c, tk[i][0] + (uint32_t)q * n, local_of(i0[i][q]) | (t << 12) | (fxq << 16), v.u);
+            }
+            continue;
+        }
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const uint32_t a0 = i0[i][q], a1 = i1[i][q];
@@ -859,6 +955,18 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
             else region[sl] = s_rec[sl];
         }
     }
+}
+
+__global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3_emit(const __half *__restrict__ grad, const float *__restrict__ inputs, const GridLevels lv,
+                                                          const Bin3Plan plan, uint32_t *__restrict__ runs, uint32_t *__restrict__ cursor,
+                                                          uint2 *__restrict__ hslab, uint2 *__restrict__ dslab, uint32_t B,
+                                                          uint32_t gridtype, int align_corners, uint32_t interp, float *__restrict__ grad_grid, uint32_t n_slots,
+                                                          uint32_t abl_arg, float *__restrict__ found_inf) {
+    const uint32_t slot = blockIdx.x % n_slots;                                     // (as in the body: level fastest)
+    if (plan.dense_slot[slot] != 0xFFFFFFFFu && plan.p.bin_first[slot + 1] - plan.p.bin_first[slot] <= B3_NARROW_CHUNKS / 2)
+        b3_emit<true>(grad, inputs, lv, plan, runs, cursor, hslab, dslab, B, gridtype, align_corners, interp, grad_grid, n_slots, abl_arg, found_inf);
+    else
+        b3_emit<false>(grad, inputs, lv, plan, runs, cursor, hslab, dslab, B, gridtype, align_corners, interp, grad_grid, n_slots, abl_arg, found_inf);
 }
 
 // per bin: dense level — exclusive prefix of the run counts (low half of the run-table words) over the point blocks -> pre, and the bin total;
@@ -1394,6 +1502,8 @@ static uint64_t b3_layout(const Bin3Plan &plan, uint32_t n_dense, uint32_t B, ui
     const uint64_t o_adamc = off; off = bn_align(off + 16);                                   // B3AdamConst of this backward pass (k_bin_scan_bins)    // count + the bins that were split (k_bin_scan_bins -> k_bin3_reduce_split)
     const uint64_t h_records = (uint64_t)ps.total_bins * plan.capb;               // bin-major regions (the dense levels' bins leave theirs unused)
     const uint64_t d_records = (uint64_t)nl * ps.nb * B3_REGION;                   // the point blocks' private regions: every record of a dense level, the spill of a hashed one
+    // (b3_emit<true>'s one-ticket samples change neither: their four slots hold the same four pair records, so a block still emits at most
+    // 8 records per sample on a level — B3_REGION — and the staging capacity B3_CAP serves the same record counts as before)
     (void)n_dense;
     const uint64_t o_h = off; off = bn_align(off + h_records * 8);
     const uint64_t o_d = off; off = bn_align(off + d_records * 8);
@@ -1471,8 +1581,13 @@ static int b3_backward(const __half *grad, const float *inputs, const GridLevels
     ad.cst = ws.adam_const;
     hipLaunchKernelGGL(k_bin3_zero, dim3(cn_div_up(ps.total_bins, 256)), dim3(256), 0, st, ws.cursor, ps.total_bins);    // (a kernel, not a memset node: hipGraph capture)
     cn_stage(0, st);
+    uint32_t emit_abl = (uint32_t)cn_tune_env("CNERF_B3_EMIT_ABL", 0);
+#ifdef CNERF_TUNING
+    static int abl_calls = 0;                                                   // tuning builds: the mask holds from this call on (a field fitted with right gradients first)
+    if (abl_calls++ < cn_tune_env("CNERF_B3_EMIT_ABL_AFTER", 0)) emit_abl = 0;
+#endif
     hipLaunchKernelGGL(k_bin3_emit, dim3(ps.nb * nl), dim3(B3_THREADS), emit_lds, st, grad, inputs, lv, plan, ws.runs, ws.cursor, ws.hslab, ws.dslab, B, gridtype, ac,
-                       interp, gemb, nl, (uint32_t)cn_tune_env("CNERF_B3_EMIT_ABL", 0), g_cn_found_inf);
+                       interp, gemb, nl, emit_abl, g_cn_found_inf);
     cn_stage(1, st);
     hipLaunchKernelGGL(k_bin3_totals, dim3(ps.total_bins), dim3(BN_SCAN_THREADS), 0, st, (const uint32_t *)ws.runs, ws.pre, (const uint32_t *)ws.cursor, ws.bin_base,
                        plan, nl);
