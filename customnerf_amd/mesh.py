@@ -1920,6 +1920,55 @@ def write_png(path, image):
         fh.write(data)
 
 
+def write_apng(path, frames, fps=30, loop=0):
+    """Animated PNG (APNG 1.0) of 8-bit RGB frames written to `path`, standard library only: the one-file stand-in for a video that
+    browsers and image viewers open (a viewer that does not know APNG shows frame 0).  frames: a sequence of [H, W, 3] uint8 tensors
+    (any device) or arrays, or one [N, H, W, 3]; every frame is shown 1 / fps seconds; loop = 0 repeats for ever.  Layout: IHDR, acTL
+    (frame count, loop count), then fcTL + IDAT for frame 0 and fcTL + fdAT for every later one — full frames, no blending, filter 0 on
+    every row — with ONE running sequence number over the fcTL and fdAT chunks, then IEND.  A single frame is accepted.
+    ValueError: no frame, a frame that is not [H, W, 3] uint8 (floating-point frames are not converted here), frames of different
+    sizes, fps or loop out of range."""
+    if torch.is_tensor(frames) or isinstance(frames, np.ndarray):
+        frames = list(frames)
+    arrs = []
+    for i, f in enumerate(frames):
+        if (f.dtype != torch.uint8) if torch.is_tensor(f) else (np.asarray(f).dtype != np.uint8):
+            raise ValueError(f"write_apng: frame {i} must be uint8, got {f.dtype if hasattr(f, 'dtype') else type(f)}")
+        a = _host(f, np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] == 0 or a.shape[1] == 0:
+            raise ValueError(f"write_apng: frame {i} must be [H, W, 3] uint8, got {a.shape}")
+        if arrs and a.shape != arrs[0].shape:
+            raise ValueError(f"write_apng: frame {i} is {a.shape}, frame 0 is {arrs[0].shape}")
+        arrs.append(a)
+    if not arrs:
+        raise ValueError("write_apng: no frames")
+    fps, loop = int(fps), int(loop)
+    if not (1 <= fps <= 65535) or loop < 0:
+        raise ValueError(f"write_apng: fps must be in [1, 65535] and loop >= 0, got {fps}, {loop}")
+    H, W = arrs[0].shape[:2]
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+    out = [b"\x89PNG\r\n\x1a\n", chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)), chunk(b"acTL", struct.pack(">II", len(arrs), loop))]
+    seq = 0
+    for i, a in enumerate(arrs):
+        # fcTL: sequence, width, height, x and y offset, delay numerator / denominator (seconds), dispose_op 0 (none), blend_op 0 (source)
+        out.append(chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, W, H, 0, 0, 1, fps, 0, 0)))
+        seq += 1
+        raw = np.zeros((H, 1 + 3 * W), dtype=np.uint8)                          # a filter-type byte (0) in front of every row
+        raw[:, 1:] = a.reshape(H, 3 * W)
+        data = zlib.compress(raw.tobytes(), 6)
+        if i == 0:
+            out.append(chunk(b"IDAT", data))
+        else:
+            out.append(chunk(b"fdAT", struct.pack(">I", seq) + data))
+            seq += 1
+    out.append(chunk(b"IEND", b""))
+    with open(path, "wb") as fh:
+        fh.write(b"".join(out))
+
+
 def write_glb(path, positions, indices, normals=None, uvs=None, tangents=None, colors=None, texture=None, normal_map=None, unlit=None):
     """glTF 2.0 binary (.glb): one mesh with one indexed triangle primitive and one material, everything in one file; json, struct and
     zlib only.  positions [W, 3] float32, indices [F, 3] (any int type; written as UNSIGNED_INT), and per vertex, all optional: normals

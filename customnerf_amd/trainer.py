@@ -306,6 +306,117 @@ class EvalMixin:
                                   outputs['fg']['image'].reshape(B, H, W, 3).float(), outputs['bg']['image'].reshape(B, H, W, 3).float()], dim=2)
         return pred_rgb, pred_depth, direction
 
+    class _eval_mode:
+        """`with self._eval_mode(models):` — model.eval() for the duration of a loop (Trainer_Nerf.evaluate_one_epoch / test do the same and
+        never switch back; here whatever mode each model was in is restored)"""
+
+        def __init__(self, *models):
+            self.models = [m for m in models if m is not None]
+
+        def __enter__(self):
+            self.was = [m.training for m in self.models]
+            for m in self.models:
+                m.eval()
+
+        def __exit__(self, *exc):
+            for m, w in zip(self.models, self.was):
+                m.train(w)
+            return False
+
+    def evaluate(self, views, save_path=None, name=None, quantize=False, against=None):
+        """The loop around eval_step (Trainer_Nerf.evaluate / evaluate_one_epoch, utils_init_nerf.py:515-518, :673-779) with the scores the
+        reference never computes.  views: an indexable of view tuples (rgbs, mask, rays_o, rays_d, H, W, path) WITH images — a
+        NerfstudioScene of split 'val', say.  Per view: eval_step, then metrics.image_metrics(prediction, ground truth) -> 'mse', 'l1',
+        'psnr', 'ssim' (metrics.py defines them; quantize=True scores what 8-bit files of the two images hold); where the view has a mask
+        (not None), the same four over the masked foreground, 'fg_*', and over the rest (1 - mask), 'bg_*', with the counted pixel-channels
+        'fg_n_pixels' / 'bg_n_pixels'; under opt.train_conf 'mask_iou', the intersection over union of render_mask > 0.5 and the mask.
+
+        against=<another field> is the background-preservation report of an edit instead: nothing is compared with the photographs; both
+        `against` (the pretrained field) and self.model render the view's rays and the scores are between those two renders, so 'bg_psnr' /
+        'bg_ssim' say how well the edit left alone what it was told to leave alone (views without images will do, a mask is needed for the
+        fg / bg part).
+
+        -> {'views': [one dict of floats per view], 'mean': {key: mean over the views, nan entries — an empty mask — left out}}.
+        save_path: the panels (eval_step's, or `against | edited`) are written as <save_path>/<name>/<i:04d>.png (mesh.write_png,
+        floor(clamp(v, 0, 1) * 255)) and the returned dict as metrics.json beside them; name defaults to 'evaluate'."""
+        import json
+        import os
+        from . import metrics as M
+        from .mesh import write_png
+        name = name or 'evaluate'
+        if save_path is not None:
+            os.makedirs(os.path.join(save_path, name), exist_ok=True)
+        dev = next(self.model.parameters()).device
+        rows = []
+        with self._eval_mode(self.model, against):
+            for i in range(len(views)):
+                data = views[i]
+                rgbs, mask, rays_o, rays_d, H, W = data[:6]
+                row = {}
+                if against is None:
+                    if rgbs is None or mask is None:
+                        raise ValueError("evaluate: the views need images and masks (a 'val' or 'train' split), or pass against=")
+                    panel = self.eval_step(data)[0]
+                    ref, pred = panel[:, :, :W].contiguous(), panel[:, :, W:2 * W].contiguous()
+                    if getattr(self.opt, 'train_conf', 0):
+                        gt_m, pr_m = panel[:, :, 3 * W:4 * W, 0] > 0.5, panel[:, :, 4 * W:5 * W, 0] > 0.5
+                        union = (gt_m | pr_m).sum()
+                        row['mask_iou'] = (gt_m & pr_m).sum().double() / union.double()          # nan when both are empty
+                else:
+                    rays_o, rays_d = rays_o.to(dev), rays_d.to(dev)
+                    B = rays_o.shape[0]
+                    ref = self._render_eval(against, rays_o, rays_d)['image'].reshape(B, H, W, 3).float()
+                    pred = self._render_eval(self.model, rays_o, rays_d)['image'].reshape(B, H, W, 3).float()
+                    panel = torch.cat([ref, pred], dim=2)
+                regions = [('', None)]
+                if mask is not None:
+                    fg = (mask.to(dev).reshape(pred.shape[0], H, W) != 0).float()
+                    regions += [('fg_', fg), ('bg_', 1.0 - fg)]
+                for prefix, m in regions:
+                    r = M.image_metrics(pred, ref, mask=m, quantize=quantize)
+                    for k in ('mse', 'l1', 'psnr', 'ssim') + (('n_pixels',) if prefix else ()):
+                        row[prefix + k] = r[k].mean() if k != 'n_pixels' else r[k].sum()
+                rows.append(row)
+                if save_path is not None:
+                    write_png(os.path.join(save_path, name, f'{i:04d}.png'), M.to_uint8(panel[0]))
+        rows = [{k: float(v) for k, v in row.items()} for row in rows]                          # the host reads the scores only after the loop
+        mean = {}
+        for k in (rows[0] if rows else {}):
+            vals = [r[k] for r in rows if k in r and r[k] == r[k]]
+            mean[k] = sum(vals) / len(vals) if vals else float('nan')
+        out = {'views': rows, 'mean': mean}
+        if save_path is not None:
+            with open(os.path.join(save_path, name, 'metrics.json'), 'w') as fh:
+                json.dump(out, fh, indent=1)                                                    # (inf / nan as Python's json writes and reads them)
+        return out
+
+    def test(self, views, save_path, name=None, write_video=True, fps=30):
+        """The loop around test_step (Trainer_Nerf.test, utils_init_nerf.py:520-569): every view of `views` (a NerfstudioScene of split 'test',
+        say; images are not needed) is rendered and written as <save_path>/<name>/<i:03d>.png by the reference's truncation
+        floor(clamp(v, 0, 1) * 255) (:550; metrics.to_uint8 — what image_metrics(quantize=True) scores).  write_video: all frames also go
+        into ONE animated PNG, <save_path>/<name>_rgb.png, `fps` frames a second (mesh.write_apng).  The reference writes an MP4 through
+        imageio there; no MP4 encoder is part of this package, and an APNG is the one-file substitute that browsers open.
+        -> {'frames': [paths], 'video': path or None}.  name defaults to 'test'."""
+        import os
+        from . import metrics as M
+        from .mesh import write_apng, write_png
+        name = name or 'test'
+        os.makedirs(os.path.join(save_path, name), exist_ok=True)
+        frames, paths = [], []
+        with self._eval_mode(self.model):
+            for i in range(len(views)):
+                pred = self.test_step(views[i])[0]
+                frame = M.to_uint8(pred[0]).cpu()
+                paths.append(os.path.join(save_path, name, f'{i:03d}.png'))
+                write_png(paths[-1], frame)
+                if write_video:
+                    frames.append(frame)
+        video = None
+        if write_video and frames:
+            video = os.path.join(save_path, f'{name}_rgb.png')
+            write_apng(video, frames, fps=fps)
+        return {'frames': paths, 'video': video}
+
 
 class ReconTrainer(CheckpointMixin, EvalMixin):
     def __init__(self, model, opt, lr=None, fp16=False, world_size=1, fused_adam=True, loss_scale='dynamic', dp_mode='allreduce'):

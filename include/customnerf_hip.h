@@ -1262,6 +1262,39 @@ int cnerf_mesh_bvh_signed_distance(const void *bvh_ws, uint64_t bvh_bytes, uint3
                                    const float *points, uint32_t Q, float beta, float *signed_dist, int32_t *face, float *winding,
                                    uint64_t *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Image scores: squared error, absolute error and SSIM between two image batches in one pass (customnerf_amd/metrics.py image_metrics /
+ * psnr / ssim, the trainers' evaluate(); csrc/metrics.hip; additive, same ABI version).  The reference scores on the host
+ * (utils_init_nerf.py:673-779) and has no SSIM.
+ *   pred, target [B][H][W][C] channel-last, float32 or float16 (dtype), C in {1, 3}: the layout eval_step / test_step return.
+ *   mask NULL or float32 [B][H][W]: a pixel counts when its mask value is nonzero.
+ *   quantize != 0: both images first go through q(v) = floor(clamp(v, 0, 1) * 255) / 255, evaluated in float32 (float16 input is widened
+ *     first): the value an 8-bit file written by truncation holds (`(pred * 255).astype(np.uint8)`, utils_init_nerf.py:550, plus a clamp).
+ *   sums_out [B][5] float64 (device), per image:
+ *     [0] sum of (a - b)^2 and [1] sum of |a - b| over the counted pixels and all channels, [2] the number of counted pixel-channels,
+ *     [3] the sum of the SSIM map over the counted windows and all channels, [4] the number of counted window-channels.
+ *     mse = [0] / [2], l1 = [1] / [2], psnr = 10 log10(1 / mse), ssim = [3] / [4] are the caller's, in float64.  An image without counted
+ *     pixels has [2] = 0 (0 / 0 = nan there): a defined result, not an error.
+ *   SSIM, because libraries differ: Wang, Bovik, Sheikh and Simoncelli 2004 with L = 1, K1 = 0.01, K2 = 0.03 (C1 = K1 K1, C2 = K2 K2); an
+ *     11-tap Gaussian window of sigma 1.5, g[k] = exp(-(k - 5)^2 / 4.5) computed in float64 and divided by its sum, applied separably
+ *     (rows first) over the valid region only — the map is (H - 10) x (W - 10) per channel, no padding; population moments
+ *     mu_a = E[a], var_a = E[a a] - mu_a mu_a, cov = E[a b] - mu_a mu_b under that window;
+ *     map = ((2 mu_a mu_b + C1) (2 cov + C2)) / ((mu_a mu_a + mu_b mu_b + C1) (var_a + var_b + C2)), per channel.
+ *     Window (y, x) of the map covers pixels [y, y + 10] x [x, x + 10]; with a mask it counts when its centre pixel (y + 5, x + 5) does.
+ *     An image's SSIM is the mean of the map over the counted windows and the channels.
+ *   Numerics: the inputs convert to float64 exactly; the five window moments, the SSIM expression and every sum are float64 (float32
+ *     moments lose 1e-4 of SSIM on flat images: DESIGN.md section 4d).  Identical images give a map of exactly 1.  Partial sums are one per
+ *     32 x 32 tile of one (image, channel), added in a fixed order: no atomics, bit-reproducible from run to run.
+ *   ssim_map NULL or float32 [B][H - 10][W - 10][C]: the whole map, rounded to float32, whatever the mask says.
+ *   workspace: cnerf_image_metrics_workspace_bytes(B, H, W, C) bytes, 8-byte aligned, contents irrelevant.
+ *   CNERF_EINVAL: C not 1 or 3, H or W below 11 or above 65535, B C above 65535, an unknown dtype, a misaligned workspace or sums_out.
+ *   CNERF_ENULL: pred, target, sums_out or workspace NULL (bytes_host for the query).  Both return before any launch; B = 0 is accepted
+ *   without one.  The caller's stream and buffers, no allocation, no host sync.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_image_metrics_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint64_t *bytes_host);
+int cnerf_image_metrics(const void *pred, const void *target, const float *mask, uint32_t B, uint32_t H, uint32_t W, uint32_t C, int dtype,
+                        int quantize, double *sums_out, float *ssim_map, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
