@@ -1050,6 +1050,18 @@ def _camera(c2w, intrinsics, H, W, what):
     return (C.c_float * 12)(*m[:3].ravel().tolist()), k, H, W
 
 
+def _cameras(c2w, N, intrinsics, H, W, what, per="image"):
+    """(c2w [N, 3|4, 4] as a host array, the N cameras' 12 floats each, (fx, fy, cx, cy), H, W) of N pinhole views with one set of
+    intrinsics; a single [3|4, 4] c2w is one view"""
+    m = _host(c2w, np.float32)
+    if m.ndim == 2:
+        m = m[None]
+    if m.ndim != 3 or m.shape[0] != N:
+        raise ValueError(f"{what}: need one c2w per {per}, got {m.shape} for {N} views")
+    _, k, H, W = _camera(np.zeros((3, 4), np.float32), intrinsics, H, W, what)
+    return m, [_camera(m[v], intrinsics, H, W, what)[0] for v in range(N)], k, H, W
+
+
 def rasterize(verts, faces, c2w, intrinsics, H, W, convention='nerfstudio', near=0.01, cull='none'):
     """Visibility buffer of a triangle mesh seen through one pinhole camera, on the device (csrc/mesh_raster.hip; the rules are in
     include/customnerf_hip.h, cnerf_mesh_raster_*).  The camera is generate_rays': c2w [3, 4] or [4, 4] (tensor or array), intrinsics
@@ -1190,15 +1202,10 @@ class TSDFVolume:
                 weights = weights[None]
             if tuple(weights.shape) != (N, H, W):
                 raise ValueError(f"TSDFVolume.integrate: weights must be shaped like depth, got {tuple(weights.shape)} and {(N, H, W)}")
-        m = _host(c2w, np.float32)
-        if m.ndim == 2:
-            m = m[None]
-        if m.ndim != 3 or m.shape[0] != N:
-            raise ValueError(f"TSDFVolume.integrate: need one c2w per depth map, got {m.shape} for {N} views")
-        _, k, H, W = _camera(np.zeros((3, 4), np.float32), intrinsics, H, W, "TSDFVolume.integrate")
+        _, views, k, H, W = _cameras(c2w, N, intrinsics, H, W, "TSDFVolume.integrate", per="depth map")
         cams = (C.c_float * (12 * max(N, 1)))()
         for v in range(N):
-            cams[12 * v:12 * v + 12] = list(_camera(m[v], intrinsics, H, W, "TSDFVolume.integrate")[0])
+            cams[12 * v:12 * v + 12] = list(views[v])
         if convention not in _CONVENTIONS:
             raise ValueError(f"TSDFVolume.integrate: convention must be 'nerfstudio' or 'ngp', got {convention!r}")
         if depth_kind not in _DEPTH_KINDS:
@@ -1295,13 +1302,7 @@ class ViewColors:
                 raise ValueError(f"ViewColors: {name} must be float32, got {t.dtype}")
             if t is not None and t.device != images.device:
                 raise ValueError(f"ViewColors: {name} lives on {t.device}, images on {images.device}")
-        m = _host(c2w, np.float32)
-        if m.ndim == 2:
-            m = m[None]
-        if m.ndim != 3 or m.shape[0] != N:
-            raise ValueError(f"ViewColors: need one c2w per image, got {m.shape} for {N} views")
-        _, k, H, W = _camera(np.zeros((3, 4), np.float32), intrinsics, H, W, "ViewColors")
-        self._cams = [_camera(m[v], intrinsics, H, W, "ViewColors")[0] for v in range(N)]
+        m, self._cams, k, H, W = _cameras(c2w, N, intrinsics, H, W, "ViewColors")
         if not np.isfinite(m[:, :3]).all():
             raise ValueError("ViewColors: c2w holds non-finite values")
         if convention not in _CONVENTIONS:

@@ -4,6 +4,7 @@ Implemented (reference lines): sample_pdf (21-55), NeRFRenderer.__init__ (199-24
 run (278-405), weights_sum_i (407-474), run_cuda (597-718), update_extra_state (1658-1715), render (1719-1733),
 convert_sigma_samples_to_ply (128-196) and the density_mesh hook (251) as NeRFRenderer.extract_mesh / save_mesh (marching cubes in mesh.hip).
 render_depth (metric depth maps; no reference counterpart) feeds extract_mesh(tsdf=...), the TSDF fusion of mesh_tsdf.hip.
+The mesh export methods are documented here and implemented in nerf/mesh_export.py.
 Out of scope: the SDF/NeuS paths, the unused run_cuda2 / render_cuda duplicates.
 Every function here ends in HIP kernels (render.hip, raymarching.hip, occupancy.hip): there is no torch restatement of the
 reference's bodies in the product — that lives in oracle/torch_oracle.py, for the tests.
@@ -23,7 +24,7 @@ import torch.nn as nn
 
 from .. import raymarching, mesh as _mesh
 from .._lib import lib, check, ptr, stream, require_cuda
-from . import render_ops
+from . import render_ops, mesh_export as _export
 
 
 def sample_pdf(bins, weights, n_samples, det=False, u=None):
@@ -441,6 +442,8 @@ class NeRFRenderer(nn.Module):
         return int(tot.item() / total_step)
 
     # ------------------------------------------------------------------------------------------ mesh export (the reference's density_mesh hook, :251)
+    # The field's side of it lives here (_mesh_lattice, _mesh_sigma, density_volume); the pipeline is nerf/mesh_export.py, and the methods
+    # below that carry its API and documentation delegate to it.
     def _mesh_lattice(self, resolution, aabb):
         aabb = (self.aabb_infer if aabb is None else torch.as_tensor(aabb, dtype=torch.float32)).detach().float().cpu().reshape(6)
         lo, hi = aabb[:3], aabb[3:]
@@ -472,8 +475,6 @@ class NeRFRenderer(nn.Module):
         part 'all': self.density(x) (the fused density pass).  part 'fg' / 'bg': sigma and confidence from forward(x, view_dir), masked as
         run() masks the edit-region / background composites (renderer.py:386-395): soft mask sigmoid((conf - conf_thr) * 100) under
         opt.soft_mask, otherwise conf > 0.5; a field without a confidence channel raises ValueError."""
-        if part not in ('all', 'fg', 'bg'):
-            raise ValueError(f"extract_mesh: part must be 'all', 'fg' or 'bg', got {part!r}")
         R = int(resolution)
         lo, step = self._mesh_lattice(R, aabb)
         dev = self.aabb_infer.device
@@ -483,115 +484,11 @@ class NeRFRenderer(nn.Module):
         for s in range(0, n, chunk):
             i = torch.arange(s, min(s + chunk, n), device=dev, dtype=torch.int64)
             ijk = torch.stack([i // (R * R), (i // R) % R, i % R], dim=1).float()
-            vol[s:s + len(i)] = self._mesh_sigma((lo + ijk * step).contiguous(), part, view_dir)
+            vol[s:s + len(i)] = self._mesh_sigma((lo + ijk * step).contiguous(), part, view_dir)      # which checks `part`
         return vol.view(R, R, R)
 
-    _TSDF_KEYS = {'poses': None, 'intrinsics': None, 'H': None, 'W': None, 'convention': 'nerfstudio', 'trunc': None, 'min_opacity': 0.5,
-                  'carve': True, 'render': None}
-
-    @staticmethod
-    def _tsdf_options(tsdf, sparse, part, max_step):
-        """extract_mesh's tsdf= dict with its defaults filled in; everything wrong with it raises ValueError before any render"""
-        if not isinstance(tsdf, dict):
-            raise ValueError(f"extract_mesh: tsdf must be None or a dict of options, got {type(tsdf).__name__}")
-        if sparse:
-            raise ValueError("extract_mesh: tsdf and sparse=True exclude each other (a brick-sparse TSDF is not built)")
-        if part != 'all':
-            raise ValueError(f"extract_mesh: tsdf fuses renders of the whole field; part must be 'all', got {part!r}")
-        unknown = sorted(set(tsdf) - set(NeRFRenderer._TSDF_KEYS))
-        if unknown:
-            raise ValueError(f"extract_mesh: unknown tsdf keys {unknown}; known: {sorted(NeRFRenderer._TSDF_KEYS)}")
-        missing = [k for k in ('poses', 'intrinsics', 'H', 'W') if tsdf.get(k) is None]
-        if missing:
-            raise ValueError(f"extract_mesh: tsdf needs {missing}")
-        cfg = {**NeRFRenderer._TSDF_KEYS, **tsdf}
-        p = cfg['poses']
-        p = torch.as_tensor(np.asarray(p.detach().cpu() if torch.is_tensor(p) else p, dtype=np.float32))
-        if p.dim() != 3 or tuple(p.shape[1:]) not in ((3, 4), (4, 4)):
-            raise ValueError(f"extract_mesh: tsdf['poses'] must be [N, 3, 4] or [N, 4, 4], got {tuple(p.shape)}")
-        if p.shape[0] == 0:
-            raise ValueError("extract_mesh: tsdf['poses'] holds no view")
-        if cfg['convention'] not in ('nerfstudio', 'ngp'):
-            raise ValueError(f"extract_mesh: tsdf['convention'] must be 'nerfstudio' or 'ngp', got {cfg['convention']!r}")
-        k = tuple(float(x) for x in cfg['intrinsics'])
-        if len(k) != 4:
-            raise ValueError(f"extract_mesh: tsdf['intrinsics'] must be (fx, fy, cx, cy), got {len(k)} values")
-        trunc = 4.0 * max_step if cfg['trunc'] is None else float(cfg['trunc'])
-        if not (math.isfinite(trunc) and trunc > 0.0):
-            raise ValueError(f"extract_mesh: tsdf['trunc'] must be finite and > 0, got {cfg['trunc']}")
-        H, W = int(cfg['H']), int(cfg['W'])
-        if H < 1 or W < 1:
-            raise ValueError(f"extract_mesh: tsdf needs H, W >= 1, got {H}, {W}")
-        cfg.update(poses=p, intrinsics=k, trunc=trunc, H=H, W=W, min_opacity=float(cfg['min_opacity']), carve=bool(cfg['carve']),
-                   render=dict(cfg['render'] or {}))
-        return cfg
-
-    _COLOR_VIEW_KEYS = {'poses': None, 'intrinsics': None, 'H': None, 'W': None, 'convention': 'nerfstudio', 'min_opacity': 0.5,
-                        'render': None, 'depth_tol': None, 'power': 2, 'min_cos': 0.2}
-
-    @staticmethod
-    def _color_view_options(color_views, tsdf, wanted, max_step):
-        """extract_mesh's color_views= (a dict, or 'tsdf' for the cameras of `tsdf`) with its defaults filled in; everything wrong with it
-        raises ValueError before any render.  `wanted`: color=True or texture=R was asked for."""
-        keys = NeRFRenderer._COLOR_VIEW_KEYS
-        if isinstance(color_views, str):
-            if color_views != 'tsdf':
-                raise ValueError(f"extract_mesh: color_views must be None, a dict of options or 'tsdf', got {color_views!r}")
-            if not isinstance(tsdf, dict):
-                raise ValueError("extract_mesh: color_views='tsdf' reuses the cameras of tsdf=, which is not given")
-            color_views = {k: tsdf[k] for k in ('poses', 'intrinsics', 'H', 'W', 'convention', 'min_opacity', 'render') if k in tsdf}
-        if not isinstance(color_views, dict):
-            raise ValueError(f"extract_mesh: color_views must be None, a dict of options or 'tsdf', got {type(color_views).__name__}")
-        if not wanted:
-            raise ValueError("extract_mesh: color_views colours the vertices or a texture; it needs color=True or texture=R")
-        unknown = sorted(set(color_views) - set(keys))
-        if unknown:
-            raise ValueError(f"extract_mesh: unknown color_views keys {unknown}; known: {sorted(keys)}")
-        missing = [k for k in ('poses', 'intrinsics', 'H', 'W') if color_views.get(k) is None]
-        if missing:
-            raise ValueError(f"extract_mesh: color_views needs {missing}")
-        cfg = {**keys, **color_views}
-        p = cfg['poses']
-        p = torch.as_tensor(np.asarray(p.detach().cpu() if torch.is_tensor(p) else p, dtype=np.float32))
-        if p.dim() != 3 or tuple(p.shape[1:]) not in ((3, 4), (4, 4)):
-            raise ValueError(f"extract_mesh: color_views['poses'] must be [N, 3, 4] or [N, 4, 4], got {tuple(p.shape)}")
-        if p.shape[0] == 0:
-            raise ValueError("extract_mesh: color_views['poses'] holds no view")
-        if not bool(torch.isfinite(p).all()):
-            raise ValueError("extract_mesh: color_views['poses'] holds non-finite values")
-        if cfg['convention'] not in ('nerfstudio', 'ngp'):
-            raise ValueError(f"extract_mesh: color_views['convention'] must be 'nerfstudio' or 'ngp', got {cfg['convention']!r}")
-        k = tuple(float(x) for x in cfg['intrinsics'])
-        if len(k) != 4:
-            raise ValueError(f"extract_mesh: color_views['intrinsics'] must be (fx, fy, cx, cy), got {len(k)} values")
-        tol = 2.0 * max_step if cfg['depth_tol'] is None else float(cfg['depth_tol'])
-        if not (math.isfinite(tol) and tol > 0.0):
-            raise ValueError(f"extract_mesh: color_views['depth_tol'] must be finite and > 0, got {cfg['depth_tol']}")
-        power, min_cos = cfg['power'], float(cfg['min_cos'])
-        if isinstance(power, bool) or not isinstance(power, (int, np.integer)) or not 1 <= power <= 8:
-            raise ValueError(f"extract_mesh: color_views['power'] must be an integer in 1..8, got {power!r}")
-        if not 0.0 <= min_cos < 1.0:
-            raise ValueError(f"extract_mesh: color_views['min_cos'] must lie in [0, 1), got {cfg['min_cos']}")
-        H, W = int(cfg['H']), int(cfg['W'])
-        if H < 2 or W < 2:
-            raise ValueError(f"extract_mesh: color_views needs H, W >= 2, got {H}, {W}")
-        cfg.update(poses=p, intrinsics=k, depth_tol=tol, power=int(power), min_cos=min_cos, H=H, W=W, min_opacity=float(cfg['min_opacity']),
-                   render=dict(cfg['render'] or {}))
-        return cfg
-
-    def _view_colors(self, cfg, verts, faces, fallback):
-        """mesh.ViewColors of the views of cfg (_color_view_options) on the surface (verts, faces): every pose rendered with render_view —
-        its opacity is the pixel weight, zero below min_opacity — and the surface rasterised from it for the visibility depth"""
-        images, depths, weights = [], [], []
-        for pose in cfg['poses']:
-            rv = self.render_view(pose, cfg['intrinsics'], cfg['H'], cfg['W'], convention=cfg['convention'], min_opacity=cfg['min_opacity'],
-                                  **cfg['render'])
-            images.append(rv['image'])
-            weights.append(torch.where(rv['opacity'] >= cfg['min_opacity'], rv['opacity'], torch.zeros_like(rv['opacity'])))
-            depths.append(_mesh.rasterize(verts, faces, pose, cfg['intrinsics'], cfg['H'], cfg['W'], convention=cfg['convention'])['depth'])
-        return _mesh.ViewColors(torch.stack(images), torch.stack(depths), cfg['poses'], cfg['intrinsics'], cfg['depth_tol'],
-                                convention=cfg['convention'], depth_kind='z', weights=torch.stack(weights), power=cfg['power'],
-                                min_cos=cfg['min_cos'], fallback=fallback)
+    _tsdf_options = staticmethod(_export.tsdf_options)                           # the names the host tests know them by
+    _color_view_options = staticmethod(_export.color_view_options)
 
     @torch.no_grad()
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, chunk=2 ** 21, part='all', view_dir=(0.0, 0.0, -1.0), color=False,
@@ -690,162 +587,13 @@ class NeRFRenderer(nn.Module):
         compare with the surface as extracted, so they report what the remesh cost, and deviation=True counts it as a lossy pass.
         'remesh' joins the dict: voxel_remesh's info (shape, origin, spacing, bricks, evaluations, rounds, offset, beta).  With
         remesh=None the key is absent and every output is what it was."""
-        if fill_holes is True or fill_holes is False:
-            fill_edges = None
-        elif isinstance(fill_holes, (int, np.integer)) and fill_holes >= 3:
-            fill_edges = int(fill_holes)
-        else:
-            raise ValueError(f"extract_mesh: fill_holes must be False, True (no length limit) or an int >= 3 (the longest loop filled), "
-                             f"got {fill_holes!r}")
-        if fill_holes is not False and int(simplify):
-            raise ValueError("extract_mesh: fill_holes and simplify exclude each other (clustered meshes need not be manifold)")
-        threshold = float(self.opt.density_thresh if threshold is None else threshold)
-        R = int(resolution)
-        lo, step = self._mesh_lattice(R, aabb)
-        k = int(simplify)
-        if k == 1 or k < 0:
-            raise ValueError(f"extract_mesh: simplify must be 0 (off) or a cluster size >= 2 lattice steps, got {simplify}")
-        tf = int(target_faces)
-        if tf < 0:
-            raise ValueError(f"extract_mesh: target_faces must be 0 (off) or a face count, got {target_faces}")
-        if tf and k:
-            raise ValueError("extract_mesh: target_faces and simplify exclude each other (clustered meshes need not be manifold)")
-        tex_r = int(texture)
-        if tex_r < 0:
-            raise ValueError(f"extract_mesh: texture must be 0 (off) or a texture resolution, got {texture}")
-        if texture_layout not in _mesh.TEXTURE_LAYOUTS:
-            raise ValueError(f"extract_mesh: texture_layout must be 'uniform', 'area' or 'projected', got {texture_layout!r}")
-        n_smooth = int(smooth)
-        if n_smooth < 0:
-            raise ValueError(f"extract_mesh: smooth must be 0 (off) or a number of iterations, got {smooth}")
-        n_ao = int(ao)
-        if n_ao < 0:
-            raise ValueError(f"extract_mesh: ao must be 0 (off) or a number of rays per vertex, got {ao}")
-        if bake_from not in ('mesh', 'source'):
-            raise ValueError(f"extract_mesh: bake_from must be 'mesh' or 'source', got {bake_from!r}")
-        from_source = bake_from == 'source'
-        if isinstance(normal_map, str) and normal_map != 'tangent':
-            raise ValueError(f"extract_mesh: normal_map must be False, True (object space) or 'tangent', got {normal_map!r}")
-        if normal_map and not tex_r:
-            raise ValueError(f"extract_mesh: normal_map={normal_map!r} needs texture=R, the resolution of the atlas it shares")
-        reach = 4.0 * float(step.max()) if bake_reach is None else float(bake_reach)
-        if from_source and not reach > 0.0:
-            raise ValueError(f"extract_mesh: bake_reach must be > 0, got {bake_reach}")
-        if int(sparse_probe) < 1:
-            raise ValueError(f"extract_mesh: sparse_probe must be >= 1 (every how many lattice points the field is probed), got {sparse_probe}")
-        remesh_kw = None
-        if remesh is not None:
-            if isinstance(remesh, dict):
-                remesh_kw = dict(remesh)
-            elif isinstance(remesh, (int, np.integer)) and not isinstance(remesh, bool):
-                remesh_kw = {'resolution': int(remesh)}
-            else:
-                raise ValueError(f"extract_mesh: remesh must be None, a resolution (int) or a dict of mesh.voxel_remesh's options, got {remesh!r}")
-            unknown = set(remesh_kw) - {'resolution', 'voxel', 'offset', 'beta', 'probe'}
-            if unknown or (remesh_kw.get('resolution') is None) == (remesh_kw.get('voxel') is None):
-                raise ValueError(f"extract_mesh: remesh takes exactly one of 'resolution' and 'voxel', and 'offset', 'beta', 'probe'; "
-                                 f"got {sorted(remesh_kw)}")
-        cv_cfg = None
-        if color_views is not None:
-            cv_cfg = self._color_view_options(color_views, tsdf, bool(color) or bool(tex_r), float(step.max()))
-        sparse_info = tsdf_info = None
-        if tsdf is not None:
-            cfg = self._tsdf_options(tsdf, sparse, part, float(step.max()))
-            poses = cfg['poses']
-            tv = _mesh.TSDFVolume((R, R, R), lo.tolist(), step.tolist(), cfg['trunc'], device=self.aabb_infer.device)
-            for s in range(0, poses.shape[0], 16):                               # a launch of the fusion takes 16 views: the volume is read once for them
-                maps = []
-                for pose in poses[s:s + 16]:
-                    d = self.render_depth(pose, cfg['intrinsics'], cfg['H'], cfg['W'], convention=cfg['convention'],
-                                          min_opacity=cfg['min_opacity'], **cfg['render'])['depth']
-                    maps.append(d if cfg['carve'] else torch.where(torch.isinf(d), torch.full_like(d, math.nan), d))
-                tv.integrate(torch.stack(maps), poses[s:s + 16], cfg['intrinsics'], convention=cfg['convention'], depth_kind='ray')
-            threshold, vol = 0.0, tv.volume()
-            verts, faces, normals, info = tv.extract()
-            tsdf_info = {'views': tv.views, 'trunc': tv.trunc, 'observed': info['observed'], 'dropped_faces': info['dropped_faces']}
-        elif sparse:
-            vol = None
-            sv = _mesh.sparse_volume(lambda x: self._mesh_sigma(x, part, view_dir), (R, R, R), lo, step, threshold, probe=int(sparse_probe),
-                                     chunk=chunk, device=self.aabb_infer.device)
-            verts, faces, normals = _mesh.marching_cubes_sparse(sv, threshold)
-            sparse_info = {'bricks': sv.n_bricks, 'evaluations': sv.evaluations, 'rounds': sv.rounds, 'points': R ** 3}
-        else:
-            vol = self.density_volume(R, aabb, chunk, part, view_dir)
-            verts, faces, normals = _mesh.marching_cubes(vol, threshold, spacing=step.tolist(), origin=lo.tolist())
-        if int(min_component_faces) > 0 or keep_largest:
-            verts, faces, normals, _ = _mesh.remove_small_components(verts, faces, normals, min_faces=int(min_component_faces),
-                                                                     largest=bool(keep_largest))
-        holes_info = None
-        if fill_holes is not False:
-            verts, faces, normals, holes_info = _mesh.fill_holes(verts, faces, normals, max_edges=fill_edges)
-        kept =(verts, faces, normals) if deviation or from_source else None     # held only for the report and the projection
-        remesh_info = None
-        if remesh_kw is not None:
-            verts, faces, normals, remesh_info = _mesh.voxel_remesh(verts, faces, chunk=chunk, **remesh_kw)
-        if n_smooth:
-            verts, normals = _mesh.smooth(verts, faces, n_smooth, smooth_lambda, smooth_mu, normals=normals)
-        if k >= 2:
-            g = (-(-(R - 1) // k),) * 3                                          # ceil((R - 1) / k) cells cover the lattice
-            verts, faces, normals = _mesh.simplify(verts, faces, (step * k).tolist(), normals=normals, origin=lo.tolist(), grid=g)
-        if tf:
-            verts, faces, normals, _ = _mesh.decimate(verts, faces, tf, normals=normals)
-        source = _mesh.bake_source(*kept) if from_source and (color or tex_r) else None
-        kinds = torch.zeros(4, dtype=torch.int64, device=verts.device) if from_source else None
-        field_color = lambda x, d: self(x, d)[1][:, :3]                         # noqa: E731
-        color_fn = field_color
-        if cv_cfg is not None:                                                   # the views on the surface the queried points lie on
-            color_fn = self._view_colors(cv_cfg, *(kept[:2] if source is not None else (verts, faces)), field_color)
-        colors = None
-        if color:
-            colors = torch.empty(verts.shape[0], 3, dtype=torch.uint8, device=verts.device)
-            for s in range(0, verts.shape[0], chunk):
-                x, look = verts[s:s + chunk].contiguous(), (-normals[s:s + chunk]).contiguous()
-                if source is not None:
-                    pr = _mesh.project_to_surface(source, x, normals[s:s + chunk], reach)
-                    x, look = pr['point'], -pr['normal']
-                    if not tex_r:
-                        kinds += (pr['kind'][:, None] == torch.arange(4, dtype=torch.uint8, device=x.device)).sum(0)
-                rgb = color_fn(x, look).float()
-                colors[s:s + chunk] = (rgb.clamp(0, 1) * 255).round().to(torch.uint8)
-        uvs = tex = nmap = tangents = None
-        if tex_r:
-            baked = _mesh.bake_texture(verts, faces, tex_r, color_fn, normals=normals, chunk=chunk,
-                                       layout=texture_layout, source=source, reach=reach if source is not None else None,
-                                       normal_map=normal_map if isinstance(normal_map, str) else bool(normal_map))
-            uvs, tex = baked[:2]
-            if len(baked) > 2:
-                nmap, kinds = baked[2]['normal_map'], baked[2]['kinds'] if source is not None else kinds
-                tangents = baked[2].get('tangents')
-        m = {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
-             'uvs': uvs, 'texture': tex, 'texture_layout': texture_layout}
-        if sparse_info is not None:
-            m['sparse'] = sparse_info
-        if tsdf_info is not None:
-            m['tsdf'] = tsdf_info
-        if holes_info is not None:
-            m['holes'] = holes_info
-        if remesh_info is not None:
-            m['remesh'] = remesh_info
-        if cv_cfg is not None:
-            m['view_colors'] = {'views': color_fn.views, 'seen': color_fn.counts, 'depth_tol': color_fn.depth_tol}
-        if topology:
-            m['topology'] = _mesh.topology(verts, faces)
-        if normal_map:
-            m['normal_map'] = nmap
-            m['normal_space'] = 'tangent' if isinstance(normal_map, str) else 'object'
-        if isinstance(normal_map, str):
-            m['tangents'] = tangents
-        if from_source:
-            m['bake_kinds'] = kinds
-        if deviation:
-            m['deviation'] = None
-            if n_smooth or k >= 2 or tf or remesh_info is not None:
-                sp = 0.5 * float(step.min()) if deviation_spacing is None else float(deviation_spacing)
-                m['deviation'] = dict(_mesh.distance(verts, faces, kept[0], kept[1], spacing=sp, max_samples=deviation_max_samples),
-                                      step=tuple(step.tolist()))
-        if n_ao:
-            m['ao'] = _mesh.ambient_occlusion(verts, faces, normals=normals, samples=n_ao)
-        return m
+        return _export.extract_mesh(
+            self, resolution=resolution, threshold=threshold, aabb=aabb, chunk=chunk, part=part, view_dir=view_dir, color=color,
+            min_component_faces=min_component_faces, keep_largest=keep_largest, simplify=simplify, target_faces=target_faces, texture=texture,
+            smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu, deviation=deviation, deviation_spacing=deviation_spacing,
+            deviation_max_samples=deviation_max_samples, ao=ao, texture_layout=texture_layout, bake_from=bake_from, bake_reach=bake_reach,
+            normal_map=normal_map, sparse=sparse, sparse_probe=sparse_probe, tsdf=tsdf, fill_holes=fill_holes, topology=topology,
+            color_views=color_views, remesh=remesh)
 
     def save_mesh(self, path, **kw):
         """extract_mesh(**kw) written to `path` -> the mesh dict.  A path ending in .obj writes a Wavefront OBJ (mesh.write_obj: positions,
@@ -860,36 +608,7 @@ class NeRFRenderer(nn.Module):
         normal_map=True is refused for .glb (glTF has no object-space slot).  A PLY written with ao=K and without color=True carries the ambient occlusion as grey vertex colours
         round(255 ao), so that a viewer shows the cavities of a geometry-only export; with color=True the field's colours are written
         unchanged (a NeRF's radiance already contains its shading, so AO is never multiplied into baked colour or texture)."""
-        obj, glb = (str(path).lower().endswith(e) for e in (".obj", ".glb"))
-        nm = kw.get('normal_map')
-        if int(kw.get('texture', 0) or 0) and not (obj or glb):
-            raise ValueError(f"save_mesh: texture= needs an .obj or .glb path (PLY carries no texture), got {path!r}")
-        if nm and not (obj or glb):
-            raise ValueError(f"save_mesh: normal_map={nm!r} needs an .obj or .glb path (PLY carries no normal map), got {path!r}")
-        if glb and nm and nm != 'tangent':
-            raise ValueError("save_mesh: glTF has no slot for an object-space normal map; use normal_map='tangent' with a .glb path")
-        if obj and nm == 'tangent':
-            raise ValueError("save_mesh: OBJ carries no tangents; normal_map='tangent' needs a .glb path")
-        m = self.extract_mesh(**kw)
-        if glb:
-            colors = m['colors']
-            if colors is None and 'ao' in m:
-                colors = (m['ao'] * 255).round().to(torch.uint8)[:, None].expand(-1, 3)
-            if m['uvs'] is not None:
-                g = _mesh.gltf_vertices(m['verts'], m['faces'], m['uvs'], m['normals'])
-                _mesh.write_glb(path, g['positions'], g['indices'], normals=g['normals'], uvs=g['uvs'], tangents=g['tangents'],
-                                texture=m['texture'], normal_map=m.get('normal_map'))
-            else:
-                _mesh.write_glb(path, m['verts'], m['faces'], normals=m['normals'], colors=colors)
-        elif obj:
-            _mesh.write_obj(path, m['verts'], m['faces'], uvs=m['uvs'], normals=m['normals'], texture=m['texture'],
-                            normal_map=m.get('normal_map'))
-        else:
-            colors = m['colors']
-            if colors is None and 'ao' in m:
-                colors = (m['ao'] * 255).round().to(torch.uint8)[:, None].expand(-1, 3)
-            _mesh.write_ply(path, m['verts'], m['faces'], normals=m['normals'], colors=colors)
-        return m
+        return _export.save_mesh(self, path, **kw)
 
     def render_mesh(self, mesh, c2w, intrinsics, H, W, path=None, map='texture', **kw):
         """Preview of an exported mesh from a camera pose, rasterised on the device (mesh.render_mesh, csrc/mesh_raster.hip).  `mesh` is the
@@ -917,70 +636,14 @@ class NeRFRenderer(nn.Module):
         is what mesh.TSDFVolume.integrate(depth_kind='ray') reads as free space.  The two paths return different things under 'depth':
         run_cuda sum(w t), and run() sum(w clamp((t - near) / (far - near), 0, 1)) as the reference does (nerf/renderer.py:435-436), so
         the latter is mapped back with the ray's own near / far (near_far_from_aabb with the box and min_near that run() used)."""
-        m = torch.as_tensor(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, dtype=np.float32))
-        if tuple(m.shape) not in ((3, 4), (4, 4)):
-            raise ValueError(f"render_depth: c2w must be [3, 4] or [4, 4], got {tuple(m.shape)}")
-        k = tuple(float(x) for x in intrinsics)
-        H, W, batch = int(H), int(W), int(max_ray_batch)
-        if len(k) != 4 or H < 1 or W < 1 or batch < 1:
-            raise ValueError(f"render_depth: need intrinsics (fx, fy, cx, cy), H, W >= 1 and max_ray_batch >= 1, got {k}, {H}, {W}, {batch}")
-        from .provider_utils import generate_rays
-        dev = self.aabb_infer.device
-        o, d = generate_rays(m[None, :3].to(dev), *k, H, W, 1.0, convention)
-        o, d = o.view(-1, 3), d.view(-1, 3)
-        depth = torch.empty(H * W, dtype=torch.float32, device=dev)
-        opacity = torch.empty_like(depth)
-        aabb = self.aabb_train if self.training else self.aabb_infer
-        for s in range(0, H * W, batch):
-            ro, rd = o[s:s + batch].contiguous(), d[s:s + batch].contiguous()
-            res = self.render(ro[None], rd[None], staged=True, perturb=False, **render_kw)
-            if 'depth' not in res:
-                raise ValueError("render_depth: render() returned no depth (run() fills its results only under opt.train_conf)")
-            acc = res['weights_sum'].reshape(-1).float()
-            t = res['depth'].reshape(-1).float() / acc                          # 0 / 0 where nothing was hit: below min_opacity anyway
-            if not self.cuda_ray:
-                near, far = raymarching.near_far_from_aabb(ro, rd, aabb, self.min_near)
-                t = near + t * (far - near)
-            depth[s:s + batch] = t * rd.norm(dim=-1)
-            opacity[s:s + batch] = acc
-        depth = torch.where(opacity >= float(min_opacity), depth, torch.full_like(depth, math.inf))
-        return {'depth': depth.view(H, W), 'opacity': opacity.view(H, W)}
+        return _export.render_view(self, c2w, intrinsics, H, W, convention, min_opacity, max_ray_batch, render_kw, False, "render_depth")
 
     @torch.no_grad()
     def render_view(self, c2w, intrinsics, H, W, convention='nerfstudio', min_opacity=0.5, max_ray_batch=1 << 16, **render_kw):
         """render_depth's view with its colour, from the same one pass per ray batch: -> {'image': [H, W, 3] float32, the composited
         colour render() returns (over its background, where one is set), 'depth', 'opacity'}; depth and opacity are render_depth's, bit
         for bit.  What extract_mesh(color_views=...) projects onto the mesh."""
-        m = torch.as_tensor(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, dtype=np.float32))
-        if tuple(m.shape) not in ((3, 4), (4, 4)):
-            raise ValueError(f"render_view: c2w must be [3, 4] or [4, 4], got {tuple(m.shape)}")
-        k = tuple(float(x) for x in intrinsics)
-        H, W, batch = int(H), int(W), int(max_ray_batch)
-        if len(k) != 4 or H < 1 or W < 1 or batch < 1:
-            raise ValueError(f"render_view: need intrinsics (fx, fy, cx, cy), H, W >= 1 and max_ray_batch >= 1, got {k}, {H}, {W}, {batch}")
-        from .provider_utils import generate_rays
-        dev = self.aabb_infer.device
-        o, d = generate_rays(m[None, :3].to(dev), *k, H, W, 1.0, convention)
-        o, d = o.view(-1, 3), d.view(-1, 3)
-        image = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
-        depth = torch.empty(H * W, dtype=torch.float32, device=dev)
-        opacity = torch.empty_like(depth)
-        aabb = self.aabb_train if self.training else self.aabb_infer
-        for s in range(0, H * W, batch):
-            ro, rd = o[s:s + batch].contiguous(), d[s:s + batch].contiguous()
-            res = self.render(ro[None], rd[None], staged=True, perturb=False, **render_kw)
-            if 'depth' not in res or 'image' not in res:
-                raise ValueError("render_view: render() returned no image or depth (run() fills its results only under opt.train_conf)")
-            acc = res['weights_sum'].reshape(-1).float()
-            t = res['depth'].reshape(-1).float() / acc                          # the arithmetic of render_depth, in its order
-            if not self.cuda_ray:
-                near, far = raymarching.near_far_from_aabb(ro, rd, aabb, self.min_near)
-                t = near + t * (far - near)
-            depth[s:s + batch] = t * rd.norm(dim=-1)
-            opacity[s:s + batch] = acc
-            image[s:s + batch] = res['image'].reshape(-1, 3).float()
-        depth = torch.where(opacity >= float(min_opacity), depth, torch.full_like(depth, math.inf))
-        return {'image': image.view(H, W, 3), 'depth': depth.view(H, W), 'opacity': opacity.view(H, W)}
+        return _export.render_view(self, c2w, intrinsics, H, W, convention, min_opacity, max_ray_batch, render_kw, True, "render_view")
 
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=2048, **kwargs):
         """renderer.py:1719-1733."""
