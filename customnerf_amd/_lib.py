@@ -50,6 +50,9 @@ SIGNATURES = {
     "cnerf_field_pack_weights": [u32, u32, u32, vp, vp, vp, vp, u64, vp],
     "cnerf_field_forward_img": [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, i32, u32, vp, vp],
     "cnerf_field_backward_img": [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp],
+    "cnerf_field_density_grad": [vp, vp, u32, u32, u32, vp, vp, vp, vp, i32, u32, vp],
+    "cnerf_grid_encode_input_grad": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, u32, i32, u32, i32, u32, vp],
+    "cnerf_composite_normals": [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp],
     "cnerf_mlp_forward": [vp, u32, vp, u32, u32, u32, u32, u32, i32, vp, u32, i32, vp],
     "cnerf_mlp_backward": [vp, u32, vp, vp, u32, u32, u32, u32, u32, u32, i32, vp, u32, vp, vp, u64, i32, vp],
     "cnerf_mlp_backward_workspace_bytes": [u32, u32, u32, u32, u32, i32, vp],

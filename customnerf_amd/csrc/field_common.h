@@ -181,6 +181,25 @@ __device__ __forceinline__ void fld_stage_layer(typename Prec<H>::elem_t *dst, c
     }
 }
 
+// The same fragment order for the TRANSPOSE of a layer whose 64 outputs arrive in C-register order (a gradient running back through it,
+// field_normal.hip): A(row, k) = W[col(k)][row] with W the layer's [64, in_stride] matrix, row = one of its `n_in` inputs (0 beyond),
+// k = its outputs in the column order of KIND 1.  T = tiles of 32 inputs, S = FLD_HID / KS.
+template <bool H>
+__device__ __forceinline__ void fld_stage_layer_t(typename Prec<H>::elem_t *dst, const float *__restrict__ W, uint32_t n_in, uint32_t in_stride,
+                                                  uint32_t T, uint32_t S, uint32_t i0, uint32_t istride) {
+    using P = Prec<H>;
+    const uint32_t total = T * S * 64 * P::J;
+    for (uint32_t i = i0; i < total; i += istride) {
+        const uint32_t j = i % P::J, lane = (i / P::J) % 64, ts = i / (P::J * 64);
+        const uint32_t s = ts % S, t = ts / S;
+        const uint32_t row = 32 * t + (lane & 31), hi = lane >> 5;
+        const uint32_t col = (uint32_t)fld_col_clayout<H>(s, hi, j);
+        float v = 0.0f;
+        if (row < n_in && col < FLD_HID) v = W[(size_t)col * in_stride + row];
+        dst[i] = (typename P::elem_t)v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ per-wave building blocks
 template <bool H>
 __device__ __forceinline__ typename Prec<H>::frag_t fld_load_frag(const typename Prec<H>::elem_t *base, uint32_t t, uint32_t S, uint32_t s, uint32_t lane) {

@@ -74,7 +74,25 @@ def field_forward_rows(enc, row0, xyz_rows, dirs, dir_group, enc_dim, n_hidden_g
           "field_forward")
 
 
-_WS = ScratchCache(factor=1.1, pad=256)          # the backward's per-workgroup partial-gradient rows
+@torch.no_grad()
+def field_density_grad(enc, xyz, enc_dim, n_hidden_geo, p_net, p_den, enc_level_stride=0, want_sigma=True):
+    """d raw / d enc of the log-density raw = MLP_den(MLP_net(enc))[0] (cnerf_field_density_grad): enc [L,P',2] (half or float) in kernel layout
+    with P' = enc_level_stride (0: enc.shape[1]) >= P samples per level, xyz [P,3] f32 -> (sigma [P] f32 or None, grad_enc [L,P,2] float32).
+    sigma is field_forward_raw's, bit for bit.  Detached: gradients through the normals are out of scope."""
+    require_cuda(enc, xyz, p_net, p_den)
+    P = xyz.shape[0]
+    stride = int(enc_level_stride) or int(enc.shape[1])          # (a flat view that starts at a row offset passes its stride explicitly)
+    assert enc.is_contiguous() and xyz.is_contiguous() and xyz.dtype == torch.float32
+    assert stride >= P and enc.numel() >= (max(enc_dim // 2, 1) - 1) * stride * 2 + 2 * P
+    dt = F16 if enc.dtype == torch.float16 else F32
+    sigma = torch.empty(P, dtype=torch.float32, device=xyz.device) if want_sigma else None
+    g_enc = torch.empty(enc_dim // 2, P, 2, dtype=torch.float32, device=xyz.device)
+    check(lib.cnerf_field_density_grad(ptr(enc), ptr(xyz), P, int(enc_dim), int(n_hidden_geo), ptr(p_net), ptr(p_den), ptr(sigma), ptr(g_enc), dt,
+                                       stride, stream()), "field_density_grad")
+    return sigma, g_enc
+
+
+_WS = ScratchCache(factor=1.1, pad=256)         # the backward's per-workgroup partial-gradient rows
 
 
 def _workspace(P, enc_dim, n_hidden_geo, n_rgb_out, dt, device):

@@ -351,6 +351,28 @@ class GridEncoder(nn.Module):
         return _grid_attach.apply(enc, inputs_unit.contiguous().float(), self.embeddings, self._offsets_host, self.per_level_scale, self.base_resolution,
                                   self.gridtype_id, self.align_corners, self.interp_id, bool(getattr(self, 'grad_in_place', False)))
 
+    @torch.no_grad()
+    def input_grad(self, unit, grad_enc, level_stride=0, half=None):
+        """grad_inputs [B, D] float32 = sum over levels and corners of d(weight)/d(unit) * (table row . grad_enc[level, b]) for unit [B, D]
+        in [0, 1] and grad_enc [L, level_stride or B, C] float32 in kernel layout (cnerf_grid_encode_input_grad): what backward() gives
+        through a materialised dy_dx (gridencoder.cu:342-368), without writing one, per unit coordinate, zero outside the unit cube, and
+        bit-reproducible.  `half` picks the table as in encode().  The fused field's configuration only (3-D, 2 features per level, linear
+        interpolation, no align_corners, at most 32 levels): anything else raises ValueError."""
+        if half is None:
+            half = torch.is_autocast_enabled() and self.level_dim % 2 == 0
+        table = self.half_table() if half else self.embeddings.detach()
+        require_cuda(unit, grad_enc, table)
+        unit = unit.contiguous().float()
+        B, D = unit.shape
+        L = self._offsets_host.shape[0] - 1
+        stride = int(level_stride) or B
+        assert grad_enc.is_contiguous() and grad_enc.dtype == torch.float32 and stride >= B and grad_enc.numel() >= ((L - 1) * stride + B) * table.shape[1]
+        out = torch.empty(B, D, dtype=torch.float32, device=unit.device)
+        check(lib.cnerf_grid_encode_input_grad(ptr(unit), ptr(table), self._offsets_host.ctypes.data, ptr(grad_enc), ptr(out), B, D, int(table.shape[1]), L,
+                                               float(np.log2(self.per_level_scale)), int(self.base_resolution), self.gridtype_id, int(self.align_corners),
+                                               self.interp_id, dtype_id(table), stride, stream()), "grid_encode_input_grad")
+        return out
+
     def forward(self, inputs, bound=1, max_level=None, return_kernel_layout=False):
         """grid.py:151-168: [..., D] -> [..., L*C]."""
         prefix_shape = list(inputs.shape[:-1])

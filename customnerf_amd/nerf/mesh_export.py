@@ -102,12 +102,13 @@ def color_view_options(color_views, tsdf, wanted, max_step):
 # k: simplify's cluster size; tf: target_faces; reach: bake_reach or its default; tsdf_cfg / cv_cfg: None or the options' dicts
 Options = namedtuple('Options', 'R lo step threshold aabb chunk part view_dir color min_component_faces keep_largest fill fill_edges remesh_kw '
                                 'n_smooth smooth_lambda smooth_mu k tf tex_r texture_layout normal_map from_source reach sparse sparse_probe '
-                                'tsdf_cfg cv_cfg deviation deviation_spacing deviation_max_samples n_ao topology')
+                                'tsdf_cfg cv_cfg deviation deviation_spacing deviation_max_samples n_ao topology field_normals')
 
 
 def parse_options(model, *, resolution, threshold, aabb, chunk, part, view_dir, color, min_component_faces, keep_largest, simplify,
                   target_faces, texture, smooth, smooth_lambda, smooth_mu, deviation, deviation_spacing, deviation_max_samples, ao,
-                  texture_layout, bake_from, bake_reach, normal_map, sparse, sparse_probe, tsdf, fill_holes, topology, color_views, remesh):
+                  texture_layout, bake_from, bake_reach, normal_map, sparse, sparse_probe, tsdf, fill_holes, topology, color_views, remesh,
+                  normals='mesh'):
     """Every check extract_mesh makes on its arguments (NeRFRenderer.extract_mesh gives their defaults and meaning), none of which
     touches the device -> Options"""
     if fill_holes is True or fill_holes is False:
@@ -117,6 +118,11 @@ def parse_options(model, *, resolution, threshold, aabb, chunk, part, view_dir, 
     else:
         raise ValueError(f"extract_mesh: fill_holes must be False, True (no length limit) or an int >= 3 (the longest loop filled), "
                          f"got {fill_holes!r}")
+    if normals not in ('mesh', 'field'):
+        raise ValueError(f"extract_mesh: normals must be 'mesh' or 'field', got {normals!r}")
+    if normals == 'field' and (part != 'all' or tsdf is not None or remesh is not None):
+        raise ValueError("extract_mesh: normals='field' are the normals of the density's level set; the surfaces of part='fg' / 'bg', tsdf= and "
+                         "remesh= are not one")
     if fill_holes is not False and int(simplify):
         raise ValueError("extract_mesh: fill_holes and simplify exclude each other (clustered meshes need not be manifold)")
     threshold = float(model.opt.density_thresh if threshold is None else threshold)
@@ -173,7 +179,7 @@ def parse_options(model, *, resolution, threshold, aabb, chunk, part, view_dir, 
                    fill_edges=fill_edges, remesh_kw=remesh_kw, n_smooth=n_smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu, k=k,
                    tf=tf, tex_r=tex_r, texture_layout=texture_layout, normal_map=normal_map, from_source=from_source, reach=reach,
                    sparse=sparse, sparse_probe=int(sparse_probe), tsdf_cfg=tsdf_cfg, cv_cfg=cv_cfg, deviation=deviation,
-                   deviation_spacing=deviation_spacing, deviation_max_samples=deviation_max_samples, n_ao=n_ao, topology=topology)
+                   deviation_spacing=deviation_spacing, deviation_max_samples=deviation_max_samples, n_ao=n_ao, topology=topology, field_normals=normals == 'field')
 
 
 # ------------------------------------------------------------------------------------------------ the surface
@@ -235,6 +241,20 @@ def lossy(o, verts, faces, normals):
     if o.tf:
         verts, faces, normals, _ = _mesh.decimate(verts, faces, o.tf, normals=normals)
     return verts, faces, normals, info, bool(o.remesh_kw is not None or o.n_smooth or o.k >= 2 or o.tf)
+
+
+def field_normals(model, o, verts, normals):
+    """the field's own normals at the vertices (model.normal); a vertex keeps its geometric normal where the field's is zero or opposes it
+    -> (normals, {'kept_geometric': how many kept theirs})"""
+    out = torch.empty_like(normals)
+    kept = torch.zeros((), dtype=torch.int64, device=verts.device)
+    for s in range(0, verts.shape[0], o.chunk):
+        geo = normals[s:s + o.chunk]
+        n = model.normal(verts[s:s + o.chunk].contiguous())
+        keep = (n * geo).sum(-1) <= 0
+        out[s:s + o.chunk] = torch.where(keep[:, None], geo, n)
+        kept += keep.sum()
+    return out, {'kept_geometric': int(kept)}
 
 
 # ------------------------------------------------------------------------------------------------ colour
@@ -305,6 +325,8 @@ def extract_mesh(model, **kw):
     verts, faces, normals, repair_info = repair(o, verts, faces, normals)
     kept = (verts, faces, normals) if o.deviation or o.from_source else None    # held only for the report and the projection
     verts, faces, normals, lossy_info, changed = lossy(o, verts, faces, normals)
+    if o.field_normals:
+        normals, lossy_info['field_normals'] = field_normals(model, o, verts, normals)
     colors, uvs, tex, colour_info = colour(model, o, verts, faces, normals, kept)
     return {'verts': verts, 'faces': faces, 'normals': normals, 'colors': colors, 'volume': vol, 'threshold': threshold,
             'uvs': uvs, 'texture': tex, 'texture_layout': o.texture_layout, **surface_info, **repair_info, **lossy_info, **colour_info,
@@ -339,7 +361,8 @@ def save_mesh(model, path, **kw):
         raise ValueError("save_mesh: glTF has no slot for an object-space normal map; use normal_map='tangent' with a .glb path")
     if obj and nm == 'tangent':
         raise ValueError("save_mesh: OBJ carries no tangents; normal_map='tangent' needs a .glb path")
-    m = model.extract_mesh(**kw)
+    normals = kw.pop('normals', 'mesh')
+    m = model.extract_mesh(**kw) if normals == 'mesh' else model.extract_mesh_normals(normals, **kw)
     if obj:
         _mesh.write_obj(path, m['verts'], m['faces'], uvs=m['uvs'], normals=m['normals'], texture=m['texture'], normal_map=m.get('normal_map'))
     elif glb and m['uvs'] is not None:
@@ -356,9 +379,21 @@ def save_mesh(model, path, **kw):
 
 
 # ------------------------------------------------------------------------------------------------ rendered views
-def render_view(model, c2w, intrinsics, H, W, convention, min_opacity, max_ray_batch, render_kw, want_image, what):
+SHADINGS = ('normal', 'lambertian', 'textureless')
+VIEW_OPTIONS = {'normals': False, 'shading': None, 'light_d': None, 'ambient_ratio': 0.1, 'path': None}     # render_view's own keywords
+
+
+def render_view(model, c2w, intrinsics, H, W, convention, min_opacity, max_ray_batch, render_kw, want_image, what, normals=False, shading=None,
+                light_d=None, ambient_ratio=0.1, path=None):
     """NeRFRenderer.render_view (want_image) and render_depth (not): one pass of model.render per ray batch -> {'image' if wanted, 'depth',
-    'opacity'}; `what` names the caller in the messages"""
+    'opacity'}; `what` names the caller in the messages.  normals / shading / light_d / ambient_ratio / path: render_view's docstring."""
+    if shading is not None and shading not in SHADINGS:
+        raise ValueError(f"{what}: shading must be None or one of {SHADINGS}, got {shading!r}")
+    if not 0.0 <= float(ambient_ratio) <= 1.0:
+        raise ValueError(f"{what}: ambient_ratio must lie in [0, 1], got {ambient_ratio}")
+    normals = bool(normals) or shading is not None
+    if normals:
+        render_kw = dict(render_kw, normals=True)
     m = torch.as_tensor(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, dtype=np.float32))
     if tuple(m.shape) not in ((3, 4), (4, 4)):
         raise ValueError(f"{what}: c2w must be [3, 4] or [4, 4], got {tuple(m.shape)}")
@@ -373,6 +408,7 @@ def render_view(model, c2w, intrinsics, H, W, convention, min_opacity, max_ray_b
     image = torch.empty(H * W, 3, dtype=torch.float32, device=dev) if want_image else None
     depth = torch.empty(H * W, dtype=torch.float32, device=dev)
     opacity = torch.empty_like(depth)
+    nmap = torch.empty(H * W, 3, dtype=torch.float32, device=dev) if normals else None
     aabb = model.aabb_train if model.training else model.aabb_infer
     for s in range(0, H * W, batch):
         ro, rd = o[s:s + batch].contiguous(), d[s:s + batch].contiguous()
@@ -389,6 +425,30 @@ def render_view(model, c2w, intrinsics, H, W, convention, min_opacity, max_ray_b
         opacity[s:s + batch] = acc
         if want_image:
             image[s:s + batch] = res['image'].reshape(-1, 3).float()
-    depth = torch.where(opacity >= float(min_opacity), depth, torch.full_like(depth, math.inf))
+        if normals:
+            nmap[s:s + batch] = res['normal_map'].reshape(-1, 3)
+    hit = opacity >= float(min_opacity)
+    depth = torch.where(hit, depth, torch.full_like(depth, math.inf))
     out = {'depth': depth.view(H, W), 'opacity': opacity.view(H, W)}
-    return {'image': image.view(H, W, 3), **out} if want_image else out
+    if want_image:
+        out = {'image': image.view(H, W, 3), **out}
+    if normals:
+        # the composited sum w n is shorter than 1 by the spread of the samples' normals: renormalised per pixel (zero stays zero)
+        length = nmap.norm(dim=-1, keepdim=True)
+        n = torch.where(hit[:, None] & (length > 0), nmap / length.clamp_min(1e-20), torch.zeros_like(nmap))
+        out['normal'] = n.view(H, W, 3)
+        if shading == 'normal':
+            out['shaded'] = ((n + 1) / 2).view(H, W, 3)
+        elif shading is not None:
+            # deferred shading of the composited normal (one evaluation per pixel, not per sample)
+            # default light: at the camera, i.e. against the view direction (the ray of the centre pixel)
+            light = -d[(H // 2) * W + W // 2] if light_d is None else torch.as_tensor(light_d, dtype=torch.float32, device=dev)
+            light = light.reshape(3) / light.norm().clamp_min(1e-20)
+            lam = float(ambient_ratio) + (1 - float(ambient_ratio)) * (n @ light).clamp_min(0)[:, None]
+            out['shaded'] = ((image if shading == 'lambertian' else 1.0) * lam).expand(H * W, 3).reshape(H, W, 3)
+    if path is not None:
+        pic = out.get('shaded', (out['normal'] + 1) / 2 if normals else out.get('image', None))
+        if pic is None:
+            raise ValueError(f"{what}: path= needs an image to write")
+        _mesh.write_png(path, (pic.clamp(0, 1) * 255).round().to(torch.uint8))
+    return out

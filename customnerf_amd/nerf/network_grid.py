@@ -8,11 +8,11 @@ and can be overridden through `opt.grid_type / opt.log2_hashmap_size / opt.desir
 import torch
 from torch import nn
 
-from .renderer import NeRFRenderer
+from .renderer import NeRFRenderer, normals_from_gradient
 from .encoding import get_encoder, get_embedder
 from .provider_utils import trunc_exp
 from .. import tcnn
-from ..field import field, field_attach, field_forward_raw, field_forward_rows, packed_weights
+from ..field import field, field_attach, field_density_grad, field_forward_raw, field_forward_rows, packed_weights
 from ..gridencoder import GridEncoder
 
 
@@ -147,6 +147,49 @@ class NeRFNetwork(NeRFRenderer):
                                          with_rgb=False, wimg=self._weight_image())
             return {'sigma': sigma}
         return {'sigma': self._geo(x)[1]}
+
+    # ---- field normals (csrc/field_normal.hip).  sigma = exp(raw(x) + blob(x)), so grad_x log sigma = grad_x raw + grad_x blob: one backward
+    # pass through the two MLPs (d raw / d enc), the trilinear derivative of the table contracted with it (per unit-cube coordinate, hence
+    # the 1 / (2 bound)), and the blob's own gradient -blob(x) x / 0.04.  The log-density gradient has the direction of grad sigma and
+    # cannot overflow.  The reference's grid network returns no normals (network_grid.py:177); its renderer calls self.normal(x).
+    def _normals_cfg(self, x, what):
+        cfg = self._fused_cfg()
+        if not cfg:
+            raise NotImplementedError(f"{what}: needs the fused field configuration (opt.fused_field, a 3-D GridEncoder with 2 features per level "
+                                      "and at most 64 in all, tcnn networks with 1 or 2 hidden layers); this model's is not")
+        if not x.is_cuda:
+            raise NotImplementedError(f"{what}: needs CUDA tensors (the gradient kernels have no CPU path), got a {x.device.type} tensor")
+        return cfg
+
+    @torch.no_grad()
+    def split_density_gradient(self, enc, unit, x):
+        """density_gradient on resident features: enc [L, P', 2] with the features of x [P, 3] in its first P rows per level, unit [P, 3]
+        their grid coordinates -> (sigma [P], grad [P, 3])"""
+        enc_dim, n_geo, _ = self._fused_cfg()
+        sigma, g_enc = field_density_grad(enc, x, enc_dim, n_geo, self.network.params, self.density_network.params, enc_level_stride=enc.shape[1])
+        grad = self.pos_en.input_grad(unit, g_enc, half=self._half())
+        grad.div_(2 * self.opt.bound)
+        grad.addcmul_(x, self.gaussian(x).unsqueeze(-1), value=-1.0 / 0.04)
+        return sigma, grad
+
+    @torch.no_grad()
+    def density_gradient(self, x):
+        """x [..., 3] -> {'sigma': [P], 'grad': [P, 3] = grad_x log sigma}, detached, in the fused field's precision (_half())."""
+        self._normals_cfg(x, "density_gradient")
+        x = x.detach().reshape(-1, 3).contiguous().float()
+        enc, unit = self.split_buffers(x.shape[0], x.device)
+        torch.add(x, self.opt.bound, out=unit)                                       # grid.py:156, as split_encode maps them
+        unit.div_(2 * self.opt.bound)
+        self.pos_en.encode_into(unit, enc, 0, half=self._half())
+        sigma, grad = self.split_density_gradient(enc, unit, x)
+        return {'sigma': sigma, 'grad': grad}
+
+    @torch.no_grad()
+    def normal(self, x):
+        """x [..., 3] -> [P, 3] unit normals -grad / |grad| of the density's level sets, zero where |grad|^2 < 1e-20 (safe_normalize's
+        epsilon, provider_utils.py:125-126): the method the reference's run_cuda calls."""
+        self._normals_cfg(x, "normal")
+        return normals_from_gradient(self.density_gradient(x)['grad'])
 
     # ---- split evaluation (renderer._run_fused): the grid features of a sample list are gathered block by block into ONE kernel-layout
     # buffer, so the coarse samples of run() — whose features the density pass needs anyway — are not gathered a second time for the

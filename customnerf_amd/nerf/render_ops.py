@@ -148,6 +148,25 @@ def composite_run_indexed_aux(sigmas, rgbc, z_vals, src_index, nears, fars, num_
     return out_w, sig_s, rgbc_s
 
 
+@torch.no_grad()
+def composite_normals(weights, src_index, grad_x, dirs):
+    """weights [V,N,S] (V = 1..3, sorted order), src_index [N,S] int32 (sorted position -> row of grad_x) or None = identity, grad_x [P,3] the
+    density gradient of the sample list, dirs [N,3] -> normal_map [V,N,3] = sum w n, orient [V,N] = sum w max(0, n . d)^2 with
+    n = -g / |g| (zero below safe_normalize's epsilon): renderer.py:469-470 and the summand of loss_orient (:428).  Detached."""
+    require_cuda(weights, src_index, grad_x, dirs)
+    weights, grad_x, dirs = weights.detach().contiguous().float(), grad_x.detach().contiguous().float(), dirs.detach().contiguous().float()
+    V, N, S = weights.shape
+    if src_index is not None:
+        src_index = src_index.contiguous()
+        assert src_index.dtype == torch.int32 and src_index.numel() == N * S
+    assert dirs.numel() == N * 3 and grad_x.dim() == 2 and grad_x.shape[1] == 3
+    nmap = torch.empty(V, N, 3, dtype=torch.float32, device=weights.device)
+    orient = torch.empty(V, N, dtype=torch.float32, device=weights.device)
+    check(lib.cnerf_composite_normals(ptr(weights), ptr(src_index), ptr(grad_x), ptr(dirs), V, N, S, grad_x.shape[0], ptr(nmap), ptr(orient), stream()),
+          "composite_normals")
+    return nmap, orient
+
+
 class _CompositeRun(Function):
     """out_ray [3,N,6] (all/fg/bg x image rgb, depth, weights_sum, render_mask), weights [3,N,S]"""
 

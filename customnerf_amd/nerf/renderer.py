@@ -16,6 +16,7 @@ Reference defects handled deliberately (SURVEY.md "Known reference defects"):
   * the output-dead density pass over the fine samples (renderer.py:353) is skipped unless
     `opt.eval_fine_density` asks for it (output-identical, tests/test_oracle_golden.py proves it on the reference).
 """
+import inspect
 import math
 
 import numpy as np
@@ -60,6 +61,14 @@ def convert_sigma_samples_to_ply(input_3d_sigma_array, voxel_grid_origin, volume
         mesh_points = mesh_points - offset
     _mesh.write_ply(ply_filename_out, mesh_points, faces)
     return verts, faces, normals
+
+
+def normals_from_gradient(grad):
+    """[..., 3] density gradient -> unit normals -grad / |grad|, zero where |grad|^2 < 1e-20 (safe_normalize's epsilon,
+    provider_utils.py:125-126; there the division by sqrt(eps) leaves a vector of length < 1, here it is the zero vector, as in
+    cnerf_composite_normals)"""
+    q = (grad * grad).sum(-1, keepdim=True)
+    return torch.where(q >= 1e-20, -grad / q.clamp_min(1e-20).sqrt(), torch.zeros_like(grad))
 
 
 class _Lazy:
@@ -139,10 +148,14 @@ class NeRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------------------------------ run (the path `-O2` takes)
     def run(self, rays_o, rays_d, num_steps=128, upsample_steps=128, light_d=None, ambient_ratio=1.0, shading='albedo',
-            bg_color=None, perturb=False, _draws=None, **kwargs):
+            bg_color=None, perturb=False, _draws=None, normals=False, **kwargs):
         """renderer.py:278-405.  rays_o, rays_d [B,N,3] (B == 1) -> result dict, on the fused HIP kernels (no torch fallback: CPU
         tensors raise).  `_draws` = dict(light, z, u) replays the RNG draws of :305, :317 and sample_pdf:37 (tests).
-        The reference fills its result dict only under `opt.train_conf` (:383-405): without it the dict is empty here too."""
+        The reference fills its result dict only under `opt.train_conf` (:383-405): without it the dict is empty here too.
+        normals=True adds the field's normals (density_gradient of the subclass; csrc/field_normal.hip), detached even when grad is enabled:
+        'normal_map' [*prefix, 3] = sum w n (renderer.py:469-470; 'fg' and 'bg' get theirs from their own weights), 'orient' [*prefix] =
+        sum w max(0, n . d)^2 (the summand of loss_orient, :428, per ray) and 'normal' [N, S, 3], the per-sample normals in sorted order
+        (computed on first access).  With the default no launch is added and no key."""
         require_cuda(rays_o, rays_d)
         if not getattr(self.opt, 'train_conf', 0):
             return {}
@@ -150,7 +163,7 @@ class NeRFRenderer(nn.Module):
             # (upsample_steps == 0 fails in the reference as well: `weights` is bound only inside `if upsample_steps > 0`, renderer.py:333-384)
             raise ValueError(f"run(): the sampling kernels take 3..128 coarse and 2..128 importance samples per ray (got {num_steps} + {upsample_steps}; "
                              "the reference's recipe is 64 + 64)")
-        return self._run_fused(rays_o, rays_d, num_steps, upsample_steps, perturb, _draws, fg_bg=bool(kwargs.get('fg_bg', True)))
+        return self._run_fused(rays_o, rays_d, num_steps, upsample_steps, perturb, _draws, fg_bg=bool(kwargs.get('fg_bg', True)), normals=bool(normals))
 
     def _dirs_twice(self, rays_d):
         """[d | d] for the split sample list, cached per view: a dataset's ray directions are resident tensors that come back every epoch
@@ -179,7 +192,7 @@ class NeRFRenderer(nn.Module):
             raise ValueError("run() with opt.train_conf needs forward() to return rgb + 1 confidence channel (network_grid.py:126-129)")
         return sigmas.reshape(-1), rgbc.reshape(-1, 4)
 
-    def _run_fused(self, rays_o, rays_d, num_steps, upsample_steps, perturb, _draws=None, fg_bg=True):
+    def _run_fused(self, rays_o, rays_d, num_steps, upsample_steps, perturb, _draws=None, fg_bg=True, normals=False):
         """run() on the fused kernels: 2 sampling launches + 2 field launches (+1 gather each) + 1 composite launch.
         Same result dict as run(); RNG draws keep the reference's order (rand(N,T) then rand(N,t)).
         fg_bg=False (the reconstruction trainer, whose loss reads the first composite only): the edit-region / background composites are not
@@ -289,6 +302,23 @@ class NeRFRenderer(nn.Module):
         if fg_bg or not split:                                               # (fg_bg=False: the two composites were not computed — no such keys)
             results['fg'] = pack(1)
             results['bg'] = pack(2)
+        if normals:
+            # the gradient of the whole sample list: on the split path from the resident features and grid coordinates (no second gather)
+            with torch.no_grad():
+                if split:
+                    grad_x = self.split_density_gradient(enc, unit, xyz_list)[1]
+                    order = src
+                else:
+                    grad_x = self.density_gradient(xyz_all.view(-1, 3))['grad']
+                    order = None
+                V = 3 if 'fg' in results else 1
+                w = [weights_of(v) for v in range(V)]
+                w = torch.stack([x.get() if isinstance(x, _Lazy) else x for x in w])
+                nmap, orient = render_ops.composite_normals(w, order, grad_x, rays_d)
+            for v, r in enumerate((results, results.get('fg'), results.get('bg'))[:V]):
+                r['normal_map'] = nmap[v].reshape(*prefix, 3)
+                r['orient'] = orient[v].reshape(*prefix)
+            results['normal'] = _Lazy(lambda: normals_from_gradient(grad_x if order is None else grad_x[order.reshape(-1).long()]).view(N, S, 3))
         return results
 
     def weights_sum_i(self, sample_dist, sigmas, normals, dirs, weights, z_vals, nears, fars, rgbs, prefix, masks=None,
@@ -328,9 +358,13 @@ class NeRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------------------------------ run_cuda (occupancy march)
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, light_d=None, ambient_ratio=1.0, shading='albedo', bg_color=None,
-                 perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4, _noises=None, **kwargs):
+                 perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4, _noises=None, normals=False, **kwargs):
         """renderer.py:597-718: occupancy-grid march.  Training: one compacted sample list per batch (march_rays_train ->
-        field -> composite_rays_train); inference: the alive-ray loop of :661-688 with device-side compaction."""
+        field -> composite_rays_train); inference: the alive-ray loop of :661-688 with device-side compaction.
+        normals=True raises NotImplementedError: normal maps exist on run() only."""
+        if normals:
+            raise NotImplementedError("run_cuda(normals=True): normal maps are composited by run() only; the occupancy march has none "
+                                      "(use a model with opt.cuda_ray off, or model.normal(x) per point)")
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.cuda().contiguous().view(-1, 3)
         rays_d = rays_d.cuda().contiguous().view(-1, 3)
@@ -586,7 +620,8 @@ class NeRFRenderer(nn.Module):
         It runs after component removal and fill_holes and before smooth, simplify and target_faces; 'deviation' and bake_from='source'
         compare with the surface as extracted, so they report what the remesh cost, and deviation=True counts it as a lossy pass.
         'remesh' joins the dict: voxel_remesh's info (shape, origin, spacing, bricks, evaluations, rounds, offset, beta).  With
-        remesh=None the key is absent and every output is what it was."""
+        remesh=None the key is absent and every output is what it was.
+        The field's own normals on the vertices: extract_mesh_normals(normals='field', ...), or save_mesh(path, normals='field', ...)."""
         return _export.extract_mesh(
             self, resolution=resolution, threshold=threshold, aabb=aabb, chunk=chunk, part=part, view_dir=view_dir, color=color,
             min_component_faces=min_component_faces, keep_largest=keep_largest, simplify=simplify, target_faces=target_faces, texture=texture,
@@ -594,6 +629,20 @@ class NeRFRenderer(nn.Module):
             deviation_max_samples=deviation_max_samples, ao=ao, texture_layout=texture_layout, bake_from=bake_from, bake_reach=bake_reach,
             normal_map=normal_map, sparse=sparse, sparse_probe=sparse_probe, tsdf=tsdf, fill_holes=fill_holes, topology=topology,
             color_views=color_views, remesh=remesh)
+
+    @torch.no_grad()
+    def extract_mesh_normals(self, normals='field', **kw):
+        """extract_mesh(**kw) with the source of the vertex normals chosen (extract_mesh itself keeps the signature its callers know).
+        normals='field' replaces the final mesh's vertex normals by the field's own, self.normal(verts) — the analytic gradient of the
+        density (csrc/field_normal.hip), which holds sub-voxel orientation that normals interpolated from the lattice cannot — after the
+        last geometry stage and before colour, texture and normal-map baking read them.  A vertex keeps its geometric normal where the
+        field's is zero or opposes it (dot <= 0); 'field_normals' joins the dict: {'kept_geometric': that count}.  Not with part != 'all',
+        tsdf= or remesh=, whose surfaces are not the density's level set (ValueError).  normals='mesh' is extract_mesh(**kw)."""
+        args = inspect.signature(NeRFRenderer.extract_mesh).bind(self, **kw)
+        args.apply_defaults()
+        kw = dict(args.arguments)
+        del kw['self']
+        return _export.extract_mesh(self, normals=normals, **kw)
 
     def save_mesh(self, path, **kw):
         """extract_mesh(**kw) written to `path` -> the mesh dict.  A path ending in .obj writes a Wavefront OBJ (mesh.write_obj: positions,
@@ -642,8 +691,18 @@ class NeRFRenderer(nn.Module):
     def render_view(self, c2w, intrinsics, H, W, convention='nerfstudio', min_opacity=0.5, max_ray_batch=1 << 16, **render_kw):
         """render_depth's view with its colour, from the same one pass per ray batch: -> {'image': [H, W, 3] float32, the composited
         colour render() returns (over its background, where one is set), 'depth', 'opacity'}; depth and opacity are render_depth's, bit
-        for bit.  What extract_mesh(color_views=...) projects onto the mesh."""
-        return _export.render_view(self, c2w, intrinsics, H, W, convention, min_opacity, max_ray_batch, render_kw, True, "render_view")
+        for bit.  What extract_mesh(color_views=...) projects onto the mesh.
+        Five keywords are taken out of **render_kw (defaults normals=False, shading=None, light_d=None, ambient_ratio=0.1, path=None):
+        normals=True (run() only: the occupancy march raises NotImplementedError) adds 'normal' [H, W, 3]: the world-space normal map
+        run(normals=True) composites, renormalised per pixel, zero where the opacity is below min_opacity.
+        shading in ('normal', 'lambertian', 'textureless') implies normals and adds 'shaded' [H, W, 3]: 'normal' (n + 1) / 2;
+        'lambertian' image * (a + (1 - a) max(0, n . l)) with a = ambient_ratio and l = light_d normalised (default: towards the camera,
+        against the view direction of the image centre); 'textureless' the same with albedo 1.  This is DEFERRED shading of the
+        composited normal, one evaluation per pixel — not the per-sample shading of stable-dreamfusion, which lights every sample before
+        compositing.  `path` writes 'shaded' (without shading: the normal map as (n + 1) / 2, without normals: the image) as a PNG
+        (mesh.write_png).  With the defaults the result is what it was."""
+        own = {k: render_kw.pop(k, v) for k, v in _export.VIEW_OPTIONS.items()}
+        return _export.render_view(self, c2w, intrinsics, H, W, convention, min_opacity, max_ray_batch, render_kw, True, "render_view", **own)
 
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=2048, **kwargs):
         """renderer.py:1719-1733."""

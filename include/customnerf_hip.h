@@ -257,6 +257,32 @@ int cnerf_field_backward_ex(const void *enc, const float *xyz, const float *dirs
                             uint64_t workspace_bytes, int dtype, const uint8_t *tile_live, void *stream);
 int cnerf_field_backward_workspace_bytes(uint32_t P, uint32_t enc_dim, uint32_t n_hidden_geo, uint32_t n_rgb_out, int dtype,
                                          uint64_t *bytes);
+/* Field normals (additive; no counterpart kernel in the reference, whose grid network returns no normals: network_grid.py:177).
+ * sigma = exp(raw + blob) with raw = MLP_den(MLP_net(enc))[0], so the surface normal is -grad_x(raw + blob) normalised; three kernels
+ * give the chain's factors and the per-ray sums of renderer.py:428, :469-470.  The blob's gradient is the caller's.
+ *
+ * cnerf_field_density_grad: grad_enc [L, P, 2] FLOAT32 (8-byte aligned) = d raw / d enc for the first P samples of enc [L, stride, 2] (dtype,
+ * kernel layout, enc_level_stride as in cnerf_field_forward_strided), and sigma [P] float32 (NULL: not wanted), bit-identical to the
+ * forward's.  One backward pass through the two MLPs with upstream gradient 1, no weight gradients, no workspace, no atomics.
+ * CNERF_F16 recomputes the forward with its roundings (the ReLU masks are the forward's) and rounds the gradient vector to half between
+ * layers, fp32 accumulate; CNERF_F32 is exact float32.  Shapes as the forward: enc_dim even <= 64, n_hidden_geo 1 | 2, else CNERF_EINVAL. */
+int cnerf_field_density_grad(const void *enc, const float *xyz, uint32_t P, uint32_t enc_dim, uint32_t n_hidden_geo, const float *params_net,
+                             const float *params_den, float *sigma, float *grad_enc, int dtype, uint32_t enc_level_stride, void *stream);
+/* grad_inputs [B, 3] float32 = sum_level sum_corner d w / d u * (embeddings[index] . grad_enc[level, b, :]), per unit-cube coordinate: what
+ * gridencoder.cu:342-368 computes from a materialised dy_dx, without writing one.  inputs [B, 3] in [0, 1] (outside: zero, as the
+ * forward's features); grad_enc [L, grad_level_stride, 2] float32, 8-byte aligned (0 = B).  fp32 accumulation, levels summed in order:
+ * the same bits on every run.  The fused field's configuration only — D = 3, C = 2, interpolation 0 (linear), align_corners 0, gridtype
+ * 0 | 1, L <= 32, embeddings of dtype CNERF_F32 | CNERF_F16 — anything else is CNERF_EINVAL. */
+int cnerf_grid_encode_input_grad(const float *inputs, const void *embeddings, const int32_t *offsets_host, const float *grad_enc,
+                                 float *grad_inputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
+                                 int align_corners, uint32_t interpolation, int dtype, uint32_t grad_level_stride, void *stream);
+/* normal_map [V, N, 3] = sum_s w n and orient [V, N] = sum_s w max(0, n . d)^2 (the summand of loss_orient, renderer.py:428) with
+ * n = -g / |g| (0 where |g|^2 < 1e-20: safe_normalize's epsilon) of g = grad_x [P, 3] read through src_index [N, S] (sorted position ->
+ * row; NULL = identity, then N S <= P), weights [V, N, S] as cnerf_composite_run_indexed returns them (V = 1..3), dirs [N, 3].
+ * Rows >= P count as zero normals.  Plain float32 in a fixed order. */
+int cnerf_composite_normals(const float *weights, const int32_t *src_index, const float *grad_x, const float *dirs, uint32_t V, uint32_t N,
+                            uint32_t S, uint32_t P, float *normal_map, float *orient, void *stream);
+
 /* Packed weights (ABI 5).  Every launch above re-derives its fp16 MFMA fragment image of the three MLPs from the float32 parameters (14 us per
  * launch, three launches per training step).  cnerf_field_pack_weights writes that image once — `image`: 16-byte aligned device buffer of
  * cnerf_field_weight_image_bytes() bytes; the caller repacks after every change of the parameters — and the _img variants copy it into LDS
