@@ -182,36 +182,50 @@ class UNet:
         ctx = ctx.to(torch.float16).contiguous()
         return {id(a): a.context_kv(ctx) for a in self.transformers()}
 
-    def forward(self, x, t, ctx, ctx_kv=None):
+    def forward(self, x, t, ctx, ctx_kv=None, taps=None):
         """x [B, h, w, 8] half (4 latent channels + zero padding), t [B] float32 on device, ctx [B, 77, D] half
-        -> eps [B, h, w, 4] half.  ctx_kv: context_kv(ctx) (then ctx itself is not read)."""
+        -> eps [B, h, w, 4] half.  ctx_kv: context_kv(ctx) (then ctx itself is not read).
+        taps: a list that receives (name, tensor) after every stage, for tests that compare the network stage by stage: "temb" (the time
+        embedding MLP), "tp" (the stacked time projection, float32 [B, sum Cout]), "conv_in", every resnet / transformer / down- and
+        upsampler convolution under its state-dict prefix ("down_blocks.1.attentions.0.", "up_blocks.0.upsamplers.0.conv."), and "out".
+        The tensors are the live activations, not copies; None (the default, and what graphed() captures) records nothing."""
+        tap = taps.append if taps is not None else None
         kvs = ctx_kv if ctx_kv is not None else {}
         cfg = self.cfg
         G, eps = cfg["groups"], cfg["eps"]
         temb = ops.timestep_embedding(t, cfg["block_out_channels"][0])
         temb = ops.linear(ops.linear(temb, self.t1w, bias=self.t1b, act=ops.ACT_SILU), self.t2w, bias=self.t2b)
+        if tap: tap(("temb", temb))
         temb_act = ops.silu(temb)                                                      # every resnet applies SiLU before time_emb_proj
         tp = ops.linear(temb_act, self.tpw, bias=self.tpb, out32=True)                 # [B, sum Cout] float32
+        if tap: tap(("tp", tp))
         pool = ops.SumsPool(4 * len(self._resnets) + 34, x.shape[0], G, x.device)        # one zero-fill for every GroupNorm of the pass (a few slices go unused)
         tbs = {id(r): tp[:, r.t_off:r.t_off + r.t_n] for r in self._resnets}          # per-block [B, Cout] strided views (bias_rows operand)
         hs0 = pool.take()
         h, ok = ops.conv2d(x, self.ciw, self.cib, 3, gn=(hs0, G, x.shape[1] * x.shape[2]))
         hs = (hs0, ok)                                                             # statistics of h for the norm that reads it next
+        if tap: tap(("conv_in", h))
         skips = [h]
-        for res, att, ds in self.down:
+        for bi, (res, att, ds) in enumerate(self.down):
             for j, r in enumerate(res):
                 h, hs = r(h, tbs[id(r)], G, eps, pool, x_sums=hs, out_gn=True)
+                if tap: tap((f"down_blocks.{bi}.resnets.{j}.", h))
                 if att is not None:
                     h, hs = att[j](h, ctx, G, pool, x_sums=hs, out_gn=True, kv=kvs.get(id(att[j])))
+                    if tap: tap((f"down_blocks.{bi}.attentions.{j}.", h))
                 skips.append(h)
             if ds is not None:
                 so = pool.take()
                 h, ok = ops.conv2d(h, ds[0], ds[1], 3, stride=2, pad=1, gn=(so, G, (h.shape[1] // 2) * (h.shape[2] // 2)))
                 hs = (so, ok)
+                if tap: tap((f"down_blocks.{bi}.downsamplers.0.conv.", h))
                 skips.append(h)
         h, hs = self.mid[0](h, tbs[id(self.mid[0])], G, eps, pool, x_sums=hs, out_gn=True)
+        if tap: tap(("mid_block.resnets.0.", h))
         h, hs = self.mid[1](h, ctx, G, pool, x_sums=hs, out_gn=True, kv=kvs.get(id(self.mid[1])))
+        if tap: tap(("mid_block.attentions.0.", h))
         h, hs = self.mid[2](h, tbs[id(self.mid[2])], G, eps, pool, x_sums=hs, out_gn=False)
+        if tap: tap(("mid_block.resnets.1.", h))
         n_up = len(self.up)
         for bi, (res, att, us) in enumerate(self.up):
             for j, r in enumerate(res):
@@ -220,16 +234,21 @@ class UNet:
                 sc_ = pool.take()
                 hc, okc = ops.concat_channels(h, skips.pop(), gn=(sc_, G, h.shape[1] * h.shape[2]))
                 h, hs = r(hc, tbs[id(r)], G, eps, pool, x_sums=(sc_, okc), out_gn=att is not None)
+                if tap: tap((f"up_blocks.{bi}.resnets.{j}.", h))
                 if att is not None:
                     last = bi == n_up - 1 and j == len(res) - 1                     # -> conv_norm_out
                     h, hs = att[j](h, ctx, G, pool, x_sums=hs, out_gn=last, kv=kvs.get(id(att[j])))
+                    if tap: tap((f"up_blocks.{bi}.attentions.{j}.", h))
             if us is not None:
                 h = ops.conv2d(h, us[0], us[1], 3, ups=2)
+                if tap: tap((f"up_blocks.{bi}.upsamplers.0.conv.", h))
         if hs is not None:
             h, _ = ops.groupnorm(h, self.now, self.nob, G, eps, True, sums=hs[0], sums_ready=hs[1])
         else:
             h, _ = ops.groupnorm(h, self.now, self.nob, G, eps, True, pool)
-        return ops.conv2d(h, self.cow, self.cob, 3)
+        out = ops.conv2d(h, self.cow, self.cob, 3)
+        if tap: tap(("out", out))
+        return out
 
     __call__ = forward
 
