@@ -372,6 +372,10 @@ __global__ void __launch_bounds__(1024) k_bin_accum(const BinRec<T> *__restrict_
 
 // the four (y, z) corner pairs of a sample on one level: entries of the x and x+1 corner, the weight of the pair, the x fraction
 // (restates ge_cell<3>, grid_common.h, in its own text: calling it changes k_bin3_emit's listing)
+// MODE: the level's index rule (ge_level_mode) as a compile-time property of the caller's body.  The third form serves dense levels and
+// power-of-two hashed / wrapped ones (b3_plan), so the rule is GE_MODE_DENSE, GE_MODE_HASH2 or GE_MODE_TILED2; each gives the entries of
+// ge_index, bit for bit
+template <int MODE>
 __device__ __forceinline__ void b3_pairs(const float (&in)[3], const GridLevels &lv, uint32_t level, uint32_t gridtype, bool align_corners,
                                          uint32_t interp, uint32_t (&i0)[4], uint32_t (&i1)[4], float (&wyz)[4], float &fx) {
     const uint32_t hashmap_size = lv.size[level];
@@ -391,15 +395,14 @@ __device__ __forceinline__ void b3_pairs(const float (&in)[3], const GridLevels 
     wyz[0] = oy * oz; wyz[1] = pos[1] * oz; wyz[2] = oy * pos[2]; wyz[3] = pos[1] * pos[2];
     // Level-uniform index arithmetic, shared between the corners (ge_index_m called once per corner recomputes the y / z hash products
     // — sixteen 32-bit multiplies, each a quarter-rate instruction — and the strided sums eight times):
-    const int mode = ge_level_mode<3>(gridtype, align_corners, hashmap_size, resolution);
-    if (mode == GE_MODE_HASH2) {
+    if constexpr (MODE == GE_MODE_HASH2) {
         const uint32_t mask = hashmap_size - 1;
         const uint32_t hy0 = pos_grid[1] * 2654435761u, hy1 = hy0 + 2654435761u, hz0 = pos_grid[2] * 805459861u, hz1 = hz0 + 805459861u;
         const uint32_t hyz[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
         const uint32_t x0 = pos_grid[0], x1 = x0 + 1;
 #pragma unroll
         for (int q = 0; q < 4; q++) { i0[q] = (x0 ^ hyz[q]) & mask; i1[q] = (x1 ^ hyz[q]) & mask; }
-    } else if (mode == GE_MODE_DENSE) {
+    } else if constexpr (MODE == GE_MODE_DENSE) {
         const uint32_t s1 = align_corners ? resolution : resolution + 1, s2 = s1 * s1;
         const uint32_t lin = pos_grid[0] + pos_grid[1] * s1 + pos_grid[2] * s2;
         i0[0] = lin; i0[1] = lin + s1; i0[2] = lin + s2; i0[3] = lin + s1 + s2;
@@ -413,15 +416,14 @@ __device__ __forceinline__ void b3_pairs(const float (&in)[3], const GridLevels 
             }
         }
     } else {
-        ge_dispatch_mode(mode, [&](auto mode_c) {
+        static_assert(MODE == GE_MODE_TILED2, "b3_plan admits power-of-two hashed slots only: a level is dense, GE_MODE_HASH2 or GE_MODE_TILED2");
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             uint32_t pgl[3] = {pos_grid[0], pos_grid[1] + (q & 1), pos_grid[2] + (q >> 1)};
-            i0[q] = ge_index_m<3, decltype(mode_c)::value>(gridtype, align_corners, hashmap_size, resolution, pgl);
+            i0[q] = ge_index_m<3, MODE>(gridtype, align_corners, hashmap_size, resolution, pgl);
             pgl[0] += 1;
-            i1[q] = ge_index_m<3, decltype(mode_c)::value>(gridtype, align_corners, hashmap_size, resolution, pgl);
+            i1[q] = ge_index_m<3, MODE>(gridtype, align_corners, hashmap_size, resolution, pgl);
         }
-        });
     }
 }
 
@@ -571,7 +573,8 @@ __device__ __forceinline__ void b3_push_record(long long *acc, B3Pending &c, con
 //                 that start at zero, scans the 128 counters (the block's own histogram) and sorts the records by bin into the LDS staging area.
 //                 Samples whose gradient is exactly zero on this level emit nothing (they add exactly zero to every fixed-point sum).
 //                 A sample of a dense level of at most 64 bins whose eight corners share a bin takes ONE ticket for its four records
-//                 (b3_emit<true>: the second counter class, see there; k_bin3_emit holds the body with and without it).
+//                 (the TWO bodies of b3_emit: the second counter class, see there).  k_bin3_emit holds one compiled body per level class — dense or hashed,
+//                 narrow or wide, with or without the second class, per index rule — and a workgroup takes the one of its level.
 //     hashed levels (interleaved bins, loads near-uniform): every bin owns a slab region of fixed capacity (1.5 x its expected load); the block
 //                 reserves its run in each bin with ONE returning atomic per (block, bin) on the bin's cursor — issued right after the scan,
 //                 consumed at copy-out — and copies its runs there: bin-major, densely packed, exactly the layout the accumulate kernel streams.
@@ -642,7 +645,10 @@ __device__ __forceinline__ bool b3_paired_h(uint32_t i0, uint32_t i1) {
     return m != 0 && m < (1u << B3_K) && (m & (m + 1)) == 0;
 }
 
-template <bool TWO>
+// One body per LEVEL CLASS, all compile-time: DENSE (contiguous bins, one run per block) or hashed / wrapped (interleaved bins, reservations), WIDE
+// (more than 128 bins: 512 counters, copy-out bin by bin) or narrow, TWO (the second counter class below: dense levels of at most 64 bins), MODE (the
+// index rule of b3_pairs).  k_bin3_emit holds the bodies that can occur and a workgroup takes the one of its level.
+template <bool DENSE, bool WIDE, bool TWO, int MODE>
 __device__ __forceinline__ void b3_emit(const __half *__restrict__ grad, const float *__restrict__ inputs, const GridLevels lv,
                                                           const Bin3Plan plan, uint32_t *__restrict__ runs, uint32_t *__restrict__ cursor,
                                                           uint2 *__restrict__ hslab, uint2 *__restrict__ dslab, uint32_t B,
@@ -669,13 +675,14 @@ __device__ __forceinline__ void b3_emit(const __half *__restrict__ grad, const f
     const uint32_t slot = blockIdx.x % n_slots, pb = blockIdx.x / n_slots;
     const uint32_t level = lv.order[slot];
     const uint32_t bin0 = plan.p.bin_first[slot], nch = plan.p.bin_first[slot + 1] - bin0;
-    const bool dense_lvl = plan.dense_slot[slot] != 0xFFFFFFFFu;
+    constexpr bool dense_lvl = DENSE;
+    static_assert(!TWO || (DENSE && !WIDE), "the two-counter class is a property of dense levels of at most 64 bins");
     const uint32_t hb = plan.hbits[slot];
     // WIDE levels (round 6: more than 128 bins — T = 2^20 / 2^21 tables, the reference field's own): B3_WIDE_CHUNKS-entry counter tables in place of
     // the one-byte bin ids of the staged records (the copy-out then goes bin by bin instead of slot by slot), so that the workgroup's LDS
     // stays below half a CU's.  Block-uniform.
-    const bool wide = nch > B3_NARROW_CHUNKS;
-    const uint32_t NBN = wide ? B3_WIDE_CHUNKS : B3_NARROW_CHUNKS;
+    constexpr bool wide = WIDE;
+    constexpr uint32_t NBN = wide ? B3_WIDE_CHUNKS : B3_NARROW_CHUNKS;
     uint32_t *cnt = reinterpret_cast<uint32_t *>(b3_lds + (size_t)B3_CAP * (wide ? 8 : 9));
     uint32_t *start = cnt + NBN;
     uint32_t *gdst = start + NBN;                                                   // hashed: first record of the block's run inside the bin's region
@@ -690,11 +697,12 @@ __device__ __forceinline__ void b3_emit(const __half *__restrict__ grad, const f
     // run per (bin, block) for the accumulate, and pair-major across the WHOLE block — corners are shared between neighbouring cells (the
     // q = 1 entry of one cell is the q = 0 entry of the next), so a stretch of the run that mixes the pairs of neighbouring samples has the
     // lanes of one accumulate instruction meet on the same LDS address (pair-major per wave, measured: docs/HISTORY.md B.31).
-    // The class is a COMPILE-TIME property of the body: k_bin3_emit holds the body twice and a workgroup takes the one of its level.  With the
+    // The class is a COMPILE-TIME property of the body, like every other class of the level (the template parameters above).  With the
     // class as a run-time flag of one body, every other level paid for it in code generation (emit +10 us on a fitted field, +14-22 us on the
-    // bear table, also with the flag never set: docs/HISTORY.md B.31).
+    // bear table, also with the flag never set: docs/HISTORY.md B.31); with dense / wide / the index rule as run-time branches of two bodies the
+    // emit ran 421 us where it now runs 390 (docs/HISTORY.md B.34).
     constexpr bool two_class = TWO;
-    if (TWO) __builtin_assume(dense_lvl && nch <= B3_NARROW_CHUNKS / 2);
+    if (TWO) __builtin_assume(nch <= B3_NARROW_CHUNKS / 2);
     if (threadIdx.x < NBN) cnt[threadIdx.x] = 0;
     __syncthreads();
     constexpr int PPT = B3_PTS / B3_THREADS;
@@ -705,7 +713,8 @@ __device__ __forceinline__ void b3_emit(const __half *__restrict__ grad, const f
     float wyz[PPT][4], fx[PPT], g0[PPT], g1[PPT];
     // ---- phase 1: corner pairs, gradients, one LDS ticket per record (ticket = rank of the record inside the block's run for its bin)
     // every load of the thread's samples first, unconditionally (clamped row): the coordinates and the gradient of a sample are independent
-    // loads — `if (in range) load gradient` made them two serial memory round trips per sample (A.1 item 7)
+    // loads — `if (in range) load gradient` made them two serial memory round trips per sample (A.1 item 7).  (Issued in FRONT of the counters'
+    // zeroing, with a first barrier that waits for LDS alone: k_bin3_emit 390 -> 436 us, measured and dropped — docs/HISTORY.md B.34.)
     float in_[PPT][3];
     FeatVec<__half, 2> gh[PPT];
 #pragma unroll
@@ -728,7 +737,7 @@ __device__ __forceinline__ void b3_emit(const __half *__restrict__ grad, const f
                 for (int q = 0; q < 4; q++) { i0[i][q] = (b * 4 + q) * 2654435761u % lv.size[level]; i1[i][q] = i0[i][q] ^ 1u; wyz[i][q] = 0.25f; }
                 fx[i] = in[0] - floorf(in[0]);
             } else {
-                b3_pairs(in, lv, level, gridtype, align_corners, interp, i0[i], i1[i], wyz[i], fx[i]);
+                b3_pairs<MODE>(in, lv, level, gridtype, align_corners, interp, i0[i], i1[i], wyz[i], fx[i]);
             }
             b3_poison(g0[i], g1[i], grad_grid, lv, level, i0[i][0], found_inf);
 #ifdef CNERF_TUNING
@@ -962,11 +971,26 @@ __global__ void __launch_bounds__(B3_THREADS, B3_THREADS >= 1024 ? 8 : 4) k_bin3
                                                           uint2 *__restrict__ hslab, uint2 *__restrict__ dslab, uint32_t B,
                                                           uint32_t gridtype, int align_corners, uint32_t interp, float *__restrict__ grad_grid, uint32_t n_slots,
                                                           uint32_t abl_arg, float *__restrict__ found_inf) {
+    // The class of the workgroup's level, from scalars: a workgroup runs ONE of the bodies below and the register allocation, the branches and
+    // the instruction-cache footprint it pays for are those of that body alone (docs/HISTORY.md B.34).  A dense slot (b3_is_dense) is a
+    // GE_MODE_DENSE level; a hashed slot has a power-of-two table (b3_plan): GE_MODE_HASH2 on a hash grid, GE_MODE_TILED2 on a tiled one.
     const uint32_t slot = blockIdx.x % n_slots;                                     // (as in the body: level fastest)
-    if (plan.dense_slot[slot] != 0xFFFFFFFFu && plan.p.bin_first[slot + 1] - plan.p.bin_first[slot] <= B3_NARROW_CHUNKS / 2)
-        b3_emit<true>(grad, inputs, lv, plan, runs, cursor, hslab, dslab, B, gridtype, align_corners, interp, grad_grid, n_slots, abl_arg, found_inf);
-    else
-        b3_emit<false>(grad, inputs, lv, plan, runs, cursor, hslab, dslab, B, gridtype, align_corners, interp, grad_grid, n_slots, abl_arg, found_inf);
+    const uint32_t nch = plan.p.bin_first[slot + 1] - plan.p.bin_first[slot];
+    const bool dense = plan.dense_slot[slot] != 0xFFFFFFFFu, wide = nch > B3_NARROW_CHUNKS;
+#define B3_EMIT_BODY(D_, W_, T_, M_) b3_emit<D_, W_, T_, M_>(grad, inputs, lv, plan, runs, cursor, hslab, dslab, B, gridtype, align_corners, interp, grad_grid, n_slots, abl_arg, found_inf)
+    if (dense) {
+        if (nch <= B3_NARROW_CHUNKS / 2) B3_EMIT_BODY(true, false, true, GE_MODE_DENSE);
+        else if (!wide) B3_EMIT_BODY(true, false, false, GE_MODE_DENSE);
+        else B3_EMIT_BODY(true, true, false, GE_MODE_DENSE);
+    } else {
+        const uint32_t level = lv.order[slot];
+        const bool hash2 = ge_level_mode<3>(gridtype, align_corners, lv.size[level], lv.resolution[level]) == GE_MODE_HASH2;
+        if (hash2 && !wide) B3_EMIT_BODY(false, false, false, GE_MODE_HASH2);
+        else if (hash2) B3_EMIT_BODY(false, true, false, GE_MODE_HASH2);
+        else if (!wide) B3_EMIT_BODY(false, false, false, GE_MODE_TILED2);
+        else B3_EMIT_BODY(false, true, false, GE_MODE_TILED2);
+    }
+#undef B3_EMIT_BODY
 }
 
 // per bin: dense level — exclusive prefix of the run counts (low half of the run-table words) over the point blocks -> pre, and the bin total;
