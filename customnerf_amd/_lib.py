@@ -76,6 +76,8 @@ SIGNATURES = {
     "cnerf_composite_run_indexed_variants": [vp, vp, vp, vp, vp, u32, u32, u32, i32, f32, vp, vp, vp, vp, vp, u32, vp],
     "cnerf_composite_run_backward_indexed": [vp, vp, vp, vp, vp, vp, u32, u32, u32, i32, f32, i32, i32, vp, vp, vp, vp],
     "cnerf_composite_run_backward_indexed_flush": [vp, vp, vp, vp, vp, vp, u32, u32, u32, i32, f32, i32, i32, vp, vp, vp, i32, vp, vp],
+    "cnerf_ray_reg_forward": [vp, vp, vp, vp, vp, u32, u32, u32, i32, f32, vp, u32, f32, vp, vp],
+    "cnerf_ray_reg_backward": [vp, vp, vp, vp, vp, vp, u32, u32, u32, i32, f32, i32, vp, u32, f32, vp, vp, vp],
     "cnerf_adam_step": [vp, vp, vp, vp, vp, u64, f32, f32, f32, f32, u32, f32, i32, vp],
     "cnerf_scaler_check": [vp, u64, vp, vp],
     "cnerf_scaler_watch": [vp],

@@ -509,6 +509,196 @@ __global__ void __launch_bounds__(RN_THREADS) k_composite_run_bwd(const float *_
     }
 }
 
+// ------------------------------------------------------------------------------------------------ ray regularisers
+// Two losses on how a ray's weight is spread along the ray, per composite variant, with w / alpha / T / delta as defined in k_composite_run_fwd:
+//   distortion (mip-NeRF 360)   D = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i,   d = delta / L, m = (z - near) / L + d / 2, L = far - near
+//   ray entropy (InfoNeRF)      H = -sum_i p_i log(p_i + 1e-10),  p = w / (W + 1e-10),  W = sum w;   reported as 0 unless W > min_opacity
+// O(S) per ray, and without a difference of large prefix sums: the samples ascend, so m_l - m_{l-1} = (d_{l-1} + d_l) / 2 =: dm_l >= 0 and
+//   A_k = sum_{j<k} w_j (m_k - m_j) = sum_{l<=k} W_{<l} dm_l        B_k = sum_{j>k} w_j (m_j - m_k) = sum_{l>k} W_{>=l} dm_l
+// are scans of non-negative terms;  D = 2 sum_i w_i A_i + (1/3) sum_i w_i^2 d_i  and  dD/dw_k = 2 (A_k + B_k) + (2/3) w_k d_k.
+//   dH/dw_k = (h_k - sum_i p_i h_i) / (W + 1e-10),  h = -(log(p + 1e-10) + p / (p + 1e-10))       (the gate is a constant)
+// A ray with !(far > near) has no length to normalise by: its losses and gradients are exact zeros (rn_norm_depth would hand on a NaN).
+template <int NCH>
+struct RrRay {                                        // one ray's samples, one per lane and chunk
+    float delta[NCH], d[NCH], dm[NCH], sigma[NCH], conf[NCH];
+    uint32_t row[NCH];
+};
+
+template <int NCH>
+__device__ __forceinline__ void rr_load(RrRay<NCH> &r, const float *__restrict__ sigmas, const float *__restrict__ rgbc, const float *__restrict__ zr,
+                                        const uint32_t *__restrict__ src_index, uint32_t n, uint32_t S, float near, float far, uint32_t num_steps,
+                                        uint32_t lane) {
+    const float L = far - near, sd = L / (float)num_steps;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+        const uint32_t i = ch * 64 + lane;
+        float delta = 0, d = 0, dm = 0, sigma = 0, conf = 0;
+        uint32_t row = 0;
+        if (i < S) {
+            const float z = zr[i];
+            delta = (i + 1 < S) ? zr[i + 1] - z : sd;
+            d = delta / L;
+            dm = i > 0 ? 0.5f * ((z - zr[i - 1]) / L + d) : 0.0f;
+            row = src_index ? src_index[(size_t)n * S + i] : n * S + i;
+            sigma = sigmas[row];
+            conf = rgbc[(size_t)row * 4 + 3];
+        }
+        r.delta[ch] = delta; r.d[ch] = d; r.dm[ch] = dm; r.sigma[ch] = sigma; r.conf[ch] = conf; r.row[ch] = row;
+    }
+}
+
+// weights of variant v and the scans the distortion needs; lanes past S hold alpha = w = 0.  Returns W = sum w (wave-uniform).
+template <int NCH>
+__device__ __forceinline__ float rr_weights(const RrRay<NCH> &r, int v, int soft, float thr, uint32_t S, uint32_t lane, float (&alpha_)[NCH],
+                                            float (&tr_)[NCH], float (&wlt_)[NCH], float (&A_)[NCH]) {
+    float cT = 1.0f, cW = 0.0f, cA = 0.0f;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+        const bool ok = ch * 64 + lane < S;
+        const float e = rn_edit(r.conf[ch], soft, thr);
+        // (expm1f: 1 - expf(-x) loses x's low bits for x << 1, and these losses weigh the faint rays that the image hardly sees)
+        const float alpha = ok ? -expm1f(-r.delta[ch] * (r.sigma[ch] * rn_variant_scale(v, e))) : 0.0f;
+        const float tr = rn_excl_prod_scan(ok ? (1.0f - alpha + 1e-15f) : 1.0f, cT);
+        const float w = alpha * tr;
+        const float wlt = rn_incl_sum_scan(w, cW) - w;                    // W_{<i}
+        alpha_[ch] = alpha; tr_[ch] = tr; wlt_[ch] = wlt;
+        A_[ch] = rn_incl_sum_scan(wlt * r.dm[ch], cA);
+    }
+    return cW;
+}
+
+// out_i = sum_{k>=i} v_k over the ray: the forward scan on mirrored lanes, chunks from the last to the first.  A suffix taken as total minus
+// prefix would lose what lies behind an opaque sample (~1e-15 of the total) to cancellation; this adds only what the suffix holds.
+template <int NCH>
+__device__ __forceinline__ void rr_suffix_incl(const float (&v)[NCH], float (&out)[NCH], uint32_t lane) {
+    float carry = 0.0f;
+#pragma unroll
+    for (int ch = NCH - 1; ch >= 0; ch--) out[ch] = __shfl(rn_incl_sum_scan(__shfl(v[ch], 63 - (int)lane), carry), 63 - (int)lane);
+}
+
+template <int NCH>
+__global__ void __launch_bounds__(RN_THREADS) k_ray_reg_fwd(const float *__restrict__ sigmas, const float *__restrict__ rgbc, const float *__restrict__ z_vals,
+                                                            const float *__restrict__ nears, const float *__restrict__ fars, uint32_t N, uint32_t S,
+                                                            uint32_t num_steps, int soft, float thr, const uint32_t *__restrict__ src_index, uint32_t vmask,
+                                                            float min_opacity, float *__restrict__ out_reg) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t n = blockIdx.x * RN_WAVES + wave;
+    if (n >= N) return;
+    const float near = nears[n], far = fars[n];
+    const bool hit = far > near;                                          // wave-uniform: the wave owns the ray
+    RrRay<NCH> r;
+    if (hit) rr_load(r, sigmas, rgbc, z_vals + (size_t)n * S, src_index, n, S, near, far, num_steps, lane);
+#pragma unroll
+    for (int v = 0; v < 3; v++) {
+        float D = 0.0f, H = 0.0f;
+        if (hit && ((vmask >> v) & 1u)) {                                 // rows of the other variants are zeros and cost no scans
+            float alpha_[NCH], tr_[NCH], wlt_[NCH], A_[NCH];
+            const float W = rr_weights(r, v, soft, thr, S, lane, alpha_, tr_, wlt_, A_);
+            float accD = 0.0f, accH = 0.0f;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ch++) {
+                const float w = alpha_[ch] * tr_[ch];
+                const float p = w / (W + 1e-10f);
+                accD += w * (2.0f * A_[ch]) + (1.0f / 3.0f) * (w * w * r.d[ch]);
+                accH -= p * logf(p + 1e-10f);
+            }
+            D = cn_wave_sum(accD);
+            H = cn_wave_sum(accH);
+            if (!(W > min_opacity)) H = 0.0f;
+        }
+        if (lane == 0) {
+            out_reg[((size_t)v * N + n) * 2] = D;
+            out_reg[((size_t)v * N + n) * 2 + 1] = H;
+        }
+    }
+}
+
+// Backward: G_i = dL/dw_i = g_D dD/dw_i + g_H dH/dw_i per variant, then the chain of k_composite_run_bwd:
+//   dL/da_i = G_i T_i - (sum_{k>i} G_k w_k) / q_i ;  da/ds_v = delta (1 - a);  no gradient to rgb.  No atomics: every row is written once.
+// (The suffix sums are scanned as such, rr_suffix_incl: the regularisers' gradient does not vanish behind a surface the way the colour's does.)
+template <int NCH>
+__global__ void __launch_bounds__(RN_THREADS) k_ray_reg_bwd(const float *__restrict__ g_reg, const float *__restrict__ sigmas, const float *__restrict__ rgbc,
+                                                            const float *__restrict__ z_vals, const float *__restrict__ nears, const float *__restrict__ fars,
+                                                            uint32_t N, uint32_t S, uint32_t num_steps, int soft, float thr, int detach_bg,
+                                                            const uint32_t *__restrict__ src_index, uint32_t vmask, float min_opacity,
+                                                            float *__restrict__ g_sigma, float *__restrict__ g_rgbc) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t n = blockIdx.x * RN_WAVES + wave;
+    if (n >= N) return;
+    const float near = nears[n], far = fars[n];
+    float gs_[NCH], ge_[NCH];
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) gs_[ch] = ge_[ch] = 0.0f;
+    RrRay<NCH> r;
+    if (far > near) {                                                     // wave-uniform
+        rr_load(r, sigmas, rgbc, z_vals + (size_t)n * S, src_index, n, S, near, far, num_steps, lane);
+#pragma unroll
+        for (int v = 0; v < 3; v++) {
+            // a variant that was not computed, or whose two outputs received no gradient, adds exact zeros: skipped (wave-uniform; `!(x == 0)`: a NaN
+            // gradient keeps its variant), as use[v] of k_composite_run_bwd
+            const float gD = g_reg[((size_t)v * N + n) * 2], gH = g_reg[((size_t)v * N + n) * 2 + 1];
+            const bool any = ((vmask >> v) & 1u) && (!(gD == 0.0f) || !(gH == 0.0f));
+            if (__builtin_amdgcn_readfirstlane(any ? 1 : 0) == 0) continue;
+            float alpha_[NCH], tr_[NCH], wlt_[NCH], A_[NCH], G_[NCH], B_[NCH];
+            const float W = rr_weights(r, v, soft, thr, S, lane, alpha_, tr_, wlt_, A_);
+            const bool gated = W > min_opacity;
+            // B_k = sum_{l>k} W_{>=l} dm_l from two suffix scans, and the entropy's mean term sum p h
+            float accPH = 0.0f;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ch++) {
+                G_[ch] = alpha_[ch] * tr_[ch];
+                const float p = G_[ch] / (W + 1e-10f);
+                accPH -= p * (logf(p + 1e-10f) + p / (p + 1e-10f));
+            }
+            const float PH = cn_wave_sum(accPH);
+            rr_suffix_incl(G_, B_, lane);                                     // W_{>=l}
+#pragma unroll
+            for (int ch = 0; ch < NCH; ch++) G_[ch] = B_[ch] * r.dm[ch];
+            rr_suffix_incl(G_, B_, lane);
+#pragma unroll
+            for (int ch = 0; ch < NCH; ch++) {
+                const float w = alpha_[ch] * tr_[ch];
+                const float p = w / (W + 1e-10f);
+                const float h = -(logf(p + 1e-10f) + p / (p + 1e-10f));
+                const float GD = 2.0f * (A_[ch] + (B_[ch] - G_[ch])) + (2.0f / 3.0f) * (w * r.d[ch]);
+                A_[ch] = gD * GD + (gated ? gH * ((h - PH) / (W + 1e-10f)) : 0.0f);             // G = dL/dw
+                G_[ch] = A_[ch] * w;                                          // (w = 0 on the lanes past S)
+            }
+            rr_suffix_incl(G_, B_, lane);                                     // sum_{k>=i} G_k w_k
+#pragma unroll
+            for (int ch = 0; ch < NCH; ch++) {
+                const float alpha = alpha_[ch], tr = tr_[ch];
+                const float q = 1.0f - alpha + 1e-15f;
+                const float dalpha = A_[ch] * tr - (B_[ch] - G_[ch]) / q;
+                const float dsv = dalpha * r.delta[ch] * (1.0f - alpha);
+                const float e = rn_edit(r.conf[ch], soft, thr);
+                const bool detached = (v == 0) && detach_bg && !(r.conf[ch] >= 0.5f);        // as the composite: no sigma gradient from the `all` variant
+                if (!detached) gs_[ch] += dsv * rn_variant_scale(v, e);
+                if (v == 1) ge_[ch] += dsv * r.sigma[ch];
+                if (v == 2) ge_[ch] -= dsv * r.sigma[ch];
+            }
+        }
+    } else {
+        // (the rows still have to be written: only the row indices are needed)
+#pragma unroll
+        for (int ch = 0; ch < NCH; ch++) {
+            const uint32_t i = ch * 64 + lane;
+            r.row[ch] = i < S ? (src_index ? src_index[(size_t)n * S + i] : n * S + i) : 0;
+            r.conf[ch] = 0.0f;
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+        if (ch * 64 + lane >= S) continue;
+        g_sigma[r.row[ch]] = gs_[ch];
+        if (g_rgbc) {
+            const float e = rn_edit(r.conf[ch], soft, thr);
+            // edit = sigmoid((conf - thr) * 100): only the confidence channel depends on the weights' distribution
+            reinterpret_cast<float4 *>(g_rgbc)[r.row[ch]] = make_float4(0.0f, 0.0f, 0.0f, soft ? ge_[ch] * 100.0f * e * (1.0f - e) : 0.0f);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ reconstruction loss
 // train_step_pretrain's loss (utils_init_nerf.py:220-234) and its gradient in one launch instead of ~35 elementwise / reduce launches:
 //   loss = w_rgb * mean((image - rgb_gt)^2) + w_conf * mean((render_mask - mask_gt)^2)      (image / render_mask of the `all` composite)
@@ -691,6 +881,39 @@ int cnerf_composite_run_backward(const float *grad_out_ray, const float *sigmas,
     return cnerf_composite_run_backward_indexed(grad_out_ray, sigmas, rgbc, z_vals, nears, fars, N, S, num_steps, soft_mask, conf_thr, detach_bg,
                                                 detach_mask_from_field, nullptr, grad_sigmas, grad_rgbc, stream);
 }
+
+#define RR_LAUNCH(KERNEL, ...)                                                                                                          \
+    switch (cn_div_up(S, 64)) {                                                                                                        \
+        case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(cn_div_up(N, RN_WAVES)), dim3(RN_THREADS), 0, CN_STREAM(stream), __VA_ARGS__); break; \
+        case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(cn_div_up(N, RN_WAVES)), dim3(RN_THREADS), 0, CN_STREAM(stream), __VA_ARGS__); break; \
+        case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(cn_div_up(N, RN_WAVES)), dim3(RN_THREADS), 0, CN_STREAM(stream), __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL(KERNEL<4>, dim3(cn_div_up(N, RN_WAVES)), dim3(RN_THREADS), 0, CN_STREAM(stream), __VA_ARGS__); break; \
+    }
+
+int cnerf_ray_reg_forward(const float *sigmas, const float *rgbc, const float *z_vals, const float *nears, const float *fars, uint32_t N, uint32_t S,
+                          uint32_t num_steps, int soft_mask, float conf_thr, const uint32_t *src_index, uint32_t variant_mask, float min_opacity,
+                          float *out_reg, void *stream) {
+    if (S == 0 || S > 64 * RN_MAXCH || num_steps == 0 || variant_mask == 0 || variant_mask > 7u) return CNERF_EINVAL;
+    if ((uint64_t)N * S > 0xFFFFFFFFull) return CNERF_EINVAL;                        // (row indices are 32-bit, as src_index's)
+    if (N == 0) return CNERF_OK;
+    if (!sigmas || !rgbc || !z_vals || !nears || !fars || !out_reg) return CNERF_ENULL;
+    RR_LAUNCH(k_ray_reg_fwd, sigmas, rgbc, z_vals, nears, fars, N, S, num_steps, soft_mask, conf_thr, src_index, variant_mask, min_opacity, out_reg)
+    return cn_launch_status();
+}
+
+int cnerf_ray_reg_backward(const float *grad_reg, const float *sigmas, const float *rgbc, const float *z_vals, const float *nears, const float *fars,
+                           uint32_t N, uint32_t S, uint32_t num_steps, int soft_mask, float conf_thr, int detach_bg, const uint32_t *src_index,
+                           uint32_t variant_mask, float min_opacity, float *grad_sigmas, float *grad_rgbc, void *stream) {
+    if (S == 0 || S > 64 * RN_MAXCH || num_steps == 0 || variant_mask == 0 || variant_mask > 7u) return CNERF_EINVAL;
+    if ((uint64_t)N * S > 0xFFFFFFFFull) return CNERF_EINVAL;
+    if (N == 0) return CNERF_OK;
+    if (!grad_reg || !sigmas || !rgbc || !z_vals || !nears || !fars || !grad_sigmas) return CNERF_ENULL;
+    if (((uintptr_t)grad_rgbc) & 15) return CNERF_EINVAL;
+    RR_LAUNCH(k_ray_reg_bwd, grad_reg, sigmas, rgbc, z_vals, nears, fars, N, S, num_steps, soft_mask, conf_thr, detach_bg, src_index, variant_mask,
+              min_opacity, grad_sigmas, grad_rgbc)
+    return cn_launch_status();
+}
+#undef RR_LAUNCH
 
 int cnerf_recon_loss_scaled(const float *out_ray, const float *rgb_gt, const float *mask_gt, uint32_t N, float w_rgb, float w_conf,
                             const float *grad_scale, float *loss, float *grad_out_ray, void *stream) {

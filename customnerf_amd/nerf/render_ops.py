@@ -204,6 +204,51 @@ def composite_run(sigmas, rgbc, z_vals, nears, fars, num_steps, soft_mask, conf_
     return _CompositeRun.apply(sigmas, rgbc, z_vals, nears, fars, num_steps, soft_mask, conf_thr, detach_bg, detach_mask)
 
 
+class _RayRegularizers(Function):
+    """out_reg [3,N,2] (all/fg/bg x distortion, ray entropy) of the composites' sample weights (k_ray_reg_fwd / k_ray_reg_bwd)"""
+
+    @staticmethod
+    def forward(ctx, sigmas, rgbc, z_vals, src_index, nears, fars, num_steps, soft_mask, conf_thr, detach_bg, variants, min_opacity):
+        require_cuda(sigmas, rgbc, z_vals, src_index, nears, fars)
+        sigmas = sigmas.contiguous().float()
+        rgbc = rgbc.contiguous().float()
+        z_vals, nears, fars = z_vals.contiguous().float(), nears.contiguous().float(), fars.contiguous().float()
+        N, S = z_vals.shape
+        assert sigmas.numel() == N * S and rgbc.numel() == 4 * N * S and nears.numel() == N and fars.numel() == N
+        if src_index is not None:
+            src_index = src_index.contiguous()
+            assert src_index.dtype == torch.int32 and src_index.numel() == N * S
+        out = torch.empty(3, N, 2, dtype=torch.float32, device=z_vals.device)
+        check(lib.cnerf_ray_reg_forward(ptr(sigmas), ptr(rgbc), ptr(z_vals), ptr(nears), ptr(fars), N, S, int(num_steps), int(soft_mask), float(conf_thr),
+                                        ptr(src_index), int(variants), float(min_opacity), ptr(out), stream()), "ray_reg_forward")
+        ctx.save_for_backward(sigmas, rgbc, z_vals, src_index, nears, fars)
+        ctx.cfg = (int(num_steps), int(soft_mask), float(conf_thr), int(detach_bg), int(variants), float(min_opacity))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_reg):
+        sigmas, rgbc, z_vals, src_index, nears, fars = ctx.saved_tensors
+        num_steps, soft, thr, dbg, variants, min_opacity = ctx.cfg
+        N, S = z_vals.shape
+        g_reg = g_reg.contiguous().float()
+        g_sigma = torch.empty_like(sigmas)
+        # the confidence enters through the soft edit mask of the edit-region / background variants only
+        g_rgbc = torch.empty_like(rgbc) if (soft and (variants & 6) and ctx.needs_input_grad[1]) else None
+        check(lib.cnerf_ray_reg_backward(ptr(g_reg), ptr(sigmas), ptr(rgbc), ptr(z_vals), ptr(nears), ptr(fars), N, S, num_steps, soft, thr, dbg,
+                                         ptr(src_index), variants, min_opacity, ptr(g_sigma), ptr(g_rgbc), stream()), "ray_reg_backward")
+        return (g_sigma, g_rgbc) + (None,) * 10
+
+
+def ray_regularizers(sigmas, rgbc, z_vals, src_index, nears, fars, num_steps, soft_mask, conf_thr, detach_bg=False, variants=1, min_opacity=0.1):
+    """Distortion loss (mip-NeRF 360) and ray entropy (InfoNeRF) of the composites' sample weights, per ray and composite variant:
+    sigmas [P], rgbc [P,4] (rows of the sample list; src_index [N,S] int32 = row of every sorted position, None = the rows are in sorted order),
+    z_vals [N,S] non-decreasing along each ray -> [3,N,2] (variant x ray x (distortion, entropy)); the definitions are in DESIGN.md.
+    variants: bit mask (1 all, 2 edit region, 4 background); the rows of the others are zeros.  The entropy is reported (and has a gradient)
+    only where the ray's weights sum to more than min_opacity.  Differentiable in sigmas and in the confidence channel of rgbc (None where
+    nothing depends on it: hard mask, or variant 0 only); z_vals / nears / fars are constants.  No host synchronisation."""
+    return _RayRegularizers.apply(sigmas, rgbc, z_vals, src_index, nears, fars, num_steps, soft_mask, conf_thr, detach_bg, variants, min_opacity)
+
+
 class _ReconLoss(Function):
     """loss [] = w_rgb * mse(image, rgb_gt) + w_conf * mse(render_mask, mask_gt) on out_ray [3,N,6]; the gradient comes out of the same launch"""
 

@@ -148,14 +148,17 @@ class NeRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------------------------------ run (the path `-O2` takes)
     def run(self, rays_o, rays_d, num_steps=128, upsample_steps=128, light_d=None, ambient_ratio=1.0, shading='albedo',
-            bg_color=None, perturb=False, _draws=None, normals=False, **kwargs):
+            bg_color=None, perturb=False, _draws=None, normals=False, ray_reg=False, **kwargs):
         """renderer.py:278-405.  rays_o, rays_d [B,N,3] (B == 1) -> result dict, on the fused HIP kernels (no torch fallback: CPU
         tensors raise).  `_draws` = dict(light, z, u) replays the RNG draws of :305, :317 and sample_pdf:37 (tests).
         The reference fills its result dict only under `opt.train_conf` (:383-405): without it the dict is empty here too.
         normals=True adds the field's normals (density_gradient of the subclass; csrc/field_normal.hip), detached even when grad is enabled:
         'normal_map' [*prefix, 3] = sum w n (renderer.py:469-470; 'fg' and 'bg' get theirs from their own weights), 'orient' [*prefix] =
         sum w max(0, n . d)^2 (the summand of loss_orient, :428, per ray) and 'normal' [N, S, 3], the per-sample normals in sorted order
-        (computed on first access).  With the default no launch is added and no key."""
+        (computed on first access).  With the default no launch is added and no key.
+        ray_reg=True adds the two regularisers of the sample weights (render_ops.ray_regularizers; one launch, one more in the backward):
+        'distortion' and 'ray_entropy' [*prefix], differentiable, and the same two keys in 'fg' / 'bg' where those composites are computed.
+        The entropy is gated by `opt.ray_reg_min_opacity` (default 0.1).  With the default no launch is added and no key."""
         require_cuda(rays_o, rays_d)
         if not getattr(self.opt, 'train_conf', 0):
             return {}
@@ -163,7 +166,8 @@ class NeRFRenderer(nn.Module):
             # (upsample_steps == 0 fails in the reference as well: `weights` is bound only inside `if upsample_steps > 0`, renderer.py:333-384)
             raise ValueError(f"run(): the sampling kernels take 3..128 coarse and 2..128 importance samples per ray (got {num_steps} + {upsample_steps}; "
                              "the reference's recipe is 64 + 64)")
-        return self._run_fused(rays_o, rays_d, num_steps, upsample_steps, perturb, _draws, fg_bg=bool(kwargs.get('fg_bg', True)), normals=bool(normals))
+        return self._run_fused(rays_o, rays_d, num_steps, upsample_steps, perturb, _draws, fg_bg=bool(kwargs.get('fg_bg', True)), normals=bool(normals),
+                               ray_reg=bool(ray_reg))
 
     def _dirs_twice(self, rays_d):
         """[d | d] for the split sample list, cached per view: a dataset's ray directions are resident tensors that come back every epoch
@@ -192,7 +196,7 @@ class NeRFRenderer(nn.Module):
             raise ValueError("run() with opt.train_conf needs forward() to return rgb + 1 confidence channel (network_grid.py:126-129)")
         return sigmas.reshape(-1), rgbc.reshape(-1, 4)
 
-    def _run_fused(self, rays_o, rays_d, num_steps, upsample_steps, perturb, _draws=None, fg_bg=True, normals=False):
+    def _run_fused(self, rays_o, rays_d, num_steps, upsample_steps, perturb, _draws=None, fg_bg=True, normals=False, ray_reg=False):
         """run() on the fused kernels: 2 sampling launches + 2 field launches (+1 gather each) + 1 composite launch.
         Same result dict as run(); RNG draws keep the reference's order (rand(N,T) then rand(N,t)).
         fg_bg=False (the reconstruction trainer, whose loss reads the first composite only): the edit-region / background composites are not
@@ -302,6 +306,17 @@ class NeRFRenderer(nn.Module):
         if fg_bg or not split:                                               # (fg_bg=False: the two composites were not computed — no such keys)
             results['fg'] = pack(1)
             results['bg'] = pack(2)
+        if ray_reg:
+            # distortion / ray entropy of the weights of every composite that was computed: the same samples, through the same index
+            if split:
+                reg_in = (sig_l, rgbc_l, z_all, src)
+            else:
+                reg_in = (sigmas, rgbc, z_all, None)
+            reg = render_ops.ray_regularizers(*reg_in, nears, fars, num_steps, soft, thr, dbg, variants=7 if 'fg' in results else 1,
+                                              min_opacity=float(getattr(self.opt, 'ray_reg_min_opacity', 0.1)))
+            for v, r in enumerate((results, results.get('fg'), results.get('bg'))[:3 if 'fg' in results else 1]):
+                r['distortion'] = reg[v, :, 0].reshape(*prefix)
+                r['ray_entropy'] = reg[v, :, 1].reshape(*prefix)
         if normals:
             # the gradient of the whole sample list: on the split path from the resident features and grid coordinates (no second gather)
             with torch.no_grad():
@@ -362,6 +377,9 @@ class NeRFRenderer(nn.Module):
         """renderer.py:597-718: occupancy-grid march.  Training: one compacted sample list per batch (march_rays_train ->
         field -> composite_rays_train); inference: the alive-ray loop of :661-688 with device-side compaction.
         normals=True raises NotImplementedError: normal maps exist on run() only."""
+        if kwargs.get('ray_reg', False):
+            raise ValueError("run_cuda(ray_reg=True): the distortion / ray-entropy regularisers exist on run() only (a model with opt.cuda_ray "
+                             "off); the occupancy march keeps no per-ray sample weights to regularise")
         if normals:
             raise NotImplementedError("run_cuda(normals=True): normal maps are composited by run() only; the occupancy march has none "
                                       "(use a model with opt.cuda_ray off, or model.normal(x) per point)")

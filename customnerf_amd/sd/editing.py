@@ -11,8 +11,8 @@ import torch.nn.functional as F
 
 from ..optim import DynamicLossScaler, FusedAdam
 from .edit_fn import RayImages, ScaledL1
-from ..trainer import (CheckpointMixin, EvalMixin, allreduce_grads_flat, apply_optimizer_step, enable_grad_in_place, flat_grad_buffer, register_half_shadow,
-                       setup_sharded_dp)
+from ..trainer import (CheckpointMixin, EvalMixin, allreduce_grads_flat, apply_optimizer_step, enable_grad_in_place, flat_grad_buffer, ray_reg_loss,
+                       ray_reg_wanted, register_half_shadow, setup_sharded_dp)
 
 
 class EditTrainer(CheckpointMixin, EvalMixin):
@@ -124,6 +124,18 @@ class EditTrainer(CheckpointMixin, EvalMixin):
         t_val = int(rp['t'] * t_ratio) if 't' in rp else None                                                     # sd.py:132
         return self.guidance.train_step(latents, text_emb, system=self, t_ratio=t_ratio, t_val=t_val, noise=noise)
 
+    def _edit_render_kw(self):
+        """the options as render() keywords; ray_reg only where opt.lambda_distortion / opt.lambda_ray_entropy ask for a regulariser"""
+        return dict(self._render_kw, ray_reg=True) if ray_reg_wanted(self.opt) else self._render_kw
+
+    def _ray_reg_terms(self, outputs):
+        """the regularisers of the ray weights on the region opt.ray_reg_region names ('all', the default, or 'fg', the edit region)
+        -> (weighted sum, its terms for loss_dict)"""
+        region = getattr(self.opt, 'ray_reg_region', 'all')
+        if region not in ('all', 'fg'):
+            raise ValueError(f"opt.ray_reg_region must be 'all' or 'fg' (got {region!r})")
+        return ray_reg_loss(self.opt, outputs if region == 'all' else outputs['fg'])
+
     def train_step_editing(self, data):
         """utils_init_nerf.py:353-394.  data = (rgbs, mask, rays_o, rays_d, H, W, img_path)"""
         rgbs, mask, rays_o, rays_d, H, W, img_path = data
@@ -131,7 +143,7 @@ class EditTrainer(CheckpointMixin, EvalMixin):
         opt = self.opt
         bg_color = self._bg_color(rays_o, B, N)
         with torch.autocast('cuda', dtype=torch.float16, enabled=self.fp16):
-            outputs = self.model.render(rays_o, rays_d, staged=False, perturb=True, force_all_rays=True, bg_color=bg_color, **self._render_kw)
+            outputs = self.model.render(rays_o, rays_d, staged=False, perturb=True, force_all_rays=True, bg_color=bg_color, **self._edit_render_kw())
         pred_rgb, pred_rgb_fg, pred_rgb_bg = self._pred_images(outputs, B, H, W)
         pred_ws = outputs['weights_sum'].reshape(B, H, W)
         pt_rgb_fg, pt_rgb_bg, pt_mask, pt_depth_fg, match_probs = self.get_pt(rays_o, rays_d, img_path, bg_color, B, H, W)
@@ -146,6 +158,10 @@ class EditTrainer(CheckpointMixin, EvalMixin):
             loss_bg = ScaledL1.apply(pt_rgb_bg, pred_rgb_bg, float(opt.keep_bg))            # opt.keep_bg * F.l1_loss(pt_rgb_bg, pred_rgb_bg): :389-391
             loss = loss + loss_bg
             loss_dict['loss_bg'] = loss_bg.detach()
+        if ray_reg_wanted(opt):
+            loss_reg, terms = self._ray_reg_terms(outputs)
+            loss = loss + loss_reg
+            loss_dict.update(terms)
         return pred_rgb, pred_ws, loss, loss_dict
 
     @staticmethod
@@ -165,14 +181,14 @@ class EditTrainer(CheckpointMixin, EvalMixin):
         and noise.  loss = mean over the views of the single-view loss."""
         opt = self.opt
         V = len(views)
-        preds, preds_fg, losses_bg, match = [], [], [], None
+        preds, preds_fg, losses_bg, regs, match = [], [], [], [], None
         pred_rgb = pred_ws = None
         for data in views:
             rgbs, mask, rays_o, rays_d, H, W, img_path = data
             B, N = rays_o.shape[:2]
             bg_color = self._bg_color(rays_o, B, N)
             with torch.autocast('cuda', dtype=torch.float16, enabled=self.fp16):
-                outputs = self.model.render(rays_o, rays_d, staged=False, perturb=True, force_all_rays=True, bg_color=bg_color, **self._render_kw)
+                outputs = self.model.render(rays_o, rays_d, staged=False, perturb=True, force_all_rays=True, bg_color=bg_color, **self._edit_render_kw())
             pred_rgb, pred_rgb_fg, pred_rgb_bg = self._pred_images(outputs, B, H, W)
             pred_ws = outputs['weights_sum'].reshape(B, H, W)
             pt_rgb_fg, pt_rgb_bg, pt_mask, pt_depth_fg, match = self.get_pt(rays_o, rays_d, img_path, bg_color, B, H, W)
@@ -183,6 +199,8 @@ class EditTrainer(CheckpointMixin, EvalMixin):
             preds_fg.append(pred_rgb_fg)
             if opt.keep_bg:
                 losses_bg.append(ScaledL1.apply(pt_rgb_bg, pred_rgb_bg, float(opt.keep_bg)))
+            if ray_reg_wanted(opt):
+                regs.append(self._ray_reg_terms(outputs))
         loss, loss_dict = 0.0, {}
         if opt.lambda_sd:
             loss, loss_dict = self.train_step_sd(torch.cat(preds, 0), torch.cat(preds_fg, 0), None if self.clip_view is False else match)
@@ -191,6 +209,9 @@ class EditTrainer(CheckpointMixin, EvalMixin):
             loss_bg = torch.stack(losses_bg).mean()
             loss = loss + loss_bg
             loss_dict['loss_bg'] = loss_bg.detach()
+        if regs:
+            loss = loss + sum(r[0] for r in regs) / V
+            loss_dict.update({k: sum(r[1][k] for r in regs) / V for k in regs[0][1]})
         return pred_rgb, pred_ws, loss, loss_dict
 
     def guidance_preview(self, data, path=None, t=None, seed=0):

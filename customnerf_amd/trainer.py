@@ -101,6 +101,25 @@ class packed_weights_window:
         return False
 
 
+def ray_reg_wanted(opt):
+    """do the options ask for a regulariser of the ray weights (opt.lambda_distortion / opt.lambda_ray_entropy, both 0 by default)?  The trainers
+    pass ray_reg=True to the renderer only then: without it no launch is added and the result dict keeps its keys."""
+    return bool(getattr(opt, 'lambda_distortion', 0) or getattr(opt, 'lambda_ray_entropy', 0))
+
+
+def ray_reg_loss(opt, outputs):
+    """lambda_distortion * mean over rays of outputs['distortion'] + lambda_ray_entropy * mean of outputs['ray_entropy'] (run(ray_reg=True); pass
+    the result dict, or its 'fg' / 'bg' entry) -> (sum, {'loss_distortion': ..., 'loss_ray_entropy': ...} with the weighted terms, detached)"""
+    total, terms = 0.0, {}
+    for lam, key, name in ((getattr(opt, 'lambda_distortion', 0), 'distortion', 'loss_distortion'),
+                           (getattr(opt, 'lambda_ray_entropy', 0), 'ray_entropy', 'loss_ray_entropy')):
+        if lam:
+            term = float(lam) * outputs[key].float().mean()
+            total = total + term
+            terms[name] = term.detach()
+    return total, terms
+
+
 def inf_check_is_folded(trainer):
     """Round 6: GradScaler's inf check is a pass over every gradient (9 us for the benchmark table, 30 us for the reference
     field's).  With the scaler WATCHED (DynamicLossScaler.watch) the two kernels that produce the gradients raise found_inf themselves — the field
@@ -459,6 +478,14 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
         return "fp32 grad all-reduce, in place on the flat buffer"
 
     def loss(self, outputs, rgbs, mask):
+        """utils_init_nerf.py:220-234, plus the regularisers of the ray weights (`all` composite) where opt.lambda_distortion /
+        opt.lambda_ray_entropy ask for them"""
+        loss = ReconTrainer.recon_loss(self, outputs, rgbs, mask)               # (callers may pass any object with `opt` as self)
+        if ray_reg_wanted(self.opt):
+            loss = loss + ray_reg_loss(self.opt, outputs)[0]
+        return loss
+
+    def recon_loss(self, outputs, rgbs, mask):
         """utils_init_nerf.py:220-234"""
         if '_out_ray' in outputs and outputs['_out_ray'].is_cuda and getattr(self.opt, 'fused_loss', True):
             from .nerf.render_ops import recon_loss                   # loss + gradient in one launch on the fused renderer's composite output
@@ -523,6 +550,8 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
         self.model.train()
         rays_o, rays_d, rgbs, mask = self.select_rays(rays_o, rays_d, rgbs, mask, select_inds)
         render_kw.setdefault('fg_bg', getattr(self, 'needs_fg_bg', False))       # the reconstruction loss reads the first composite only
+        if ray_reg_wanted(self.opt):
+            render_kw.setdefault('ray_reg', True)
         with torch.autocast('cuda', dtype=torch.float16, enabled=self.fp16):
             outputs = self.model.render(rays_o, rays_d, staged=False, perturb=True, force_all_rays=True, **render_kw)
             loss = self.loss(outputs, rgbs, mask)
@@ -568,6 +597,8 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
         if not (self.fused_adam and self.scaler is not None) or int(getattr(self.opt, 'batch_rays', -1) or -1) > 0:
             raise ValueError("train_step_graphed: fused Adam with the dynamic loss scaler, no batch_rays")
         from ._lib import scratch_generation
+        if ray_reg_wanted(self.opt):
+            render_kw.setdefault('ray_reg', True)
         tensors = (rays_o, rays_d, rgbs, mask)
         key = tuple((t.data_ptr(), tuple(t.shape), t.dtype) for t in tensors) + (tuple(sorted(render_kw.items())),)
         cache = self.__dict__.setdefault('_graphs', {})

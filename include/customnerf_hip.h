@@ -54,7 +54,8 @@ extern "C" {
  *    closest-point tree (additive, same version) — cnerf_mesh_winding_workspace_bytes / _build / _query and
  *    cnerf_mesh_bvh_signed_distance.
  * 8: the scatter's ahead-of-time plan is gone — cnerf_grid_encode_backward_prepare / _needs_plan / _prepared (cnerf_grid_encode_backward is
- *    the one call, on one stream) — and so is cnerf_grid_encode_forward_strided (cnerf_grid_encode_forward_ordered with CNERF_GRID_LEVEL_MAJOR). */
+ *    the one call, on one stream) — and so is cnerf_grid_encode_forward_strided (cnerf_grid_encode_forward_ordered with CNERF_GRID_LEVEL_MAJOR).
+ *    Ray regularisers (additive, same version) — cnerf_ray_reg_forward / cnerf_ray_reg_backward. */
 #define CNERF_ABI_VERSION 8
 int cnerf_abi_version(void);
 /* name of the code object's target ("gfx950") */
@@ -449,6 +450,26 @@ int cnerf_composite_run_backward_indexed_flush(const float *grad_out_ray, const 
                                                int soft_mask, float conf_thr, int detach_bg, int detach_mask_from_field,
                                                const uint32_t *src_index, float *grad_sigmas, float *grad_rgbc, int flush_half_zero,
                                                uint8_t *tile_live, void *stream);
+
+/* Ray regularisers (additive, same ABI version): two losses on how a ray's weight is distributed along the ray, per composite variant, from the
+ * same inputs and with the same w / alpha / T / delta as cnerf_composite_run_indexed (src_index NULL = rows in sorted order).  With
+ * L = far - near, d_i = delta_i / L, m_i = (z_i - near) / L + d_i / 2:
+ *   out_reg[v][n][0] = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i                          (distortion loss of mip-NeRF 360)
+ *   out_reg[v][n][1] = -sum_i p_i log(p_i + 1e-10), p = w / (W + 1e-10), W = sum w, if W > min_opacity, else 0     (ray entropy of InfoNeRF)
+ * out_reg is float [3][N][2]; rows of variants outside variant_mask (bit 0 all, 1 edit region, 2 background) are zeros.  O(S) per ray by prefix
+ * sums: z_vals must be non-decreasing along each ray (cnerf_sample_fine_merge's output is).  A ray with !(far > near) gives exact zeros, never
+ * a NaN.  1 <= S <= 256, num_steps >= 1 (the last interval is (far - near) / num_steps). */
+int cnerf_ray_reg_forward(const float *sigmas, const float *rgbc, const float *z_vals, const float *nears, const float *fars, uint32_t N,
+                          uint32_t S, uint32_t num_steps, int soft_mask, float conf_thr, const uint32_t *src_index, uint32_t variant_mask,
+                          float min_opacity, float *out_reg, void *stream);
+/* Its gradient: grad_reg float [3][N][2] -> grad_sigmas [P] and, when grad_rgbc is given (16-byte aligned; NULL where nothing depends on the
+ * confidence: hard mask, or variant 0 only), grad_rgbc [P][4] with zeros in the rgb lanes.  Every row is written; z_vals / nears / fars are
+ * constants and the min_opacity gate is one too.  detach_bg as in cnerf_composite_run_backward.  A variant outside variant_mask, or whose two
+ * incoming gradients are both zero, is skipped.  No atomics: the result is bit-reproducible. */
+int cnerf_ray_reg_backward(const float *grad_reg, const float *sigmas, const float *rgbc, const float *z_vals, const float *nears,
+                           const float *fars, uint32_t N, uint32_t S, uint32_t num_steps, int soft_mask, float conf_thr, int detach_bg,
+                           const uint32_t *src_index, uint32_t variant_mask, float min_opacity, float *grad_sigmas, float *grad_rgbc,
+                           void *stream);
 
 /* Loss of the reconstruction step (Trainer_Nerf.train_step_pretrain, utils_init_nerf.py:220-234) with its gradient, one launch:
  *   loss = w_rgb * mean((image - rgb_gt)^2) + w_conf * mean((render_mask - mask_gt)^2)
