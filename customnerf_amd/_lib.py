@@ -163,6 +163,8 @@ SIGNATURES = {
     "cnerf_mesh_bvh_signed_distance": [vp, u64, u32, u32, vp, u64, vp, u32, f32, vp, vp, vp, vp, vp],
     "cnerf_image_metrics_workspace_bytes": [u32, u32, u32, u32, vp],
     "cnerf_image_metrics": [vp, vp, vp, u32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
+    "cnerf_ssim_grad_workspace_bytes": [u32, u32, u32, u32, vp],
+    "cnerf_ssim_grad": [vp, vp, vp, u32, u32, u32, u32, i32, vp, vp, vp, vp],
     # ---- include/customnerf_sd.h (score-distillation primitives)
     "cnerf_sd_gemm": [vp, vp, u64, vp],
     "cnerf_sd_gemm_workspace_bytes": [vp, vp],

@@ -1,4 +1,5 @@
-"""Image scores on the GPU: PSNR, L1 and SSIM of rendered views (cnerf_image_metrics, csrc/metrics.hip), and the CLIP scores of an edit.
+"""Image scores on the GPU: PSNR, L1 and SSIM of rendered views (cnerf_image_metrics, csrc/metrics.hip), the differentiable SSIM loss
+(ssim_loss / ssim_with_grad, cnerf_ssim_grad), and the CLIP scores of an edit.
 
 The reference's evaluate loop feeds numpy arrays to a host-side PSNR meter (nerf/utils_init_nerf.py:673-779) and has no SSIM; here one fused
 kernel pass returns per-image float64 sums and this module derives the scores from them in float64.
@@ -22,28 +23,24 @@ from ._lib import lib, check, ptr, stream, require_cuda, dtype_id, query_u64
 WINDOW = 11                      # taps of the Gaussian window; the map loses WINDOW - 1 rows and columns
 
 
-def _as_batch(t, what):
+def _as_batch(t, what, who="image_metrics"):
     if not torch.is_tensor(t):
-        raise TypeError(f"image_metrics: {what} must be a tensor")
+        raise TypeError(f"{who}: {what} must be a tensor")
     require_cuda(t)
     if t.dim() == 3:
         t = t[None]
     if t.dim() != 4:
-        raise ValueError(f"image_metrics: {what} must be [B, H, W, C] or [H, W, C], got {tuple(t.shape)}")
+        raise ValueError(f"{who}: {what} must be [B, H, W, C] or [H, W, C], got {tuple(t.shape)}")
     return t
 
 
-def image_metrics(pred, target, mask=None, quantize=False, want_map=False):
-    """pred, target: CUDA tensors [B, H, W, C] or [H, W, C], float32 or float16 (both the same), C in {1, 3}, values nominally in [0, 1];
-    mask: None or [B, H, W] / [H, W] (any real dtype or bool; nonzero = the pixel counts).  Non-contiguous tensors are made contiguous.
-    -> dict of [B] float64 CUDA tensors: 'mse', 'l1', 'psnr' (= 10 log10(1 / mse), inf at mse == 0), 'ssim', 'n_pixels' (counted
-    pixel-channels), 'n_windows' (counted window-channels), and with want_map 'ssim_map' [B, H - 10, W - 10, C] float32 (the whole map,
-    whatever the mask says).  The module docstring defines SSIM and `quantize`.  Runs on the current stream, no host sync."""
-    pred, target = _as_batch(pred, "pred"), _as_batch(target, "target")
+def _prepare(pred, target, mask, who):
+    """the argument rules image_metrics and the SSIM gradient share -> contiguous pred, target [B, H, W, C], mask float32 [B, H, W] or None, dtype id"""
+    pred, target = _as_batch(pred, "pred", who), _as_batch(target, "target", who)
     if pred.shape != target.shape:
-        raise ValueError(f"image_metrics: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
+        raise ValueError(f"{who}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
     if pred.dtype != target.dtype:
-        raise ValueError(f"image_metrics: pred is {pred.dtype}, target {target.dtype}")
+        raise ValueError(f"{who}: pred is {pred.dtype}, target {target.dtype}")
     dt = dtype_id(pred)
     B, H, W, C = pred.shape
     pred, target = pred.contiguous(), target.contiguous()
@@ -52,8 +49,19 @@ def image_metrics(pred, target, mask=None, quantize=False, want_map=False):
         if mask.dim() == 2:
             mask = mask[None]
         if tuple(mask.shape) != (B, H, W):
-            raise ValueError(f"image_metrics: mask must be [B, H, W] = {(B, H, W)}, got {tuple(mask.shape)}")
+            raise ValueError(f"{who}: mask must be [B, H, W] = {(B, H, W)}, got {tuple(mask.shape)}")
         mask = mask.to(torch.float32).contiguous()
+    return pred, target, mask, dt
+
+
+def image_metrics(pred, target, mask=None, quantize=False, want_map=False):
+    """pred, target: CUDA tensors [B, H, W, C] or [H, W, C], float32 or float16 (both the same), C in {1, 3}, values nominally in [0, 1];
+    mask: None or [B, H, W] / [H, W] (any real dtype or bool; nonzero = the pixel counts).  Non-contiguous tensors are made contiguous.
+    -> dict of [B] float64 CUDA tensors: 'mse', 'l1', 'psnr' (= 10 log10(1 / mse), inf at mse == 0), 'ssim', 'n_pixels' (counted
+    pixel-channels), 'n_windows' (counted window-channels), and with want_map 'ssim_map' [B, H - 10, W - 10, C] float32 (the whole map,
+    whatever the mask says).  The module docstring defines SSIM and `quantize`.  Runs on the current stream, no host sync."""
+    pred, target, mask, dt = _prepare(pred, target, mask, "image_metrics")
+    B, H, W, C = pred.shape
     dev = pred.device
     with torch.cuda.device(dev):
         need = query_u64(lib.cnerf_image_metrics_workspace_bytes, B, H, W, C)         # ValueError on an unsupported shape, before any allocation
@@ -68,6 +76,68 @@ def image_metrics(pred, target, mask=None, quantize=False, want_map=False):
     if want_map:
         out['ssim_map'] = smap
     return out
+
+
+def _ssim_grad_call(pred, target, mask, who):
+    """one cnerf_ssim_grad call -> (sums [B, 5] float64 as image_metrics forms them, grad_unit [B, H, W, C] float32)"""
+    pred, target, mask, dt = _prepare(pred, target, mask, who)
+    B, H, W, C = pred.shape
+    dev = pred.device
+    with torch.cuda.device(dev):
+        need = query_u64(lib.cnerf_ssim_grad_workspace_bytes, B, H, W, C)               # ValueError on an unsupported shape, before any allocation
+        sums = torch.empty(B, 5, dtype=torch.float64, device=dev)
+        grad = torch.empty(B, H, W, C, dtype=torch.float32, device=dev)
+        ws = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
+        check(lib.cnerf_ssim_grad(ptr(pred), ptr(target), ptr(mask), B, H, W, C, dt, ptr(sums), ptr(grad), ptr(ws), stream()), who)
+    return sums, grad
+
+
+def ssim_with_grad(pred, target, mask=None):
+    """The raw pieces of the SSIM loss, arguments as image_metrics: -> (ssim [B] float64, grad_unit [B, H, W, C] float32), grad_unit =
+    d ssim_b / d pred (include/customnerf_hip.h cnerf_ssim_grad has the formulas): float64 throughout, rounded to float32 once, bit-reproducible.
+    An image with no counted window has ssim nan (as image_metrics reports it) and a gradient of exact zeros.  Nothing here is recorded by
+    autograd; no host sync."""
+    with torch.no_grad():
+        sums, grad = _ssim_grad_call(pred, target, mask, "ssim_with_grad")
+        return sums[:, 3] / sums[:, 4], grad
+
+
+class _SsimLoss(torch.autograd.Function):
+    """[B] float32 1 - ssim_b (0 where no window counts); the gradient comes out of the forward's one cnerf_ssim_grad call (as _ReconLoss does)"""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask):
+        sums, grad = _ssim_grad_call(pred, target, mask, "ssim_loss")
+        counted = sums[:, 4] > 0
+        loss = torch.where(counted, 1.0 - sums[:, 3] / sums[:, 4], torch.zeros_like(sums[:, 3])).to(torch.float32)
+        ctx.save_for_backward(grad)
+        ctx.like = (pred.dtype, tuple(pred.shape))
+        ctx.mark_non_differentiable(counted)
+        return loss, counted
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_counted):
+        grad, = ctx.saved_tensors
+        dtype, shape = ctx.like
+        g = (grad * (-g_loss.to(torch.float32)).reshape(-1, 1, 1, 1)).to(dtype)          # the product in float32, one rounding to pred's dtype
+        return g.reshape(shape), None, None
+
+
+def ssim_loss(pred, target, mask=None, reduction='mean'):
+    """The D-SSIM term of a training loss: float32 1 - ssim_b, SSIM as the module docstring defines it (what image_metrics scores, unquantized).
+    pred, target: [B, H, W, C] or [H, W, C], float32 or float16 (both the same), C in {1, 3}; mask as in image_metrics (a window counts when its
+    centre pixel does).  reduction 'none' -> [B], 0 for an image with no counted window; 'mean' -> the mean over the images that have one, 0 if
+    none has.  Differentiable in pred only: target and mask get NO gradient (a target that requires grad keeps grad None).  The backward
+    multiplies the gradient stored by the forward pass in float32 and casts to pred.dtype once, so a loss scaler's factor is applied before any
+    half rounding.  One cnerf_ssim_grad call in the forward pass, no host sync: it can be captured in a graph."""
+    if reduction not in ('mean', 'none'):
+        raise ValueError(f"ssim_loss: reduction must be 'mean' or 'none', got {reduction!r}")
+    if torch.is_tensor(target):
+        target = target.detach()
+    loss, counted = _SsimLoss.apply(pred, target, mask)
+    if reduction == 'none':
+        return loss
+    return loss.sum() / counted.sum().clamp(min=1).to(torch.float32)
 
 
 def to_uint8(image):

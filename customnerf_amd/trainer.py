@@ -120,6 +120,41 @@ def ray_reg_loss(opt, outputs):
     return total, terms
 
 
+def dssim_wanted(opt):
+    """do the options ask for the structural image term (opt.lambda_dssim, absent or 0 by default)?  Without it the step adds no launch."""
+    return bool(getattr(opt, 'lambda_dssim', 0))
+
+
+def dssim_check(opt, image_hw, n_rays, select_inds=None):
+    """The D-SSIM term reads the step's rays as ONE whole H x W view, row-major: with opt.lambda_dssim set, image_hw = (H, W) is required,
+    H W is the number of rays, nothing subsamples them and both extents hold a window.  ValueError otherwise, before anything is rendered."""
+    if not dssim_wanted(opt):
+        return
+    if image_hw is None:
+        raise ValueError("lambda_dssim: pass image_hw=(H, W), the extents of the view the rays cover")
+    try:
+        H, W = (int(v) for v in image_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f"lambda_dssim: image_hw must be (H, W), got {image_hw!r}") from None
+    if int(getattr(opt, 'batch_rays', 0) or 0) > 0 or select_inds is not None:
+        raise ValueError("lambda_dssim: the term needs the whole view, not a batch_rays subset of its rays")
+    if H * W != n_rays:
+        raise ValueError(f"lambda_dssim: image_hw {H} x {W} does not cover the step's {n_rays} rays")
+    if H < 11 or W < 11:
+        raise ValueError(f"lambda_dssim: a view of {H} x {W} is smaller than one 11 x 11 SSIM window")
+
+
+def dssim_loss(opt, outputs, rgbs, image_hw):
+    """lambda_dssim * (1 - SSIM(outputs['image'], rgbs)) on the view as one [1, H, W, 3] image (metrics.ssim_loss: the 3D-Gaussian-splatting
+    recipe's structural term; the gradient goes to the prediction only)"""
+    from .metrics import ssim_loss
+    if image_hw is None:
+        raise ValueError("lambda_dssim: pass image_hw=(H, W), the extents of the view the rays cover")
+    H, W = (int(v) for v in image_hw)
+    image = outputs['image'].reshape(1, H, W, 3).float()
+    return float(opt.lambda_dssim) * ssim_loss(image, rgbs.reshape(1, H, W, 3).to(image.dtype))
+
+
 def inf_check_is_folded(trainer):
     """Round 6: GradScaler's inf check is a pass over every gradient (9 us for the benchmark table, 30 us for the reference
     field's).  With the scaler WATCHED (DynamicLossScaler.watch) the two kernels that produce the gradients raise found_inf themselves — the field
@@ -477,12 +512,16 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
             return self._dp.describe()
         return "fp32 grad all-reduce, in place on the flat buffer"
 
-    def loss(self, outputs, rgbs, mask):
+    def loss(self, outputs, rgbs, mask, image_hw=None):
         """utils_init_nerf.py:220-234, plus the regularisers of the ray weights (`all` composite) where opt.lambda_distortion /
-        opt.lambda_ray_entropy ask for them"""
+        opt.lambda_ray_entropy ask for them, plus opt.lambda_dssim * (1 - SSIM) of the view (image_hw = (H, W), row-major rays) where
+        that is set.  outputs['image'] is a view of the composite output the fused loss reads: autograd adds the two gradients before
+        the one compositing backward."""
         loss = ReconTrainer.recon_loss(self, outputs, rgbs, mask)               # (callers may pass any object with `opt` as self)
         if ray_reg_wanted(self.opt):
             loss = loss + ray_reg_loss(self.opt, outputs)[0]
+        if dssim_wanted(self.opt):
+            loss = loss + dssim_loss(self.opt, outputs, rgbs, image_hw)
         return loss
 
     def recon_loss(self, outputs, rgbs, mask):
@@ -547,6 +586,8 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
         return self.optimizer.arm_in_backward(self.model.pos_en.embeddings)
 
     def _train_step(self, rays_o, rays_d, rgbs, mask, select_inds=None, **render_kw):
+        image_hw = render_kw.pop('image_hw', None)                               # (H, W) of the view: the D-SSIM term's, not the renderer's
+        dssim_check(self.opt, image_hw, rays_o.reshape(-1, 3).shape[0], select_inds)
         self.model.train()
         rays_o, rays_d, rgbs, mask = self.select_rays(rays_o, rays_d, rgbs, mask, select_inds)
         render_kw.setdefault('fg_bg', getattr(self, 'needs_fg_bg', False))       # the reconstruction loss reads the first composite only
@@ -554,7 +595,8 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
             render_kw.setdefault('ray_reg', True)
         with torch.autocast('cuda', dtype=torch.float16, enabled=self.fp16):
             outputs = self.model.render(rays_o, rays_d, staged=False, perturb=True, force_all_rays=True, **render_kw)
-            loss = self.loss(outputs, rgbs, mask)
+            # (image_hw only where the term is on: a subclass's three-argument loss() keeps working with the option off)
+            loss = self.loss(outputs, rgbs, mask, image_hw) if dssim_wanted(self.opt) else self.loss(outputs, rgbs, mask)
         if self.scaler is not None:
             self._arm_table_step()
             try:
@@ -597,10 +639,13 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
         if not (self.fused_adam and self.scaler is not None) or int(getattr(self.opt, 'batch_rays', -1) or -1) > 0:
             raise ValueError("train_step_graphed: fused Adam with the dynamic loss scaler, no batch_rays")
         from ._lib import scratch_generation
+        image_hw = render_kw.pop('image_hw', None)
+        dssim_check(self.opt, image_hw, rays_o.reshape(-1, 3).shape[0])
+        image_hw = tuple(int(v) for v in image_hw) if image_hw is not None else None
         if ray_reg_wanted(self.opt):
             render_kw.setdefault('ray_reg', True)
         tensors = (rays_o, rays_d, rgbs, mask)
-        key = tuple((t.data_ptr(), tuple(t.shape), t.dtype) for t in tensors) + (tuple(sorted(render_kw.items())),)
+        key = tuple((t.data_ptr(), tuple(t.shape), t.dtype) for t in tensors) + (tuple(sorted(render_kw.items())), image_hw)
         cache = self.__dict__.setdefault('_graphs', {})
         if cache and self._graph_gen != scratch_generation():
             # a grow-on-demand workspace (scatter records, partial-gradient rows) was reallocated since a cached graph was captured — e.g. by an
@@ -611,7 +656,7 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
         if ent is None:
             gen0 = scratch_generation()
             for _ in range(2):
-                self.train_step(rays_o, rays_d, rgbs, mask, **render_kw)
+                self.train_step(rays_o, rays_d, rgbs, mask, image_hw=image_hw, **render_kw)
             torch.cuda.synchronize()
             self.model.train()
             graph = torch.cuda.CUDAGraph()
@@ -621,7 +666,7 @@ class ReconTrainer(CheckpointMixin, EvalMixin):
                     with torch.autocast('cuda', dtype=torch.float16, enabled=self.fp16):
                         outputs = self.model.render(rays_o, rays_d, staged=False, perturb=True, force_all_rays=True,
                                                     **dict(render_kw, fg_bg=render_kw.get('fg_bg', getattr(self, 'needs_fg_bg', False))))
-                        loss = self.loss(outputs, rgbs, mask)
+                        loss = self.loss(outputs, rgbs, mask, image_hw) if dssim_wanted(self.opt) else self.loss(outputs, rgbs, mask)
                     self.scaler.backward(loss)
                     loss = loss.detach()
             finally:
@@ -661,8 +706,9 @@ def train_one_epoch(trainer, views, shard=None, log=None):
             loss, loss_dict = trainer.train_step(data)
         else:
             rgbs, mask, rays_o, rays_d, H, W, _ = data
+            extra = dict(image_hw=(int(H), int(W))) if dssim_wanted(opt) else {}    # the D-SSIM term reads the rays as the H x W view they are
             loss, _ = trainer.train_step(rays_o, rays_d, rgbs, mask, num_steps=opt.num_steps, upsample_steps=opt.upsample_steps,
-                                         dt_gamma=getattr(opt, 'dt_gamma', 0), max_steps=opt.max_steps)
+                                         dt_gamma=getattr(opt, 'dt_gamma', 0), max_steps=opt.max_steps, **extra)
         total = total + loss                                           # stays on the device: no per-step host sync
         n += 1
     avg = float(total) / max(n, 1)

@@ -1342,6 +1342,35 @@ int cnerf_image_metrics_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint
 int cnerf_image_metrics(const void *pred, const void *target, const float *mask, uint32_t B, uint32_t H, uint32_t W, uint32_t C, int dtype,
                         int quantize, double *sums_out, float *ssim_map, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The gradient of an image's SSIM with respect to pred (customnerf_amd/metrics.py ssim_with_grad / ssim_loss, the trainers'
+ * opt.lambda_dssim; csrc/metrics.hip; additive, same ABI version).  The definition of SSIM, the layouts of pred / target / mask, the dtypes
+ * and the counting rule are those of cnerf_image_metrics above, with quantize = 0.
+ *   sums_out [B][5] float64 (device): the five sums of cnerf_image_metrics, bit for bit (one device routine forms both).
+ *   grad_unit [B][H][W][C] float32 (device): d ssim_b / d pred, ssim_b = sums_out[b][3] / sums_out[b][4].
+ *   Per channel plane, a = pred, b = target, <.> the windowed mean, per window p:
+ *     mu_a = <a>, mu_b = <b>
+ *     A1 = 2 mu_a mu_b + C1                   A2 = 2 (<ab> - mu_a mu_b) + C2
+ *     B1 = mu_a mu_a + mu_b mu_b + C1         B2 = (<aa> - mu_a mu_a) + (<bb> - mu_b mu_b) + C2          s = A1 A2 / (B1 B2)
+ *     d_ab = 2 A1 / (B1 B2)       d_aa = -s / B2       d_mu = 2 mu_b (A2 - A1) / (B1 B2) + 2 mu_a s (1 / B2 - 1 / B1)
+ *   (d_ab = ds / d<ab>, d_aa = ds / d<aa>, d_mu = ds / d mu_a with the second moments held).  With the weight g_p = 1 / sums_out[b][4] for
+ *   a counted window and 0 for any other, and Wt the TRANSPOSED window filter, Wt[m](y, x) = sum_k sum_l g[k] g[l] m(y - k, x - l) with m zero
+ *   outside the (H - 10) x (W - 10) map, the gradient at pixel q is
+ *     grad_unit_q = Wt[g d_mu]_q + 2 a_q Wt[g d_aa]_q + b_q Wt[g d_ab]_q.
+ *   An image without a counted window gets a plane of exact zeros (never NaN); its sums_out is what cnerf_image_metrics reports.
+ *   Numerics: moments, coefficient maps and the transposed filter are float64; each gradient element is rounded to float32 once, after the
+ *     division by the window count.  A gather (one thread per pixel reads the maps), no atomics: bit-reproducible from run to run.
+ *   Launches: coefficient maps + tile partials, the partial sum, the gather — which reads the window count from sums_out on the device, so
+ *     there is no host sync and the call can be captured in a graph.
+ *   workspace: cnerf_ssim_grad_workspace_bytes(B, H, W, C) bytes (the tile partials and three float64 maps [B C][3][H - 10][W - 10]),
+ *     8-byte aligned, contents irrelevant.
+ *   CNERF_EINVAL / CNERF_ENULL as for cnerf_image_metrics (grad_unit is required too); both return before any launch; B = 0 is accepted
+ *   without one.  The caller's stream and buffers, no allocation.
+ * ---------------------------------------------------------------------------------------------- */
+int cnerf_ssim_grad_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint64_t *bytes_host);
+int cnerf_ssim_grad(const void *pred, const void *target, const float *mask, uint32_t B, uint32_t H, uint32_t W, uint32_t C, int dtype,
+                    double *sums_out, float *grad_unit, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
