@@ -132,7 +132,14 @@ __global__ void __launch_bounds__(256) k_dp_pack(float *__restrict__ g, __half *
         reinterpret_cast<uint2 *>(out)[i] = cn_pack_half4(make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale));
         reinterpret_cast<float4 *>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    for (uint64_t i = n4 * 4 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) { out[i] = __float2half_rn(g[i] * scale); g[i] = 0.f; }
+    for (uint64_t i = n4 * 4 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        // The empty asm keeps the float32 product a value of its own, as in the vector body: without it the compiler folds cvt_f16(g * scale) into
+        // one v_fma_mixlo_f16 with a +0 addend, which turns a -0 product into +0 and rounds once where the body rounds twice (ge_opaque, grid_common.h)
+        float x = g[i] * scale;
+        asm("" : "+v"(x));
+        out[i] = __float2half_rn(x);
+        g[i] = 0.f;
+    }
 }
 
 __global__ void __launch_bounds__(256) k_dp_reduce(const __half *__restrict__ recv, uint32_t world, uint64_t shard, float *__restrict__ out,

@@ -35,7 +35,11 @@ __device__ __forceinline__ void cn_scaler_update(float *state, bool skip, float 
     else {
         state[3] += 1.0f;
         const float t = state[1] + 1.0f;
-        if (t >= interval) { state[0] *= growth; state[1] = 0.0f; } else state[1] = t;
+        if (t >= interval) {
+            const float grown = state[0] * growth;                        // torch keeps the old scale when the grown one would overflow,
+            if (isfinite(grown)) state[0] = grown;                        // and resets the tracker either way
+            state[1] = 0.0f;
+        } else state[1] = t;
     }
     state[2] = 0.0f;
 }

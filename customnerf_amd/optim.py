@@ -77,6 +77,24 @@ class DynamicLossScaler:
         self.state[3:4].fill_(float(n))
 
 
+def _require_same_layout(p, g, m, v, p_half):
+    """The per-tensor kernels walk numel() elements from data_ptr() in memory order and pair p, g, m, v (and the fp16 shadow) by position: that
+    is the same element in each only if every tensor is dense (its numel() elements fill one gap-free block) and all have the same strides,
+    which is what autograd and zeros_like produce for a dense parameter, transposed or not.  Anything else would be updated in the wrong order."""
+    dims = sorted((st, sz) for st, sz in zip(p.stride(), p.shape) if sz != 1)
+    expect, dense = 1, True
+    for st, sz in dims:
+        dense, expect = dense and st == expect, expect * sz
+    if not dense and p.numel():
+        raise ValueError(f"FusedAdam: parameter of shape {tuple(p.shape)} with strides {p.stride()} is not dense; make it contiguous")
+    for name, t in (("grad", g), ("exp_avg", m), ("exp_avg_sq", v), ("half shadow", p_half)):
+        if t is None or (t.numel() == p.numel() and t.is_contiguous() and p.is_contiguous()):       # (the shadow may be a flat view of the table)
+            continue
+        if t.shape != p.shape or any(a != b for a, b, sz in zip(t.stride(), p.stride(), p.shape) if sz != 1):
+            raise ValueError(f"FusedAdam: {name} of shape {tuple(t.shape)}, strides {t.stride()} does not lie in memory like its parameter "
+                             f"(shape {tuple(p.shape)}, strides {p.stride()}): the kernel would pair their elements in the wrong order")
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam-compatible surface (param groups with per-group lr) over cnerf_adam_step.
     `half_shadows`: {param: fp16 tensor} refreshed in the same pass (GridEncoder.set_half_table)."""
@@ -161,6 +179,7 @@ class FusedAdam(torch.optim.Optimizer):
                         and group['eps'] == eps0 and p.grad.is_contiguous() and p.is_contiguous()):
                     small.append((p, st, group))
                     continue
+                _require_same_layout(p, p.grad, st['exp_avg'], st['exp_avg_sq'], self.half_shadows.get(p))
                 if self.scaler is not None:
                     require_cuda(p.data, p.grad, st['exp_avg'], st['exp_avg_sq'], self.half_shadows.get(p))
                     check(lib.cnerf_adam_step_scaled(ptr(p.data), ptr(p.grad), ptr(st['exp_avg']), ptr(st['exp_avg_sq']), ptr(self.half_shadows.get(p)),
